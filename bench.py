@@ -13,7 +13,7 @@ With N > 1 (BASELINE configs[3]) each rank owns 8 different prompts (weak scalin
 conditioning for all ranks and broadcasts it over RCCL, waveforms are gathered to rank 0; no collective runs
 inside the DDIM loop.
 
-Secondary workloads (reported under "secondary" in the same JSON line at N = 1; hifigan64 / mixed also alone with --workload):
+Secondary workloads (reported under "secondary" of the --full line at N = 1; hifigan64 / mixed also alone with --workload):
   t2a_bf16     -- configs[1] literally in bf16 (one MFMA per multiply-add) with its measured mel-L1 / wav-RMS against the bf16x3 run
   t2a_bigvgan  -- configs[1] with BigVGAN, the vocoder the T2A tool actually loads (audio-chatgpt.py:145)
   tool_latency -- one T2A.txt2audio call (n_samples 3, CFG, BigVGAN per sample, CLAP best-of-3) and one I2A.img2audio call, ms
@@ -27,16 +27,23 @@ Secondary workloads (reported under "secondary" in the same JSON line at N = 1; 
 
 Steps overlap: `--inflight 3` (default) keeps three consecutive steps -- independent batches of 8 prompts -- in flight per GPU on
 three pipeline replicas (streams); every batch is still sampled as configs[1] says.  The METHOD IS PART OF THE METRIC STRING
-("... [3 batches of 8 in flight per GPU]"); `one_batch_in_flight` in the same JSON line is the strictly sequential
+("... [3 batches of 8 in flight per GPU]"); `one_batch_in_flight` in the --full line is the strictly sequential
 measurement (one batch of 8 owning the GPU: the number comparable with round 1 and with a latency reading of configs[1]),
 `ms_per_step` is elapsed / steps (the throughput period, as the contract defines it) and `batch_latency_ms` says how long
 one batch takes from its first kernel to its waveforms under each of the two arrangements.
 
-Output: ONE JSON line on rank 0 with metric/value plus
+Output: ONE JSON line on rank 0 with metric/value/unit/ms_per_step (milliseconds of one timed step).  A plain run does only
+that: set-up, warm-up, the timed steps and the line.  `--full` adds everything else, after the timed steps:
   roofline     -- the dominant kernel (the implicit-GEMM engine): algorithmic FLOPs (2*M*N*K) of its launches / their
                   summed hipEvent durations, against the dense MFMA peak of the precision mode (157.3 TFLOP/s fp32,
                   2500 TFLOP/s bf16; bf16x3 spends 3 MFMAs per algorithmic multiply-add)
   cpu_baseline -- the CPU oracle (a port of the reference path) on this box's host cores, bounded sample
+  one_batch_in_flight, the secondary workloads, `box` (clocks during the timed region, calibration loops), `wav_sha16` and the
+  full record in a detail file.  The --no-* switches drop single parts of a --full run.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): `waveform` [B, samples] (rank 0's
+gathered waveforms), `mel` [B, 80, frames] and `latent` [B, 4, 10, 78] of rank 0's own prompts.  Inputs and weights are seeded,
+so two runs with the same arguments get the same inputs.
 """
 import argparse
 import json
@@ -61,6 +68,14 @@ from benchlib.line import LINE_LIMIT, emit, slim_line, slim_workload      # noqa
 from benchlib.roofline import attach_traffic, roofline_of      # noqa: E402,F401
 from benchlib.secondary import (mixed_inpaint, mixed_inputs, one_batch_records, run_hifigan64, run_mixed,      # noqa: E402,F401
                                 run_secondaries, run_t2a_variant, run_tool_latency)
+
+
+def dump_outputs(d, arrays):
+    """arrays {name: tensor or None} -> d/<name>.npy, float32."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        if t is not None:
+            np.save(os.path.join(d, name + ".npy"), t.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy())
 
 
 def main(argv=None):
@@ -106,7 +121,16 @@ def main(argv=None):
     ap.add_argument("--json-out", default=None, help="also write the FULL record (what gpurun_out/bench_detail.json holds) to this file")
     ap.add_argument("--full-line", action="store_true",
                     help="print the full record on stdout instead of the <= 6 kB line (per-kernel tables included: ~25 kB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline pass, CPU baseline, one batch in flight, "
+                         "secondary workloads, box clocks and calibration, waveform hash, detail record file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's waveform / mel / latent to DIR/<name>.npy (float32)")
     args = ap.parse_args(argv)
+    if not args.full:      # a plain run: set-up, warm-up, the timed steps and the line, nothing else
+        args.no_roofline = args.no_cpu_baseline = args.no_secondary = args.no_one_batch = True
+    if args.dump_outputs and args.workload != "t2a":
+        raise SystemExit("bench.py: --dump-outputs writes the t2a workload's outputs only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # `python bench.py --gpus N` with no launcher around it: become the launcher (one rank per GPU under torch.distributed.run on
@@ -196,6 +220,8 @@ def main(argv=None):
     x_T = start_codes(55, n * world, LATENT, world, rank).to(dev)
     cond_shape, counts = (n * world, 77, 1024), [n] * world
 
+    last_mel_latent = {}      # replica -> (mel, latent) of its latest batch (kept for --dump-outputs only)
+
     def make_generator(p_, k_=0):
         first = [args.stagger_ms > 0 and k_ > 0]
 
@@ -207,15 +233,17 @@ def main(argv=None):
                 first[0] = False
                 time.sleep(k_ * args.stagger_ms * 1e-3)
             if p_.stream is None:
-                wav = p_.generate_here(x_T, c_, uc_, CFG_SCALE, S, use_graph=use_graph)[0]
+                wav, spec, z = p_.generate_here(x_T, c_, uc_, CFG_SCALE, S, use_graph=use_graph)
                 done.record(None if stub else torch.cuda.current_stream(dev))
             else:
                 with torch.cuda.stream(p_.stream):
                     p_.stream.wait_event(ready)
                     for t in (c_, uc_):          # allocated on the main thread's stream, read on this one: tell the allocator
                         t.record_stream(p_.stream)
-                    wav = p_.generate_here(x_T, c_, uc_, CFG_SCALE, S, use_graph=use_graph)[0]
+                    wav, spec, z = p_.generate_here(x_T, c_, uc_, CFG_SCALE, S, use_graph=use_graph)
                     done.record(p_.stream)
+            if args.dump_outputs:
+                last_mel_latent[k_] = (spec, z)
             return wav, done
         return generate
 
@@ -262,7 +290,7 @@ def main(argv=None):
         v.clear()
     # box calibration right before the timed region (rank 0): what a fixed MFMA loop and a fixed copy reach on this box now
     calib = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             calib = pipe.ctx.calib() if not stub else {"stub": 1.0}
             calib["note"] = ("csrc/calib.hip on the first replica's stream: dense bf16 MFMA loop (peak 2500 TFLOP/s at 2.4 GHz), "
@@ -271,7 +299,7 @@ def main(argv=None):
         except Exception as e:      # never lose the line to the calibration
             calib = {"error": str(e)[:200]}
     barrier()      # EVERY rank (a collective): rank 0's calibration loops must not run into the other ranks' timed region
-    sampler = BoxSampler(dev) if (rank == 0 and not stub) else None
+    sampler = BoxSampler(dev) if (rank == 0 and not stub and args.full) else None
     if sampler is not None:
         sampler.__enter__()
     t0 = time.perf_counter()
@@ -289,6 +317,9 @@ def main(argv=None):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs and out is not None:      # what the last timed step computed (the barrier synchronised it)
+        mel, latent = last_mel_latent[(args.steps - 1) % inflight]
+        dump_outputs(args.dump_outputs, {"waveform": out, "mel": mel, "latent": latent})
     seen = ranks_seen(dev, dist, force=force) if (world > 1 or force) else None
 
     # device time of the two collectives of a step (events on the main thread's stream, this rank): their share of a step is
@@ -355,7 +386,7 @@ def main(argv=None):
     if rank == 0 and world == 1 and not args.no_secondary:
         run_secondaries(result, pipes, dev, args)
     if rank == 0:
-        if out is not None:      # identity of the last step's gathered waveforms (bit-identity checks between arrangements)
+        if out is not None and args.full:      # identity of the last step's gathered waveforms (bit-identity checks between arrangements)
             import hashlib
             result["wav_sha16"] = hashlib.sha256(out.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
         if stub:

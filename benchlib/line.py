@@ -125,6 +125,12 @@ def slim_line(result, detail_path=None, limit=LINE_LIMIT):
 
 def emit(result, args):
     """Full record -> gpurun_out/bench_detail.json (and --json-out), slim line -> stdout."""
+    if not getattr(args, "full", True):      # a plain run (no --full): no detail file, only --json-out if asked for
+        if getattr(args, "json_out", None):
+            with open(args.json_out, "w") as f:
+                f.write(json.dumps(result))
+        print(json.dumps(result) if getattr(args, "full_line", False) else slim_line(result), flush=True)
+        return
     detail_rel = os.path.join("gpurun_out", "bench_detail.json")
     try:
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)

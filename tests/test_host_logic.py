@@ -469,10 +469,35 @@ def test_bench_stdout_line_fits_the_drivers_capture(capsys):
     assert d["secondary"]["t2a_bf16"]["parity"]["meets_gate"] is False and d["secondary"]["t2a_bigvgan"]["parity"]["meets_gate"] is True
     assert d["secondary"]["t2a_bf16"]["one_batch_in_flight"]["value"] > 0
     # the stub path of main() prints exactly one line, through the same function
-    bench.main(["--stub-cpu", "--steps", "2", "--warmup", "1", "--inflight", "2"])
+    bench.main(["--stub-cpu", "--full", "--steps", "2", "--warmup", "1", "--inflight", "2"])
     out = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
     assert len(out) == 1 and len(out[0]) <= bench.LINE_LIMIT
     assert json.loads(out[0])["detail"].endswith("bench_detail.json")
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path, capsys):
+    """A plain run (no --full) prints the contract line only -- no detail file, no hash -- and --dump-outputs writes the last
+    timed step's arrays as float32 .npy files, the same ones on every run with the same arguments."""
+    import json
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        bench.main(["--stub-cpu", "--steps", "3", "--warmup", "1", "--inflight", "2", "--dump-outputs", str(d)])
+        out = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+        dumps.append({p.name: np.load(str(p)) for p in d.iterdir()})
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and "detail" not in line and "wav_sha16" not in line
+    assert set(dumps[0]) == {"waveform.npy"}      # (the stub pipeline makes no mel / latent)
+    w = dumps[0]["waveform.npy"]
+    assert w.dtype == np.float32 and w.shape == (8, 64) and np.isfinite(w).all()
+    assert np.array_equal(w, dumps[1]["waveform.npy"])
 
 
 def test_box_class_thresholds():
