@@ -262,6 +262,52 @@ class UNet:
 
     __call__ = forward
 
+    def _ddim_args(self, what, x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep):
+        """maa_ddim_args for the latent x (on the device) and the S-step schedule, with the conditioning checked and kept alive in
+        `keep`; `what` names the caller in the messages."""
+        dev = self.ctx.device
+        B, Cc, H, W = x.shape
+        a = L.maa_ddim_args()
+        ts = np.ascontiguousarray(np.asarray(timesteps), dtype=np.int32)
+        al = np.ascontiguousarray(np.asarray(alphas), dtype=np.float32)
+        ap = np.ascontiguousarray(np.asarray(alphas_prev), dtype=np.float32)
+        a.S, a.B, a.C, a.H, a.W = len(ts), B, Cc, H, W
+        a.scale = float(scale)
+        keep += [ts, al, ap]            # (the host tables are read by the call)
+        # shapes are checked here (the C ABI sees bare pointers): the reference raises from torch.cat / the attention
+        # einsum on any of these mismatches (ddim.py:177-199, ddpm.py:1404-1406)
+        if cond is not None:
+            cond = _f32(cond, dev)
+            cdim = self.cfg["context_dim"] or 0
+            if cond.dim() != 3 or cond.shape[0] != B or cond.shape[2] != cdim:
+                raise L.MaaError(what + ": conditioning must be [B=%d, L, %d], got %s" % (B, cdim, tuple(cond.shape)))
+            keep.append(cond)
+            a.d_cond = cond.data_ptr()
+            a.L = cond.shape[1]
+        if uncond is not None:
+            if cond is None:
+                raise L.MaaError(what + ": unconditional_conditioning without conditioning")
+            uncond = _f32(uncond, dev)
+            if tuple(uncond.shape) != tuple(cond.shape):
+                raise L.MaaError(what + ": unconditional_conditioning %s must have the shape of conditioning %s"
+                                 % (tuple(uncond.shape), tuple(cond.shape)))
+            keep.append(uncond)
+            a.d_uncond = uncond.data_ptr()
+        if concat is not None:
+            concat = _f32(concat, dev)
+            if concat.dim() != 4 or concat.shape[0] != B or tuple(concat.shape[2:]) != (H, W) \
+                    or Cc + concat.shape[1] != self.cfg["in_channels"]:
+                raise L.MaaError(what + ": concat conditioning must be [B=%d, %d, %d, %d], got %s"
+                                 % (B, self.cfg["in_channels"] - Cc, H, W, tuple(concat.shape)))
+            keep.append(concat)
+            a.d_concat = concat.data_ptr()
+            a.Cc = concat.shape[1]
+        a.h_timesteps = ts.ctypes.data_as(C.POINTER(C.c_int32))
+        a.h_alphas = al.ctypes.data_as(C.POINTER(C.c_float))
+        a.h_alphas_prev = ap.ctypes.data_as(C.POINTER(C.c_float))
+        a.use_graph = int(use_graph)
+        return a, B, Cc, H, W
+
     def ddim_sample(self, x_T, timesteps, alphas, alphas_prev, cond=None, uncond=None, scale=1.0, concat=None,
                     use_graph=True, mask=None, x0=None, noise_q=None, sqrt_ac=None, sqrt_1mac=None, sigmas=None,
                     noise_p=None, temperature=1.0, log_every_t=None):
@@ -272,47 +318,9 @@ class UNet:
         are in loop order (first step first)."""
         dev = self.ctx.device
         x = _f32(x_T, dev).clone()
-        B, Cc, H, W = x.shape
-        a = L.maa_ddim_args()
-        ts = np.ascontiguousarray(np.asarray(timesteps), dtype=np.int32)
-        al = np.ascontiguousarray(np.asarray(alphas), dtype=np.float32)
-        ap = np.ascontiguousarray(np.asarray(alphas_prev), dtype=np.float32)
-        a.S, a.B, a.C, a.H, a.W = len(ts), B, Cc, H, W
-        a.scale = float(scale)
         keep = []
-        # shapes are checked here (the C ABI sees bare pointers): the reference raises from torch.cat / the attention
-        # einsum on any of these mismatches (ddim.py:177-199, ddpm.py:1404-1406)
-        if cond is not None:
-            cond = _f32(cond, dev)
-            cdim = self.cfg["context_dim"] or 0
-            if cond.dim() != 3 or cond.shape[0] != B or cond.shape[2] != cdim:
-                raise L.MaaError("ddim_sample: conditioning must be [B=%d, L, %d], got %s" % (B, cdim, tuple(cond.shape)))
-            keep.append(cond)
-            a.d_cond = cond.data_ptr()
-            a.L = cond.shape[1]
-        if uncond is not None:
-            if cond is None:
-                raise L.MaaError("ddim_sample: unconditional_conditioning without conditioning")
-            uncond = _f32(uncond, dev)
-            if tuple(uncond.shape) != tuple(cond.shape):
-                raise L.MaaError("ddim_sample: unconditional_conditioning %s must have the shape of conditioning %s"
-                                 % (tuple(uncond.shape), tuple(cond.shape)))
-            keep.append(uncond)
-            a.d_uncond = uncond.data_ptr()
-        if concat is not None:
-            concat = _f32(concat, dev)
-            if concat.dim() != 4 or concat.shape[0] != B or tuple(concat.shape[2:]) != (H, W) \
-                    or Cc + concat.shape[1] != self.cfg["in_channels"]:
-                raise L.MaaError("ddim_sample: concat conditioning must be [B=%d, %d, %d, %d], got %s"
-                                 % (B, self.cfg["in_channels"] - Cc, H, W, tuple(concat.shape)))
-            keep.append(concat)
-            a.d_concat = concat.data_ptr()
-            a.Cc = concat.shape[1]
-        a.h_timesteps = ts.ctypes.data_as(C.POINTER(C.c_int32))
-        a.h_alphas = al.ctypes.data_as(C.POINTER(C.c_float))
-        a.h_alphas_prev = ap.ctypes.data_as(C.POINTER(C.c_float))
-        a.use_graph = int(use_graph)
-        S = len(ts)
+        a, B, Cc, H, W = self._ddim_args("ddim_sample", x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep)
+        S = a.S
 
         def host_table(v, what):
             t = np.ascontiguousarray(np.asarray(v), dtype=np.float32)
@@ -376,6 +384,38 @@ class UNet:
                 return x, out[0], out[1]
         return x
 
+    def ddim_decode(self, x_latent, t_start, timesteps, alphas, alphas_prev, cond=None, uncond=None, scale=1.0, concat=None,
+                    use_graph=True, sigmas=None, noise_p=None, temperature=1.0):
+        """DDIMSampler.decode (ddim.py:243-261) on the device: the DDIM steps of indices t_start - 1 .. 0 of the S-step schedule
+        (timesteps / alphas / alphas_prev as for ddim_sample) from x_latent; t_start = 0 returns a copy of x_latent.  Guidance and
+        concat conditioning as for ddim_sample; sigmas [S] / noise_p [t_start, B, C, H, W] (loop order) / temperature: the eta > 0
+        term.  With the same S, shapes and guidance as the last ddim_sample on this context the kept step graph is replayed."""
+        dev = self.ctx.device
+        x = _f32(x_latent, dev).clone()
+        keep = []
+        a, B, Cc, H, W = self._ddim_args("ddim_decode", x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep)
+        S = a.S
+        t_start = int(t_start)
+        if not 0 <= t_start <= S:
+            raise L.MaaError("ddim_decode: t_start must lie in [0, S=%d], got %d" % (S, t_start))
+        if sigmas is not None:
+            if noise_p is None:
+                raise L.MaaError("ddim_decode: sigmas (eta > 0) need noise_p")
+            sg = np.ascontiguousarray(np.asarray(sigmas), dtype=np.float32)
+            if sg.shape != (S,):
+                raise L.MaaError("ddim_decode: sigmas must hold one value per DDIM step (%d), got %s" % (S, sg.shape))
+            z = _f32(noise_p, dev)
+            if tuple(z.shape) != (t_start, B, Cc, H, W):
+                raise L.MaaError("ddim_decode: noise_p must be [t_start=%d, %d, %d, %d, %d], got %s"
+                                 % (t_start, B, Cc, H, W, tuple(z.shape)))
+            keep += [sg, z]
+            a.h_sigmas = sg.ctypes.data_as(C.POINTER(C.c_float))
+            a.d_noise_p = z.data_ptr() if t_start > 0 else None
+        a.temperature = float(temperature)
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_ddim_decode(self.ctx.h, self.h, C.byref(a), t_start, L.dptr(x)))
+        return x
+
     def ddim_update(self, x, eps_uncond, eps_cond, scale, a_t, a_prev, sigma_t, sqrt_one_minus_at):
         """p_sample_ddim's elementwise tail for ONE step (ddim.py:199, 210-225 without the noise term) through
         `maa_ddim_update`: e = eu + scale (ec - eu) (eps_cond None: e = eps_uncond), returns (x_prev, pred_x0).  Used by the
@@ -400,6 +440,55 @@ class UNet:
             self.close()
         except Exception:
             pass
+
+
+def ddim_stochastic_encode(ctx, x0, t, sqrt_a, sqrt_1ma, noise, moments=False, scale_factor=1.0, noise_post=None):
+    """DDIMSampler.stochastic_encode (ddim.py:227-241) through maa_ddim_stochastic_encode:
+    out[b] = sqrt_a[t[b]] * x0[b] + sqrt_1ma[t[b]] * noise[b].  t: an int or [1] / [B] indices into the two tables
+    (sqrt(ddim_alphas) / ddim_sqrt_one_minus_alphas, or the 1000-step sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod).
+    moments=True: x0 is the VAE's moments [B, 2C, H, W] and the latent is formed in the same pass,
+    scale_factor * (mean + exp(0.5 clamp(logvar, -30, 20)) * noise_post) (posterior.sample() + get_first_stage_encoding)."""
+    dev = ctx.device
+    src = _f32(x0, dev)
+    if src.dim() != 4:
+        raise L.MaaError("stochastic_encode: x0 must be [B, C, H, W], got %s" % (tuple(src.shape),))
+    B, C2, H, W = src.shape
+    if moments:
+        if C2 % 2 or noise_post is None:
+            raise L.MaaError("stochastic_encode: moments must be [B, 2C, H, W] and need noise_post, got %s" % (tuple(src.shape),))
+        Cc = C2 // 2
+    else:
+        Cc = C2
+    shape = (B, Cc, H, W)
+    noise = _f32(noise, dev)
+    if tuple(noise.shape) != shape:
+        raise L.MaaError("stochastic_encode: noise must be %s, got %s" % (shape, tuple(noise.shape)))
+    npost = None
+    if moments:
+        npost = _f32(noise_post, dev)
+        if tuple(npost.shape) != shape:
+            raise L.MaaError("stochastic_encode: noise_post must be %s, got %s" % (shape, tuple(npost.shape)))
+    ta = np.ascontiguousarray(np.asarray(sqrt_a.detach().cpu() if torch.is_tensor(sqrt_a) else sqrt_a), dtype=np.float32)
+    tb = np.ascontiguousarray(np.asarray(sqrt_1ma.detach().cpu() if torch.is_tensor(sqrt_1ma) else sqrt_1ma), dtype=np.float32)
+    if ta.ndim != 1 or ta.shape != tb.shape or ta.size == 0:
+        raise L.MaaError("stochastic_encode: the two tables must be 1-D and of one length, got %s / %s" % (ta.shape, tb.shape))
+    n_tab = ta.shape[0]
+    th = np.asarray(t.detach().cpu() if torch.is_tensor(t) else t).reshape(-1)
+    if th.size == 1:
+        th = np.repeat(th, B)
+    if th.shape != (B,) or not np.issubdtype(th.dtype, np.integer):
+        raise L.MaaError("stochastic_encode: t must hold one integer index per sample (B=%d), got %s %s" % (B, th.shape, th.dtype))
+    if th.min() < 0 or th.max() >= n_tab:
+        raise L.MaaError("stochastic_encode: t must lie in [0, %d), got %s" % (n_tab, th.tolist()))
+    td = torch.from_numpy(th.astype(np.int32)).to(dev)
+    out = torch.empty(shape, device=dev)
+    fp = C.POINTER(C.c_float)
+    with ctx.lock:
+        L.check(ctx.lib.maa_ddim_stochastic_encode(ctx.h, L.dptr(src), int(bool(moments)), float(scale_factor),
+                                                   L.dptr(npost) if npost is not None else None, C.c_void_p(td.data_ptr()),
+                                                   ta.ctypes.data_as(fp), tb.ctypes.data_as(fp), n_tab, L.dptr(noise),
+                                                   B, Cc, H, W, L.dptr(out)))
+    return out
 
 
 class VAE:

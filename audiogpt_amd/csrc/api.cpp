@@ -301,6 +301,30 @@ int maa_ddim_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, float*
         maa::ddim_sample(ctx->c, *u->m, *args, d_x);
     });
 }
+// (the arguments are checked before the context is bound: a malformed call fails the same way with or without a device)
+int maa_ddim_stochastic_encode(maa_ctx* ctx, const float* d_x0_or_moments, int from_moments, float scale_factor,
+                               const float* d_noise_post, const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab,
+                               const float* d_noise, int B, int C, int H, int W, float* d_out) {
+    return guarded([&] {
+        MAA_CHECK(d_x0_or_moments && d_t && h_sqrt_a && h_sqrt_1ma && d_noise && d_out, "bad stochastic_encode arguments: null pointer");
+        MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "bad stochastic_encode arguments: empty shape or table");
+        MAA_CHECK(!from_moments || d_noise_post, "bad stochastic_encode arguments: the moments need their posterior noise");
+        bind(ctx);
+        maa::ddim_stochastic_encode(ctx->c, d_x0_or_moments, from_moments != 0, scale_factor, d_noise_post, d_t, h_sqrt_a, h_sqrt_1ma,
+                                    n_tab, d_noise, B, C, H, W, d_out);
+    });
+}
+int maa_ddim_decode(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, int t_start, float* d_x) {
+    return guarded([&] {
+        MAA_CHECK(u && args && d_x && args->h_timesteps && args->h_alphas && args->h_alphas_prev, "bad ddim_decode arguments");
+        MAA_CHECK(args->S > 0 && args->B > 0, "bad ddim_decode arguments: empty problem");
+        MAA_CHECK(t_start >= 0 && t_start <= args->S, "bad ddim_decode arguments: t_start must lie in [0, S]");
+        MAA_CHECK(!args->d_mask && !args->d_x0 && !args->d_noise_q, "bad ddim_decode arguments: decode takes no mask / x0");
+        MAA_CHECK(args->n_log == 0 && !args->d_log_x && !args->d_log_x0, "bad ddim_decode arguments: decode logs no intermediates");
+        bind(ctx);
+        maa::ddim_decode(ctx->c, *u->m, *args, t_start, d_x);
+    });
+}
 
 // ------------------------------------------------------------------------------------------ VAE
 int maa_vae_create(maa_ctx* ctx, const maa_vae_config* cfg, const maa_tensor* tensors, int n_tensors, maa_vae** out) {

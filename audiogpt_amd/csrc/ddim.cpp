@@ -30,8 +30,15 @@
 
 namespace maa {
 
-void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
+namespace {
+
+// The loop body of sample() and decode(): n_steps steps of the S-step schedule `a` describes, from DDIM index `start` down to
+// start - n_steps + 1.  sample() is (S - 1, S); decode(t_start) is (t_start - 1, t_start).  The start only sets the device step
+// index before the first step, so it is not part of the step graph's key: a decode with the same S, shapes, guidance and buffers
+// as the last sample replays the kept graph.  noise_p: the pointer the step kernel indexes as noise_p + (S - 1 - idx) * n.
+void ddim_run(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int start, int n_steps, const float* noise_p, float* d_x) {
     MAA_CHECK(a.S > 0 && a.B > 0, "ddim: empty problem");
+    MAA_CHECK(start >= 0 && start < a.S && n_steps > 0 && n_steps <= start + 1, "ddim: steps outside the schedule");
     MAA_CHECK(!a.d_uncond || a.d_cond, "ddim: unconditional conditioning given without conditioning");
     MAA_CHECK(!a.d_cond || a.L > 0, "ddim: conditioning needs its token count L");
     MAA_CHECK(!a.d_concat || a.Cc > 0, "ddim: concat conditioning needs its channel count");
@@ -48,6 +55,7 @@ void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
     const bool masked = a.d_mask != nullptr;
     MAA_CHECK(!masked || (a.d_x0 && a.d_noise_q && a.h_sqrt_ac && a.h_sqrt_1mac), "ddim: mask needs x0, its noise and the q_sample tables");
     MAA_CHECK(!a.h_sigmas || a.d_noise_p, "ddim: eta > 0 needs the steps' noise");
+    // (noise_p itself may point before the caller's buffer -- decode's offset -- so it is tested through a.d_noise_p only)
     const bool logging = a.n_log > 0;
     MAA_CHECK(!logging || (a.d_log_x && a.d_log_x0 && a.log_every_t > 0), "ddim: intermediates need their buffers and log_every_t");
     std::vector<float> h_tab((size_t)a.S * 9);
@@ -85,7 +93,7 @@ void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
     MAA_HIP(hipMemcpyAsync(xs, d_x, (size_t)a.B * per * 4, hipMemcpyDeviceToDevice, ctx.stream));
     if (concat) MAA_HIP(hipMemcpyAsync(ccs, a.d_concat, n_cc * 4, hipMemcpyDeviceToDevice, ctx.stream));
     int* d_step = reinterpret_cast<int*>(slab + o_step);
-    const int h_step = a.S - 1;                        // ddim.py:143-145: flipped timesteps, index = total - i - 1
+    const int h_step = start;                          // ddim.py:143-145: flipped timesteps, index = total - i - 1
     MAA_HIP(hipMemcpyAsync(slab + o_tab, h_tab.data(), h_tab.size() * 4, hipMemcpyHostToDevice, ctx.stream));
     MAA_HIP(hipMemcpyAsync(d_step, &h_step, 4, hipMemcpyHostToDevice, ctx.stream));
 
@@ -130,7 +138,7 @@ void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
             // (one stream: the halves of cat([x] * 2) share every layer before the first cross-attention -- unet.cpp `dup`)
             unet.forward(ctx, xin, cur_t, unet.context_ptr, nB, a.H, a.W, eps, emb_hoist ? cur_emb : nullptr, -1, share ? 1 : 0);
         launch_ddim_step(ctx, xin, per, per_in, eps, cfg ? eps + a.B * per : nullptr, a.scale, cur_coef, (long long)a.B * per, xs,
-                         a.h_sigmas ? a.d_noise_p : nullptr, a.temperature, a.S, logging ? a.d_log_x : nullptr,
+                         a.h_sigmas ? noise_p : nullptr, a.temperature, a.S, logging ? a.d_log_x : nullptr,
                          logging ? a.d_log_x0 : nullptr, d_step);
     };
 
@@ -153,7 +161,7 @@ void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
                                      (unsigned long long)reinterpret_cast<uintptr_t>(a.d_mask),
                                      (unsigned long long)reinterpret_cast<uintptr_t>(a.d_x0),
                                      (unsigned long long)reinterpret_cast<uintptr_t>(a.d_noise_q),
-                                     (unsigned long long)reinterpret_cast<uintptr_t>(a.h_sigmas ? a.d_noise_p : nullptr),
+                                     (unsigned long long)reinterpret_cast<uintptr_t>(a.h_sigmas ? noise_p : nullptr),
                                      (unsigned long long)reinterpret_cast<uintptr_t>(logging ? a.d_log_x : nullptr),
                                      (unsigned long long)reinterpret_cast<uintptr_t>(logging ? a.d_log_x0 : nullptr),
                                      (unsigned long long)(a.h_sigmas ? 1 : 0),
@@ -177,7 +185,7 @@ void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
         sg.clear();
         step_body();                      // first step eager: sizes the workspace before any capture
         first = 1;
-        if (a.S > 1) {
+        if (n_steps > 1) {
             MAA_HIP(hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeRelaxed));
             try {
                 step_body();
@@ -192,10 +200,10 @@ void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
             sg.key = make_key();
         }
     }
-    for (int i = first; i < a.S; ++i) {
+    for (int i = first; i < n_steps; ++i) {
 #ifdef MAA_ROCTX
         char range[48];
-        std::snprintf(range, sizeof(range), "ddim_step %d/%d t=%d", i + 1, a.S, (int)a.h_timesteps[a.S - 1 - i]);
+        std::snprintf(range, sizeof(range), "ddim_step %d/%d t=%d", i + 1, n_steps, (int)a.h_timesteps[start - i]);
 #endif
         MAA_RANGE_PUSH(range);
         if (a.use_graph)
@@ -206,6 +214,55 @@ void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
     }
     MAA_HIP(hipMemcpyAsync(d_x, xs, (size_t)a.B * per * 4, hipMemcpyDeviceToDevice, ctx.stream));
     MAA_HIP(hipStreamSynchronize(ctx.stream));   // the host tables go out of scope; the call returns a finished latent
+}
+
+}  // namespace
+
+void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) { ddim_run(ctx, unet, a, a.S - 1, a.S, a.d_noise_p, d_x); }
+
+// ddim.py:243-261: decode runs p_sample_ddim over timesteps[:t_start] flipped, i.e. DDIM indices t_start - 1 .. 0 with the tables
+// of the whole schedule -- the tail of sample()'s loop.  Its caller's noise holds t_start draws (first step first); the step kernel
+// reads draw S - 1 - idx of its pointer, so the pointer handed over starts S - t_start draws before the caller's buffer (only
+// draws S - t_start .. S - 1 of it, the caller's 0 .. t_start - 1, are ever read).
+void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, float* d_x) {
+    MAA_CHECK(a.S > 0 && a.B > 0, "ddim_decode: empty problem");
+    MAA_CHECK(t_start >= 0 && t_start <= a.S, "ddim_decode: t_start must lie in [0, S]");
+    MAA_CHECK(!a.d_mask && !a.d_x0 && !a.d_noise_q && !a.h_sqrt_ac && !a.h_sqrt_1mac,
+              "ddim_decode: decode has no mask / x0 (ddim.py:243-245)");
+    MAA_CHECK(a.n_log == 0 && !a.d_log_x && !a.d_log_x0, "ddim_decode: decode logs no intermediates");
+    if (t_start == 0) return;                          // the reference's loop is empty: x_latent comes back unchanged
+    const float* noise_p = nullptr;
+    if (a.h_sigmas && a.d_noise_p) {
+        const long long n = (long long)a.B * a.C * a.H * a.W;
+        noise_p = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(a.d_noise_p) -
+                                                 (uintptr_t)((long long)(a.S - t_start) * n * (long long)sizeof(float)));
+    }
+    ddim_run(ctx, unet, a, t_start - 1, t_start, noise_p, d_x);
+}
+
+// ddim.py:227-241.  The two coefficient tables go up once per call next to an error flag in the context's own slab; the flag is
+// read back after the launch (the call synchronises the stream: the host tables and the caller's t are its inputs).
+void ddim_stochastic_encode(Ctx& ctx, const float* d_x0_or_moments, bool from_moments, float scale_factor, const float* d_noise_post,
+                            const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab, const float* d_noise, int B,
+                            int C, int H, int W, float* d_out) {
+    MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "stochastic_encode: empty problem");
+    MAA_CHECK(!from_moments || d_noise_post, "stochastic_encode: the moments need their posterior noise");
+    const long long per = (long long)C * H * W;
+    // [flag | pad to 256 B | A (n_tab) | B (n_tab)]
+    char* slab = static_cast<char*>(ctx.encode_scratch.get(256 + 2 * (size_t)n_tab * sizeof(float), ctx.stream));
+    int* bad = reinterpret_cast<int*>(slab);
+    float* tab = reinterpret_cast<float*>(slab + 256);
+    std::vector<float> h_tab((size_t)2 * n_tab);
+    std::memcpy(h_tab.data(), h_sqrt_a, (size_t)n_tab * sizeof(float));
+    std::memcpy(h_tab.data() + n_tab, h_sqrt_1ma, (size_t)n_tab * sizeof(float));
+    MAA_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx.stream));
+    MAA_HIP(hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
+    launch_ddim_stochastic_encode(ctx, from_moments ? nullptr : d_x0_or_moments, from_moments ? d_x0_or_moments : nullptr,
+                                  scale_factor, from_moments ? d_noise_post : nullptr, d_t, tab, n_tab, d_noise, B, per, d_out, bad);
+    int h_bad = 0;
+    MAA_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+    MAA_HIP(hipStreamSynchronize(ctx.stream));
+    MAA_CHECK(h_bad == 0, "stochastic_encode: some t[b] lies outside [0, n_tab)");
 }
 
 }  // namespace maa

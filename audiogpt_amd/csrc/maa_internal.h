@@ -164,6 +164,7 @@ struct Ctx {
     Tuning tune;
     StepGraph ddim_graph;
     DevSlab sampler_scratch;  // DDIM loop state (tables, step slots, UNet input, eps): reused by every sample() call
+    DevSlab encode_scratch;   // stochastic_encode's coefficient tables and error flag (apart from the loop's slab, whose address the step graph keeps)
     Profiler* prof = nullptr;
     float* zeros = nullptr;   // 256 B zero page (device), source of masked tile loads
     int device = 0;
@@ -323,6 +324,12 @@ void launch_ddim_prepare(const Ctx& ctx, const float* x, const float* concat, in
 void launch_ddim_step(const Ctx& ctx, const float* xin, long long per, long long per_in, const float* eps_u, const float* eps_c,
                       float scale, const float* coef, long long n, float* x_prev, const float* noise_p, float temperature, int S,
                       float* log_x, float* log_x0, int* step);
+// DDIMSampler.stochastic_encode (ddim.py:227-241): out[b] = tab[t[b]] * x0[b] + tab[n_tab + t[b]] * noise[b] over [B, per];
+// moments / n_post instead of x0: x0 = scale_factor * (mean + exp(0.5 clamp(logvar, -30, 20)) * n_post) from the VAE moments
+// [B, 2, per]; t [B] device int32; *bad (device) is set when some t[b] lies outside [0, n_tab)
+void launch_ddim_stochastic_encode(const Ctx& ctx, const float* x0, const float* moments, float scale_factor, const float* n_post,
+                                   const int* t, const float* tab, int n_tab, const float* noise, int B, long long per, float* out,
+                                   int* bad);
 // BigVGAN Activation1d on [B, L, C]: up2 FIR -> snake -> down2 FIR (replicate padding)
 void launch_snake_aa(const Ctx& ctx, const float* x, int B, int L, int C, const float* inv_beta, const float* alpha,
                      float* out);

@@ -291,6 +291,76 @@ __global__ void ddim_step_kernel(const float* __restrict__ xin, long long per, l
     }
 }
 
+// SDEdit's forward noising, DDIMSampler.stochastic_encode (ddim.py:227-241):
+//   out[b] = A[t[b]] * x0[b] + B[t[b]] * noise[b]      (extract_into_tensor gathers one row per sample; term order as torch's)
+// tab = [A | B], n_tab floats each; t [B] int32 on the device.  moments != null: x0 is formed here from the VAE moments
+// [B, 2C, H, W] (mean | logvar) and the posterior noise, as DiagonalGaussianDistribution.sample() followed by
+// get_first_stage_encoding (ldm/latent_diffusion.py): x0 = scale_factor * (mean + exp(0.5 * clamp(logvar, -30, 20)) * n_post).
+// V floats per thread (V = 4: 16-byte accesses; needs per % 4 == 0 so that a vector never straddles two samples).  An index
+// outside [0, n_tab) raises *bad and writes zeros: the table is never read out of bounds.
+template <int V>
+struct FVec {
+    float v[V];
+};
+template <int V>
+__device__ __forceinline__ FVec<V> load_v(const float* p) {
+    FVec<V> r;
+    if constexpr (V == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        r.v[0] = q.x, r.v[1] = q.y, r.v[2] = q.z, r.v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) r.v[k] = p[k];
+    }
+    return r;
+}
+template <int V>
+__device__ __forceinline__ void store_v(float* p, const FVec<V>& r) {
+    if constexpr (V == 4)
+        *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    else
+#pragma unroll
+        for (int k = 0; k < V; ++k) p[k] = r.v[k];
+}
+
+template <int V>
+__global__ void ddim_stochastic_encode_kernel(const float* __restrict__ x0, const float* __restrict__ moments, float scale_factor,
+                                              const float* __restrict__ n_post, const int* __restrict__ t,
+                                              const float* __restrict__ tab, int n_tab, const float* __restrict__ noise,
+                                              long long per, long long n, float* __restrict__ out, int* __restrict__ bad) {
+    const long long nv = n / V;
+    for (long long iv = blockIdx.x * (long long)blockDim.x + threadIdx.x; iv < nv; iv += (long long)gridDim.x * blockDim.x) {
+        const long long i = iv * V;
+        const long long b = i / per, r = i - b * per;
+        const int ti = t[b];
+        FVec<V> o;
+        if (ti < 0 || ti >= n_tab) {
+            *bad = 1;
+#pragma unroll
+            for (int k = 0; k < V; ++k) o.v[k] = 0.f;
+            store_v<V>(out + i, o);
+            continue;
+        }
+        const float ca = tab[ti], cb = tab[n_tab + ti];
+        FVec<V> x;
+        if (moments) {
+            const FVec<V> mean = load_v<V>(moments + b * 2 * per + r), lv = load_v<V>(moments + b * 2 * per + per + r);
+            const FVec<V> z = load_v<V>(n_post + i);
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const float sd = expf(0.5f * fminf(fmaxf(lv.v[k], -30.f), 20.f));
+                x.v[k] = scale_factor * (mean.v[k] + sd * z.v[k]);
+            }
+        } else {
+            x = load_v<V>(x0 + i);
+        }
+        const FVec<V> z = load_v<V>(noise + i);
+#pragma unroll
+        for (int k = 0; k < V; ++k) o.v[k] = ca * x.v[k] + cb * z.v[k];
+        store_v<V>(out + i, o);
+    }
+}
+
 // UNet input and scalars of one DDIM step, with nothing from the host: idx = *step selects the row of the device
 // tables; xin[b'] = cat(x[b' % B], concat[b' % B]) for b' < nB (nB = 2B duplicates the latents for CFG in the order
 // [uncond ; cond], ddim.py:177-179; concat is the inpaint model's conditioning, ddpm.py:1404-1406).
@@ -546,6 +616,21 @@ void launch_ddim_step(const Ctx& ctx, const float* xin, long long per, long long
                       float* log_x, float* log_x0, int* step) {
     MAA_LAUNCH1(ddim_step_kernel, n, xin, per, per_in, eps_u, eps_c, scale, coef, n, x_prev, noise_p, temperature, S, log_x, log_x0,
                 step);
+}
+void launch_ddim_stochastic_encode(const Ctx& ctx, const float* x0, const float* moments, float scale_factor, const float* n_post,
+                                   const int* t, const float* tab, int n_tab, const float* noise, int B, long long per, float* out,
+                                   int* bad) {
+    MAA_CHECK(B > 0 && per > 0 && n_tab > 0, "stochastic_encode: empty problem");
+    MAA_CHECK((moments != nullptr) == (n_post != nullptr) && (moments != nullptr) != (x0 != nullptr),
+              "stochastic_encode: give x0, or the moments and their posterior noise");
+    const long long n = (long long)B * per;
+    auto al16 = [](const void* p) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    const bool vec = per % 4 == 0 && al16(x0) && al16(moments) && al16(n_post) && al16(noise) && al16(out);
+    if (vec) {
+        MAA_LAUNCH1(ddim_stochastic_encode_kernel<4>, n / 4, x0, moments, scale_factor, n_post, t, tab, n_tab, noise, per, n, out, bad);
+    } else {
+        MAA_LAUNCH1(ddim_stochastic_encode_kernel<1>, n, x0, moments, scale_factor, n_post, t, tab, n_tab, noise, per, n, out, bad);
+    }
 }
 
 static std::once_flag g_fir_once[64];      // one upload of the FIR taps per device (thread-safe: contexts on several threads)

@@ -141,5 +141,12 @@ private:
 };
 
 void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x);
+// DDIMSampler.decode (ddim.py:243-261): DDIM indices t_start - 1 .. 0 of the S-step schedule `a` describes; d_noise_p holds t_start
+// draws in loop order
+void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, float* d_x);
+// DDIMSampler.stochastic_encode (ddim.py:227-241) with host tables of n_tab rows; checks every t[b] against n_tab
+void ddim_stochastic_encode(Ctx& ctx, const float* d_x0_or_moments, bool from_moments, float scale_factor, const float* d_noise_post,
+                            const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab, const float* d_noise, int B,
+                            int C, int H, int W, float* d_out);
 
 }  // namespace maa

@@ -26,6 +26,7 @@ discretisation raises NotImplementedError.
 import numpy as np
 import torch
 
+from ..backend import ddim_stochastic_encode
 from ..pipeline import ddim_schedule
 
 
@@ -52,6 +53,10 @@ class DDIMSampler(object):
         rec = (np.float32(1.0) / (np.float32(1.0) - alphas.astype(np.float32))).astype(np.float64)
         self.ddim_sigmas = ddim_eta * np.sqrt((1 - ap64) * rec * (1 - a64 / ap64))
         self.ddim_sqrt_one_minus_alphas = torch.sqrt(1.0 - self.ddim_alphas)
+        # ddim.py:39-40: q(x_t | x_0)'s coefficients over all DDPM steps, numpy's fp32 sqrt of the fp32 alphas_cumprod as there
+        # (torch's CPU sqrt can differ from it in the last bit)
+        self.sqrt_alphas_cumprod = torch.from_numpy(np.sqrt(ac))
+        self.sqrt_one_minus_alphas_cumprod = torch.from_numpy(np.sqrt(np.float32(1.0) - ac))
         if verbose:
             print(f"Selected timesteps for ddim sampler: {steps}")
 
@@ -112,6 +117,57 @@ class DDIMSampler(object):
         # ddim.py:138, 161-163: the start point, then the logged steps
         intermediates = {"x_inter": [x_T] + list(x_log), "pred_x0": [x_T] + list(x0_log)}
         return img, intermediates
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+        """ddim.py:227-241, the first half of an SDEdit edit: x0 noised to DDIM index t (per sample),
+        sqrt(a_t) x0 + sqrt(1 - a_t) noise, in one device kernel (maa_ddim_stochastic_encode).  use_original_steps: t indexes
+        the DDPM steps' sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod instead of the DDIM tables.  noise=None draws
+        randn_like(x0) on the model's device, as the reference.  Needs an earlier make_schedule (or sample): without one the
+        tables are missing and this raises AttributeError, as the reference does."""
+        if use_original_steps:
+            sqrt_a, sqrt_1ma = self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod
+        else:
+            sqrt_a, sqrt_1ma = torch.sqrt(self.ddim_alphas), self.ddim_sqrt_one_minus_alphas
+        x0 = x0.to(device=self.device, dtype=torch.float32)
+        if noise is None:
+            noise = torch.randn_like(x0)
+        return ddim_stochastic_encode(self.model.unet.ctx, x0, t, sqrt_a, sqrt_1ma, noise)
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
+               use_original_steps=False):
+        """ddim.py:243-261, the second half of an SDEdit edit: the DDIM steps of indices t_start - 1 .. 0 from x_latent, on the
+        device (maa_ddim_decode; the step graph of an earlier sample with the same S, shapes and guidance is replayed).  The
+        steps' sigmas are those of the last make_schedule (its eta); as p_sample_ddim does every step whatever sigma is, one
+        noise_like draw per step is made, up front and in loop order, so a seeded caller's generator ends where the reference's
+        does.  t_start slices the schedule as the reference's `timesteps[:t_start]` does.  Needs an earlier make_schedule (or
+        sample), as the reference.
+        use_original_steps=True fails in the reference: p_sample_ddim then reads `model.ddim_sigmas_for_original_num_steps`,
+        which LatentDiffusion never defines (ddpm.py register_schedule), so any call that runs a step raises that
+        AttributeError; it is raised here too."""
+        if use_original_steps:
+            n = len(np.arange(self.ddpm_num_timesteps)[:t_start])
+            if n == 0:
+                return x_latent
+            getattr(self.model, "ddim_sigmas_for_original_num_steps")       # AttributeError, as in the reference
+            raise NotImplementedError("decode(use_original_steps=True) over the DDPM steps is not supported")
+        steps = np.asarray(self.ddim_timesteps)
+        n = len(steps[:t_start])
+        x = x_latent.to(device=self.device, dtype=torch.float32)
+        if n == 0:
+            return x_latent
+        noise_p = torch.stack([torch.randn(x.shape, device=self.device) for _ in range(n)])      # util.py:264-267, per step
+        kw = dict(scale=float(unconditional_guidance_scale))
+        if self.model.conditioning_key == "concat":
+            kw["concat"] = cond
+        else:
+            kw["cond"] = cond
+            kw["uncond"] = unconditional_conditioning
+        sigmas = np.asarray(self.ddim_sigmas, dtype=np.float32)
+        if np.any(sigmas != 0.0):
+            kw.update(sigmas=sigmas, noise_p=noise_p)
+        return self.model.unet.ddim_decode(x, n, steps, self.ddim_alphas.numpy(), self.ddim_alphas_prev, **kw)
 
     def _host_loop(self, cond, x_T, callback, img_callback, quantize_denoised, mask, x0, noise_dropout, temperature,
                    score_corrector, corrector_kwargs, log_every_t, unconditional_guidance_scale, unconditional_conditioning,

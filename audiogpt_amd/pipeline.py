@@ -10,7 +10,8 @@ import torch
 
 from . import config as C
 from . import weights as WT
-from .backend import Context, UNet, VAE, Vocoder
+from ._lib import MaaError
+from .backend import Context, UNet, VAE, Vocoder, ddim_stochastic_encode
 
 
 def make_beta_schedule_linear(timesteps, linear_start, linear_end):
@@ -54,6 +55,7 @@ class MakeAnAudio:
         vocoder_sd = vocoder_sd if vocoder_sd is not None else WT.make_vocoder_state_dict(self.vocoder_cfg, seed=seeds[2])
         self.unet = UNet(self.ctx, self.ldm["unet"], unet_sd)
         self.vae = VAE(self.ctx, self.ldm["vae"], vae_sd)
+        self.has_encoder = any(k.startswith("encoder.") for k in vae_sd)
         self.vocoder = Vocoder(self.ctx, self.vocoder_cfg, vocoder_sd)
         self.scale_factor = float(self.ldm.get("scale_factor", 1.0))
         self.alphas_cumprod = alphas_cumprod_f32(self.ldm["timesteps"], self.ldm["linear_start"], self.ldm["linear_end"])
@@ -87,6 +89,57 @@ class MakeAnAudio:
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             out = self.generate_here(x_T, cond, uncond, scale, S, concat, use_graph)
+        cur.wait_stream(self.stream)
+        for t in out:
+            t.record_stream(cur)
+        return out
+
+    def edit_here(self, mel, cond, uncond=None, scale=1.0, S=100, strength=0.5, noise=None, use_graph=True):
+        """Text-guided editing of an existing recording (SDEdit, Make-An-Audio's img2img form): the mel's latent is noised
+        part of the way down an S-step DDIM schedule and denoised under `cond`.  mel [B, 1, 80, T] in [-1, 1] (as
+        Inpaint.make_batch_sd forms it) -> (wav [B, T*hop], spec [B, 80, T], z [B, 4, 10, T/8]), all on the device, on the
+        CURRENT torch stream (as generate_here).
+        The chain: VAE encode (moments) -> one kernel forming the posterior sample * scale_factor and noising it to DDIM
+        index t_enc = int(strength * S) (DDIMSampler.stochastic_encode) -> the DDIM steps of indices t_enc - 1 .. 0
+        (DDIMSampler.decode) -> VAE decode + clamp -> vocoder.  As in the reference's img2img, the noise level is that of
+        index t_enc and the first denoising step is index t_enc - 1; strength must lie in [0, 1), so that t_enc < S (an
+        S-step schedule has no index S); at t_enc = 0 the latent is noised at index 0 and no step runs.
+        noise: None (the posterior noise, then the q_sample noise, drawn from the model's device generator) or the pair
+        (n_post, n_q), each [B, 4, h, w]."""
+        if not self.has_encoder:
+            raise MaaError("edit: the VAE has no encoder weights -- build MakeAnAudio with with_encoder=True (or a vae_sd with "
+                           "encoder.* / quant_conv.*)")
+        if not 0.0 <= float(strength) < 1.0:
+            raise MaaError("edit: strength must lie in [0, 1), got %r" % (strength,))
+        t_enc = int(float(strength) * S)
+        mel = mel.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        if mel.dim() != 4 or mel.shape[1] != 1:
+            raise MaaError("edit: mel must be [B, 1, n_mels, T], got %s" % (tuple(mel.shape),))
+        moments = self.vae.encode_moments(mel)
+        B, C2, h, w = moments.shape
+        shape = (B, C2 // 2, h, w)
+        if noise is None:
+            n_post = torch.randn(shape, device=self.device)      # posterior.sample() (distributions.py:35)
+            n_q = torch.randn(shape, device=self.device)         # stochastic_encode's randn_like (ddim.py:238-239)
+        else:
+            n_post, n_q = noise
+        steps, a, ap = ddim_schedule(S, self.alphas_cumprod)
+        a_t = torch.from_numpy(a)
+        z_enc = ddim_stochastic_encode(self.ctx, moments, t_enc, torch.sqrt(a_t), torch.sqrt(1.0 - a_t), n_q, moments=True,
+                                       scale_factor=self.scale_factor, noise_post=n_post)
+        z = self.unet.ddim_decode(z_enc, t_enc, steps, a, ap, cond=cond, uncond=uncond, scale=scale, use_graph=use_graph)
+        spec = self.decode(z)
+        return self.vocode(spec), spec, z
+
+    def edit(self, mel, cond, uncond=None, scale=1.0, S=100, strength=0.5, noise=None, use_graph=True):
+        """edit_here with generate()'s stream ordering: with a private stream the work is ordered after the caller's current
+        stream on entry and the caller's stream after it on return."""
+        if self.stream is None:
+            return self.edit_here(mel, cond, uncond, scale, S, strength, noise, use_graph)
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            out = self.edit_here(mel, cond, uncond, scale, S, strength, noise, use_graph)
         cur.wait_stream(self.stream)
         for t in out:
             t.record_stream(cur)

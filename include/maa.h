@@ -190,6 +190,23 @@ typedef struct maa_ddim_args {
 } maa_ddim_args;
 int maa_ddim_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, float* d_x);
 
+/* Text-guided editing (SDEdit): noise an existing latent part of the way, then denoise it under a new prompt.
+ * replaces: DDIMSampler.stochastic_encode (ddim.py:227-241):
+ *   d_out[b] = h_sqrt_a[t[b]] * x0[b] + h_sqrt_1ma[t[b]] * d_noise[b]      over [B, C, H, W]
+ *   d_t [B] device int32, each in [0, n_tab) (checked; an index outside fails the call); h_sqrt_a / h_sqrt_1ma [n_tab] host fp32:
+ *   sqrt(ddim_alphas) and ddim_sqrt_one_minus_alphas, or sqrt_alphas_cumprod and sqrt_one_minus_alphas_cumprod (use_original_steps).
+ *   from_moments = 0: d_x0_or_moments is x0 [B, C, H, W].  from_moments = 1: it is the VAE moments [B, 2C, H, W] (mean | logvar,
+ *   maa_vae_encode_moments) and x0 = scale_factor * (mean + exp(0.5 * clamp(logvar, -30, 20)) * d_noise_post) is formed in the same
+ *   pass (DiagonalGaussianDistribution.sample + get_first_stage_encoding).  Synchronises the context's stream. */
+int maa_ddim_stochastic_encode(maa_ctx* ctx, const float* d_x0_or_moments, int from_moments, float scale_factor,
+                               const float* d_noise_post, const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab,
+                               const float* d_noise, int B, int C, int H, int W, float* d_out);
+/* replaces: DDIMSampler.decode (ddim.py:243-261): args describes the whole S-step schedule as for maa_ddim_sample; the call runs
+ * DDIM indices t_start - 1 .. 0 of it on d_x in place (t_start = 0: d_x unchanged; t_start > S: error).  Guidance, concat
+ * conditioning and eta > 0 (h_sigmas, d_noise_p [t_start][B, C, H, W] in loop order) as for sample; mask / x0 / logs are rejected.
+ * The start index is device state: a decode with the same S, shapes, guidance and buffers as the last sample replays its step graph. */
+int maa_ddim_decode(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, int t_start, float* d_x);
+
 /* ---- VAE ----------------------------------------------------------------------------------------
  * ddconfig of ldm.models.autoencoder.AutoencoderKL (txt2audio_args.yaml:54-68) */
 typedef struct maa_vae_config {
