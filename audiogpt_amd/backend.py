@@ -316,29 +316,45 @@ class UNet:
         mask / x0 / noise_q [S, B, C, H, W] / sqrt_ac, sqrt_1mac [S]: the mask blend of ddim.py:147-150;
         sigmas [S] / noise_p [S, B, C, H, W] / temperature: the eta > 0 noise term of ddim.py:210-225.  Noise tensors
         are in loop order (first step first)."""
+        return self._sample("ddim_sample", self.ctx.lib.maa_ddim_sample, x_T, timesteps, alphas, alphas_prev, cond, uncond, scale,
+                            concat, use_graph, mask, x0, noise_q, sqrt_ac, sqrt_1mac, sigmas, noise_p, temperature, log_every_t)
+
+    def plms_sample(self, x_T, timesteps, alphas, alphas_prev, cond=None, uncond=None, scale=1.0, concat=None,
+                    use_graph=True, mask=None, x0=None, noise_q=None, sqrt_ac=None, sqrt_1mac=None, log_every_t=None):
+        """Whole PLMS trajectory on the device (PLMSSampler.plms_sampling, plms.py:115-236) through maa_ldm_plms_sample:
+        the pseudo improved Euler step, then Adams-Bashforth steps of order up to 4; S steps make S + 1 UNet evaluations.
+        Arguments and return value as ddim_sample's with eta 0 (PLMS has no noise term): the same tables, conditioning,
+        mask / x0 / noise_q [S, B, C, H, W] / sqrt_ac, sqrt_1mac [S] blend before each step's first evaluation, and the logs
+        of the final x_prev / pred_x0 of the logged steps."""
+        return self._sample("plms_sample", self.ctx.lib.maa_ldm_plms_sample, x_T, timesteps, alphas, alphas_prev, cond, uncond,
+                            scale, concat, use_graph, mask, x0, noise_q, sqrt_ac, sqrt_1mac, None, None, 1.0, log_every_t)
+
+    def _sample(self, what, entry, x_T, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, mask, x0, noise_q,
+                sqrt_ac, sqrt_1mac, sigmas, noise_p, temperature, log_every_t):
+        """ddim_sample / plms_sample: the maa_ddim_args of a whole trajectory, the C entry `entry` on them and the logs."""
         dev = self.ctx.device
         x = _f32(x_T, dev).clone()
         keep = []
-        a, B, Cc, H, W = self._ddim_args("ddim_sample", x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep)
+        a, B, Cc, H, W = self._ddim_args(what, x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep)
         S = a.S
 
-        def host_table(v, what):
+        def host_table(v, name):
             t = np.ascontiguousarray(np.asarray(v), dtype=np.float32)
             if t.shape != (S,):
-                raise L.MaaError("ddim_sample: %s must hold one value per DDIM step (%d), got %s" % (what, S, t.shape))
+                raise L.MaaError("%s: %s must hold one value per DDIM step (%d), got %s" % (what, name, S, t.shape))
             keep.append(t)
             return t.ctypes.data_as(C.POINTER(C.c_float))
 
-        def step_noise(v, what):
+        def step_noise(v, name):
             t = _f32(v, dev)
             if tuple(t.shape) != (S, B, Cc, H, W):
-                raise L.MaaError("ddim_sample: %s must be [S=%d, %d, %d, %d, %d], got %s" % (what, S, B, Cc, H, W, tuple(t.shape)))
+                raise L.MaaError("%s: %s must be [S=%d, %d, %d, %d, %d], got %s" % (what, name, S, B, Cc, H, W, tuple(t.shape)))
             keep.append(t)
             return t.data_ptr()
 
         if mask is not None:
             if x0 is None or noise_q is None or sqrt_ac is None or sqrt_1mac is None:
-                raise L.MaaError("ddim_sample: mask needs x0, noise_q and the q_sample tables")      # ddim.py:148 asserts x0
+                raise L.MaaError(what + ": mask needs x0, noise_q and the q_sample tables")      # ddim.py:148 asserts x0
             m = _f32(mask, dev).expand(B, Cc, H, W).contiguous()
             z0 = _f32(x0, dev).expand(B, Cc, H, W).contiguous()
             keep += [m, z0]
@@ -347,7 +363,7 @@ class UNet:
             a.h_sqrt_ac, a.h_sqrt_1mac = host_table(sqrt_ac, "sqrt_ac"), host_table(sqrt_1mac, "sqrt_1mac")
         if sigmas is not None:
             if noise_p is None:
-                raise L.MaaError("ddim_sample: sigmas (eta > 0) need noise_p")
+                raise L.MaaError(what + ": sigmas (eta > 0) need noise_p")
             a.h_sigmas = host_table(sigmas, "sigmas")
             a.d_noise_p = step_noise(noise_p, "noise_p")
         a.temperature = float(temperature)
@@ -367,7 +383,7 @@ class UNet:
             a.log_every_t, a.n_log = int(log_every_t), n_log
             a.d_log_x, a.d_log_x0 = logs[0].data_ptr(), logs[1].data_ptr()
         with self.ctx.lock:
-            L.check(self.ctx.lib.maa_ddim_sample(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
+            L.check(entry(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
             if logs is not None:
                 # the slabs are shared by every call on this model: copy them out before the lock is released, ordered behind the
                 # context's own stream (a private torch stream: copy on it; a library-created blocking stream orders against

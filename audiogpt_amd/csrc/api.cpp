@@ -151,6 +151,7 @@ int maa_ctx_reload_tuning(maa_ctx* ctx) {
         bind(ctx);
         ctx->c.tune.load();
         ctx->c.ddim_graph.clear();      // a kept step graph was captured under the old knobs
+        ctx->c.plms_graph.clear();
     });
 }
 int maa_ctx_synchronize(maa_ctx* ctx) {
@@ -180,8 +181,10 @@ int maa_ctx_set_concurrency(maa_ctx* ctx, int n) {
     return guarded([&] {
         bind(ctx);
         MAA_CHECK(n >= -1 && n != 0, "concurrency: -1 (guess from the live contexts) or the number of contexts kept in flight (>= 1)");
-        if (ctx->c.kept_full() != (n >= 3))
-            ctx->c.ddim_graph.clear();      // the kept step graph was captured under the other arrangement's launches
+        if (ctx->c.kept_full() != (n >= 3)) {
+            ctx->c.ddim_graph.clear();      // the kept step graphs were captured under the other arrangement's launches
+            ctx->c.plms_graph.clear();
+        }
         ctx->c.concurrency = n;
     });
 }
@@ -323,6 +326,16 @@ int maa_ddim_decode(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, int t_
         MAA_CHECK(args->n_log == 0 && !args->d_log_x && !args->d_log_x0, "bad ddim_decode arguments: decode logs no intermediates");
         bind(ctx);
         maa::ddim_decode(ctx->c, *u->m, *args, t_start, d_x);
+    });
+}
+int maa_ldm_plms_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, float* d_x) {
+    return guarded([&] {
+        MAA_CHECK(u && args && d_x && args->h_timesteps && args->h_alphas && args->h_alphas_prev, "bad ldm_plms_sample arguments");
+        MAA_CHECK(args->S > 0 && args->B > 0, "bad ldm_plms_sample arguments: empty problem");
+        MAA_CHECK(!args->h_sigmas && !args->d_noise_p,
+                  "bad ldm_plms_sample arguments: ddim_eta must be 0 for PLMS (h_sigmas and d_noise_p must be NULL)");
+        bind(ctx);
+        maa::ldm_plms_sample(ctx->c, *u->m, *args, d_x);
     });
 }
 

@@ -32,99 +32,116 @@ namespace maa {
 
 namespace {
 
-// The loop body of sample() and decode(): n_steps steps of the S-step schedule `a` describes, from DDIM index `start` down to
-// start - n_steps + 1.  sample() is (S - 1, S); decode(t_start) is (t_start - 1, t_start).  The start only sets the device step
-// index before the first step, so it is not part of the step graph's key: a decode with the same S, shapes, guidance and buffers
-// as the last sample replays the kept graph.  noise_p: the pointer the step kernel indexes as noise_p + (S - 1 - idx) * n.
-void ddim_run(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int start, int n_steps, const float* noise_p, float* d_x) {
-    MAA_CHECK(a.S > 0 && a.B > 0, "ddim: empty problem");
-    MAA_CHECK(start >= 0 && start < a.S && n_steps > 0 && n_steps <= start + 1, "ddim: steps outside the schedule");
-    MAA_CHECK(!a.d_uncond || a.d_cond, "ddim: unconditional conditioning given without conditioning");
-    MAA_CHECK(!a.d_cond || a.L > 0, "ddim: conditioning needs its token count L");
-    MAA_CHECK(!a.d_concat || a.Cc > 0, "ddim: concat conditioning needs its channel count");
-    const bool concat = a.d_concat != nullptr;
-    const bool cfg = !concat && a.d_uncond != nullptr && a.scale != 1.0f;
-    const int nB = cfg ? 2 * a.B : a.B;
-    const int Cin = concat ? a.C + a.Cc : a.C;
-    const long long per = (long long)a.C * a.H * a.W;           // latent elements per sample
-    const long long per_in = (long long)Cin * a.H * a.W;
-    MAA_CHECK(unet.config().in_channels == Cin, "ddim: UNet in_channels does not match latent (+concat) channels");
+// What every device loop over the DDIM tables shares -- DDIM's sample() / decode() and PLMS: the checks of the arguments, the
+// loop's device state in the context's slab (tables, step index, slots, UNet input and output, the latent's and the concat
+// conditioning's copies, the hoisted embeddings), the context projection and the guided forward's arrangement.  The
+// constructor uploads everything and sets the device step index to `start`; prepare() and forward() are the launches of a
+// step up to the UNet's output.
+struct Loop {
+    Ctx& ctx;
+    UNet& unet;
+    const maa_ddim_args& a;
+    bool concat, cfg, masked, logging, emb_hoist, share;
+    int nB, Cin;
+    long long per, per_in;          // latent elements per sample, UNet input elements per sample
+    size_t emb_w;
+    std::vector<float> h_tab;       // (h_tab and h_step are read by async copies: they live until the loop's final synchronisation)
+    int h_step;
+    float *slab, *tab_t, *tab_coef, *cur_t, *cur_coef, *xin, *eps, *xs, *ccs, *emb_tab, *cur_emb;
+    int* d_step;
+    Ctx* lane2;
 
-    // ---- device state of the loop, in one slab the context keeps across calls: tables (one row per DDIM index), the
-    // device step index, the step's timestep / coefficient slots, UNet input and output
-    const bool masked = a.d_mask != nullptr;
-    MAA_CHECK(!masked || (a.d_x0 && a.d_noise_q && a.h_sqrt_ac && a.h_sqrt_1mac), "ddim: mask needs x0, its noise and the q_sample tables");
-    MAA_CHECK(!a.h_sigmas || a.d_noise_p, "ddim: eta > 0 needs the steps' noise");
-    // (noise_p itself may point before the caller's buffer -- decode's offset -- so it is tested through a.d_noise_p only)
-    const bool logging = a.n_log > 0;
-    MAA_CHECK(!logging || (a.d_log_x && a.d_log_x0 && a.log_every_t > 0), "ddim: intermediates need their buffers and log_every_t");
-    std::vector<float> h_tab((size_t)a.S * 9);
-    int n_logged = 0;
-    for (int v = 0; v < a.S; ++v) {                    // visiting order: index S-1 first (ddim.py:143-145)
-        const int i = a.S - 1 - v;
-        h_tab[i] = (float)a.h_timesteps[i];
-        float* cf = &h_tab[(size_t)a.S + (size_t)i * 8];
-        cf[0] = a.h_alphas[i];
-        cf[1] = a.h_alphas_prev[i];
-        cf[2] = a.h_sigmas ? a.h_sigmas[i] : 0.f;      // eta = 0: no noise term
-        cf[3] = std::sqrt(1.0f - a.h_alphas[i]);       // ddim.py:52 (fp32 sqrt of fp32 1-a)
-        cf[4] = masked ? a.h_sqrt_ac[i] : 0.f;
-        cf[5] = masked ? a.h_sqrt_1mac[i] : 0.f;
-        const bool logged = logging && (i % a.log_every_t == 0 || i == a.S - 1);      // ddim.py:161
-        cf[6] = logged ? (float)n_logged++ : -1.f;
-        cf[7] = (float)i;
+    Loop(Ctx& ctx_, UNet& unet_, const maa_ddim_args& a_, int start, const float* d_x) : ctx(ctx_), unet(unet_), a(a_) {
+        MAA_CHECK(!a.d_uncond || a.d_cond, "ddim: unconditional conditioning given without conditioning");
+        MAA_CHECK(!a.d_cond || a.L > 0, "ddim: conditioning needs its token count L");
+        MAA_CHECK(!a.d_concat || a.Cc > 0, "ddim: concat conditioning needs its channel count");
+        concat = a.d_concat != nullptr;
+        cfg = !concat && a.d_uncond != nullptr && a.scale != 1.0f;
+        nB = cfg ? 2 * a.B : a.B;
+        Cin = concat ? a.C + a.Cc : a.C;
+        per = (long long)a.C * a.H * a.W;
+        per_in = (long long)Cin * a.H * a.W;
+        MAA_CHECK(unet.config().in_channels == Cin, "ddim: UNet in_channels does not match latent (+concat) channels");
+
+        // ---- device state of the loop, in one slab the context keeps across calls: tables (one row per DDIM index), the
+        // device step index, the step's timestep / coefficient slots, UNet input and output
+        masked = a.d_mask != nullptr;
+        MAA_CHECK(!masked || (a.d_x0 && a.d_noise_q && a.h_sqrt_ac && a.h_sqrt_1mac), "ddim: mask needs x0, its noise and the q_sample tables");
+        MAA_CHECK(!a.h_sigmas || a.d_noise_p, "ddim: eta > 0 needs the steps' noise");
+        // (noise_p itself may point before the caller's buffer -- decode's offset -- so it is tested through a.d_noise_p only)
+        logging = a.n_log > 0;
+        MAA_CHECK(!logging || (a.d_log_x && a.d_log_x0 && a.log_every_t > 0), "ddim: intermediates need their buffers and log_every_t");
+        h_tab.assign((size_t)a.S * 9, 0.f);
+        int n_logged = 0;
+        for (int v = 0; v < a.S; ++v) {                    // visiting order: index S-1 first (ddim.py:143-145)
+            const int i = a.S - 1 - v;
+            h_tab[i] = (float)a.h_timesteps[i];
+            float* cf = &h_tab[(size_t)a.S + (size_t)i * 8];
+            cf[0] = a.h_alphas[i];
+            cf[1] = a.h_alphas_prev[i];
+            cf[2] = a.h_sigmas ? a.h_sigmas[i] : 0.f;      // eta = 0: no noise term
+            cf[3] = std::sqrt(1.0f - a.h_alphas[i]);       // ddim.py:52 (fp32 sqrt of fp32 1-a)
+            cf[4] = masked ? a.h_sqrt_ac[i] : 0.f;
+            cf[5] = masked ? a.h_sqrt_1mac[i] : 0.f;
+            const bool logged = logging && (i % a.log_every_t == 0 || i == a.S - 1);      // ddim.py:161
+            cf[6] = logged ? (float)n_logged++ : -1.f;
+            cf[7] = (float)i;
+        }
+        MAA_CHECK(!logging || n_logged == a.n_log, "ddim: n_log does not match log_every_t");
+        auto up = [](size_t n) { return (n + 63) / 64 * 64; };      // floats, 256-byte aligned pieces
+        const size_t n_cc = concat ? (size_t)a.B * (per_in - per) : 0;
+        // the ResBlocks' time-embedding rows of all S steps, computed once per call (every sample of a step shares t; the I2A
+        // variant adds the sample's context to the embedding and keeps the per-forward computation): six launches leave every step
+        emb_hoist = !unet.config().add_context_to_emb;
+        emb_w = emb_hoist ? (size_t)unet.emb_width() : 0;
+        const size_t o_tab = 0, o_step = o_tab + up(h_tab.size()), o_t = o_step + 64, o_coef = o_t + up(nB),
+                     o_xin = o_coef + 64, o_eps = o_xin + up((size_t)nB * per_in), o_x = o_eps + up((size_t)nB * per),
+                     o_cc = o_x + up((size_t)a.B * per), o_embt = o_cc + up(n_cc), o_emb = o_embt + up((size_t)a.S * emb_w),
+                     total = o_emb + up(emb_w);
+        slab = static_cast<float*>(ctx.sampler_scratch.get(total * sizeof(float), ctx.stream));
+        tab_t = slab + o_tab, tab_coef = slab + o_tab + a.S, cur_t = slab + o_t, cur_coef = slab + o_coef, xin = slab + o_xin,
+        eps = slab + o_eps, xs = slab + o_x, ccs = slab + o_cc, emb_tab = slab + o_embt, cur_emb = slab + o_emb;
+        // the trajectory runs on the slab's copy of the latent (and of the concat conditioning)
+        MAA_HIP(hipMemcpyAsync(xs, d_x, (size_t)a.B * per * 4, hipMemcpyDeviceToDevice, ctx.stream));
+        if (concat) MAA_HIP(hipMemcpyAsync(ccs, a.d_concat, n_cc * 4, hipMemcpyDeviceToDevice, ctx.stream));
+        d_step = reinterpret_cast<int*>(slab + o_step);
+        MAA_HIP(hipMemcpyAsync(slab + o_tab, h_tab.data(), h_tab.size() * 4, hipMemcpyHostToDevice, ctx.stream));
+        h_step = start;                                  // ddim.py:143-145: flipped timesteps, index = total - i - 1
+        MAA_HIP(hipMemcpyAsync(d_step, &h_step, 4, hipMemcpyHostToDevice, ctx.stream));
+
+        if (emb_hoist) unet.emb_table(ctx, tab_t, a.S, emb_tab);      // (tab_t: the S timesteps as floats, uploaded above)
+
+        // ---- conditioning: constant over the trajectory -> project K/V once
+        if (!concat && a.d_cond) {
+            if (cfg)
+                unet.set_context_cfg(ctx, a.d_uncond, a.d_cond, a.B, a.L);
+            else
+                unet.set_context(ctx, a.d_cond, nB, a.L);
+        }
+
+        // Classifier-free guidance: the reference evaluates the model once on cat([x] * 2) (ddim.py:177-199); the two halves are
+        // independent until the combine, and one batch of 8 prompts leaves much of the chip idle, so the step
+        // forks after the UNet input is built -- the unconditional half on the context's stream, the conditional half on the
+        // second lane's stream and workspace -- and joins before the update kernel.  Captured, the halves are two branches of the
+        // step graph.  Every kernel is batch-invariant bit for bit, so the result equals the one-stream form's.
+        const bool two_lanes = cfg && ctx.split_cfg();
+        lane2 = two_lanes ? &side_lane(ctx) : nullptr;
+        if (lane2 && ctx.prof && !lane2->prof) {
+            lane2->prof = new Profiler;
+            lane2->prof->detail = ctx.prof->detail;
+        }
+        // a guided step's halves are the same tensor up to the first cross-attention: computed once (MAA_CFG_SHARED=0: twice)
+        share = cfg && emb_hoist && ctx.tune.cfg_shared;
     }
-    MAA_CHECK(!logging || n_logged == a.n_log, "ddim: n_log does not match log_every_t");
-    auto up = [](size_t n) { return (n + 63) / 64 * 64; };      // floats, 256-byte aligned pieces
-    const size_t n_cc = concat ? (size_t)a.B * (per_in - per) : 0;
-    // the ResBlocks' time-embedding rows of all S steps, computed once per call (every sample of a step shares t; the I2A variant
-    // adds the sample's context to the embedding and keeps the per-forward computation): six launches leave every step
-    const bool emb_hoist = !unet.config().add_context_to_emb;
-    const size_t emb_w = emb_hoist ? (size_t)unet.emb_width() : 0;
-    const size_t o_tab = 0, o_step = o_tab + up(h_tab.size()), o_t = o_step + 64, o_coef = o_t + up(nB),
-                 o_xin = o_coef + 64, o_eps = o_xin + up((size_t)nB * per_in), o_x = o_eps + up((size_t)nB * per),
-                 o_cc = o_x + up((size_t)a.B * per), o_embt = o_cc + up(n_cc), o_emb = o_embt + up((size_t)a.S * emb_w),
-                 total = o_emb + up(emb_w);
-    float* slab = static_cast<float*>(ctx.sampler_scratch.get(total * sizeof(float), ctx.stream));
-    float *tab_t = slab + o_tab, *tab_coef = slab + o_tab + a.S, *cur_t = slab + o_t, *cur_coef = slab + o_coef,
-          *xin = slab + o_xin, *eps = slab + o_eps, *xs = slab + o_x, *ccs = slab + o_cc, *emb_tab = slab + o_embt,
-          *cur_emb = slab + o_emb;
-    // the trajectory runs on the slab's copy of the latent (and of the concat conditioning)
-    MAA_HIP(hipMemcpyAsync(xs, d_x, (size_t)a.B * per * 4, hipMemcpyDeviceToDevice, ctx.stream));
-    if (concat) MAA_HIP(hipMemcpyAsync(ccs, a.d_concat, n_cc * 4, hipMemcpyDeviceToDevice, ctx.stream));
-    int* d_step = reinterpret_cast<int*>(slab + o_step);
-    const int h_step = start;                          // ddim.py:143-145: flipped timesteps, index = total - i - 1
-    MAA_HIP(hipMemcpyAsync(slab + o_tab, h_tab.data(), h_tab.size() * 4, hipMemcpyHostToDevice, ctx.stream));
-    MAA_HIP(hipMemcpyAsync(d_step, &h_step, 4, hipMemcpyHostToDevice, ctx.stream));
 
-    if (emb_hoist) unet.emb_table(ctx, tab_t, a.S, emb_tab);      // (tab_t: the S timesteps as floats, uploaded above)
-
-    // ---- conditioning: constant over the trajectory -> project K/V once
-    if (!concat && a.d_cond) {
-        if (cfg)
-            unet.set_context_cfg(ctx, a.d_uncond, a.d_cond, a.B, a.L);
-        else
-            unet.set_context(ctx, a.d_cond, nB, a.L);
+    // the step's UNet input (cat([x] * 2) / cat([x, c]), the mask blend) and its timestep / coefficient / embedding slots
+    void prepare() {
+        launch_ddim_prepare(ctx, xs, concat ? ccs : nullptr, a.B, nB, per, per_in - per, tab_t, tab_coef, d_step, xin, cur_t,
+                            cur_coef, a.d_mask, a.d_x0, a.d_noise_q, a.S, emb_hoist ? emb_tab : nullptr, (int)emb_w, cur_emb);
     }
 
-    // Classifier-free guidance: the reference evaluates the model once on cat([x] * 2) (ddim.py:177-199); the two halves are
-    // independent until the combine, and one batch of 8 prompts leaves much of the chip idle, so the step forks
-    // after the UNet input is built -- the unconditional half on the context's stream, the conditional half on the second lane's
-    // stream and workspace -- and joins before the update kernel.  Captured, the halves are two branches of the step graph.
-    // Every kernel is batch-invariant bit for bit, so the result equals the one-stream form's.
-    const bool two_lanes = cfg && ctx.split_cfg();
-    Ctx* lane2 = two_lanes ? &side_lane(ctx) : nullptr;
-    if (lane2 && ctx.prof && !lane2->prof) {
-        lane2->prof = new Profiler;
-        lane2->prof->detail = ctx.prof->detail;
-    }
-
-    // a guided step's halves are the same tensor up to the first cross-attention: computed once (MAA_CFG_SHARED=0: twice)
-    const bool share = cfg && emb_hoist && ctx.tune.cfg_shared;
-    // one step: identical launches on identical addresses whatever the step (the index lives on the device)
-    auto step_body = [&]() {
-        launch_ddim_prepare(ctx, xs, concat ? ccs : nullptr, a.B, nB, per, per_in - per, tab_t, tab_coef, d_step, xin,
-                            cur_t, cur_coef, a.d_mask, a.d_x0, a.d_noise_q, a.S, emb_hoist ? emb_tab : nullptr, (int)emb_w, cur_emb);
+    // eps = UNet(xin, cur_t) over nB rows (with CFG: [uncond ; cond], on one stream or as two lanes)
+    void forward() {
         if (lane2) {
             MAA_HIP(hipEventRecord(ctx.ev_fork, ctx.stream));
             MAA_HIP(hipStreamWaitEvent(lane2->stream, ctx.ev_fork, 0));
@@ -137,15 +154,12 @@ void ddim_run(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int start, int n_ste
         } else
             // (one stream: the halves of cat([x] * 2) share every layer before the first cross-attention -- unet.cpp `dup`)
             unet.forward(ctx, xin, cur_t, unet.context_ptr, nB, a.H, a.W, eps, emb_hoist ? cur_emb : nullptr, -1, share ? 1 : 0);
-        launch_ddim_step(ctx, xin, per, per_in, eps, cfg ? eps + a.B * per : nullptr, a.scale, cur_coef, (long long)a.B * per, xs,
-                         a.h_sigmas ? noise_p : nullptr, a.temperature, a.S, logging ? a.d_log_x : nullptr,
-                         logging ? a.d_log_x0 : nullptr, d_step);
-    };
+    }
 
     // Everything a captured step depends on besides the device-side state it reads: the model and its own buffers, the
     // shapes, the guidance scale, the slab (every slot's offset is a function of the numbers listed) and the workspace.
     // (The workspace base / capacity go in AFTER the first eager step, which may grow it.)
-    auto make_key = [&]() {
+    std::vector<unsigned long long> key(const float* noise_p) const {
         std::vector<unsigned long long> k;
         unet.graph_key(k);
         unsigned scale_bits, temp_bits;
@@ -174,31 +188,54 @@ void ddim_run(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int start, int n_ste
                                      (unsigned long long)(lane2 ? lane2->ws.capacity() : 0)})
             k.push_back(v);
         return k;
+    }
+};
+
+// Captures one call of `body` on the context's stream into sg (instantiated) under `key`.
+template <class F>
+void capture_step(Ctx& ctx, StepGraph& sg, F&& body, std::vector<unsigned long long> key) {
+    MAA_HIP(hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeRelaxed));
+    try {
+        body();
+    } catch (...) {
+        hipGraph_t dead = nullptr;
+        (void)hipStreamEndCapture(ctx.stream, &dead);
+        if (dead) (void)hipGraphDestroy(dead);
+        throw;
+    }
+    MAA_HIP(hipStreamEndCapture(ctx.stream, &sg.graph));
+    MAA_HIP(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
+    sg.key = std::move(key);
+}
+
+// The loop body of sample() and decode(): n_steps steps of the S-step schedule `a` describes, from DDIM index `start` down to
+// start - n_steps + 1.  sample() is (S - 1, S); decode(t_start) is (t_start - 1, t_start).  The start only sets the device step
+// index before the first step, so it is not part of the step graph's key: a decode with the same S, shapes, guidance and buffers
+// as the last sample replays the kept graph.  noise_p: the pointer the step kernel indexes as noise_p + (S - 1 - idx) * n.
+void ddim_run(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int start, int n_steps, const float* noise_p, float* d_x) {
+    MAA_CHECK(a.S > 0 && a.B > 0, "ddim: empty problem");
+    MAA_CHECK(start >= 0 && start < a.S && n_steps > 0 && n_steps <= start + 1, "ddim: steps outside the schedule");
+    Loop lp(ctx, unet, a, start, d_x);
+
+    // one step: identical launches on identical addresses whatever the step (the index lives on the device)
+    auto step_body = [&]() {
+        lp.prepare();
+        lp.forward();
+        launch_ddim_step(ctx, lp.xin, lp.per, lp.per_in, lp.eps, lp.cfg ? lp.eps + a.B * lp.per : nullptr, a.scale, lp.cur_coef,
+                         (long long)a.B * lp.per, lp.xs, a.h_sigmas ? noise_p : nullptr, a.temperature, a.S,
+                         lp.logging ? a.d_log_x : nullptr, lp.logging ? a.d_log_x0 : nullptr, lp.d_step);
     };
 
     StepGraph& sg = ctx.ddim_graph;
     int first = 0;
-    if (a.use_graph && sg.exec && sg.key == make_key()) {
+    if (a.use_graph && sg.exec && sg.key == lp.key(noise_p)) {
         // same step as the last call's: replay from the first step on (the workspace the graph was captured over is still
         // this context's, at the same address and size)
     } else if (a.use_graph) {
         sg.clear();
         step_body();                      // first step eager: sizes the workspace before any capture
         first = 1;
-        if (n_steps > 1) {
-            MAA_HIP(hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeRelaxed));
-            try {
-                step_body();
-            } catch (...) {
-                hipGraph_t dead = nullptr;
-                (void)hipStreamEndCapture(ctx.stream, &dead);
-                if (dead) (void)hipGraphDestroy(dead);
-                throw;
-            }
-            MAA_HIP(hipStreamEndCapture(ctx.stream, &sg.graph));
-            MAA_HIP(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
-            sg.key = make_key();
-        }
+        if (n_steps > 1) capture_step(ctx, sg, step_body, lp.key(noise_p));
     }
     for (int i = first; i < n_steps; ++i) {
 #ifdef MAA_ROCTX
@@ -212,7 +249,7 @@ void ddim_run(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int start, int n_ste
             step_body();
         MAA_RANGE_POP();
     }
-    MAA_HIP(hipMemcpyAsync(d_x, xs, (size_t)a.B * per * 4, hipMemcpyDeviceToDevice, ctx.stream));
+    MAA_HIP(hipMemcpyAsync(d_x, lp.xs, (size_t)a.B * lp.per * 4, hipMemcpyDeviceToDevice, ctx.stream));
     MAA_HIP(hipStreamSynchronize(ctx.stream));   // the host tables go out of scope; the call returns a finished latent
 }
 
@@ -238,6 +275,67 @@ void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, floa
                                                  (uintptr_t)((long long)(a.S - t_start) * n * (long long)sizeof(float)));
     }
     ddim_run(ctx, unet, a, t_start - 1, t_start, noise_p, d_x);
+}
+
+// PLMSSampler.plms_sampling + p_sample_plms (plms.py:115-236) on the DDIM loop's state (Loop above) with sigma = 0 (the
+// reference's noise draws are multiplied by it; the caller makes them) and a ring of three e_t slabs (ldm_plms_* in misc.hip):
+//   step 0 (no history): prepare, eps(x, t), Euler mid-point kernel (e_t -> ring slot 0, the blended x -> the latent slab,
+//     x_mid -> the UNet input, t / embedding slots -> t_next), eps(x_mid, t_next), final kernel (update with (e_t + e_next) / 2);
+//   steps 1 .. S-1: prepare, eps(x, t), one kernel (Adams-Bashforth over the ring, update, logs).
+// Step 0 runs eager (its two forwards size the workspace); the Adams-Bashforth step is captured once into Ctx::plms_graph and
+// replayed: its launches are the same for every step (the ring slot and the order follow from the device index).  The graph is
+// kept across calls under the DDIM loop's key plus the ring's address, apart from the DDIM graph.
+void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
+    MAA_CHECK(a.S > 0 && a.B > 0, "plms: empty problem");
+    MAA_CHECK(!a.h_sigmas && !a.d_noise_p, "plms: ddim_eta must be 0 for PLMS (no sigmas, no step noise)");
+    Loop lp(ctx, unet, a, a.S - 1, d_x);
+    const long long n = (long long)a.B * lp.per;
+    float* ring = static_cast<float*>(ctx.plms_ring.get((size_t)3 * n * sizeof(float), ctx.stream));
+    const float* eps_c = lp.cfg ? lp.eps + n : nullptr;
+    float* log_x = lp.logging ? a.d_log_x : nullptr;
+    float* log_x0 = lp.logging ? a.d_log_x0 : nullptr;
+
+    auto euler_step = [&]() {
+        lp.prepare();
+        lp.forward();
+        launch_ldm_plms_euler_mid(ctx, lp.xin, lp.per, lp.per_in, a.B, lp.nB, lp.eps, eps_c, a.scale, lp.cur_coef, lp.xs, ring,
+                                  lp.tab_t, lp.cur_t, lp.emb_hoist ? lp.emb_tab : nullptr, (int)lp.emb_w, lp.cur_emb);
+        lp.forward();
+        launch_ldm_plms_euler_final(ctx, lp.eps, eps_c, a.scale, lp.cur_coef, n, lp.xs, ring, log_x, log_x0, lp.d_step);
+    };
+    auto ab_step = [&]() {
+        lp.prepare();
+        lp.forward();
+        launch_ldm_plms_step(ctx, lp.xin, lp.per, lp.per_in, lp.eps, eps_c, a.scale, lp.cur_coef, n, lp.xs, ring, a.S, log_x, log_x0,
+                             lp.d_step);
+    };
+
+    MAA_RANGE_PUSH("plms_step 1 (Euler pair)");
+    euler_step();
+    MAA_RANGE_POP();
+    StepGraph& sg = ctx.plms_graph;
+    if (a.use_graph && a.S > 1) {
+        std::vector<unsigned long long> key = lp.key(nullptr);      // (after step 0: the workspace is sized)
+        key.push_back((unsigned long long)reinterpret_cast<uintptr_t>(ring));
+        if (!(sg.exec && sg.key == key)) {
+            sg.clear();
+            capture_step(ctx, sg, ab_step, std::move(key));
+        }
+    }
+    for (int i = 1; i < a.S; ++i) {
+#ifdef MAA_ROCTX
+        char range[48];
+        std::snprintf(range, sizeof(range), "plms_step %d/%d t=%d", i + 1, a.S, (int)a.h_timesteps[a.S - 1 - i]);
+#endif
+        MAA_RANGE_PUSH(range);
+        if (a.use_graph)
+            MAA_HIP(hipGraphLaunch(sg.exec, ctx.stream));
+        else
+            ab_step();
+        MAA_RANGE_POP();
+    }
+    MAA_HIP(hipMemcpyAsync(d_x, lp.xs, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx.stream));
+    MAA_HIP(hipStreamSynchronize(ctx.stream));
 }
 
 // ddim.py:227-241.  The two coefficient tables go up once per call next to an error flag in the context's own slab; the flag is

@@ -165,6 +165,8 @@ struct Ctx {
     StepGraph ddim_graph;
     DevSlab sampler_scratch;  // DDIM loop state (tables, step slots, UNet input, eps): reused by every sample() call
     DevSlab encode_scratch;   // stochastic_encode's coefficient tables and error flag (apart from the loop's slab, whose address the step graph keeps)
+    StepGraph plms_graph;     // the PLMS loop's captured Adams-Bashforth step (steps 1 .. S-1), kept apart from ddim_graph
+    DevSlab plms_ring;        // the PLMS loop's ring of three e_t slabs (apart from sampler_scratch, which keeps DDIM's size)
     Profiler* prof = nullptr;
     float* zeros = nullptr;   // 256 B zero page (device), source of masked tile loads
     int device = 0;
@@ -324,6 +326,20 @@ void launch_ddim_prepare(const Ctx& ctx, const float* x, const float* concat, in
 void launch_ddim_step(const Ctx& ctx, const float* xin, long long per, long long per_in, const float* eps_u, const float* eps_c,
                       float scale, const float* coef, long long n, float* x_prev, const float* noise_p, float temperature, int S,
                       float* log_x, float* log_x0, int* step);
+// PLMSSampler (plms.py:115-236), ldm_plms_* kernels: ring = three [n] slabs of e_t (step i writes slot i % 3).
+// step (steps i >= 1, i = S - 1 - coef[7]): CFG combine, Adams-Bashforth e' of order min(i, 3) + 1, x_prev = update(x from xin, e'),
+// logs as launch_ddim_step, *step = idx - 1
+void launch_ldm_plms_step(const Ctx& ctx, const float* xin, long long per, long long per_in, const float* eps_u, const float* eps_c,
+                          float scale, const float* coef, long long n, float* x_prev, float* ring, int S, float* log_x, float* log_x0,
+                          int* step);
+// step 0 after its first evaluation: e_t -> e_keep, x (first B rows of xin) -> x_save, x_mid = update(x, e_t) -> xin's latent
+// channels of all nB rows, cur_t [nB] / cur_emb to t_next = tab_t[max(idx - 1, 0)] (its hoisted embedding row when emb_tab)
+void launch_ldm_plms_euler_mid(const Ctx& ctx, float* xin, long long per, long long per_in, int B, int nB, const float* eps_u,
+                               const float* eps_c, float scale, const float* coef, float* x_save, float* e_keep, const float* tab_t,
+                               float* cur_t, const float* emb_tab, int emb_w, float* cur_emb);
+// step 0 after its second evaluation: x = update(x, (e_keep + e_next) / 2) in place, logs, *step = idx - 1
+void launch_ldm_plms_euler_final(const Ctx& ctx, const float* eps_u, const float* eps_c, float scale, const float* coef, long long n,
+                                 float* x, const float* e_keep, float* log_x, float* log_x0, int* step);
 // DDIMSampler.stochastic_encode (ddim.py:227-241): out[b] = tab[t[b]] * x0[b] + tab[n_tab + t[b]] * noise[b] over [B, per];
 // moments / n_post instead of x0: x0 = scale_factor * (mean + exp(0.5 clamp(logvar, -30, 20)) * n_post) from the VAE moments
 // [B, 2, per]; t [B] device int32; *bad (device) is set when some t[b] lies outside [0, n_tab)

@@ -361,6 +361,157 @@ __global__ void ddim_stochastic_encode_kernel(const float* __restrict__ x0, cons
     }
 }
 
+// ---- PLMSSampler (plms.py:115-236): the DDIM update with sigma = 0 applied to a combination e' of the step's eps.
+// The loop's state is the DDIM loop's (csrc/ddim.cpp) plus a ring of three [B, per] slabs holding the last first evaluations
+// e_t: step i (i = S - 1 - idx, idx the DDIM index in the coefficient slot) writes its e_t to slot i % 3 and reads h_k, the
+// e_t of step i - k, from slot (i - k) % 3.  Everything follows from the device index, so steps 1 .. S-1 launch the same
+// kernels on the same addresses.  CFG combine as ddim_step_kernel; term order as torch's (-ffp-contract=off), divisions kept.
+// V floats per thread (V = 4: 16-byte accesses; needs per % 4 == 0 and per_in % 4 == 0 so that a vector never straddles two
+// samples).
+
+template <int V>
+__device__ __forceinline__ FVec<V> plms_eps(const float* __restrict__ eu, const float* __restrict__ ec, float scale, long long i) {
+    FVec<V> e = load_v<V>(eu + i);
+    if (ec) {
+        const FVec<V> c = load_v<V>(ec + i);
+#pragma unroll
+        for (int k = 0; k < V; ++k) e.v[k] = e.v[k] + scale * (c.v[k] - e.v[k]);
+    }
+    return e;
+}
+
+// get_x_prev_and_pred_x0 (plms.py:206-222) with sigma = 0: pred_x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t),
+// x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev - 0) e  (the noise term is sigma * z = 0 and is not formed)
+template <int V>
+__device__ __forceinline__ void plms_update(const FVec<V>& x, const FVec<V>& e, float somat, float sqrt_at, float sqrt_ap, float dir,
+                                            FVec<V>& x_prev, FVec<V>& x0) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        x0.v[k] = (x.v[k] - somat * e.v[k]) / sqrt_at;
+        x_prev.v[k] = sqrt_ap * x0.v[k] + dir * e.v[k];
+    }
+}
+
+// Steps i >= 1 (plms.py:226-233): Adams-Bashforth of order min(i, 3) + 1 over e_t and the ring.  x is the (mask-blended)
+// latent in the step's UNet input, as ddim_step_kernel reads it.  h3 and this step's e_t share slot i % 3: each thread reads
+// its h3 element before it writes e_t there, so `ring` is not __restrict__.
+template <int V>
+__global__ void ldm_plms_step_kernel(const float* __restrict__ xin, long long per, long long per_in, const float* __restrict__ eu,
+                                     const float* __restrict__ ec, float scale, const float* __restrict__ coef, long long n,
+                                     float* __restrict__ x_prev, float* ring, int S, float* __restrict__ log_x,
+                                     float* __restrict__ log_x0, int* __restrict__ step) {
+    const int idx = (int)coef[7];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *step = idx - 1;
+    const int i_step = S - 1 - idx;
+    const int order = i_step < 3 ? i_step : 3;
+    float* e_slot = ring + (long long)(i_step % 3) * n;
+    const float* h1 = ring + (long long)((i_step + 2) % 3) * n;
+    const float* h2 = ring + (long long)((i_step + 1) % 3) * n;
+    const float* h3 = e_slot;
+    const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], somat = coef[3];
+    const int slot = (int)coef[6];
+    const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev), dir = sqrtf(1.f - a_prev - sigma * sigma);
+    const long long nv = n / V;
+    for (long long iv = blockIdx.x * (long long)blockDim.x + threadIdx.x; iv < nv; iv += (long long)gridDim.x * blockDim.x) {
+        const long long i = iv * V;
+        const long long b = i / per;
+        const FVec<V> e = plms_eps<V>(eu, ec, scale, i);
+        const FVec<V> x = load_v<V>(xin + b * per_in + (i - b * per));
+        FVec<V> ep;
+        if (order >= 1) {
+            const FVec<V> p1 = load_v<V>(h1 + i);
+            if (order == 1) {
+#pragma unroll
+                for (int k = 0; k < V; ++k) ep.v[k] = (3.f * e.v[k] - p1.v[k]) / 2.f;
+            } else {
+                const FVec<V> p2 = load_v<V>(h2 + i);
+                if (order == 2) {
+#pragma unroll
+                    for (int k = 0; k < V; ++k) ep.v[k] = ((23.f * e.v[k] - 16.f * p1.v[k]) + 5.f * p2.v[k]) / 12.f;
+                } else {
+                    const FVec<V> p3 = load_v<V>(h3 + i);
+#pragma unroll
+                    for (int k = 0; k < V; ++k)
+                        ep.v[k] = (((55.f * e.v[k] - 59.f * p1.v[k]) + 37.f * p2.v[k]) - 9.f * p3.v[k]) / 24.f;
+                }
+            }
+        } else {
+            ep = e;          // (step 0 runs the Euler pair below; never reached from the loop)
+        }
+        store_v<V>(e_slot + i, e);
+        FVec<V> xp, x0;
+        plms_update<V>(x, ep, somat, sqrt_at, sqrt_ap, dir, xp, x0);
+        store_v<V>(x_prev + i, xp);
+        if (slot >= 0 && log_x) {
+            store_v<V>(log_x + (long long)slot * n + i, xp);
+            store_v<V>(log_x0 + (long long)slot * n + i, x0);
+        }
+    }
+}
+
+// Step 0, first half (plms.py:223-225): after the first evaluation, e_t -> ring slot 0, the blended x (first B samples of xin)
+// -> x_save, x_mid = update(e_t) -> the latent channels of xin for all nB rows (the CFG duplicate too; concat channels stay),
+// and the step's timestep / embedding slots move to t_next = tab_t[max(idx - 1, 0)] (plms.py:146: time_range[min(i + 1,
+// len - 1)]) for the second evaluation.  Each thread reads the xin elements it then writes; no other thread reads them.
+template <int V>
+__global__ void ldm_plms_euler_mid_kernel(float* __restrict__ xin, long long per, long long per_in, int B, int nB,
+                                          const float* __restrict__ eu, const float* __restrict__ ec, float scale,
+                                          const float* __restrict__ coef, long long n, float* __restrict__ x_save,
+                                          float* __restrict__ e_keep, const float* __restrict__ tab_t, float* __restrict__ cur_t,
+                                          const float* __restrict__ emb_tab, int emb_w, float* __restrict__ cur_emb) {
+    const int idx = (int)coef[7];
+    const int idx_next = idx > 0 ? idx - 1 : 0;
+    if (blockIdx.x == 0 && threadIdx.x < nB) cur_t[threadIdx.x] = tab_t[idx_next];
+    if (emb_tab)
+        for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < emb_w; k += gridDim.x * blockDim.x)
+            cur_emb[k] = emb_tab[(long long)idx_next * emb_w + k];
+    const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], somat = coef[3];
+    const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev), dir = sqrtf(1.f - a_prev - sigma * sigma);
+    const long long nv = n / V;
+    for (long long iv = blockIdx.x * (long long)blockDim.x + threadIdx.x; iv < nv; iv += (long long)gridDim.x * blockDim.x) {
+        const long long i = iv * V;
+        const long long b = i / per, r = i - b * per;
+        const FVec<V> e = plms_eps<V>(eu, ec, scale, i);
+        store_v<V>(e_keep + i, e);
+        const FVec<V> x = load_v<V>(xin + b * per_in + r);
+        store_v<V>(x_save + i, x);
+        FVec<V> xm, x0;
+        plms_update<V>(x, e, somat, sqrt_at, sqrt_ap, dir, xm, x0);
+        store_v<V>(xin + b * per_in + r, xm);
+        if (nB > B) store_v<V>(xin + (b + B) * per_in + r, xm);
+    }
+}
+
+// Step 0, second half (plms.py:226, 235): e' = (e_t + e_next) / 2 with e_next the second evaluation (CFG-combined), the update
+// from the saved x into x (in place: each thread reads the element it writes), the logs, and the next DDIM index.
+template <int V>
+__global__ void ldm_plms_euler_final_kernel(const float* __restrict__ eu, const float* __restrict__ ec, float scale,
+                                            const float* __restrict__ coef, long long n, float* x, const float* __restrict__ e_keep,
+                                            float* __restrict__ log_x, float* __restrict__ log_x0, int* __restrict__ step) {
+    const int idx = (int)coef[7];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *step = idx - 1;
+    const float a_t = coef[0], a_prev = coef[1], sigma = coef[2], somat = coef[3];
+    const int slot = (int)coef[6];
+    const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev), dir = sqrtf(1.f - a_prev - sigma * sigma);
+    const long long nv = n / V;
+    for (long long iv = blockIdx.x * (long long)blockDim.x + threadIdx.x; iv < nv; iv += (long long)gridDim.x * blockDim.x) {
+        const long long i = iv * V;
+        const FVec<V> en = plms_eps<V>(eu, ec, scale, i);
+        const FVec<V> et = load_v<V>(e_keep + i);
+        const FVec<V> xv = load_v<V>(x + i);
+        FVec<V> ep;
+#pragma unroll
+        for (int k = 0; k < V; ++k) ep.v[k] = (et.v[k] + en.v[k]) / 2.f;
+        FVec<V> xp, x0;
+        plms_update<V>(xv, ep, somat, sqrt_at, sqrt_ap, dir, xp, x0);
+        store_v<V>(x + i, xp);
+        if (slot >= 0 && log_x) {
+            store_v<V>(log_x + (long long)slot * n + i, xp);
+            store_v<V>(log_x0 + (long long)slot * n + i, x0);
+        }
+    }
+}
+
 // UNet input and scalars of one DDIM step, with nothing from the host: idx = *step selects the row of the device
 // tables; xin[b'] = cat(x[b' % B], concat[b' % B]) for b' < nB (nB = 2B duplicates the latents for CFG in the order
 // [uncond ; cond], ddim.py:177-179; concat is the inpaint model's conditioning, ddpm.py:1404-1406).
@@ -630,6 +781,47 @@ void launch_ddim_stochastic_encode(const Ctx& ctx, const float* x0, const float*
         MAA_LAUNCH1(ddim_stochastic_encode_kernel<4>, n / 4, x0, moments, scale_factor, n_post, t, tab, n_tab, noise, per, n, out, bad);
     } else {
         MAA_LAUNCH1(ddim_stochastic_encode_kernel<1>, n, x0, moments, scale_factor, n_post, t, tab, n_tab, noise, per, n, out, bad);
+    }
+}
+
+namespace {
+bool al16(const void* p) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+}  // namespace
+void launch_ldm_plms_step(const Ctx& ctx, const float* xin, long long per, long long per_in, const float* eps_u, const float* eps_c,
+                          float scale, const float* coef, long long n, float* x_prev, float* ring, int S, float* log_x, float* log_x0,
+                          int* step) {
+    MAA_CHECK(per > 0 && n % per == 0, "plms: empty problem");
+    const bool vec = per % 4 == 0 && per_in % 4 == 0 && al16(xin) && al16(eps_u) && al16(eps_c) && al16(x_prev) && al16(ring) &&
+                     al16(log_x) && al16(log_x0);
+    if (vec) {
+        MAA_LAUNCH1(ldm_plms_step_kernel<4>, n / 4, xin, per, per_in, eps_u, eps_c, scale, coef, n, x_prev, ring, S, log_x, log_x0,
+                    step);
+    } else {
+        MAA_LAUNCH1(ldm_plms_step_kernel<1>, n, xin, per, per_in, eps_u, eps_c, scale, coef, n, x_prev, ring, S, log_x, log_x0, step);
+    }
+}
+void launch_ldm_plms_euler_mid(const Ctx& ctx, float* xin, long long per, long long per_in, int B, int nB, const float* eps_u,
+                               const float* eps_c, float scale, const float* coef, float* x_save, float* e_keep, const float* tab_t,
+                               float* cur_t, const float* emb_tab, int emb_w, float* cur_emb) {
+    MAA_CHECK(per > 0 && B > 0 && (nB == B || nB == 2 * B) && nB <= 256, "plms: bad step shape");
+    const long long n = (long long)B * per;
+    const bool vec = per % 4 == 0 && per_in % 4 == 0 && al16(xin) && al16(eps_u) && al16(eps_c) && al16(x_save) && al16(e_keep);
+    if (vec) {
+        MAA_LAUNCH1(ldm_plms_euler_mid_kernel<4>, n / 4, xin, per, per_in, B, nB, eps_u, eps_c, scale, coef, n, x_save, e_keep, tab_t,
+                    cur_t, emb_tab, emb_w, cur_emb);
+    } else {
+        MAA_LAUNCH1(ldm_plms_euler_mid_kernel<1>, n, xin, per, per_in, B, nB, eps_u, eps_c, scale, coef, n, x_save, e_keep, tab_t,
+                    cur_t, emb_tab, emb_w, cur_emb);
+    }
+}
+void launch_ldm_plms_euler_final(const Ctx& ctx, const float* eps_u, const float* eps_c, float scale, const float* coef, long long n,
+                                 float* x, const float* e_keep, float* log_x, float* log_x0, int* step) {
+    MAA_CHECK(n > 0, "plms: empty problem");
+    const bool vec = n % 4 == 0 && al16(eps_u) && al16(eps_c) && al16(x) && al16(e_keep) && al16(log_x) && al16(log_x0);
+    if (vec) {
+        MAA_LAUNCH1(ldm_plms_euler_final_kernel<4>, n / 4, eps_u, eps_c, scale, coef, n, x, e_keep, log_x, log_x0, step);
+    } else {
+        MAA_LAUNCH1(ldm_plms_euler_final_kernel<1>, n, eps_u, eps_c, scale, coef, n, x, e_keep, log_x, log_x0, step);
     }
 }
 

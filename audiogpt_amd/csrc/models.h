@@ -144,6 +144,8 @@ void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x);
 // DDIMSampler.decode (ddim.py:243-261): DDIM indices t_start - 1 .. 0 of the S-step schedule `a` describes; d_noise_p holds t_start
 // draws in loop order
 void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, float* d_x);
+// PLMSSampler.plms_sampling (plms.py:115-236) over the S-step schedule `a` describes (eta 0: no sigmas, no step noise)
+void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x);
 // DDIMSampler.stochastic_encode (ddim.py:227-241) with host tables of n_tab rows; checks every t[b] against n_tab
 void ddim_stochastic_encode(Ctx& ctx, const float* d_x0_or_moments, bool from_moments, float scale_factor, const float* d_noise_post,
                             const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab, const float* d_noise, int B,

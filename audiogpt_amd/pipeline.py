@@ -1,4 +1,4 @@
-"""Make-An-Audio generation pipeline on one MI355X: DDIM (UNet) -> VAE decode -> clamp -> vocoder.
+"""Make-An-Audio generation pipeline on one MI355X: DDIM or PLMS (UNet) -> VAE decode -> clamp -> vocoder.
 
 This is the body of the reference's `T2A.txt2audio` / `I2A.img2audio` / `Inpaint.inpaint`
 (audio-chatgpt.py:158-183, 232-261, 500-528) between conditioning and waveform, run by
@@ -61,10 +61,14 @@ class MakeAnAudio:
         self.alphas_cumprod = alphas_cumprod_f32(self.ldm["timesteps"], self.ldm["linear_start"], self.ldm["linear_end"])
 
     # ---- stages ----------------------------------------------------------------------------------
-    def sample_latents(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True):
+    def sample_latents(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim"):
+        """x_T -> x_0 over the S-step schedule: sampler "ddim" (DDIMSampler, S UNet evaluations) or "plms" (PLMSSampler,
+        S + 1 evaluations)."""
+        if sampler not in ("ddim", "plms"):
+            raise MaaError('sampler must be "ddim" or "plms", got %r' % (sampler,))
         steps, a, ap = ddim_schedule(S, self.alphas_cumprod)
-        return self.unet.ddim_sample(x_T, steps, a, ap, cond=cond, uncond=uncond, scale=scale, concat=concat,
-                                     use_graph=use_graph)
+        run = self.unet.plms_sample if sampler == "plms" else self.unet.ddim_sample
+        return run(x_T, steps, a, ap, cond=cond, uncond=uncond, scale=scale, concat=concat, use_graph=use_graph)
 
     def decode(self, z):
         """decode_first_stage then the tools' clamp((x+1)/2, 0, 1) (audio-chatgpt.py:175-176) -> [B,80,T]."""
@@ -73,22 +77,23 @@ class MakeAnAudio:
     def vocode(self, spec):
         return self.vocoder(spec)[:, 0]
 
-    def generate_here(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True):
+    def generate_here(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim"):
         """generate() on the CURRENT torch stream, which must be this replica's stream when it has one (the caller orders
         inputs and outputs against other streams itself: bench.py's worker threads)."""
-        z = self.sample_latents(x_T, cond, uncond, scale, S, concat, use_graph)
+        z = self.sample_latents(x_T, cond, uncond, scale, S, concat, use_graph, sampler=sampler)
         spec = self.decode(z)
         return self.vocode(spec), spec, z
 
-    def generate(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True):
+    def generate(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim"):
         """x_T [B,4,h,w] -> (wav [B, T*hop], spec [B,80,T], z [B,4,h,w]); all on the device.  With a private stream the
-        work is ordered after the caller's current stream on entry and the caller's stream after it on return."""
+        work is ordered after the caller's current stream on entry and the caller's stream after it on return.
+        sampler: "ddim" or "plms" (sample_latents)."""
         if self.stream is None:
-            return self.generate_here(x_T, cond, uncond, scale, S, concat, use_graph)
+            return self.generate_here(x_T, cond, uncond, scale, S, concat, use_graph, sampler=sampler)
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            out = self.generate_here(x_T, cond, uncond, scale, S, concat, use_graph)
+            out = self.generate_here(x_T, cond, uncond, scale, S, concat, use_graph, sampler=sampler)
         cur.wait_stream(self.stream)
         for t in out:
             t.record_stream(cur)

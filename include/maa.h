@@ -206,6 +206,15 @@ int maa_ddim_stochastic_encode(maa_ctx* ctx, const float* d_x0_or_moments, int f
  * conditioning and eta > 0 (h_sigmas, d_noise_p [t_start][B, C, H, W] in loop order) as for sample; mask / x0 / logs are rejected.
  * The start index is device state: a decode with the same S, shapes, guidance and buffers as the last sample replays its step graph. */
 int maa_ddim_decode(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, int t_start, float* d_x);
+/* replaces: PLMSSampler.sample / plms_sampling / p_sample_plms (Make-An-Audio ldm/models/diffusion/plms.py:115-236): the
+ * pseudo linear multistep trajectory over the S-step schedule args describes, on the device.  Step 0 is the pseudo improved
+ * Euler step (two UNet evaluations: eps(x, t) and eps(x_mid, t_next), t_next the next step's timestep, or t itself at the last
+ * step); steps 1 .. S-1 are Adams-Bashforth of order min(i, 3) + 1 over the first evaluations of the last three steps (one UNet
+ * evaluation each, S + 1 in all).  maa_ddim_args as for maa_ddim_sample (guidance, concat conditioning, mask / x0 before each
+ * step's first evaluation, the logs of the final x_prev / pred_x0), except eta: PLMS requires ddim_eta = 0, so h_sigmas and
+ * d_noise_p must be NULL (the call fails otherwise) and temperature is ignored.  With use_graph, steps 1 .. S-1 are one captured
+ * step replayed, kept on the context apart from maa_ddim_sample's.  (Not the DiffSinger maa_plms_sample below.) */
+int maa_ldm_plms_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, float* d_x);
 
 /* ---- VAE ----------------------------------------------------------------------------------------
  * ddconfig of ldm.models.autoencoder.AutoencoderKL (txt2audio_args.yaml:54-68) */
