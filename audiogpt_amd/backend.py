@@ -184,6 +184,20 @@ class Context:
                                           float(alpha), L.dptr(y)))
         return y
 
+    def op_attention_ex(self, q, ldq, hsq, k, ldk, hsk, v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, out, ldo,
+                        out_split=0, causal=0):
+        """maa_op_attention_ex: the library's internal attention call on device tensors the caller has laid out
+        (q / k / v / out are fp32 device tensors, possibly views into one buffer; pitches and head strides in floats).
+        Writes into `out`; nothing is allocated, copied or checked beyond what the C entry point checks."""
+        for t in (q, k, v, out):
+            assert t.is_cuda and t.dtype == torch.float32, (t.device, t.dtype)
+        L.check(self.lib.maa_op_attention_ex(self.h, C.c_void_p(q.data_ptr()), int(ldq), int(hsq),
+                                             C.c_void_p(k.data_ptr()), int(ldk), int(hsk),
+                                             C.c_void_p(v.data_ptr()), int(ldv), int(hsv), int(B), int(heads), int(dh),
+                                             int(Nq), int(Nk), float(alpha), C.c_void_p(out.data_ptr()), int(ldo),
+                                             int(out_split), int(causal)))
+        return out
+
     def op_conv_transpose1d(self, x, w, b, stride, leaky=0.0):
         x = _f32(x, self.device)
         B, Cin, Ln = x.shape

@@ -701,6 +701,24 @@ int maa_op_attention(maa_ctx* ctx, const float* d_q, const float* d_k, const flo
     });
 }
 
+int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const float* d_k, int ldk, int hsk,
+                        const float* d_v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
+                        float* d_y, int ldo, int out_split, int causal) {
+    return guarded([&] {
+        bind(ctx);
+        MAA_CHECK(d_q && d_k && d_v && d_y, "bad op_attention_ex arguments");
+        MAA_CHECK(B > 0 && heads > 0 && dh > 0 && Nq > 0 && Nk > 0, "bad op_attention_ex sizes");
+        MAA_CHECK(ldq >= dh && ldk >= dh && ldv >= dh && hsq >= 0 && hsk >= 0 && hsv >= 0 && ldo >= heads * dh,
+                  "bad op_attention_ex strides");
+        maa::Ctx& c = ctx->c;
+        maa::run_sized(c, [&] {
+            maa::attention_into(c, d_q, ldq, hsq, d_k, ldk, hsk, d_v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, d_y, ldo,
+                                out_split, causal);
+        });
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
 int maa_op_conv_transpose1d(maa_ctx* ctx, const float* d_x, int B, int Cin, int L, const float* h_w,
                             const float* h_bias, int Cout, int k, int stride, float leaky_slope, float* d_y) {
     return guarded([&] {

@@ -420,6 +420,14 @@ int maa_op_layernorm(maa_ctx* ctx, const float* d_x, int rows, int C, const floa
 /* softmax(alpha * q k^T) v per head; q [B,Nq,heads*dh], k/v [B,Nk,heads*dh] -> y [B,Nq,heads*dh] */
 int maa_op_attention(maa_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int B, int heads, int dh,
                      int Nq, int Nk, float alpha, float* d_y);
+/* The same operator with every argument of the library's internal attention call (tests of the models' layouts):
+ * rows of q [B,Nq,*] / k, v [B,Nk,*] have pitch ld{q,k,v} floats and head h starts at column h*hs{q,k,v} of its
+ * row; y [B,Nq,*] has pitch ldo >= heads*dh and holds heads*dh dense columns.  out_split = 1 writes y as split32
+ * rows (per 32 columns: 32 bf16 high halves, then 32 bf16 low halves; only where the fused kernel runs, an error
+ * elsewhere); causal = 1: query i sees keys 0 .. i (Nq == Nk, an error otherwise). */
+int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const float* d_k, int ldk, int hsk,
+                        const float* d_v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
+                        float* d_y, int ldo, int out_split, int causal);
 /* ConvTranspose1d, d_x [B,Cin,L], torch weight [Cin,Cout,k] on the HOST, padding (k-stride)/2 -> [B,Cout,L*stride] */
 int maa_op_conv_transpose1d(maa_ctx* ctx, const float* d_x, int B, int Cin, int L, const float* h_w,
                             const float* h_bias, int Cout, int k, int stride, float leaky_slope, float* d_y);
