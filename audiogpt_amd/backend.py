@@ -209,6 +209,22 @@ class Context:
                                                  L.dptr(y)))
         return y
 
+    def op_mrf_pair(self, x, w1, b1, d1, slope1, w2=None, b2=None, d2=1, slope2=0.0, out_scale=1.0, out=None):
+        """One MRF residual step through the generators' own dispatch.  x [B,C,L]; w1 / w2 [C,C,k] (w2 None: a ResBlock2 step);
+        returns (c2(leaky(c1(leaky(x, slope1)), slope2)) + x) * out_scale, added to `out` [B,C,L] where one is given."""
+        x = _f32(x, self.device)
+        B, Cc, Ln = x.shape
+        w1t, w1p = L.host_f32(w1)
+        b1t, b1p = L.host_f32(b1) if b1 is not None else (None, None)
+        w2t, w2p = L.host_f32(w2) if w2 is not None else (None, None)
+        b2t, b2p = L.host_f32(b2) if b2 is not None else (None, None)
+        y = _f32(out, self.device).clone() if out is not None else torch.empty_like(x)
+        assert y.shape == x.shape
+        L.check(self.lib.maa_op_mrf_pair(self.h, L.dptr(x), B, Cc, Ln, w1p, b1p, w1.shape[2], int(d1), float(slope1), w2p, b2p,
+                                         w2.shape[2] if w2 is not None else 1, int(d2), float(slope2), float(out_scale),
+                                         int(out is not None), L.dptr(y)))
+        return y
+
     def op_bench_conv(self, B, H, W, Cin, Cout, taps=9, pre_split=True, iters=20):
         """Kernel-only time (ms per launch) of one conv in this context's precision mode, synthetic data."""
         ms = C.c_float()

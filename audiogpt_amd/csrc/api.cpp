@@ -379,10 +379,12 @@ int maa_vae_encode_moments(maa_ctx* ctx, maa_vae* v, const float* d_mel, int B, 
 int maa_vocoder_create(maa_ctx* ctx, const maa_vocoder_config* cfg, const maa_tensor* tensors, int n_tensors,
                        maa_vocoder** out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(cfg && out && cfg->n_upsamples > 0 && cfg->n_upsamples <= 8 && cfg->n_kernels > 0 &&
                       cfg->n_kernels <= 8 && cfg->n_dilations > 0 && cfg->n_dilations <= 8,
                   "bad vocoder config");
+        // (the generator's build refuses these too; here a config it cannot run is refused before the device is touched)
+        for (int i = 0; i < cfg->n_upsamples; ++i) maa::check_convtr_polyphase(cfg->upsample_kernel_sizes[i], cfg->upsample_rates[i]);
+        bind(ctx);
         auto sd = to_state_dict(tensors, n_tensors);
         auto* v = new maa_vocoder;
         v->m.reset(new maa::Vocoder(*cfg, sd, ctx->c.dtype));
@@ -722,8 +724,9 @@ int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const 
 int maa_op_conv_transpose1d(maa_ctx* ctx, const float* d_x, int B, int Cin, int L, const float* h_w,
                             const float* h_bias, int Cout, int k, int stride, float leaky_slope, float* d_y) {
     return guarded([&] {
+        MAA_CHECK(d_x && h_w && h_bias && d_y && B > 0 && Cin > 0 && Cout > 0 && L > 0, "bad op_conv_transpose1d arguments");
+        maa::check_convtr_polyphase(k, stride);
         bind(ctx);
-        MAA_CHECK(d_x && h_w && h_bias && d_y, "bad op_conv_transpose1d arguments");
         OneShot s;
         s.add("w", h_w, {Cin, Cout, k});
         s.add("b", h_bias, {Cout});
@@ -876,6 +879,39 @@ int maa_op_snake_aa(maa_ctx* ctx, const float* d_x, int B, int C, int L, const f
             maa::launch_nchw_to_nhwc(c, d_x, B, C, L, x.p);
             maa::launch_snake_aa(c, x.p, B, L, C, dib, da, y.p);
             maa::launch_nhwc_to_nchw(c, y.p, B, C, L, d_y, C);
+        });
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
+int maa_op_mrf_pair(maa_ctx* ctx, const float* d_x, int B, int C, int L, const float* h_w1, const float* h_b1, int k1, int d1,
+                    float slope1, const float* h_w2, const float* h_b2, int k2, int d2, float slope2, float out_scale,
+                    int accumulate, float* d_out) {
+    return guarded([&] {
+        MAA_CHECK(d_x && h_w1 && d_out && B > 0 && C > 0 && L > 0, "bad op_mrf_pair arguments");
+        MAA_CHECK(k1 >= 1 && (k1 & 1) && d1 >= 1, "op_mrf_pair: k1 must be odd and d1 >= 1 (\"same\" padding)");
+        MAA_CHECK(!h_w2 || (k2 >= 1 && (k2 & 1) && d2 >= 1), "op_mrf_pair: k2 must be odd and d2 >= 1 (\"same\" padding)");
+        bind(ctx);
+        OneShot s;
+        s.add("w1", h_w1, {C, C, 1, k1});
+        if (h_b1) s.add("b1", h_b1, {C});
+        if (h_w2) s.add("w2", h_w2, {C, C, 1, k2});
+        if (h_w2 && h_b2) s.add("b2", h_b2, {C});
+        maa::WeightStore ws(ctx->c.dtype != 0);
+        maa::Ctx& c = ctx->c;
+        maa::PackedW pw1 = ws.pack_conv(s.sd, "w1", h_b1 ? "b1" : "", 1, k1), pw2;
+        if (h_w2) pw2 = ws.pack_conv(s.sd, "w2", h_b2 ? "b2" : "", 1, k2);
+        maa::run_sized(c, [&] {
+            maa::T4 x = maa::alloc_t(c, B, 1, L, C), y = maa::alloc_t(c, B, 1, L, C);
+            maa::launch_nchw_to_nhwc(c, d_x, B, C, L, x.p);
+            if (accumulate) maa::launch_nchw_to_nhwc(c, d_out, B, C, L, y.p);
+            if (h_w2) {      // a ResBlock1 step; the residual is x
+                maa::T4 t1 = maa::alloc_t(c, B, 1, L, C);
+                maa::mrf_pair(c, x, pw1, k1, d1, slope1, pw2, k2, d2, slope2, x.p, out_scale, accumulate, t1, y);
+            } else {         // a ResBlock2 step
+                maa::conv1d_same(c, x, pw1, k1, d1, slope1, x.p, out_scale, accumulate, y);
+            }
+            maa::launch_nhwc_to_nchw(c, y.p, B, C, L, d_out, C);
         });
         MAA_HIP(hipStreamSynchronize(c.stream));
     });

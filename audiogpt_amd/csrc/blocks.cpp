@@ -58,6 +58,48 @@ void conv_into(Ctx& ctx, const T4& x1, const T4* x2, const PackedW& w, const Con
     launch_igemm(ctx, p);
 }
 
+void conv1d_same(Ctx& ctx, const T4& x, const PackedW& w, int k, int dil, float leaky, const float* res, float out_scale,
+                 int accumulate, T4& out) {
+    // narrow stages (C = 32 / 64): input tile staged once in LDS for all taps -- HBM-bound instead of L2-re-read-bound
+    if (x.C == out.C && !x.split && x.H == 1 && x.ld == 0 &&
+        launch_halo_conv1d(ctx, x.p, x.B, x.W, x.C, w, k, dil, leaky != 0.f ? leaky : 1.f, res, out_scale, accumulate, out.p))
+        return;
+    ConvOpt o;
+    o.KH = 1;
+    o.KW = k;
+    o.dil = dil;
+    o.pad = (k * dil - dil) / 2;
+    o.pad_h = 0;
+    if (leaky != 0.f) {
+        o.a_act = 1;
+        o.a_slope = leaky;
+    }
+    o.res = res;
+    o.out_scale = out_scale;
+    o.accumulate = accumulate;
+    conv_into(ctx, x, nullptr, w, o, out);
+}
+
+void mrf_pair(Ctx& ctx, const T4& x, const PackedW& w1, int k1, int d1, float slope1, const PackedW& w2, int k2, int d2,
+              float slope2, const float* res, float out_scale, int accumulate, T4& t1, T4& out) {
+    // narrow stages (C = 32 / 64): the pair in one launch, xt stays in LDS (halo_conv1d.hip)
+    if (!x.split && x.ld == 0 &&
+        launch_halo_pair(ctx, x.p, x.B, x.W, x.C, w1, k1, d1, slope1 != 0.f ? slope1 : 1.f, w2, k2, d2,
+                         slope2 != 0.f ? slope2 : 1.f, res, out_scale, accumulate, out.p))
+        return;
+    conv1d_same(ctx, x, w1, k1, d1, slope1, nullptr, 1.f, 0, t1);
+    conv1d_same(ctx, t1, w2, k2, d2, slope2, res, out_scale, accumulate, out);
+}
+
+void check_convtr_polyphase(int k, int stride) {
+    const std::string at = " (kernel " + std::to_string(k) + ", stride " + std::to_string(stride) + ")";
+    MAA_CHECK(stride >= 1 && k >= stride, "conv-transpose needs stride >= 1 and kernel >= stride" + at);
+    MAA_CHECK(k % stride == 0, "conv-transpose kernel must be a multiple of the stride" + at);
+    MAA_CHECK((k - stride) % 2 == 0, "conv-transpose kernel - stride must be even: padding (kernel - stride) / 2 gives length * stride outputs" + at);
+    MAA_CHECK((stride - 1 + (k - stride) / 2) / stride <= 1,
+              "conv-transpose polyphase carry (stride - 1 + (kernel - stride) / 2) / stride must be 0 or 1" + at);
+}
+
 bool conv_up2_into(Ctx& ctx, const T4& x, const PackedW& w4, T4& out) {
     if (!ctx.tune.up2 || !w4.w || w4.phase_rows == 0 || ctx.dtype == 0 || x.split || x.C % 32 != 0 || x.ld != 0) return false;
     MAA_CHECK(out.B == x.B && out.H == 2 * x.H && out.W == 2 * x.W && out.C == w4.N, "conv_up2: output shape");

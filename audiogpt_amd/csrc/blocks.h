@@ -45,6 +45,18 @@ struct ConvOpt {
 
 // out = conv(x1 ++ x2) with packed weight `w`; output spatial size given by (Ho, Wo)
 void conv_into(Ctx& ctx, const T4& x1, const T4* x2, const PackedW& w, const ConvOpt& o, T4& out);
+// Dilated "same" Conv1d(C, C, k, dilation = dil) on a sequence [B, 1, L, C] with a leaky-ReLU prologue (leaky = 0: none) and the
+// shared epilogue out = (conv + bias + res) * out_scale (+ out): the halo kernel (halo_conv1d.hip) where it accepts the layer,
+// else the implicit GEMM.  The vocoders' MRF convolutions and maa_op_mrf_pair go through this one dispatch.
+void conv1d_same(Ctx& ctx, const T4& x, const PackedW& w, int k, int dil, float leaky, const float* res, float out_scale,
+                 int accumulate, T4& out);
+// One ResBlock1 step, out = (c2(leaky(c1(leaky(x, slope1)), slope2)) + res) * out_scale (+ out): the fused pair kernel where it
+// accepts the layer, else two conv1d_same calls through the scratch tensor t1 (x's shape).
+void mrf_pair(Ctx& ctx, const T4& x, const PackedW& w1, int k1, int d1, float slope1, const PackedW& w2, int k2, int d2,
+              float slope2, const float* res, float out_scale, int accumulate, T4& t1, T4& out);
+// ConvTranspose1d(k, stride, padding = (k - stride) / 2) as the polyphase GEMMs of WeightStore::pack_convtr_phase: throws on a
+// (k, stride) they do not cover -- L * stride output rows and the carry groups 0 and 1 are all that is launched.
+void check_convtr_polyphase(int k, int stride);
 // linear over rows of a [rows, K] matrix (any leading layout, row pitch lda)
 // Upsample (nearest 2x) + conv3x3 as four 2x2 phase convolutions of the low-resolution source (4 / 9 of the multiplications; bf16
 // modes, weights from WeightStore::pack_conv_up2).  false: not applicable here -- the caller runs the 3x3 convolution with ConvOpt::up

@@ -119,6 +119,7 @@ struct Vocoder::Impl {
             u.k = cfg.upsample_kernel_sizes[i];
             u.cin = ch;
             u.cout = ch / 2;
+            check_convtr_polyphase(u.k, u.stride);
             const int pad = (u.k - u.stride) / 2;
             for (int carry = 0; carry < 2; ++carry) {
                 bool any = false;
@@ -190,28 +191,10 @@ struct Vocoder::Impl {
         }
     }
 
-    // dilated "same" conv1d on [B, L, C]
+    // dilated "same" conv1d on [B, L, C] (blocks.cpp: halo kernel where it accepts the layer, else the implicit GEMM)
     void conv1d(Ctx& ctx, const T4& x, const ConvK& c, float leaky, const float* res, float out_scale, int accumulate,
                 T4& out) {
-        // narrow stages (C = 32 / 64): input tile staged once in LDS for all taps -- HBM-bound instead of L2-re-read-bound
-        if (x.C == out.C && !x.split && x.H == 1 && x.ld == 0 &&
-            launch_halo_conv1d(ctx, x.p, x.B, x.W, x.C, c.w, c.k, c.dil, leaky != 0.f ? leaky : 1.f, res, out_scale, accumulate,
-                               out.p))
-            return;
-        ConvOpt o;
-        o.KH = 1;
-        o.KW = c.k;
-        o.dil = c.dil;
-        o.pad = (c.k * c.dil - c.dil) / 2;
-        o.pad_h = 0;
-        if (leaky != 0.f) {
-            o.a_act = 1;
-            o.a_slope = leaky;
-        }
-        o.res = res;
-        o.out_scale = out_scale;
-        o.accumulate = accumulate;
-        conv_into(ctx, x, nullptr, c.w, o, out);
+        conv1d_same(ctx, x, c.w, c.k, c.dil, leaky, res, out_scale, accumulate, out);
     }
 
     // The same conv on a PRE-ACTIVATED, PRE-SPLIT input (split32 lines of leaky(x)): both operands go to LDS by DMA and the
@@ -375,28 +358,22 @@ struct Vocoder::Impl {
                         }
                         continue;
                     }
-                    if (big) {
-                        launch_snake_aa(ctx, cur.p, B, L, u.cout, rb.inv_beta[2 * mth], rb.alpha[2 * mth], act.p);
-                        conv1d(ctx, act, rb.c1[mth], 0.f, nullptr, 1.f, 0, t1);
-                        launch_snake_aa(ctx, t1.p, B, L, u.cout, rb.inv_beta[2 * mth + 1], rb.alpha[2 * mth + 1], act.p);
-                    } else {
-                        // narrow stages (C = 32 / 64): the pair in one launch, xt stays in LDS (halo_conv1d.hip)
+                    if (!big) {
+                        // one launch at the narrow stages (C = 32 / 64), else c1 into t1 and c2 out of it (blocks.cpp mrf_pair)
                         T4& dstp = last ? xs : ((cur.p == bufA.p) ? bufB : bufA);
-                        if (!cur.split && cur.ld == 0 &&
-                            launch_halo_pair(ctx, cur.p, B, L, u.cout, rb.c1[mth].w, rb.c1[mth].k, rb.c1[mth].dil, 0.1f, rb.c2[mth].w,
-                                             rb.c2[mth].k, rb.c2[mth].dil, 0.1f, cur.p, last ? inv_n : 1.f, last ? (j > 0) : 0, dstp.p)) {
-                            if (!last) cur = dstp;
-                            continue;
-                        }
-                        conv1d(ctx, cur, rb.c1[mth], 0.1f, nullptr, 1.f, 0, t1);
+                        mrf_pair(ctx, cur, rb.c1[mth].w, rb.c1[mth].k, rb.c1[mth].dil, 0.1f, rb.c2[mth].w, rb.c2[mth].k,
+                                 rb.c2[mth].dil, 0.1f, cur.p, last ? inv_n : 1.f, last ? (j > 0) : 0, t1, dstp);
+                        if (!last) cur = dstp;
+                        continue;
                     }
-                    const T4& in2 = big ? act : t1;
-                    const float lk2 = big ? 0.f : 0.1f;
+                    launch_snake_aa(ctx, cur.p, B, L, u.cout, rb.inv_beta[2 * mth], rb.alpha[2 * mth], act.p);
+                    conv1d(ctx, act, rb.c1[mth], 0.f, nullptr, 1.f, 0, t1);
+                    launch_snake_aa(ctx, t1.p, B, L, u.cout, rb.inv_beta[2 * mth + 1], rb.alpha[2 * mth + 1], act.p);
                     if (last) {
-                        conv1d(ctx, in2, rb.c2[mth], lk2, cur.p, inv_n, j > 0, xs);
+                        conv1d(ctx, act, rb.c2[mth], 0.f, cur.p, inv_n, j > 0, xs);
                     } else {
                         T4& dst = (cur.p == bufA.p) ? bufB : bufA;
-                        conv1d(ctx, in2, rb.c2[mth], lk2, cur.p, 1.f, 0, dst);
+                        conv1d(ctx, act, rb.c2[mth], 0.f, cur.p, 1.f, 0, dst);
                         cur = dst;
                     }
                 }

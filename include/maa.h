@@ -428,7 +428,9 @@ int maa_op_attention(maa_ctx* ctx, const float* d_q, const float* d_k, const flo
 int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const float* d_k, int ldk, int hsk,
                         const float* d_v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
                         float* d_y, int ldo, int out_split, int causal);
-/* ConvTranspose1d, d_x [B,Cin,L], torch weight [Cin,Cout,k] on the HOST, padding (k-stride)/2 -> [B,Cout,L*stride] */
+/* ConvTranspose1d, d_x [B,Cin,L], torch weight [Cin,Cout,k] on the HOST, padding (k-stride)/2 -> [B,Cout,L*stride].
+ * Runs as polyphase GEMMs and refuses what they do not cover: k a multiple of stride, k - stride even, and
+ * (stride - 1 + (k - stride) / 2) / stride <= 1 (every k = stride, 2 stride, 3 stride with k - stride even passes). */
 int maa_op_conv_transpose1d(maa_ctx* ctx, const float* d_x, int B, int Cin, int L, const float* h_w,
                             const float* h_bias, int Cout, int k, int stride, float leaky_slope, float* d_y);
 /* Kernel-only timing of one 3x3 (taps = 9) or 1x1 (taps = 1) convolution [B,H,W,Cin] -> [B,H,W,Cout] in the
@@ -439,6 +441,14 @@ int maa_op_bench_conv(maa_ctx* ctx, int B, int H, int W, int Cin, int Cout, int 
 /* BigVGAN Activation1d (up2 FIR -> snake(beta) -> down2 FIR) on d_x [B,C,L] */
 int maa_op_snake_aa(maa_ctx* ctx, const float* d_x, int B, int C, int L, const float* h_alpha, const float* h_beta,
                     int logscale, float* d_y);
+/* One residual step of an MRF resblock through the dispatch the generators run (fused pair kernel / halo kernel / implicit
+ * GEMM), d_x [B,C,L], torch Conv1d weights [C,C,k] and biases (or NULL) on the HOST, "same" zero padding, odd kernels:
+ *   ResBlock1 step:          out = (c2(leaky(c1(leaky(x, slope1)), slope2)) + x) * out_scale
+ *   ResBlock2 step (h_w2 NULL): out = (c1(leaky(x, slope1)) + x) * out_scale
+ * slope 0 = no activation.  accumulate = 1 adds the result to what d_out [B,C,L] holds; else d_out is overwritten. */
+int maa_op_mrf_pair(maa_ctx* ctx, const float* d_x, int B, int C, int L, const float* h_w1, const float* h_b1, int k1, int d1,
+                    float slope1, const float* h_w2, const float* h_b2, int k2, int d2, float slope2, float out_scale,
+                    int accumulate, float* d_out);
 
 #ifdef __cplusplus
 }
