@@ -5,11 +5,9 @@
 Objects are cached under audiogpt_amd/csrc/_build keyed by source mtime; the shared object is written
 next to this file so that it travels with the repo snapshot to the GPU box.
 
-Diagnostic variants (tracing / sanitizer rows) are separate libraries beside the product one -- they never
+Diagnostic variants (tracing rows) are separate libraries beside the product one -- they never
 replace it; load one with AUDIOGPT_AMD_LIB=<path>:
     MAA_BUILD_ROCTX=1      libaudiogpt_mi355x_roctx.so      per-DDIM-step roctx ranges (csrc/ddim.cpp) for rocprofv3 --marker-trace
-    MAA_BUILD_ASAN=1       libaudiogpt_mi355x_asan.so       -fsanitize=address on host AND device code (gfx950:xnack+, -O1 -g): run with
-                                                            HSA_XNACK=1 and LD_PRELOAD=$(hipcc -print-file-name=libclang_rt.asan-x86_64.so)
     MAA_BUILD_NO_TUNING=1  libaudiogpt_mi355x_notuning.so   deployment build: the MAA_* test / A-B switches compiled out (runtime.cpp)
 """
 import os
@@ -20,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libaudiogpt_mi355x.so")
-SOURCES = ["igemm_f32.hip", "igemm_bf16.hip", "igemm_dma.hip", "igemm_dma2.hip", "igemm_pp.hip", "calib.hip", "nsf.hip", "diffsinger.hip", "halo_conv1d.hip", "encoders.hip", "spectral.hip", "flash_attn.hip", "norm.hip", "misc.hip", "runtime.cpp", "blocks.cpp", "unet.cpp", "vae.cpp",
+SOURCES = ["igemm_f32.hip", "igemm_bf16.hip", "igemm_dma.hip", "igemm_dma2.hip", "igemm_pp.hip", "calib.hip", "nsf.hip", "diffsinger.hip", "halo_conv1d.hip", "encoders.hip", "spectral.hip", "flash_attn.hip", "norm.hip", "misc.hip", "igemm_dispatch.cpp", "runtime.cpp", "blocks.cpp", "unet.cpp", "vae.cpp",
            "vocoder.cpp", "diffnet.cpp", "encoders.cpp", "clap_audio.cpp", "ddim.cpp", "api.cpp"]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-Wall", "-Wno-unused-function",
@@ -31,11 +29,6 @@ if os.environ.get("MAA_BUILD_ROCTX") == "1":      # per-DDIM-step roctx ranges (
     FLAGS = FLAGS + ["-DMAA_ROCTX"]
     LINK = ["-L/opt/rocm/lib", "-lroctx64"]
     VARIANT += "_roctx"
-if os.environ.get("MAA_BUILD_ASAN") == "1":       # address sanitizer, host and device (the device side needs xnack+ code objects)
-    ARCH = "gfx950:xnack+"
-    FLAGS = ["--offload-arch=" + ARCH, "-O1", "-g"] + FLAGS[2:] + ["-fsanitize=address", "-shared-libsan"]
-    LINK = LINK + ["-fsanitize=address", "-shared-libsan"]
-    VARIANT += "_asan"
 if os.environ.get("MAA_BUILD_NO_TUNING") == "1":  # deployment build: the MAA_* test / A-B switches are compiled out (runtime.cpp)
     FLAGS = FLAGS + ["-DMAA_NO_TUNING"]
     VARIANT += "_notuning"

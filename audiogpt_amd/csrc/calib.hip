@@ -7,12 +7,10 @@
 //   kind 3  128 MiB re-read by the whole grid (past L2, inside the 256 MiB Infinity Cache) -> GB/s out of the fabric side
 //           (kinds 2 and 3, round 4: the boxes that run the short-K / slab kernels 1.5-2x slower have kinds 0 and 1 normal)
 // Not part of the reference's interface; nothing in the product path calls it.
+#include "igemm_device.h"
 #include "maa_internal.h"
 
 namespace maa {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 

@@ -14,16 +14,13 @@
 //                  the k-slot -> key map of the MFMA is free as long as A and B agree, so P never moves between
 //                  lanes; the running rescale exp(m_old - m_new) is one scalar per lane.
 // O^T is transposed through LDS at the end so that the output rows are written as contiguous runs of d.
+#include "igemm_device.h"
 #include "maa_internal.h"
 
 #include <cstdlib>
 
 namespace maa {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct FlashArgs {
     const float *q, *k, *v;
@@ -36,7 +33,7 @@ struct FlashArgs {
     int ldo;
     int out_split;                // write split32 lines (the to_out projection reads them with no conversion)
     int causal;                   // query i sees keys 0 .. i only (OpenCLIP's text tower)
-    int qtiles, xcd_on;           // 128-query tiles per (sample, head); XCD-contiguous work order (maa_internal.h)
+    int qtiles;                   // 128-query tiles per (sample, head)
     long long o_bs;
     const float* zeros;
 };
@@ -83,7 +80,7 @@ __global__ __launch_bounds__(NT, 1) void flash_attn_kernel(const FlashArgs a) {
     const int lq = lane & 31, lh = lane >> 5;
     // work item = ((sample, head), query tile), sample-major; XCD-contiguous: the workgroups of a sample share one XCD, where the
     // q / k / v rows of that sample were written by the projection's tiles and its K / V tiles are fetched into L2 once
-    const int w = xcd_contiguous((int)blockIdx.x, (int)gridDim.x, a.xcd_on);
+    const int w = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
     const int bh = w / a.qtiles, b = bh / a.heads, h = bh - b * a.heads;
     const int q0 = (w - bh * a.qtiles) * 128 + wid * 32;
     const bool wave_live = q0 < a.Nq;          // wave-uniform
@@ -410,7 +407,6 @@ bool launch_flash_attention(const Ctx& ctx, const float* q, int ldq, int hsq, co
     a.o_bs = (long long)Nq * ldo;
     a.zeros = ctx.zeros;
     a.qtiles = (Nq + 127) / 128;
-    a.xcd_on = 1;
     const double flops = 4.0 * B * heads * (double)Nq * Nk * dh;
     const double bytes = 4.0 * B * heads * ((double)2 * Nq * dh + 2.0 * Nk * dh);
     ProfScope prof(ctx, "flash_attention", flops, bytes);

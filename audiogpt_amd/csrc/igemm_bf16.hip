@@ -21,10 +21,6 @@
 
 namespace maa {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int NT = 256;
@@ -49,7 +45,6 @@ __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned&
 // is fp32 and is split while its tile is written to LDS (once per tile, i.e. once per tap and per N-tile for a
 // conv -- which is why producers pre-split).
 __device__ __forceinline__ void st16(unsigned short* dst, const float4& v) {   // 16-byte LDS store, by members
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const f32x4 t = {v.x, v.y, v.z, v.w};
     *reinterpret_cast<f32x4*>(dst) = t;
 }
@@ -81,24 +76,8 @@ __global__ __launch_bounds__(NT) void igemm_bf16_kernel(const IGemm p, int ntile
     extern __shared__ __attribute__((aligned(16))) unsigned short smem[];   // [buf][plane][row][LDK]
 
     const int tid = threadIdx.x;
-    // XCD-aware tile order: workgroup b runs on XCD b % 8 (each XCD has its own 4 MB L2), so consecutive TILES are
-    // handed to the SAME XCD -- the N-tiles of one M-tile and the neighbouring M-tiles (which share A rows through
-    // the conv halo) then hit in one L2 instead of being fetched over the fabric once per XCD.  Bijective for any
-    // grid size; a pure speed choice, results do not depend on placement.
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x, xcd = bid & 7, qq = nblk >> 3, rr = nblk & 7;
-        bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-    }
-    int nt, mt;
-    if (p.m_fastest) {             // an XCD's contiguous range = all M-tiles of a few N-tiles: weights fetched once chip-wide
-        const int mtiles = gridDim.x / ntiles;
-        mt = bid % mtiles;
-        nt = bid / mtiles;
-    } else {
-        nt = bid % ntiles;
-        mt = bid / ntiles;
-    }
+    const int bid = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);      // consecutive tiles (N-tiles fastest) on one XCD: igemm_device.h
+    const int nt = bid % ntiles, mt = bid / ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
     const int z = blockIdx.y;
     const int zo = z / p.zin, zi = z - zo * p.zin;
@@ -355,146 +334,14 @@ void launch_split(const Ctx& ctx, const IGemm& p, int cfg, int Nb) {
         launch_tile<TERMS, false, false, BKT>(ctx, p, cfg, Nb);
 }
 
-template <int TERMS>
-void launch_terms(const Ctx& ctx, const IGemm& p, int cfg, int Nb) {
-    launch_split<TERMS, 32>(ctx, p, cfg, Nb);
-}
-
 }  // namespace
 
-// Returns false when the problem cannot take this path (B not k-contiguous, channel counts that are not a
-// multiple of 32 under a multi-tap gather, unaligned rows): the caller then uses the fp32 kernel.
-bool launch_igemm_bf16(const Ctx& ctx, const IGemm& p, int terms) {
-    if (!p.b_nk) {
-        MAA_CHECK(!p.a_split && !p.b_split, "split operands need the k-contiguous bf16 engine");
-        return false;
-    }
-    const int taps = p.KH * p.KW, Ctot = p.C1 + p.C2;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    constexpr int BK = 32;      // channel granularity of the multi-tap gather (64-deep stages take two taps' worth)
-    bool fast;
-    if (p.a_split) {
-        // split32 lines: whole 32-channel groups, rows pitched like their fp32 form
-        fast = p.C2 == 0 && Ctot % 32 == 0 && p.lda1 % 32 == 0 && al16(p.a1) && p.Z == 1 && p.a_act == 0;
-    } else {
-        fast = (taps == 1 ? (p.C2 == 0 ? (Ctot % 4 == 0 || p.lda1 >= (Ctot + 3) / 4 * 4)
-                                       : (p.C1 % BK == 0 && Ctot % 4 == 0))
-                          : (Ctot % BK == 0 && p.C1 % BK == 0)) &&
-               p.lda1 % 4 == 0 && al16(p.a1) && p.a_so % 4 == 0 && p.a_si % 4 == 0;
-        if (p.C2 > 0) fast = fast && p.lda2 % 4 == 0 && al16(p.a2);
-    }
-    if (p.b_split)
-        fast = fast && p.ldb % 32 == 0 && al16(p.b) && p.K % 32 == 0 && p.ldb >= p.K && p.Z == 1;
+// fp32 or half-split operands (split on the fly), and every bf16 problem under MAA_NO_DMA
+void launch_igemm_bf16_reg(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl) {
+    if (ctx.dtype == 2)
+        launch_split<1, 32>(ctx, p, pl.cfg, pl.Nb);
     else
-        fast = fast && p.ldb % 4 == 0 && al16(p.b) && p.b_so % 4 == 0 && p.b_si % 4 == 0 && p.ldb >= (p.K + 3) / 4 * 4;
-    fast = fast && p.K == taps * Ctot && (p.a_act == 0 || p.a_act == 1);
-    if (!fast) {
-        MAA_CHECK(!p.a_split && !p.b_split, "split operand given to a problem the bf16 engine cannot take");
-        return false;
-    }
-    MAA_CHECK(!(p.c_split || p.c2) || p.N % 32 == 0, "split32 outputs are whole 32-channel lines");
-    const int ncols = p.N * (p.geglu ? 2 : 1);
-    const int Nb = ncols;       // rows of B that exist
-    int cfg;
-    if (p.geglu) {
-        if (ncols % 64 != 0) return false;
-        cfg = 0;
-    } else if (ncols <= 32) {
-        // 256-row tiles; 128-row ones while those would leave most of the chip idle (the UNet's 320 -> 4 output convolution:
-        // 49 workgroups of 90 chunks each).  No K split either way: the two tiles give bit-identical results.
-        cfg = (long long)((p.M + 255) / 256) * p.Z < 128 ? 4 : 3;
-    } else {
-        cfg = choose_tile(p.M, ncols, p.Z, true, ctx.kept_full() ? 1 : 0);
-    }
-    const bool no_dma = ctx.tune.no_dma;      // tests: same arithmetic, register staging
-    // both bf16 modes: split32 x split32 problems go to the LDS-DMA engines (TERMS = 1: the hi halves are the bf16 operands)
-    const bool dma = p.a_split && p.b_split && cfg < 3 && !no_dma;
-    const PPPlan planp = dma ? igemm_pp_plan(ctx, p) : PPPlan();
-    if (planp.bn) {
-        // halo-staged ping-pong engine for the 3x3 convolutions (igemm_pp.hip); slabs borrowed like the second engine's
-        const size_t mk = ctx.ws.mark();
-        const size_t nf = igemm_pp_workspace_floats(p, planp);
-        float* part = nf ? ctx.ws.alloc_f(nf) : nullptr;
-        if (!ctx.ws.dry) {
-            char shapep[64];
-            const char* namep = igemm_pp_name(planp, terms);
-            if (ctx.prof && ctx.prof->detail) {
-                std::snprintf(shapep, sizeof(shapep), "pp%d M%d N%d K%d S%d", planp.bn, p.M, ncols, p.K, planp.S);
-                namep = shapep;
-            }
-            ProfScope profp(ctx, namep, 2.0 * p.M * (double)ncols * p.K, 4.0 * ((double)p.K * ncols + (double)p.M * p.N));
-            launch_igemm_pp(ctx, p, Nb, planp, part);
-            MAA_HIP(hipGetLastError());
-        }
-        ctx.ws.release(mk);
-        return true;
-    }
-    const PPPlan planq = dma && !planp.bn ? igemm_pp1_plan(ctx, p) : PPPlan();
-    if (planq.bn) {
-        const size_t mk = ctx.ws.mark();
-        const size_t nf = igemm_pp1_workspace_floats(p, planq);
-        float* part = nf ? ctx.ws.alloc_f(nf) : nullptr;
-        if (!ctx.ws.dry) {
-            char shapeq[64];
-            const char* nameq = igemm_pp1_name(planq, terms);
-            if (ctx.prof && ctx.prof->detail) {
-                std::snprintf(shapeq, sizeof(shapeq), "pq%d M%d N%d K%d S%d", planq.bn, p.M, ncols, p.K, planq.S);
-                nameq = shapeq;
-            }
-            ProfScope profq(ctx, nameq, 2.0 * p.M * (double)ncols * p.K, 4.0 * ((double)p.K * ncols + (double)p.M * p.N));
-            launch_igemm_pp1(ctx, p, Nb, planq, part);
-            MAA_HIP(hipGetLastError());
-        }
-        ctx.ws.release(mk);
-        return true;
-    }
-    const Dma2Plan plan2 = dma ? igemm_dma2_plan(ctx, p) : Dma2Plan();
-    if (plan2.cfg >= 0) {
-        // wide tiles + split-K; the slabs are borrowed from the arena for the duration of the two launches (stream order
-        // protects them from later borrowers)
-        const size_t mk = ctx.ws.mark();
-        const size_t nf = igemm_dma2_workspace_floats(p, plan2);
-        float* part = nf ? ctx.ws.alloc_f(nf) : nullptr;
-        if (!ctx.ws.dry) {
-            const double flops2 = 2.0 * p.M * (double)ncols * p.K;
-            const double bytes2 = 4.0 * ((double)p.K * ncols + (double)p.M * p.N);
-            char shape2[64];
-            const char* name2 = igemm_dma2_name(plan2, terms);
-            if (ctx.prof && ctx.prof->detail) {
-                std::snprintf(shape2, sizeof(shape2), "b2 M%d N%d K%d t%d", p.M, ncols, p.K, taps);
-                name2 = shape2;
-            }
-            ProfScope prof2(ctx, name2, flops2, bytes2);
-            launch_igemm_dma2(ctx, p, Nb, plan2, part);
-            MAA_HIP(hipGetLastError());
-        }
-        ctx.ws.release(mk);
-        return true;
-    }
-    if (ctx.ws.dry) return true;
-    if (dma) cfg = igemm_dma_tile(p, cfg);
-    const double flops = 2.0 * p.M * (double)ncols * p.K * p.Z;
-    const double bytes = 4.0 * ((double)p.K * ncols + (double)p.M * p.N * p.Z);
-    static const char* kNamesD[3] = {"igemm_dma_bf16x3<128x128>", "igemm_dma_bf16x3<128x64>", "igemm_dma_bf16x3<64x64>"};
-    static const char* kNamesD1[3] = {"igemm_dma_bf16<128x128>", "igemm_dma_bf16<128x64>", "igemm_dma_bf16<64x64>"};
-    static const char* kNames3[5] = {"igemm_bf16x3<128x128>", "igemm_bf16x3<128x64>", "igemm_bf16x3<64x64>", "igemm_bf16x3<256x32>", "igemm_bf16x3<128x32>"};
-    static const char* kNames1[5] = {"igemm_bf16<128x128>", "igemm_bf16<128x64>", "igemm_bf16<64x64>", "igemm_bf16<256x32>", "igemm_bf16<128x32>"};
-    char shape_name[48];
-    const char* pname = dma ? (terms == 3 ? kNamesD[cfg] : kNamesD1[cfg]) : terms == 3 ? kNames3[cfg] : kNames1[cfg];
-    if (ctx.prof && ctx.prof->detail) {
-        std::snprintf(shape_name, sizeof(shape_name), "b%c%d M%d N%d K%d t%d Z%d", dma ? 'd' : 'g', cfg, p.M, ncols, p.K, taps, p.Z);
-        pname = shape_name;
-    }
-    ProfScope prof(ctx, pname, flops, bytes);
-    IGemm q = p;      // (tile order: N-tiles fastest inside an XCD's range -- M-fastest measured +4 % step time and was retired)
-    if (dma)
-        launch_igemm_dma(ctx, q, cfg, Nb);
-    else if (terms == 3)
-        launch_terms<3>(ctx, q, cfg, Nb);
-    else
-        launch_terms<1>(ctx, q, cfg, Nb);
-    MAA_HIP(hipGetLastError());
-    return true;
+        launch_split<3, 32>(ctx, p, pl.cfg, pl.Nb);
 }
 
 }  // namespace maa

@@ -26,20 +26,9 @@
 
 namespace maa {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int NT = 256;
-constexpr int BK = 32;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // TERMS = 3: bf16x3 (lo.hi, hi.lo, hi.hi); TERMS = 1: the context's plain-bf16 mode -- the operands are the hi halves of the
 // same split32 lines (hi = bf16(x) is exactly the rounding that mode asks for), one MFMA per k-step, the lo halves are never read
@@ -56,21 +45,8 @@ __global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
-    // XCD-aware tile order (see igemm_bf16.hip)
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x, xcd = bid & 7, qq = nblk >> 3, rr = nblk & 7;
-        bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-    }
-    int nt, mt;
-    if (p.m_fastest) {             // an XCD's contiguous range = all M-tiles of a few N-tiles: weights fetched once chip-wide
-        const int mtiles = gridDim.x / ntiles;
-        mt = bid % mtiles;
-        nt = bid / mtiles;
-    } else {
-        nt = bid % ntiles;
-        mt = bid / ntiles;
-    }
+    const int bid = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);      // consecutive tiles (N-tiles fastest) on one XCD: igemm_device.h
+    const int nt = bid % ntiles, mt = bid / ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
 
     const int Ctot = p.C1;                     // single split32 source (checked by the launcher)
@@ -257,19 +233,21 @@ void launch_one(const Ctx& ctx, const IGemm& p, int Nb) {
 
 }  // namespace
 
-// cfg: 0 = 128x128, 1 = 128x64, 2 = 64x64: the caller's tile choice passed through igemm_dma_tile().  The caller has
-// checked the split32 conditions (both operands split, single source, C % 32 == 0, K % 32 == 0, 16-byte aligned rows,
-// Z == 1, no A activation).
+// Takes whatever split32 x split32 problem the engines before it in the cascade left (single source, C % 32 == 0, K % 32 == 0,
+// 16-byte aligned rows, Z == 1, no A activation: checked by igemm_plan) on the generic tile choice, 0 = 128x128, 1 = 128x64,
+// 2 = 64x64, with one correction.
 // Measured on the UNet's shapes (profiles/r1_bf16x3_dma_sweep.txt): 128x64 beats 64x64 by ~12 % once it still yields
 // about two workgroups per CU and K is long (the 10x78-resolution convolutions); two LDS stages (more workgroups per
 // CU) beat deeper copy queues except when there is only about one workgroup per CU (the 3x20-resolution layers).
-int igemm_dma_tile(const IGemm& p, int cfg) {
+bool igemm_dma_takes(const Ctx&, const IGemm& p, IGemmPlan& pl) {
     const long long ncols = (long long)p.N * (p.geglu ? 2 : 1);
-    if (cfg == 2 && p.K >= 1024 && ((p.M + 127) / 128) * ((ncols + 63) / 64) >= 448) cfg = 1;
-    return cfg;
+    if (pl.cfg == 2 && p.K >= 1024 && ((p.M + 127) / 128) * ((ncols + 63) / 64) >= 448) pl.cfg = 1;
+    pl.engine = IGemmPlan::DMA;
+    return true;
 }
 
-void launch_igemm_dma(const Ctx& ctx, const IGemm& p, int cfg, int Nb) {
+void launch_igemm_dma(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl) {
+    const int cfg = pl.cfg, Nb = pl.Nb;
     const long long ncols = (long long)p.N * (p.geglu ? 2 : 1);
     // LDS stages: inside the UNet the weights of every layer come cold from HBM (each layer's weights are 3-4x an
     // XCD's L2 and the whole model streams through once per DDIM step), so the deeper copy queue wins there even

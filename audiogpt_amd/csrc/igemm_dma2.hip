@@ -39,29 +39,7 @@
 
 namespace maa {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-constexpr int BK = 32;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// compile-time loop: f(std::integral_constant<int, I>) for I in [0, N) -- indices into register arrays stay literal
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 // TERMS: 3 = bf16x3; 1 = the context's plain-bf16 mode (operands = the hi halves of the same split32 lines, one MFMA per k-step)
 template <int BM, int BN, int WGM, int WGN, int NS, int TERMS>
@@ -90,14 +68,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_dma2_kernel(const IGemm 
     // chunks -- the copies of the next item's first chunks are in flight while this item's epilogue runs, so the cold
     // start (address set-up, first-touch latency of the operands) and the store tail of an item overlap the neighbours'
     // MFMA work instead of adding up per round of workgroups.
-    int w_lo, w_cnt, w_step;
-    {
-        const int G = gridDim.x, xcd = blockIdx.x & 7, qq = items >> 3, rr = items & 7;
-        w_lo = xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq;
-        w_cnt = qq + (xcd < rr ? 1 : 0);
-        w_step = (G - xcd + 7) >> 3;
-    }
-    const int w_first = (int)(blockIdx.x >> 3);
+    const XcdRange wr = xcd_range(items);
+    const int w_lo = wr.lo, w_cnt = wr.cnt, w_step = wr.step, w_first = wr.first;
     if (w_first >= w_cnt) return;              // (never when grid <= items; uniform for the workgroup)
 
     const int Ctot = p.C1;                     // single split32 source (checked by the launcher)
@@ -357,11 +329,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_dma2_kernel(const IGemm 
 // (j, j+1) -- of one tile, so every thread reads back exactly the registers its GEMM twin wrote.
 template <int JW>
 __global__ void splitk_reduce_kernel(const IGemm p, const float* __restrict__ part, int S, int tiles, int ntiles, int Nb,
-                                     int BM, int BN, int WGN, int MI, int NI, int xcd_on) {
+                                     int BM, int BN, int WGN, int MI, int NI) {
     const int NTH = blockDim.x;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int njb = NI / JW, nblk = MI * njb;
-    const int wi = xcd_contiguous((int)blockIdx.x, (int)gridDim.x, xcd_on);      // the blocks of a tile, and neighbouring tiles' rows, on one XCD
+    const int wi = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);      // the blocks of a tile, and neighbouring tiles' rows, on one XCD
     const int tile = wi / nblk, blk = wi - tile * nblk;
     const int i = blk / njb, j = (blk - i * njb) * JW;
     const int mt = tile / ntiles, nt = tile - mt * ntiles;
@@ -389,10 +361,6 @@ __global__ void splitk_reduce_kernel(const IGemm p, const float* __restrict__ pa
     igemm_epilogue<1, JW>(p, acc, mt * BM + wm * WTM + i * 32, nt * BN + wn * WTN + j * 32, lane & 31, lane >> 5, 0, Nb, rpb);
 }
 
-// Persistent grids: at most this many workgroups per CU's worth of LDS, times the CUs.  MAA_DMA2_PERSIST=0 launches one
-// workgroup per work item instead (A/B).
-int cu_count(const Ctx& ctx) { return device_cu_count(ctx.device); }
-
 template <int BM, int BN, int WGM, int WGN, int NS>
 void launch_one(const Ctx& ctx, const IGemm& p, int Nb, int S, float* part) {
     constexpr int NW = WGM * WGN, NTH = 64 * NW;
@@ -410,8 +378,9 @@ void launch_one(const Ctx& ctx, const IGemm& p, int Nb, int S, float* part) {
     const long long items = (long long)tiles * S;
     long long grid = items;
     {
+        // persistent grid: at most what the CUs hold at once
         const int per_cu = (int)(163840 / lds) < 32 / NW ? (int)(163840 / lds) : 32 / NW;      // LDS- and wave-limited residency
-        const long long cap = (long long)cu_count(ctx) * (per_cu < 1 ? 1 : per_cu);
+        const long long cap = (long long)device_cu_count(ctx.device) * (per_cu < 1 ? 1 : per_cu);
         if (grid > cap) grid = cap;
     }
     auto go = [&](auto kern) {
@@ -426,82 +395,52 @@ void launch_one(const Ctx& ctx, const IGemm& p, int Nb, int S, float* part) {
     if (S > 1) launch_splitk_reduce(ctx, p, part, S, tiles, ntiles, Nb, BM, BN, WGN, MI, NI, NTH);
 }
 
-// slices for a K of `nchunks` 32-deep chunks such that no slice is empty: the largest S' <= S with
-// ceil(nchunks / ceil(nchunks / S')) == S'
-int fit_slices(int nchunks, int S) {
-    if (S < 1) S = 1;
-    if (S > nchunks) S = nchunks;
-    for (; S > 1; --S) {
-        const int cps = (nchunks + S - 1) / S;
-        if ((nchunks + cps - 1) / cps == S) break;
-    }
-    return S;
-}
-
-// Which problems take this engine and with how many K slices: a function of the layer (K, packed N) only.
-// MAA_DMA2 = "off" | "0,4,1,S[,kmin[,kmax]]" (tile, stages, pipelining -- one instantiation is kept -- and K slices) overrides
-// the policy for kmin <= K <= kmax (tests; parsed when the context is created).
-Dma2Plan plan_impl(const Ctx& ctx, const IGemm& p) {
-    Dma2Plan pl;
-    const int ncols = p.N * (p.geglu ? 2 : 1);
-    const int nchunks = p.K / BK;
-    const std::string* env = ctx.tune.dma2.empty() ? nullptr : &ctx.tune.dma2;
-    if (env) {
-        if (*env == "off") return pl;
-        int cfg = 0, ns = 4, pipe = 1, S = 1, kmin = 0, kmax = 1 << 30;
-        const int k = std::sscanf(env->c_str(), "%d,%d,%d,%d,%d,%d", &cfg, &ns, &pipe, &S, &kmin, &kmax);
-        if (k >= 4) {      // (format validated by Tuning::load when the context was created)
-            if (p.K < kmin) return pl;
-            if (p.K <= kmax) {
-                pl.cfg = 0;
-                pl.S = fit_slices(nchunks, S);
-                return pl;
-            }
-        }
-    }
-    // default policy (profiles/r2_dma2_sweep*.txt, r2_dma2_inpipe*.txt): long-K contractions only (K >= 2048:
-    // what the ping-pong engine does not take -- ff.net.2 at 5x39, the VAE's wide 3x3 convolutions); 128x128 tiles, four LDS
-    // stages, in-wave pipelined loop; two K slices (more lose to the reduce traffic, fewer leave half the CUs idle at 5x39).
-    if (p.K < 2048 || ncols < 128 || p.geglu) return pl;
-    pl.cfg = 0;
-    pl.S = fit_slices(nchunks, 2);
-    return pl;
-}
-
 }  // namespace
 
 void launch_splitk_reduce(const Ctx& ctx, const IGemm& p, const float* part, int S, int tiles, int ntiles, int Nb, int BM,
                           int BN, int WGN, int MI, int NI, int NTH) {
     if (p.geglu && NI % 2 == 0) {
         hipLaunchKernelGGL(splitk_reduce_kernel<2>, dim3((unsigned)(tiles * MI * (NI / 2))), dim3(NTH), 0, ctx.stream, p, part, S,
-                           tiles, ntiles, Nb, BM, BN, WGN, MI, NI, 1);
+                           tiles, ntiles, Nb, BM, BN, WGN, MI, NI);
         return;
     }
     MAA_CHECK(!p.geglu, "split-K reduce: GEGLU needs value / gate block pairs inside a wave");
     hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3((unsigned)(tiles * MI * NI)), dim3(NTH), 0, ctx.stream, p, part, S, tiles,
-                       ntiles, Nb, BM, BN, WGN, MI, NI, 1);
+                       ntiles, Nb, BM, BN, WGN, MI, NI);
 }
 
-Dma2Plan igemm_dma2_plan(const Ctx& ctx, const IGemm& p) { return plan_impl(ctx, p); }
-
-size_t igemm_dma2_workspace_floats(const IGemm& p, const Dma2Plan& pl) {
-    if (pl.cfg < 0 || pl.S <= 1) return 0;
+// Which problems take this engine and with how many K slices: a function of the layer (K, packed N) only.
+// MAA_DMA2 = "off" | "0,4,1,S[,kmin[,kmax]]" (the first three fields are fixed: one instantiation is kept; S = K slices) overrides
+// the policy for kmin <= K <= kmax (tests; parsed when the context is created).
+bool igemm_dma2_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl) {
     const int ncols = p.N * (p.geglu ? 2 : 1);
-    const long long tiles = (long long)((p.M + 127) / 128) * ((ncols + 127) / 128);
-    return (size_t)(tiles * pl.S * 128 * 128);
+    int S = 0;
+    if (!ctx.tune.dma2.empty()) {
+        if (ctx.tune.dma2 == "off") return false;
+        int cfg = 0, ns = 4, pipe = 1, s = 1, kmin = 0, kmax = 1 << 30;
+        const int k = std::sscanf(ctx.tune.dma2.c_str(), "%d,%d,%d,%d,%d,%d", &cfg, &ns, &pipe, &s, &kmin, &kmax);
+        if (k >= 4) {      // (format validated by Tuning::load when the context was created)
+            if (p.K < kmin) return false;
+            if (p.K <= kmax) S = s < 1 ? 1 : s;
+        }
+    }
+    if (S == 0) {
+        // default policy (profiles/r2_dma2_sweep*.txt, r2_dma2_inpipe*.txt): long-K contractions only (K >= 2048:
+        // what the ping-pong engine does not take -- ff.net.2 at 5x39, the VAE's wide 3x3 convolutions); 128x128 tiles, four LDS
+        // stages, in-wave pipelined loop; two K slices (more lose to the reduce traffic, fewer leave half the CUs idle at 5x39).
+        if (p.K < 2048 || ncols < 128 || p.geglu) return false;
+        S = 2;
+    }
+    pl.engine = IGemmPlan::DMA2;
+    pl.cfg = 0;
+    pl.S = fit_slices(p.K / BK, S);
+    return true;
 }
 
-const char* igemm_dma2_name(const Dma2Plan& pl, int terms) {
-    if (terms == 1) return pl.S > 1 ? "igemm_dma2_bf16<128x128,splitK>" : "igemm_dma2_bf16<128x128>";
-    return pl.S > 1 ? "igemm_dma2_bf16x3<128x128,splitK>" : "igemm_dma2_bf16x3<128x128>";
-}
-
-// The caller has checked the split32 conditions (both operands split, single source, C % 32 == 0, K % 32 == 0, 16-byte
-// aligned rows, Z == 1, no A activation) and provides `part` = igemm_dma2_workspace_floats() floats when that is > 0.
-void launch_igemm_dma2(const Ctx& ctx, const IGemm& p, int Nb, const Dma2Plan& pl, float* part) {
-    MAA_CHECK(pl.cfg == 0, "igemm_dma2: problem not planned for this engine");
+// `part`: pl.slab_floats floats when pl.S > 1
+void launch_igemm_dma2(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
     MAA_CHECK(pl.S == 1 || part != nullptr, "igemm_dma2: split-K needs its slab workspace");
-    launch_one<128, 128, 2, 2, 4>(ctx, p, Nb, pl.S, part);      // 4 waves of 64x64, four LDS stages, in-wave pipelined loop
+    launch_one<128, 128, 2, 2, 4>(ctx, p, pl.Nb, pl.S, part);      // 4 waves of 64x64, four LDS stages, in-wave pipelined loop
 }
 
 }  // namespace maa

@@ -2,11 +2,10 @@
 // for every input dtype on gfx950 (lane l, register r: column l&31, row (r&3) + 8*(r>>2) + 4*(l>>5)), so the
 // fp32 and the bf16-split kernels share this code.
 #pragma once
+#include "igemm_device.h"
 #include "maa_internal.h"
 
 namespace maa {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // erf for the GELU of the GEGLU epilogue: branch-free, ~25 VALU instructions (libm's erff costs ~100 and was a
 // third of the ff.net.0 launch).  |x| < 1: x * P5(x^2); else 1 - exp(-Q7(|x|)) with |x| clamped to 4 (erf = 1 in
@@ -179,7 +178,6 @@ __device__ __forceinline__ void igemm_epilogue_impl(const IGemm& p, f32x16 (&acc
                         const int r = 2 * rp + (even ? 0 : 1);
                         const int m = mb + (r & 3) + 8 * (r >> 2) + 4 * lk;
                         if (m < p.M) {
-                            typedef float f32x2 __attribute__((ext_vector_type(2)));
                             const f32x2 v2 = even ? f32x2{keep, got} : f32x2{got, keep};
                             *reinterpret_cast<f32x2*>(cp + (long long)m * p.ldc + (n & ~1)) = v2;
                         }
@@ -208,7 +206,7 @@ __device__ __forceinline__ void igemm_epilogue_impl(const IGemm& p, f32x16 (&acc
 template <int MI, int NI>
 __device__ __forceinline__ void igemm_epilogue(const IGemm& p, f32x16 (&acc)[MI][NI], int m_base, int n_base, int lrow,
                                                int lk, long long coff, int Nb, int rpb) {
-    const bool pair = !p.no_pair && !p.geglu && !p.c_split && p.c2 == nullptr && (p.N & 1) == 0 && (p.ldc & 1) == 0 && (coff & 1) == 0 &&
+    const bool pair = !p.geglu && !p.c_split && p.c2 == nullptr && (p.N & 1) == 0 && (p.ldc & 1) == 0 && (coff & 1) == 0 &&
                       (reinterpret_cast<uintptr_t>(p.c) & 7) == 0;
     if (pair)
         igemm_epilogue_impl<MI, NI, true>(p, acc, m_base, n_base, lrow, lk, coff, Nb, rpb);

@@ -16,15 +16,14 @@
 // Pipeline: global -> registers two K-chunks ahead (two register sets) -> LDS double buffer, one barrier per
 // 16-deep chunk.  The gather state (row pointers, validity) is recomputed only when the tap changes, so the
 // steady-state loop is loads + LDS traffic + MFMA with no integer division or 64-bit multiplies.
+#include "igemm_device.h"
 #include "maa_internal.h"
 
 namespace maa {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
 
-constexpr int BK = 16;
+constexpr int BK16 = 16;      // K depth of one LDS stage (the bf16 engines' BK is 32)
 constexpr int NT = 256;
 
 // GENERIC = true: per-element gather for convs whose channel count is not a multiple of 16 (first convs with
@@ -39,20 +38,12 @@ __global__ __launch_bounds__(NT) void igemm_f32_kernel(const IGemm p, int ntiles
     constexpr int BL = (BN * 4 + NT - 1) / NT;        // float4 of B per thread per chunk
     static_assert(WGM * WGN == 4, "4 waves");
     static_assert(BM % 64 == 0, "BM");
-    __shared__ __attribute__((aligned(16))) float smem[2 * BK * LDA + 2 * BK * LDB];
+    __shared__ __attribute__((aligned(16))) float smem[2 * BK16 * LDA + 2 * BK16 * LDB];
     float* As = smem;
-    float* Bs = smem + 2 * BK * LDA;
+    float* Bs = smem + 2 * BK16 * LDA;
 
     const int tid = threadIdx.x;
-    // XCD-aware tile order: workgroup b runs on XCD b % 8 (each XCD has its own 4 MB L2), so consecutive TILES are
-    // handed to the SAME XCD -- the N-tiles of one M-tile and the neighbouring M-tiles (which share A rows through
-    // the conv halo) then hit in one L2 instead of being fetched over the fabric once per XCD.  Bijective for any
-    // grid size; a pure speed choice, results do not depend on placement.
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x, xcd = bid & 7, qq = nblk >> 3, rr = nblk & 7;
-        bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-    }
+    const int bid = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);      // consecutive tiles (N-tiles fastest) on one XCD: igemm_device.h
     const int nt = bid % ntiles, mt = bid / ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
     const int z = blockIdx.y;
@@ -125,7 +116,7 @@ __global__ __launch_bounds__(NT) void igemm_f32_kernel(const IGemm p, int ntiles
                 // (the activation is applied when the tile is written to LDS: the loaded value is not used
                 //  here, so the load stays in flight across the MFMA block)
             }
-            g_ci += BK;
+            g_ci += BK16;
             if (g_ci >= Ctot && g_tap + 1 < taps) {
                 g_ci = 0;
                 ++g_tap;
@@ -170,7 +161,7 @@ __global__ __launch_bounds__(NT) void igemm_f32_kernel(const IGemm p, int ntiles
             const int idx = tid + NT * j;
             const int kr = idx / (BN / 4), nq = idx - kr * (BN / 4);
             const int n = n0 + nq * 4;
-            b_ok[j] = kr < BK && n < Nb;
+            b_ok[j] = kr < BK16 && n < Nb;
             b_ptr[j] = bp + (long long)kr * p.ldb + (b_ok[j] ? n : 0);
         }
     }
@@ -189,8 +180,8 @@ __global__ __launch_bounds__(NT) void igemm_f32_kernel(const IGemm p, int ntiles
     };
 
     auto store_tiles = [&](const float4 (&ra)[AL], const float4 (&rb)[BL], int buf) {
-        float* A = As + buf * BK * LDA;
-        float* B = Bs + buf * BK * LDB;
+        float* A = As + buf * BK16 * LDA;
+        float* B = Bs + buf * BK16 * LDB;
 #pragma unroll
         for (int j = 0; j < AL; ++j) {
             const int row = (tid >> 2) + 64 * j;
@@ -215,7 +206,7 @@ __global__ __launch_bounds__(NT) void igemm_f32_kernel(const IGemm p, int ntiles
             for (int j = 0; j < BL; ++j) {
                 const int idx = tid + NT * j;
                 const int kr = idx / (BN / 4), nq = idx - kr * (BN / 4);
-                if (kr < BK) *reinterpret_cast<float4*>(&B[kr * LDB + nq * 4]) = rb[j];
+                if (kr < BK16) *reinterpret_cast<float4*>(&B[kr * LDB + nq * 4]) = rb[j];
             }
         }
     };
@@ -235,10 +226,10 @@ __global__ __launch_bounds__(NT) void igemm_f32_kernel(const IGemm p, int ntiles
     const int a_base = wm * WTM + lrow, b_base = wn * WTN + lrow;
 
     auto compute = [&](int buf) {
-        const float* A = As + buf * BK * LDA;
-        const float* B = Bs + buf * BK * LDB;
+        const float* A = As + buf * BK16 * LDA;
+        const float* B = Bs + buf * BK16 * LDB;
 #pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
+        for (int kk = 0; kk < BK16; kk += 2) {
             float av[MI], bv[NI];
 #pragma unroll
             for (int i = 0; i < MI; ++i) av[i] = A[(kk + lk) * LDA + a_base + i * 32];
@@ -253,27 +244,27 @@ __global__ __launch_bounds__(NT) void igemm_f32_kernel(const IGemm p, int ntiles
     };
 
     // ---- main loop: register sets R0/R1 hold chunks c+1 / c+2 while chunk c is computed from LDS
-    const int nchunks = (p.K + BK - 1) / BK;
+    const int nchunks = (p.K + BK16 - 1) / BK16;
     float4 ra0[AL], rb0[BL], ra1[AL], rb1[BL];
     if constexpr (!GENERIC) set_tap(0);
     load_a(ra0, 0);
     load_b(rb0, 0);
-    load_a(ra1, BK);
-    load_b(rb1, BK);
+    load_a(ra1, BK16);
+    load_b(rb1, BK16);
     store_tiles(ra0, rb0, 0);
     __syncthreads();
     // The loop body is branch-free: chunks past K load zeros (and add nothing), so an odd chunk count costs
     // one empty MFMA block instead of a data-dependent exit in the middle of the pipeline.
     for (int c = 0; c < nchunks; c += 2) {
         // even step: chunk c in LDS buf 0, chunk c+1 in R1, R0 free -> prefetch chunk c+2
-        load_a(ra0, (c + 2) * BK);
-        load_b(rb0, (c + 2) * BK);
+        load_a(ra0, (c + 2) * BK16);
+        load_b(rb0, (c + 2) * BK16);
         compute(0);
         store_tiles(ra1, rb1, 1);
         __syncthreads();
         // odd step: chunk c+1 in LDS buf 1, chunk c+2 in R0, R1 free -> prefetch chunk c+3
-        load_a(ra1, (c + 3) * BK);
-        load_b(rb1, (c + 3) * BK);
+        load_a(ra1, (c + 3) * BK16);
+        load_b(rb1, (c + 3) * BK16);
         compute(1);
         store_tiles(ra0, rb0, 0);
         __syncthreads();
@@ -390,79 +381,15 @@ void launch_cfg(const Ctx& ctx, const IGemm& p, bool generic, int Nb) {
     }
 }
 
-inline double tile_cost(long long M, long long N, int Z, int BM, int BN, double eff) {
-    const long long blocks = ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * Z;
-    const long long rounds = (blocks + 255) / 256;
-    return (double)rounds * BM * BN / eff;
-}
-
 }  // namespace
 
-void launch_igemm(const Ctx& ctx, const IGemm& p_in) {
-    IGemm p = p_in;
-    p.zeros = ctx.zeros;
-    p.no_pair = 0;
-    MAA_CHECK(p.zeros != nullptr, "context has no zero page");
-    // precision mode of the context: 1 = bf16x3 split, 2 = plain bf16 operands; problems the bf16 engine cannot
-    // take (B not k-contiguous, odd channel counts) run on the exact-fp32 kernel below.  (launch_igemm_bf16 also runs
-    // in the workspace dry run: its split-K slabs come from the arena.)
-    if (ctx.dtype == 1 && launch_igemm_bf16(ctx, p, 3)) return;
-    if (ctx.dtype == 2 && launch_igemm_bf16(ctx, p, 1)) return;
-    if (ctx.ws.dry) return;
-    MAA_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "empty igemm");
-    MAA_CHECK(!p.c_split, "split32 output asked of a problem only the fp32 engine can take");
-    const int taps = p.KH * p.KW, Ctot = p.C1 + p.C2;
-    MAA_CHECK(p.K <= taps * Ctot && p.K > (taps - 1) * Ctot, "igemm K mismatch");
-    MAA_CHECK(p.a_act == 0 || p.a_act == 1, "igemm A activation");
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    // fast gather: 16-channel chunks never straddle a tap or a source, float4 loads are aligned
-    // (single source, K % 4 != 0: the last float4 over-reads up to 3 floats of the same row, which must exist
-    //  and be finite -- e.g. the zeroed padding columns of the attention scores; they meet zero rows of B)
-    bool fast = (taps == 1 ? (p.C2 == 0 ? (Ctot % 4 == 0 || p.lda1 >= (Ctot + 3) / 4 * 4)
-                                        : (p.C1 % BK == 0 && Ctot % 4 == 0))
-                           : (Ctot % BK == 0 && p.C1 % BK == 0)) &&
-                p.lda1 % 4 == 0 && al16(p.a1) && p.a_so % 4 == 0 && p.a_si % 4 == 0;
-    if (p.C2 > 0) fast = fast && p.lda2 % 4 == 0 && al16(p.a2);
-    if (p.Z > 1) MAA_CHECK(p.C2 == 0, "batched igemm takes one A source");
-    MAA_CHECK(fast || p.K == taps * Ctot, "padded K needs the aligned gather");
-    // columns that may be read from B: packed weights are zero-padded to a multiple of 32
-    const int ncols = p.N * (p.geglu ? 2 : 1);
-    int Nb = ncols;
-    MAA_CHECK(p.ldb % 4 == 0 && al16(p.b) && p.b_so % 4 == 0 && p.b_si % 4 == 0, "B operand alignment");
-    if (!p.b_nk) {
-        Nb = (ncols + 3) / 4 * 4;
-        if (Nb > p.ldb) Nb = p.ldb / 4 * 4;
-    } else {
-        MAA_CHECK(p.ldb >= (p.K + 3) / 4 * 4, "B [N][K] rows must be padded to a multiple of 4");
+void launch_igemm_f32(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl) {
+    switch (pl.cfg) {
+        case 0: launch_cfg<128, 128, 2, 2>(ctx, p, !pl.fast, pl.Nb); break;
+        case 1: launch_cfg<128, 64, 2, 2>(ctx, p, !pl.fast, pl.Nb); break;
+        case 2: launch_cfg<64, 64, 2, 2>(ctx, p, !pl.fast, pl.Nb); break;
+        default: launch_cfg<256, 32, 4, 1>(ctx, p, !pl.fast, pl.Nb); break;
     }
-    // algorithmic work of this launch: 2*M*N*K per batch entry (GEGLU computes 2N columns)
-    const double flops = 2.0 * p.M * (double)ncols * p.K * p.Z;
-    const double bytes = 4.0 * ((double)p.K * ncols + (double)p.M * p.N * p.Z);   // weights once + output once
-    int cfg = 0;
-    if (p.geglu) {
-        MAA_CHECK(ncols % 64 == 0, "geglu needs packed N multiple of 64");
-        cfg = 0;
-    } else if (ncols <= 32) {
-        cfg = 3;
-    } else {
-        cfg = choose_tile(p.M, ncols, p.Z, false);
-    }
-    static const char* kNames[4] = {"igemm_f32<128x128>", "igemm_f32<128x64>", "igemm_f32<64x64>", "igemm_f32<256x32>"};
-    char shape_name[48];
-    const char* pname = kNames[cfg];
-    if (ctx.prof && ctx.prof->detail) {
-        std::snprintf(shape_name, sizeof(shape_name), "ig%d M%d N%d K%d t%d Z%d%s", cfg, p.M, ncols, p.K, taps, p.Z,
-                      p.b_nk ? "T" : "");
-        pname = shape_name;
-    }
-    ProfScope prof(ctx, pname, flops, bytes);
-    switch (cfg) {
-        case 0: launch_cfg<128, 128, 2, 2>(ctx, p, !fast, Nb); break;
-        case 1: launch_cfg<128, 64, 2, 2>(ctx, p, !fast, Nb); break;
-        case 2: launch_cfg<64, 64, 2, 2>(ctx, p, !fast, Nb); break;
-        default: launch_cfg<256, 32, 4, 1>(ctx, p, !fast, Nb); break;
-    }
-    MAA_HIP(hipGetLastError());
 }
 
 }  // namespace maa

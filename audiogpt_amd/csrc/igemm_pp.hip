@@ -37,31 +37,12 @@
 
 namespace maa {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr int BK = 32;          // channels per chunk = one split32 line
 constexpr int BM = 256;         // output rows per workgroup
 constexpr int NSB = 3;          // weight ring
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 struct PPArgs {
     int W, H;            // image width / height (stride 1, "same" padding: output = input geometry; 1-D: H = 1, W = L)
@@ -77,10 +58,9 @@ struct PPArgs {
     int Nb;              // rows of the packed weight that exist
     float* part;         // split-K slabs or null
     int S, tile_major;   // K slices; 1: the slices of a tile are neighbours in the item order (one XCD writes a tile's slabs, the XCD
-                         // whose reduce blocks read them and whose rows the consumer reads: xcd_contiguous, maa_internal.h), 0: slice-major
+                         // whose reduce blocks read them and whose rows the consumer reads: xcd_contiguous, igemm_device.h), 0: slice-major
     int tiles_pp;        // UP2: tiles of ONE phase (items = 4 phases x tiles_pp); phase = (py, px) of the 2x-upsampled output pixel
     long long b_phase;   // UP2: floats between the packed weights of consecutive phases
-    int dbg;             // TUNE instantiation only (MAA_PP_DBG): 1 no MFMAs, 2 no copies after the prologue, 4 no fragment reads, 8 no vmcnt wait
 };
 
 // MI x NI fragments of 32x32 per wave; a group's 128 x BN block is GWM x GWN waves (GWM GWN = 4, GWM 32 MI = 128)
@@ -88,8 +68,7 @@ struct PPArgs {
 // has only two taps' worth of phases to arrive in)
 // PERSIST = false: a launch whose grid covers every item (the UNet's: 196-208 items on 256 CUs) -- the epilogue does not carry
 // the next item's staging state, which is what made the 256 x 160 instantiation spill 81 VGPRs
-// OUT: 0 = the result leaves through the fused epilogue or as a split-K slab (run-time choice; the TUNE build), 1 = epilogue
-// only, 2 = slab only -- the UNet's launches are all of the last kind, and an instantiation without the epilogue's registers
+// OUT: 1 = the result leaves through the fused epilogue, 2 = as a split-K slab -- the UNet's launches are all of the last kind, and an instantiation without the epilogue's registers
 // has no scratch at all
 // TERMS: 3 = bf16x3; 1 = the context's plain-bf16 mode: the hi halves of the same split32 lines are the operands (one MFMA per
 // k-step, the lo halves are staged with their lines but never read) -- the same schedule, a third of the matrix phase
@@ -98,7 +77,7 @@ struct PPArgs {
 // weight at load (runtime.cpp pack_conv_up2) -- 4 / 9 of the multiplications.  One launch: item -> (phase, tile); a phase has its
 // own packed weights (b + phase * b_phase), padding (ph, pw) = (1 - py, 1 - px) and output plane (c + phase * M * ldc, interleaved
 // into the image by pixel_shuffle2_kernel afterwards).  No K split (OUT = 1).
-template <int MI, int NI, int GWM, int GWN, int NPA, bool TUNE, bool PERSIST, int OUT, int TERMS, bool UP2 = false>
+template <int MI, int NI, int GWM, int GWN, int NPA, bool PERSIST, int OUT, int TERMS, bool UP2 = false>
 __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPArgs q) {
     constexpr int BN = GWN * NI * 32;
     constexpr int BPG = BN / 16;                    // weight pieces (8 rows x 128 B) per group and chunk: half a chunk
@@ -125,14 +104,9 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
     // and its workgroups walk it with a stride of their number.  A workgroup is persistent (the grid is capped at one per CU:
     // the LDS holds one): it issues the first copies of its next item before the epilogue of the current one, so the cold
     // start of an item hides under the stores of its predecessor (the vocoders' layers are 16 384 items of 12-44 chunks).
-    int w_lo, w_cnt, w_step;
-    {
-        const int G = (int)gridDim.x, xcd = blockIdx.x & 7, qq = q.items >> 3, rr = q.items & 7;
-        w_lo = xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq;
-        w_cnt = qq + (xcd < rr ? 1 : 0);
-        w_step = (G - xcd + 7) >> 3;
-    }
-    int w_cur = (int)(blockIdx.x >> 3);
+    const XcdRange wr = xcd_range(q.items);
+    const int w_lo = wr.lo, w_cnt = wr.cnt, w_step = wr.step;
+    int w_cur = wr.first;
     if (w_cur >= w_cnt) return;              // (never when grid <= items; uniform for the workgroup)
     const int TAPS = q.T;
     const int W = q.W, H = q.H;
@@ -313,10 +287,10 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
     // reads, or the fragments waited for only at the head of the matrix phase, are both 25-30 % slower; s_setprio on either
     // phase changes nothing.)
     auto load_phase = [&](int j) __attribute__((always_inline)) {
-        if (!TUNE || !(q.dbg & 4)) reads();
-        if (!TUNE || !(q.dbg & 2)) copies(j);
+        reads();
+        copies(j);
         wait_lgkm0();
-        if (!TUNE || !(q.dbg & 8)) wait_vmcnt<NP>();       // all but the NP pieces just issued have landed
+        wait_vmcnt<NP>();       // all but the NP pieces just issued have landed
     };
     auto advance = [&]() __attribute__((always_inline)) {
         shift += q.colstep;
@@ -393,7 +367,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            if (!TUNE || !(q.dbg & 1)) mma_phase();
+            mma_phase();
             __builtin_amdgcn_sched_barrier(0);
             if (!(grp == 1 && j == NQ - 1)) __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
@@ -415,7 +389,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
         // ---- epilogue or slab
         const int rpb = p.Hout * p.Wout;
         const int row_base = e_m0 + grp * 128 + wm * (32 * MI), col_base = e_n0 + wn * (32 * NI);
-        if (OUT == 1 || (OUT == 0 && q.part == nullptr)) {
+        if constexpr (OUT == 1) {
             igemm_epilogue<MI, NI>(p, acc, row_base, col_base, lrow, lk, UP2 ? (long long)e_phase * p.M * p.ldc : 0LL, q.Nb, rpb);
         } else {
             // slab of this (slice, tile): [MI NI blocks][4 register quads][512 threads][4 floats]
@@ -436,7 +410,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
     wait_vmcnt<0>();        // (dummies only) nothing may land in LDS after the workgroup has given it back
 }
 
-// Tap geometry of a problem this engine takes (igemm_pp_plan checks eligibility)
+// Tap geometry of a problem this engine takes (igemm_pp_takes checks eligibility)
 struct PPGeom {
     int T, KW, rowstep, colstep, padflat, NLp, npa;
 };
@@ -481,10 +455,10 @@ void launch_npa_terms(const Ctx& ctx, const IGemm& p, const PPArgs& q, int items
         hipLaunchKernelGGL(kern, dim3((unsigned)items), dim3(512), lds, ctx.stream, p, q);
     };
     const bool persist = q.items > items, slab = q.part != nullptr;      // (more items than workgroups: persistent)
-    if (persist && slab) go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, false, true, 2, TERMS>);
-    else if (persist) go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, false, true, 1, TERMS>);
-    else if (slab) go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, false, false, 2, TERMS>);
-    else go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, false, false, 1, TERMS>);
+    if (persist && slab) go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, true, 2, TERMS>);
+    else if (persist) go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, true, 1, TERMS>);
+    else if (slab) go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, false, 2, TERMS>);
+    else go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, false, 1, TERMS>);
 }
 
 template <int MI, int NI, int GWM, int GWN, int NPA>
@@ -496,7 +470,8 @@ void launch_npa(const Ctx& ctx, const IGemm& p, const PPArgs& q, int items, size
 }
 
 template <int MI, int NI, int GWM, int GWN>
-void launch_one(const Ctx& ctx, const IGemm& p, int Nb, const PPPlan& pl, float* part) {
+void launch_one(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
+    const int Nb = pl.Nb;
     constexpr int BN = GWN * NI * 32;
     const int ncols = p.N;
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (ncols + BN - 1) / BN;
@@ -526,7 +501,6 @@ void launch_one(const Ctx& ctx, const IGemm& p, int Nb, const PPPlan& pl, float*
     // L2 streams 1 / S of the packed weights; tile-major (round 5's default) gave it a few tiles with ALL their slices and every L2
     // streamed the whole weight tensor: FETCH_SIZE x 3.4 at the 5 x 39 level for the same run time (profiles/r5/r5_bf16x3_pmc_fetch_write.txt)
     q.tile_major = ctx.tune.pp_tile_major && pl.S > 1 ? 1 : 0;
-    q.dbg = 0;
     q.tiles_pp = q.tiles;
     q.b_phase = 0;
     MAA_CHECK((q.nci + q.cps - 1) / q.cps == pl.S, "igemm_pp: K split leaves an empty slice");
@@ -578,7 +552,6 @@ void launch_up2(const Ctx& ctx, const IGemm& p, int Nb, long long b_phase) {
     q.S = 1;
     q.tile_major = 0;
     q.b_phase = b_phase;
-    q.dbg = 0;
     MAA_CHECK(q.CAPl > 0, "igemm_pp up2: the A ring does not fit beside the weight ring");
     const size_t lds = (size_t)q.CAPl * 128 + (size_t)NSB * BN * 128 + 128 + 1024;
     MAA_CHECK(lds <= 163840, "igemm_pp up2: LDS per workgroup");
@@ -591,11 +564,11 @@ void launch_up2(const Ctx& ctx, const IGemm& p, int Nb, long long b_phase) {
     };
     const bool one = ctx.dtype == 2;
     if (g.npa == 1) {
-        if (one) go(igemm_pp_kernel<MI, NI, GWM, GWN, 1, false, true, 1, 1, true>);
-        else go(igemm_pp_kernel<MI, NI, GWM, GWN, 1, false, true, 1, 3, true>);
+        if (one) go(igemm_pp_kernel<MI, NI, GWM, GWN, 1, true, 1, 1, true>);
+        else go(igemm_pp_kernel<MI, NI, GWM, GWN, 1, true, 1, 3, true>);
     } else {
-        if (one) go(igemm_pp_kernel<MI, NI, GWM, GWN, 3, false, true, 1, 1, true>);
-        else go(igemm_pp_kernel<MI, NI, GWM, GWN, 3, false, true, 1, 3, true>);
+        if (one) go(igemm_pp_kernel<MI, NI, GWM, GWN, 3, true, 1, 1, true>);
+        else go(igemm_pp_kernel<MI, NI, GWM, GWN, 3, true, 1, 3, true>);
     }
 }
 
@@ -632,11 +605,7 @@ __global__ __launch_bounds__(512) void igemm_pp1_kernel(const IGemm p, const PP1
     const int wm = wq / GWN, wn = wq - wm * GWN;
     const int lrow = lane & 31, lk = lane >> 5;
 
-    int item;
-    {
-        const int items = (int)gridDim.x, xcd = blockIdx.x & 7, qq = items >> 3, rr = items & 7;
-        item = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (int)(blockIdx.x >> 3);
-    }
+    const int item = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
     const int slice = __builtin_amdgcn_readfirstlane(item / q.tiles), tile = item - slice * q.tiles;
     const int mt = __builtin_amdgcn_readfirstlane(tile / q.ntiles), nt = tile - mt * q.ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
@@ -788,7 +757,8 @@ __global__ __launch_bounds__(512) void igemm_pp1_kernel(const IGemm p, const PP1
 }
 
 template <int MI, int NI, int GWM, int GWN>
-void launch_one1(const Ctx& ctx, const IGemm& p, int Nb, const PPPlan& pl, float* part) {
+void launch_one1(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
+    const int Nb = pl.Nb;
     constexpr int BN = GWN * NI * 32;
     const int ncols = p.N * (p.geglu ? 2 : 1);
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (ncols + BN - 1) / BN;
@@ -820,21 +790,20 @@ void launch_one1(const Ctx& ctx, const IGemm& p, int Nb, const PPPlan& pl, float
 // of 3 / 7 / 11 taps -- on one split32 source with split32 weights, a whole number of 32-channel chunks, and an A ring + the
 // weight ring that fit the CU's LDS.  The tile width and the number of K slices depend on the layer only (never on M).
 // MAA_PP = "off" | "bn,S" overrides (tuning and tests; parsed when the context is created).
-PPPlan igemm_pp_plan(const Ctx& ctx, const IGemm& p) {
-    PPPlan pl;
+bool igemm_pp_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl) {
     const int T = p.KH * p.KW;
-    if (!(T >= 3 && T <= 32 && p.sh == 1 && p.sw == 1 && p.up == 0)) return pl;
-    if (!(2 * p.ph == p.dh * (p.KH - 1) && 2 * p.pw == p.dw * (p.KW - 1))) return pl;          // "same" padding, odd kernels
-    if (!(p.KH == 1 || p.dh * p.Win >= (p.KW - 1) * p.dw)) return pl;                         // tap offsets ascend with t
-    if (!(p.a_split && p.b_split && p.b_nk && p.C2 == 0 && p.C1 % BK == 0 && p.Z == 1 && p.a_act == 0 && !p.geglu)) return pl;
-    if (p.Hout != p.Hin || p.Wout != p.Win || p.K != T * p.C1 || p.N < 64) return pl;
+    if (!(T >= 3 && T <= 32 && p.sh == 1 && p.sw == 1 && p.up == 0)) return false;
+    if (!(2 * p.ph == p.dh * (p.KH - 1) && 2 * p.pw == p.dw * (p.KW - 1))) return false;          // "same" padding, odd kernels
+    if (!(p.KH == 1 || p.dh * p.Win >= (p.KW - 1) * p.dw)) return false;                         // tap offsets ascend with t
+    if (!(p.a_split && p.b_split && p.b_nk && p.C2 == 0 && p.C1 % BK == 0 && p.Z == 1 && p.a_act == 0 && !p.geglu)) return false;
+    if (p.Hout != p.Hin || p.Wout != p.Win || p.K != T * p.C1 || p.N < 64) return false;
     const PPGeom g = pp_geom(p);
-    if (g.npa == 0) return pl;
+    if (g.npa == 0) return false;
     auto fits = [&](int bn) { return pp_ring_lines(g, bn) > 0; };
     const int nci = p.C1 / BK;
     int bn = 0, S = 0;
     if (!ctx.tune.pp.empty()) {
-        if (ctx.tune.pp[0] == 'o') return pl;
+        if (ctx.tune.pp[0] == 'o') return false;
         std::sscanf(ctx.tune.pp.c_str(), "%d,%d", &bn, &S);
     }
     if (bn != 128 && bn != 160) {
@@ -846,7 +815,7 @@ PPPlan igemm_pp_plan(const Ctx& ctx, const IGemm& p) {
         if (bn == 160 && fits(128))
             bn = 128;
         else
-            return pl;
+            return false;
     }
     if (S <= 0) {
         if (p.KH == 1) {
@@ -858,38 +827,20 @@ PPPlan igemm_pp_plan(const Ctx& ctx, const IGemm& p) {
             S = ntiles >= 4 ? ctx.tune.pp_s_wide : ctx.tune.pp_s_narrow;
         }
     }
-    if (S > nci) S = nci;
-    for (; S > 1; --S) {
-        const int cps = (nci + S - 1) / S;
-        if ((nci + cps - 1) / cps == S) break;
-    }
+    pl.engine = IGemmPlan::PP;
     pl.bn = bn;
-    pl.S = S < 1 ? 1 : S;
-    return pl;
+    pl.S = fit_slices(nci, S);
+    return true;
 }
 
-size_t igemm_pp_workspace_floats(const IGemm& p, const PPPlan& pl) {
-    if (pl.bn == 0 || pl.S <= 1) return 0;
-    const long long tiles = (long long)((p.M + BM - 1) / BM) * ((p.N + pl.bn - 1) / pl.bn);
-    return (size_t)(tiles * pl.S * BM * pl.bn);
-}
-
-const char* igemm_pp_name(const PPPlan& pl, int terms) {
-    if (terms == 1) {
-        if (pl.bn == 160) return pl.S > 1 ? "igemm_pp_bf16<256x160,splitK>" : "igemm_pp_bf16<256x160>";
-        return pl.S > 1 ? "igemm_pp_bf16<256x128,splitK>" : "igemm_pp_bf16<256x128>";
-    }
-    if (pl.bn == 160) return pl.S > 1 ? "igemm_pp_bf16x3<256x160,splitK>" : "igemm_pp_bf16x3<256x160>";
-    return pl.S > 1 ? "igemm_pp_bf16x3<256x128,splitK>" : "igemm_pp_bf16x3<256x128>";
-}
-
-void launch_igemm_pp(const Ctx& ctx, const IGemm& p, int Nb, const PPPlan& pl, float* part) {
+// `part`: pl.slab_floats floats when pl.S > 1
+void launch_igemm_pp(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
     MAA_CHECK(pl.bn == 128 || pl.bn == 160, "igemm_pp: problem not planned for this engine");
     MAA_CHECK(pl.S == 1 || part != nullptr, "igemm_pp: split-K needs its slab workspace");
     if (pl.bn == 128)
-        launch_one<2, 2, 2, 2>(ctx, p, Nb, pl, part);
+        launch_one<2, 2, 2, 2>(ctx, p, pl, part);
     else
-        launch_one<1, 5, 4, 1>(ctx, p, Nb, pl, part);
+        launch_one<1, 5, 4, 1>(ctx, p, pl, part);
 }
 
 
@@ -920,14 +871,13 @@ bool launch_igemm_pp_up2(const Ctx& ctx, const IGemm& p, int Nb, long long b_pha
 // 1x1 / Linear problems (both operands split32, one source, a whole number of 32-deep chunks).  Without a K split the engine
 // is bit-identical to the others, so taking it may depend on M: only when the 256-row tiles fill a useful part of the chip.
 // The number of K slices follows the second engine's layer-only rule (K >= 2048: two slices).  MAA_PP1 = "off" | "bn,S".
-PPPlan igemm_pp1_plan(const Ctx& ctx, const IGemm& p) {
-    PPPlan pl;
-    if (!(p.KH == 1 && p.KW == 1 && p.a_split && p.b_split && p.b_nk && p.C2 == 0 && p.Z == 1 && p.a_act == 0 && p.up == 0)) return pl;
-    if (p.K % BK != 0 || p.K != p.C1 || p.K < 64) return pl;
+bool igemm_pp1_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl) {
+    if (!(p.KH == 1 && p.KW == 1 && p.a_split && p.b_split && p.b_nk && p.C2 == 0 && p.Z == 1 && p.a_act == 0 && p.up == 0)) return false;
+    if (p.K % BK != 0 || p.K != p.C1 || p.K < 64) return false;
     const int ncols = p.N * (p.geglu ? 2 : 1);
     int bn = 0, S = 0;
     if (!ctx.tune.pp1.empty()) {
-        if (ctx.tune.pp1[0] == 'o') return pl;
+        if (ctx.tune.pp1[0] == 'o') return false;
         std::sscanf(ctx.tune.pp1.c_str(), "%d,%d", &bn, &S);
     }
     const bool forced = bn == 128 || bn == 160;
@@ -938,44 +888,24 @@ PPPlan igemm_pp1_plan(const Ctx& ctx, const IGemm& p) {
         // GEGLU projection at 10x78: 980 tiles = 3.8 rounds, -7 %); everywhere else the smaller-tile engines stay.
         const long long tiles = (long long)((p.M + BM - 1) / BM) * ((ncols + bn - 1) / bn);
         const long long rounds = (tiles + 255) / 256;
-        if (ncols < 128 || tiles < 768 || rounds * 256 - tiles > 64) return pl;
+        if (ncols < 128 || tiles < 768 || rounds * 256 - tiles > 64) return false;
     }
     if (p.geglu) bn = 128;
     const int nchunks = p.K / BK;
     if (S <= 0) S = (p.K >= 2048 && !p.geglu) ? 2 : 1;
-    if (S > nchunks) S = nchunks;
-    for (; S > 1; --S) {
-        const int cps = (nchunks + S - 1) / S;
-        if ((nchunks + cps - 1) / cps == S) break;
-    }
+    pl.engine = IGemmPlan::PP1;
     pl.bn = bn;
-    pl.S = S < 1 ? 1 : S;
-    return pl;
+    pl.S = fit_slices(nchunks, S);
+    return true;
 }
 
-size_t igemm_pp1_workspace_floats(const IGemm& p, const PPPlan& pl) {
-    if (pl.bn == 0 || pl.S <= 1) return 0;
-    const int ncols = p.N * (p.geglu ? 2 : 1);
-    const long long tiles = (long long)((p.M + BM - 1) / BM) * ((ncols + pl.bn - 1) / pl.bn);
-    return (size_t)(tiles * pl.S * BM * pl.bn);
-}
-
-const char* igemm_pp1_name(const PPPlan& pl, int terms) {
-    if (terms == 1) {
-        if (pl.bn == 160) return pl.S > 1 ? "igemm_pp1_bf16<256x160,splitK>" : "igemm_pp1_bf16<256x160>";
-        return pl.S > 1 ? "igemm_pp1_bf16<256x128,splitK>" : "igemm_pp1_bf16<256x128>";
-    }
-    if (pl.bn == 160) return pl.S > 1 ? "igemm_pp1_bf16x3<256x160,splitK>" : "igemm_pp1_bf16x3<256x160>";
-    return pl.S > 1 ? "igemm_pp1_bf16x3<256x128,splitK>" : "igemm_pp1_bf16x3<256x128>";
-}
-
-void launch_igemm_pp1(const Ctx& ctx, const IGemm& p, int Nb, const PPPlan& pl, float* part) {
+void launch_igemm_pp1(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
     MAA_CHECK(pl.bn == 128 || pl.bn == 160, "igemm_pp1: problem not planned for this engine");
     MAA_CHECK(pl.S == 1 || part != nullptr, "igemm_pp1: split-K needs its slab workspace");
     if (pl.bn == 128)
-        launch_one1<2, 2, 2, 2>(ctx, p, Nb, pl, part);
+        launch_one1<2, 2, 2, 2>(ctx, p, pl, part);
     else
-        launch_one1<1, 5, 4, 1>(ctx, p, Nb, pl, part);
+        launch_one1<1, 5, 4, 1>(ctx, p, pl, part);
 }
 
 }  // namespace maa

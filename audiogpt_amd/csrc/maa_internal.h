@@ -82,19 +82,6 @@ struct ProfScope {     // records an event pair around the launches issued durin
     size_t idx_ = 0;
 };
 
-// XCD-contiguous work order (device code).  Workgroup `bid` of a 1-D grid of `n` runs on XCD bid % 8 (observed placement, used for
-// speed only: MI355X_MICROARCH.md); XCD x takes the x-th contiguous eighth of the work items, workgroup by workgroup -- the order every
-// implicit-GEMM engine gives its tiles (M-major), so that the rows a workgroup of a normalisation / attention / reduce launch reads
-// were written, and the rows it writes will be read, by workgroups of the SAME XCD: its L2 (4 MB, not shared between XCDs) instead
-// of the fabric.  `on` = 0: the identity (A/B).
-#if defined(__HIPCC__)
-__device__ __forceinline__ int xcd_contiguous(int bid, int n, int on) {
-    if (!on) return bid;
-    const int xcd = bid & 7, q = n >> 3, r = n & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-#endif
-
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device); safe from several launching threads
 void ensure_dynamic_lds(const void* kernel, int device, int bytes);
 int device_cu_count(int device);      // multiProcessorCount, cached per device
@@ -222,49 +209,40 @@ struct IGemm {
     float* c2 = nullptr;
     int ldc2 = 0;
     float c2_slope = 1.f;
-    int no_pair = 0;                 // (A/B, retired) plain 4-byte fp32 stores in the epilogue
     const float* zeros = nullptr;    // >= 16 B of zeros in device memory (filled in by launch_igemm)
-    int m_fastest = 0;               // tile order inside an XCD's range: 1 = M-tiles fastest (MAA_TILE_ORDER=1: weights are
-                                     // then fetched once chip-wide, but the conv's A re-reads lose their L2: +4 % step time)
 };
+// What runs a contraction (igemm_dispatch.cpp: the one place that decides).
+struct IGemmPlan {
+    enum Engine { F32, BF16_REG, DMA, DMA2, PP, PP1 } engine = F32;
+    int cfg = 0;                // F32 / BF16_REG / DMA: tile 0 = 128x128, 1 = 128x64, 2 = 64x64, 3 = 256x32, 4 = 128x32
+    int bn = 0;                 // PP / PP1: tile width, 128 or 160 (256 rows)
+    int S = 1;                  // K slices (DMA2 / PP / PP1); > 1: finished by launch_splitk_reduce
+    int Nb = 0;                 // columns (rows, for [N][K]) of B that exist
+    bool fast = false;          // F32: the aligned gather (else the per-element one)
+    size_t slab_floats = 0;     // split-K slabs the launch borrows from the arena
+};
+IGemmPlan igemm_plan(const Ctx& ctx, const IGemm& p);      // checks + the decision cascade; launches nothing
 void launch_igemm(const Ctx& ctx, const IGemm& p);
-// Tile choice shared by the fp32 and bf16 engines: 0 = 128x128, 1 = 128x64, 2 = 64x64 (3 = 256x32 is chosen by
-// the callers for N <= 32).  Cost = CU-rounds x tile area / (tile efficiency x latency hiding at that many
-// co-resident blocks per CU); knobs can be overridden for tuning with MAA_TILE_EFF / MAA_CONC_EFF / MAA_FORCE_CFG.
-int choose_tile(long long M, long long N, int Z, bool bf16, int mode = 0);      // mode 1: least total workgroup time (several contexts keep the chip full)
-bool launch_igemm_bf16(const Ctx& ctx, const IGemm& p, int terms);   // false: not eligible, use the fp32 kernel
-// bf16x3 with LDS-DMA tile copies, both operands split32 (igemm_dma.hip); called by launch_igemm_bf16
-int igemm_dma_tile(const IGemm& p, int cfg);      // tile the DMA engine runs for the generic choice `cfg`
-void launch_igemm_dma(const Ctx& ctx, const IGemm& p, int cfg, int Nb);
-// second LDS-DMA engine (igemm_dma2.hip): 128x128 / 256x128 tiles, 64x64 outputs per wave, split-K finished by a
-// fixed-order reduce kernel.  `takes` and the slab size depend on the layer (K, packed N) only, never on M.
-struct Dma2Plan {
-    int cfg = -1;       // -1: not taken; 0: the 128x128 tile (4 waves of 64x64)
-    int ns = 4, pipe = 1, S = 1;      // LDS stages, in-wave pipelining, K slices
-};
-Dma2Plan igemm_dma2_plan(const Ctx& ctx, const IGemm& p);
-size_t igemm_dma2_workspace_floats(const IGemm& p, const Dma2Plan& pl);      // 0: no split-K for this problem
-const char* igemm_dma2_name(const Dma2Plan& pl, int terms);
-void launch_igemm_dma2(const Ctx& ctx, const IGemm& p, int Nb, const Dma2Plan& pl, float* part);
-
+// 0 = 128x128, 1 = 128x64, 2 = 64x64; mode 1: least total workgroup time (several contexts keep the chip full)
+int choose_tile(long long M, long long N, int Z, bool bf16, int mode = 0);
+int fit_slices(int nchunks, int S);      // the largest S' <= S that leaves no K slice empty
+// The engines.  igemm_*_takes: does the engine take this problem (both operands split32, checked by igemm_plan)?  When it does it
+// fills in the plan's engine, tile and K slices -- functions of the layer (K, packed N) only, never of M.  launch_*: run a plan
+// (`part`: plan.slab_floats floats when that is > 0).
+void launch_igemm_f32(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl);            // igemm_f32.hip: exact fp32 MFMA
+void launch_igemm_bf16_reg(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl);       // igemm_bf16.hip: register-staged, fp32 or split32 operands
+bool igemm_dma_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl);                   // igemm_dma.hip: LDS-DMA tile copies (always; picks its tile)
+void launch_igemm_dma(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl);
+bool igemm_dma2_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl);                  // igemm_dma2.hip: persistent 128x128 tiles, split-K for long K
+void launch_igemm_dma2(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part);
+bool igemm_pp_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl);                    // igemm_pp.hip: halo-staged ping-pong engine, stride-1 "same" convolutions
+void launch_igemm_pp(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part);
+bool igemm_pp1_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl);                   // ... and its 1x1 / Linear form (no halo; A and the weights share one ring)
+void launch_igemm_pp1(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part);
 // adds the S slabs a split-K engine wrote in fragment order ([slice][tile][MI NI blocks][4 quads][NTH threads][4 floats]) in
 // slice order and applies the epilogue (igemm_dma2.hip); WGN / MI / NI / NTH describe the GEMM workgroup's wave geometry
 void launch_splitk_reduce(const Ctx& ctx, const IGemm& p, const float* part, int S, int tiles, int ntiles, int Nb, int BM,
                           int BN, int WGN, int MI, int NI, int NTH);
-// third LDS-DMA engine (igemm_pp.hip): 3x3 convolutions with the A operand halo-staged once per channel chunk and two wave
-// groups alternating matrix / memory phases.  bn = 0: not taken.  Tile width and K slices depend on the layer only.
-struct PPPlan {
-    int bn = 0, S = 1;
-};
-PPPlan igemm_pp_plan(const Ctx& ctx, const IGemm& p);
-size_t igemm_pp_workspace_floats(const IGemm& p, const PPPlan& pl);
-const char* igemm_pp_name(const PPPlan& pl, int terms);
-void launch_igemm_pp(const Ctx& ctx, const IGemm& p, int Nb, const PPPlan& pl, float* part);
-// ... and its 1x1 / Linear form (no halo; A and the weights share one ring)
-PPPlan igemm_pp1_plan(const Ctx& ctx, const IGemm& p);
-size_t igemm_pp1_workspace_floats(const IGemm& p, const PPPlan& pl);
-const char* igemm_pp1_name(const PPPlan& pl, int terms);
-void launch_igemm_pp1(const Ctx& ctx, const IGemm& p, int Nb, const PPPlan& pl, float* part);
 
 // ------------------------------------------------------------------------------------------ norms etc.
 // GroupNorm(32 groups) over a channels-last tensor given as a virtual concat of two sources; writes

@@ -4,6 +4,7 @@
 //   LayerNorm: ldm/modules/attention.py:203-205 (eps 1e-5)
 //   softmax:   ldm/modules/attention.py:188, openaimodel.py:370, model.py:191
 // All three are HBM/L2-bound; reductions are wave64 shuffles plus one LDS hop across the 4 waves.
+#include "igemm_device.h"
 #include "maa_internal.h"
 
 namespace maa {
@@ -31,8 +32,6 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 __device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     f32x2 f = {a, b};
     bf16x2 h = __builtin_convertvector(f, bf16x2);
     return __builtin_bit_cast(unsigned, h);
@@ -174,13 +173,13 @@ __global__ __launch_bounds__(1024) void gn_fused_kernel(const float* __restrict_
                                                         const float* __restrict__ x2, int ld2, int C2, int HW, int groups,
                                                         int GPB, float eps, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int silu, float* __restrict__ out,
-                                                        int split, float* __restrict__ raw_split, int nblk, int xcd_on) {
+                                                        int split, float* __restrict__ raw_split, int nblk) {
     extern __shared__ float gsm[];      // red[RL Q 8] | colsum[2 CB] | gstat[2 GPB]
     const int C = C1 + C2, cpg = C / groups, CB = GPB * cpg, Q = CB >> 2;
     const int RL = (int)blockDim.x / Q;                      // (blockDim.x == RL Q)
     // work item = (sample, group block), sample-major; XCD-contiguous: a sample's rows are read and written on the XCD whose
     // igemm tiles produce / consume them
-    const int w = xcd_contiguous((int)blockIdx.x, (int)gridDim.x, xcd_on);
+    const int w = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);
     const int b = w / nblk, c_lo = (w - b * nblk) * CB;
     const int t = threadIdx.x, ty = t / Q, tx = t - ty * Q;
     const int c = c_lo + 4 * tx;
@@ -324,9 +323,9 @@ template <int NR>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, long long rows, int C,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps,
-                                                        float* __restrict__ out, int split, int xcd_on) {
+                                                        float* __restrict__ out, int split) {
     const int lane = threadIdx.x & 63;
-    const long long row = (long long)xcd_contiguous((int)blockIdx.x, (int)gridDim.x, xcd_on) * 4 + (threadIdx.x >> 6);
+    const long long row = (long long)xcd_contiguous((int)blockIdx.x, (int)gridDim.x) * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* src = x + row * C;
     float4 v[NR];
@@ -483,7 +482,7 @@ void launch_groupnorm(Ctx& ctx, const float* x1, int ld1, int C1, const float* x
         dim3 grid((unsigned)(nblk * B));
         auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, grid, dim3((unsigned)fp.threads), fp.lds, ctx.stream, x1, ld1, C1, x2, ld2, C2, HW, groups, fp.gpb, eps,
-                               gamma, beta, silu, out, out_split, raw_split, nblk, 1);
+                               gamma, beta, silu, out, out_split, raw_split, nblk);
         };
         switch (fp.nr) {
             case 1: go(gn_fused_kernel<1>); break;
@@ -512,15 +511,14 @@ void launch_layernorm(const Ctx& ctx, const float* x, long long rows, int C, con
     MAA_CHECK(C <= 2048 && C % 4 == 0, "layernorm width");
     ProfScope prof(ctx, "layernorm", 0.0, 8.0 * rows * (double)C);
     dim3 grid((unsigned)((rows + 3) / 4));
-    const int xa = 1;
     if (C <= 256)
-        hipLaunchKernelGGL(layernorm_kernel<1>, grid, dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, out, out_split, xa);
+        hipLaunchKernelGGL(layernorm_kernel<1>, grid, dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, out, out_split);
     else if (C <= 512)
-        hipLaunchKernelGGL(layernorm_kernel<2>, grid, dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, out, out_split, xa);
+        hipLaunchKernelGGL(layernorm_kernel<2>, grid, dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, out, out_split);
     else if (C <= 1024)
-        hipLaunchKernelGGL(layernorm_kernel<4>, grid, dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, out, out_split, xa);
+        hipLaunchKernelGGL(layernorm_kernel<4>, grid, dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, out, out_split);
     else      // the ViT-H image tower's 1280-wide rows
-        hipLaunchKernelGGL(layernorm_kernel<8>, grid, dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, out, out_split, xa);
+        hipLaunchKernelGGL(layernorm_kernel<8>, grid, dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, out, out_split);
     MAA_HIP(hipGetLastError());
 }
 

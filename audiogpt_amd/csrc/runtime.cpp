@@ -110,35 +110,6 @@ ProfScope::~ProfScope() {
     if (ctx_) (void)hipEventRecord(ctx_->prof->pending[idx_].e1, ctx_->stream);
 }
 
-// ------------------------------------------------------------------------------------------ tile choice
-namespace {
-struct TileKnobs {
-    double eff[3] = {1.00, 0.92, 0.80};       // per-block efficiency of 128x128 / 128x64 / 64x64
-    double conc[3] = {0.55, 0.85, 1.00};      // latency hiding with 1 / 2 / >=3 co-resident blocks per CU
-};
-}  // namespace
-int choose_tile(long long M, long long N, int Z, bool bf16, int mode) {
-    static const TileKnobs k;
-    static const int bm[3] = {128, 128, 64}, bn[3] = {128, 64, 64};
-    const int max_occ[3] = {bf16 ? 2 : 3, bf16 ? 2 : 4, 4};   // blocks per CU allowed by LDS / registers
-    int best = 0;
-    double best_cost = 1e300;
-    for (int c = 0; c < 3; ++c) {
-        const long long blocks = ((M + bm[c] - 1) / bm[c]) * ((N + bn[c] - 1) / bn[c]) * Z;
-        const long long per_cu = (blocks + 255) / 256;
-        const int co = (int)(per_cu < max_occ[c] ? per_cu : max_occ[c]);
-        // mode 1: the chip is kept full from outside (other contexts' launches run on the CUs this one leaves idle), so what a
-        // launch costs is the sum of its workgroups' time, padding included -- not the rounds its own grid makes
-        const double cost = mode == 1 ? (double)blocks * bm[c] * bn[c] / k.eff[c]
-                                      : (double)per_cu * bm[c] * bn[c] / (k.eff[c] * k.conc[co >= 3 ? 2 : co - 1]);
-        if (cost < best_cost) {
-            best_cost = cost;
-            best = c;
-        }
-    }
-    return best;
-}
-
 // ------------------------------------------------------------------------------------------ StateDict helpers
 const HostTensor& get(const StateDict& sd, const std::string& name) {
     auto it = sd.find(name);

@@ -83,19 +83,12 @@ def mfma_loops_without_scratch(body):
     return len(inner), len(bad)
 
 
-def _pp_tune_build(name):
-    """igemm_pp_kernel<MI, NI, GWM, GWN, NPA, TUNE, PERSIST, OUT, TERMS>: TUNE is the first bool of the mangled argument list."""
-    return "igemm_pp_kernel" in name and re.search(r"Li[13]ELb1ELb[01]ELi\dELi[13]ELb[01]EEEv", name) is not None
-
-
 def test_no_scratch_inside_any_mfma_loop(asm):
     seen = 0
     for f, text in asm.items():
         for name, body in kernels(text).items():
             if not any("v_mfma" in l for l in body):
                 continue
-            if f == "igemm_pp.hip" and _pp_tune_build(name):
-                continue      # TUNE = true: the ablation build of rounds 3 - 5 (no longer instantiated)
             if f == "igemm_f32.hip" and "ILi128ELi128ELi2ELi2ELb0E" in name:
                 # KNOWN, exact-fp32 mode only: the unaligned-operand path of the 128x128 tile indexes its staging registers
                 # at run time, which puts them in an 80-byte stack slot (8 scratch instructions per 64 MFMAs).  Not on the
@@ -132,11 +125,9 @@ def test_register_budgets(asm):
     for (f, name), (vg, spill) in meta.items():
         if f == "igemm_pp.hip":
             assert vg <= 256, (name, vg)
-            if _pp_tune_build(name):
-                continue
             # the 160-wide tile spills only where its result leaves through the fused epilogue (the vocoders' 1-D layers never
             # take it: they are 128 wide); the slab-only instantiations -- every 3x3 convolution of the UNet -- have no scratch
-            if "igemm_pp_kernel" in name and "ILi1ELi5E" in name and re.search(r"ELb[01]ELi1ELi[13]ELb[01]EEEv", name):      # OUT = 1
+            if "igemm_pp_kernel" in name and "ILi1ELi5E" in name and re.search(r"Li[13]ELb[01]ELi1ELi[13]ELb[01]EEEv", name):      # <.., NPA, PERSIST, OUT = 1, TERMS, UP2>
                 continue
             if "igemm_pp1_kernel" in name and "ILi1ELi5E" in name:      # (the 1x1 form's 160-wide tile: forced by MAA_PP1 only)
                 continue
