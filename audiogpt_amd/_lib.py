@@ -105,7 +105,7 @@ EXPORTS = [
     "maa_spectral_create", "maa_spectral_destroy", "maa_spectral_forward", "maa_resampler_create", "maa_resampler_destroy",
     "maa_resampler_forward", "maa_op_linear", "maa_op_conv", "maa_op_groupnorm", "maa_op_layernorm",
     "maa_op_attention", "maa_op_attention_ex", "maa_op_conv_transpose1d", "maa_op_snake_aa", "maa_op_bench_conv", "maa_calib",
-    "maa_op_mrf_pair",
+    "maa_op_mrf_pair", "maa_op_groupnorm_ex", "maa_op_layernorm_ex", "maa_op_split32",
 ]
 
 _lib = None
@@ -185,6 +185,9 @@ def load():
         "maa_op_bench_conv": [vp, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)],
         "maa_calib": [vp, ci, C.POINTER(C.c_double)],
         "maa_op_mrf_pair": [vp, vp, ci, ci, ci, fp, fp, ci, ci, cf, fp, fp, ci, ci, cf, cf, ci, vp],
+        "maa_op_groupnorm_ex": [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, fp, fp, cf, ci, vp, ci, vp],
+        "maa_op_layernorm_ex": [vp, vp, ci, ci, fp, fp, cf, vp, ci],
+        "maa_op_split32": [vp, vp, ci, ci, cf, ci, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)

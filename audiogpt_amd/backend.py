@@ -198,6 +198,39 @@ class Context:
                                              int(out_split), int(causal)))
         return out
 
+    def op_groupnorm_ex(self, x1, ld1, C1, x2, ld2, C2, B, HW, groups, gamma, beta, eps, silu, out, out_split=0, raw=None):
+        """maa_op_groupnorm_ex: the library's internal GroupNorm call on channels-last device tensors the caller has laid out
+        (x1 / x2 / out / raw are fp32 device tensors, possibly views into wider buffers; pitches in floats; x2 None with C2 = 0 for
+        one source).  Writes into `out` (and `raw`); nothing is allocated, copied or checked beyond what the C entry point checks."""
+        for t in (x1, x2, out, raw):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32), (t.device, t.dtype)
+        gt, gp = L.host_f32(gamma)
+        bt, bp = L.host_f32(beta)
+        assert gt.numel() == C1 + C2 and bt.numel() == C1 + C2
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        L.check(self.lib.maa_op_groupnorm_ex(self.h, ptr(x1), int(ld1), int(C1), ptr(x2), int(ld2), int(C2), int(B), int(HW),
+                                             int(groups), gp, bp, float(eps), int(silu), ptr(out), int(out_split), ptr(raw)))
+        return out
+
+    def op_layernorm_ex(self, x, gamma, beta, eps=1e-5, out_split=0):
+        """LayerNorm over the last dim of x [rows, C]; out_split = 1: the result as split32 rows in an fp32-typed tensor."""
+        x = _f32(x, self.device)
+        rows, Cc = x.reshape(-1, x.shape[-1]).shape
+        gt, gp = L.host_f32(gamma)
+        bt, bp = L.host_f32(beta)
+        y = torch.empty_like(x)
+        L.check(self.lib.maa_op_layernorm_ex(self.h, L.dptr(x), rows, Cc, gp, bp, float(eps), L.dptr(y), int(out_split)))
+        return y
+
+    def op_split32(self, x, slope=1.0, unpack=False):
+        """x [rows, C] fp32 -> the split32 rows of leaky_relu(x, slope) (launch_split32_pack), or, with unpack, split32 rows ->
+        hi + lo as fp32 (launch_split32_unpack)."""
+        x = _f32(x, self.device)
+        rows, Cc = x.shape
+        y = torch.empty_like(x)
+        L.check(self.lib.maa_op_split32(self.h, L.dptr(x), rows, Cc, float(slope), int(unpack), L.dptr(y)))
+        return y
+
     def op_conv_transpose1d(self, x, w, b, stride, leaky=0.0):
         x = _f32(x, self.device)
         B, Cin, Ln = x.shape

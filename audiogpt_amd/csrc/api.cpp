@@ -2,6 +2,7 @@
 // exception -> status translation.  No C++ type or exception crosses this file's boundary.
 #include "models.h"
 
+#include <cstdint>
 #include <cstring>
 #include <memory>
 
@@ -717,6 +718,62 @@ int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const 
             maa::attention_into(c, d_q, ldq, hsq, d_k, ldk, hsk, d_v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, d_y, ldo,
                                 out_split, causal);
         });
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
+int maa_op_groupnorm_ex(maa_ctx* ctx, const float* d_x1, int ld1, int C1, const float* d_x2, int ld2, int C2, int B, int HW,
+                        int groups, const float* h_gamma, const float* h_beta, float eps, int silu, float* d_y, int out_split,
+                        float* d_raw) {
+    return guarded([&] {
+        bind(ctx);
+        MAA_CHECK(d_x1 && h_gamma && h_beta && d_y, "bad op_groupnorm_ex arguments");
+        MAA_CHECK(B > 0 && HW > 0 && groups > 0 && C1 > 0 && C2 >= 0 && eps > 0.f, "bad op_groupnorm_ex sizes");
+        MAA_CHECK((C2 == 0) == (d_x2 == nullptr), "op_groupnorm_ex: a second source needs both d_x2 and C2");
+        MAA_CHECK(ld1 >= C1 && (C2 == 0 || ld2 >= C2), "bad op_groupnorm_ex strides");
+        const int C = C1 + C2;
+        MAA_CHECK(C % groups == 0 && C / groups <= 256 && C1 % 4 == 0 && C2 % 4 == 0 && ld1 % 4 == 0 && ld2 % 4 == 0,
+                  "op_groupnorm_ex: channels and pitches in whole float4s, at most 256 channels per group");
+        MAA_CHECK((!out_split && !d_raw) || C % 32 == 0, "op_groupnorm_ex: split32 rows are whole 32-channel lines");
+        MAA_CHECK((reinterpret_cast<uintptr_t>(d_x1) | reinterpret_cast<uintptr_t>(d_x2) | reinterpret_cast<uintptr_t>(d_y) |
+                   reinterpret_cast<uintptr_t>(d_raw)) % 16 == 0, "op_groupnorm_ex: buffers must be 16-byte aligned");
+        maa::WeightStore ws(ctx->c.dtype != 0);
+        maa::Ctx& c = ctx->c;
+        float* g = ws.upload(std::vector<float>(h_gamma, h_gamma + C));
+        float* b = ws.upload(std::vector<float>(h_beta, h_beta + C));
+        maa::run_sized(c, [&] {
+            maa::launch_groupnorm(c, d_x1, ld1, C1, d_x2, ld2, C2, B, HW, groups, g, b, eps, silu, d_y, out_split ? 1 : 0, d_raw);
+        });
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
+int maa_op_layernorm_ex(maa_ctx* ctx, const float* d_x, int rows, int C, const float* h_gamma, const float* h_beta, float eps,
+                        float* d_y, int out_split) {
+    return guarded([&] {
+        bind(ctx);
+        MAA_CHECK(d_x && h_gamma && h_beta && d_y, "bad op_layernorm_ex arguments");
+        MAA_CHECK(rows > 0 && C > 0 && C % 4 == 0 && C <= 2048 && eps > 0.f, "bad op_layernorm_ex sizes");
+        MAA_CHECK(!out_split || C % 32 == 0, "op_layernorm_ex: split32 rows are whole 32-channel lines");
+        maa::WeightStore ws(ctx->c.dtype != 0);
+        maa::Ctx& c = ctx->c;
+        float* g = ws.upload(std::vector<float>(h_gamma, h_gamma + C));
+        float* b = ws.upload(std::vector<float>(h_beta, h_beta + C));
+        maa::launch_layernorm(c, d_x, rows, C, g, b, eps, d_y, out_split ? 1 : 0);
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
+int maa_op_split32(maa_ctx* ctx, const float* d_x, int rows, int C, float slope, int unpack, float* d_y) {
+    return guarded([&] {
+        bind(ctx);
+        MAA_CHECK(d_x && d_y && d_x != d_y, "bad op_split32 arguments");
+        MAA_CHECK(rows > 0 && C > 0 && C % 32 == 0, "op_split32: split32 rows are whole 32-channel lines");
+        maa::Ctx& c = ctx->c;
+        if (unpack)
+            maa::launch_split32_unpack(c, d_x, rows, C, d_y);
+        else
+            maa::launch_split32_pack(c, d_x, rows, C, d_y, slope);
         MAA_HIP(hipStreamSynchronize(c.stream));
     });
 }

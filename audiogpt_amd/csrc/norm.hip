@@ -56,9 +56,12 @@ __device__ __forceinline__ void store4(float* out, long long row, int c, int C, 
 
 // GroupNorm pass 1: one block per (sample, group) -> tab[(b*C + c)*2] = {scale, shift} for the group's channels
 // (scale = gamma*rstd, shift = beta - mean*scale, as ATen forms them); threads = (position
-// lane, channel-in-group).  One pass over the data: sums of d = x - pivot and d*d, with the group's first element as
-// pivot (so the subtraction var = E[d^2] - E[d]^2 cancels at most a couple of bits, like the two-pass form), eight
-// independent loads in flight per thread.  Fixed reduction order: results are bit-reproducible.
+// lane, channel-in-group).  One pass over the data: sums of d = x - pivot and d*d, eight independent loads in flight per
+// thread.  The pivot is the block-reduced mean of the group's first slab -- the first 8 * tp_n positions x cpg channels, up
+// to 2048 elements, which are each thread's first eight loads and stay in registers across the reduction -- so no single
+// element (the group's first one sits in a corner pixel next to the zero padding) and no single position decides how much
+// var = E[d^2] - E[d]^2 cancels: a whole position at 50 sigma moves this pivot by 50 / (8 tp_n) <= 6.3 sigma (cpg <= 256),
+// one element at 1000 sigma by 1000 / (8 tp_n cpg) <= 0.6 sigma.  Fixed reduction order: results are bit-reproducible.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x1, int ld1, int C1,
                                                        const float* __restrict__ x2, int ld2, int C2, int HW,
                                                        int groups, float eps, const float* __restrict__ gamma,
@@ -81,16 +84,27 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
         ld = ld2;
     }
     const int c0 = g * cpg;
-    const float pivot = c0 < C1 ? x1[(long long)b * HW * ld1 + c0] : x2[(long long)b * HW * ld2 + (c0 - C1)];
     const float n = (float)HW * (float)cpg;
     // eight independent loads in flight per thread: the pass is latency-bound (a 10 x 78 level is 31 positions per thread)
     constexpr int U = 8;
-    float sa[U], qa[U];
+    float d[U], sa[U], qa[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) sa[u] = qa[u] = 0.f;
+    for (int u = 0; u < U; ++u) {
+        const int pu = tp + u * tp_n;
+        d[u] = active && pu < HW ? src[(long long)pu * ld] : 0.f;
+        sa[u] = qa[u] = 0.f;
+    }
+    const int slab = HW < U * tp_n ? HW : U * tp_n;       // positions of the first slab
+    const float pivot = block_sum(((d[0] + d[4]) + (d[1] + d[5])) + ((d[2] + d[6]) + (d[3] + d[7])), red) / ((float)slab * (float)cpg);
     if (active) {
-        for (int pos = tp; pos < HW; pos += U * tp_n) {          // a position past the end reads as the pivot: d = 0
-            float d[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (tp + u * tp_n < HW) {
+                d[u] -= pivot;
+                sa[u] = d[u];
+                qa[u] = d[u] * d[u];
+            }
+        for (int pos = tp + U * tp_n; pos < HW; pos += U * tp_n) {          // a position past the end reads as the pivot: d = 0
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int pu = pos + u * tp_n;
@@ -164,17 +178,50 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
 // float4 column tx) loads rows ty, ty + RL, ... (NR float4s, all in flight together), the statistics are reduced through LDS in a
 // fixed order, and the normalised (+ SiLU) rows are written from the registers -- fp32 or split32, plus the optional raw split32
 // copy -- so the tensor is read once and the statistics launch, its table and the dependent second launch are gone (two launches
-// of 10 + 8 us per GroupNorm at the UNet's sizes, both latency-bound: DESIGN.md 3.4).  Same arithmetic as the two-pass kernels:
-// sums of d = x - pivot and d^2 with the group's first element as pivot, scale = gamma rstd, shift = beta - mean scale,
-// y = x scale + shift.  The layout (GPB, RL, NR) is a function of (C, HW) only and a workgroup sees one sample: a sample's result
-// does not depend on its batch.
+// of 10 + 8 us per GroupNorm at the UNet's sizes, both latency-bound: DESIGN.md 3.4).  With the rows in registers the statistics
+// are the exact two-pass ones: the group sums are reduced to the mean, the mean is broadcast, and the squares of x - mean are
+// reduced the same way (no pivot: the variance does not depend on any one element or position being typical of its group).
+// Then scale = gamma rstd, shift = beta - mean scale, y = x scale + shift, as in the two-launch kernels.  The layout (GPB, RL, NR)
+// is a function of (C, HW) only and a workgroup sees one sample: a sample's result does not depend on its batch.
+//
+// One LDS reduction of a per-thread float4 of partials (red[t]) to per-group totals (gtot[0 .. GPB)), every step in a fixed order:
+// thread (half h, channel cc) adds half of the RL row lanes' partials of its channel in four interleaved chains, then one thread
+// per group adds its 2 cpg column sums.  Starts and ends with a barrier.
+__device__ __forceinline__ void gn_group_reduce(float* red, float* colsum, float* gtot, float4 part, int t, int RL, int Q, int CB,
+                                                int GPB, int cpg) {
+    *reinterpret_cast<float4*>(red + (size_t)t * 4) = part;
+    __syncthreads();
+    if (t < 2 * CB) {
+        const int h = t / CB, cc = t - h * CB, RLh = (RL + 1) >> 1;
+        const int y1 = h ? RL : RLh;
+        const float* p0 = red + cc;                      // channel cc of row lane y: red[(y Q + cc / 4) 4 + cc % 4]
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int y = h ? RLh : 0;
+        for (; y + 3 < y1; y += 4) {
+            a0 += p0[(size_t)(y + 0) * Q * 4];
+            a1 += p0[(size_t)(y + 1) * Q * 4];
+            a2 += p0[(size_t)(y + 2) * Q * 4];
+            a3 += p0[(size_t)(y + 3) * Q * 4];
+        }
+        for (; y < y1; ++y) a0 += p0[(size_t)y * Q * 4];
+        colsum[t] = (a0 + a1) + (a2 + a3);
+    }
+    __syncthreads();
+    if (t < GPB) {
+        float s = 0.f;
+        for (int i = 0; i < cpg; ++i) s += colsum[t * cpg + i] + colsum[CB + t * cpg + i];
+        gtot[t] = s;
+    }
+    __syncthreads();
+}
+
 template <int NR>
 __global__ __launch_bounds__(1024) void gn_fused_kernel(const float* __restrict__ x1, int ld1, int C1,
                                                         const float* __restrict__ x2, int ld2, int C2, int HW, int groups,
                                                         int GPB, float eps, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int silu, float* __restrict__ out,
                                                         int split, float* __restrict__ raw_split, int nblk) {
-    extern __shared__ float gsm[];      // red[RL Q 8] | colsum[2 CB] | gstat[2 GPB]
+    extern __shared__ float gsm[];      // red[RL Q 4] | colsum[2 CB] | gsum[GPB] | gsq[GPB]
     const int C = C1 + C2, cpg = C / groups, CB = GPB * cpg, Q = CB >> 2;
     const int RL = (int)blockDim.x / Q;                      // (blockDim.x == RL Q)
     // work item = (sample, group block), sample-major; XCD-contiguous: a sample's rows are read and written on the XCD whose
@@ -184,8 +231,9 @@ __global__ __launch_bounds__(1024) void gn_fused_kernel(const float* __restrict_
     const int t = threadIdx.x, ty = t / Q, tx = t - ty * Q;
     const int c = c_lo + 4 * tx;
     float* const red = gsm;
-    float* const colsum = gsm + (size_t)RL * Q * 8;
-    float* const gstat = colsum + 2 * CB;
+    float* const colsum = gsm + (size_t)RL * Q * 4;
+    float* const gsum = colsum + 2 * CB;
+    float* const gsq = gsum + GPB;
     const float* src;
     long long ld;
     if (c < C1) {
@@ -195,76 +243,46 @@ __global__ __launch_bounds__(1024) void gn_fused_kernel(const float* __restrict_
         src = x2 + (long long)b * HW * ld2 + (c - C1);
         ld = ld2;
     }
-    // pivot of each of the float4's four channels = first element of that channel's group
+    // group (within the block) of each of the float4's four channels: one float4 can span two groups
     int gl[4];
-    float piv[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        gl[j] = (4 * tx + j) / cpg;
-        const int c0 = c_lo + gl[j] * cpg;
-        piv[j] = c0 < C1 ? x1[(long long)b * HW * ld1 + c0] : x2[(long long)b * HW * ld2 + (c0 - C1)];
-    }
+    for (int j = 0; j < 4; ++j) gl[j] = (4 * tx + j) / cpg;
     float4 v[NR];
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
         const int r = ty + RL * k;
-        v[k] = r < HW ? *reinterpret_cast<const float4*>(src + (long long)r * ld) : make_float4(piv[0], piv[1], piv[2], piv[3]);
+        v[k] = r < HW ? *reinterpret_cast<const float4*>(src + (long long)r * ld) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    float sd[4] = {0.f, 0.f, 0.f, 0.f}, qd[4] = {0.f, 0.f, 0.f, 0.f};
+    const float n = (float)HW * (float)cpg;
+    float4 sd = make_float4(0.f, 0.f, 0.f, 0.f);      // a row past the end was loaded as 0
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
-        const float d0 = v[k].x - piv[0], d1 = v[k].y - piv[1], d2 = v[k].z - piv[2], d3 = v[k].w - piv[3];
-        sd[0] += d0;
-        sd[1] += d1;
-        sd[2] += d2;
-        sd[3] += d3;
-        qd[0] += d0 * d0;
-        qd[1] += d1 * d1;
-        qd[2] += d2 * d2;
-        qd[3] += d3 * d3;
+        sd.x += v[k].x;
+        sd.y += v[k].y;
+        sd.z += v[k].z;
+        sd.w += v[k].w;
     }
-    {
-        float4* r4 = reinterpret_cast<float4*>(red + (size_t)t * 8);
-        r4[0] = make_float4(sd[0], sd[1], sd[2], sd[3]);
-        r4[1] = make_float4(qd[0], qd[1], qd[2], qd[3]);
-    }
-    __syncthreads();
-    // per channel and statistic: the RL row lanes' partials, four interleaved chains in a fixed order
-    if (t < 2 * CB) {
-        const int stat = t / CB, cc = t - stat * CB;
-        const float* p0 = red + (size_t)(cc >> 2) * 8 + stat * 4 + (cc & 3);
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int y = 0;
-        for (; y + 3 < RL; y += 4) {
-            a0 += p0[(size_t)(y + 0) * Q * 8];
-            a1 += p0[(size_t)(y + 1) * Q * 8];
-            a2 += p0[(size_t)(y + 2) * Q * 8];
-            a3 += p0[(size_t)(y + 3) * Q * 8];
+    gn_group_reduce(red, colsum, gsum, sd, t, RL, Q, CB, GPB, cpg);
+    float mu[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mu[j] = gsum[gl[j]] / n;
+    float4 qd = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < NR; ++k)
+        if (ty + RL * k < HW) {
+            const float d0 = v[k].x - mu[0], d1 = v[k].y - mu[1], d2 = v[k].z - mu[2], d3 = v[k].w - mu[3];
+            qd.x += d0 * d0;
+            qd.y += d1 * d1;
+            qd.z += d2 * d2;
+            qd.w += d3 * d3;
         }
-        for (; y < RL; ++y) a0 += p0[(size_t)y * Q * 8];
-        colsum[t] = (a0 + a1) + (a2 + a3);
-    }
-    __syncthreads();
-    if (t < GPB) {
-        float s = 0.f, q = 0.f;
-        for (int i = 0; i < cpg; ++i) {
-            s += colsum[t * cpg + i];
-            q += colsum[CB + t * cpg + i];
-        }
-        const int c0 = c_lo + t * cpg;
-        const float pv = c0 < C1 ? x1[(long long)b * HW * ld1 + c0] : x2[(long long)b * HW * ld2 + (c0 - C1)];
-        const float n = (float)HW * (float)cpg;
-        const float sm = s / n, qm = q / n;
-        const float var = fmaxf(qm - sm * sm, 0.f);
-        gstat[2 * t] = pv + sm;
-        gstat[2 * t + 1] = 1.f / sqrtf(var + eps);
-    }
-    __syncthreads();
+    gn_group_reduce(red, colsum, gsq, qd, t, RL, Q, CB, GPB, cpg);
     float sc[4], sh[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        sc[j] = gamma[c + j] * gstat[2 * gl[j] + 1];
-        sh[j] = beta[c + j] - gstat[2 * gl[j]] * sc[j];
+        const float var = fmaxf(gsq[gl[j]] / n, 0.f);
+        sc[j] = gamma[c + j] * (1.f / sqrtf(var + eps));
+        sh[j] = beta[c + j] - mu[j] * sc[j];
     }
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
@@ -312,7 +330,7 @@ GnFusedPlan gn_fused_plan(int C, int C1, int HW, int groups) {
             pl.gpb = gpb;
             pl.nr = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : need <= 12 ? 12 : 16;
             pl.threads = RL * Q;
-            pl.lds = ((size_t)RL * Q * 8 + 2 * CB + 2 * gpb) * sizeof(float);
+            pl.lds = ((size_t)RL * Q * 4 + 2 * CB + 2 * gpb) * sizeof(float);
             return pl;
         }
     return pl;

@@ -428,6 +428,21 @@ int maa_op_attention(maa_ctx* ctx, const float* d_q, const float* d_k, const flo
 int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const float* d_k, int ldk, int hsk,
                         const float* d_v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
                         float* d_y, int ldo, int out_split, int causal);
+/* GroupNorm exactly as the models call it (tests of the normalisation kernels), on channels-last DEVICE buffers the caller has
+ * laid out: rows of d_x1 [B,HW,*] have pitch ld1 >= C1 floats and hold channels 0 .. C1; the optional second source d_x2
+ * [B,HW,*] (pitch ld2 >= C2; NULL with C2 = 0 for none) holds channels C1 .. C1+C2 -- a decoder ResBlock's (h | skip) without
+ * the concatenation.  gamma / beta [C1+C2] on the HOST.  d_y [B,HW,C] is written as the kernels write it: fp32 rows, or split32
+ * rows with out_split = 1 (per 32 channels: 32 bf16 high halves, then 32 bf16 low halves; C % 32 == 0).  d_raw (or NULL)
+ * [B,HW,C] receives the un-normalised rows in the split32 form.  No layout kernels run in between. */
+int maa_op_groupnorm_ex(maa_ctx* ctx, const float* d_x1, int ld1, int C1, const float* d_x2, int ld2, int C2, int B, int HW,
+                        int groups, const float* h_gamma, const float* h_beta, float eps, int silu, float* d_y, int out_split,
+                        float* d_raw);
+/* maa_op_layernorm with the kernels' out_split argument (1: d_y [rows,C] as split32 rows, C % 32 == 0) */
+int maa_op_layernorm_ex(maa_ctx* ctx, const float* d_x, int rows, int C, const float* h_gamma, const float* h_beta, float eps,
+                        float* d_y, int out_split);
+/* The split32 row codec on its own, d_x / d_y [rows,C] on the device, C % 32 == 0: unpack = 0 writes the split32 rows of
+ * leaky_relu(x, slope) (slope 1: of x), unpack = 1 reads split32 rows and writes hi + lo as fp32 (slope is ignored). */
+int maa_op_split32(maa_ctx* ctx, const float* d_x, int rows, int C, float slope, int unpack, float* d_y);
 /* ConvTranspose1d, d_x [B,Cin,L], torch weight [Cin,Cout,k] on the HOST, padding (k-stride)/2 -> [B,Cout,L*stride].
  * Runs as polyphase GEMMs and refuses what they do not cover: k a multiple of stride, k - stride even, and
  * (stride - 1 + (k - stride) / 2) / stride <= 1 (every k = stride, 2 stride, 3 stride with k - stride even passes). */

@@ -59,3 +59,19 @@ def test_null_arguments_are_rejected(lib_path):
     assert lib.maa_unet_forward(None, None, None, None, 1, 1, 1, None) < 0
     assert lib.maa_vocoder_forward(None, None, None, 1, 1, None) < 0
     assert b"null" in lib.maa_last_error() or b"bad" in lib.maa_last_error()
+
+
+def test_normalisation_test_entries_are_bound_and_reject_null(lib_path):
+    """maa_op_groupnorm_ex / maa_op_layernorm_ex / maa_op_split32 (tests/test_gpu_norm_ops.py) are declared, exported, bound
+    with the header's argument counts, and fail with a message on null arguments."""
+    from audiogpt_amd import _lib
+    lib = _lib.load()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "maa.h")).read(), flags=re.S)
+    for name in ("maa_op_groupnorm_ex", "maa_op_layernorm_ex", "maa_op_split32"):
+        assert name in _lib.EXPORTS and name in _declared_symbols()
+        decl = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
+        assert len(getattr(lib, name).argtypes) == len(decl.split(",")), name
+    assert lib.maa_op_groupnorm_ex(None, None, 0, 0, None, 0, 0, 1, 1, 32, None, None, 1e-5, 0, None, 0, None) < 0
+    assert lib.maa_op_layernorm_ex(None, None, 1, 4, None, None, 1e-5, None, 0) < 0
+    assert lib.maa_op_split32(None, None, 1, 32, 1.0, 0, None) < 0
+    assert len(lib.maa_last_error()) > 0
