@@ -46,7 +46,9 @@ class maa_ddim_args(C.Structure):
                 ("d_mask", C.c_void_p), ("d_x0", C.c_void_p), ("d_noise_q", C.c_void_p),
                 ("h_sqrt_ac", C.POINTER(C.c_float)), ("h_sqrt_1mac", C.POINTER(C.c_float)),
                 ("h_sigmas", C.POINTER(C.c_float)), ("d_noise_p", C.c_void_p), ("temperature", C.c_float),
-                ("log_every_t", C.c_int), ("n_log", C.c_int), ("d_log_x", C.c_void_p), ("d_log_x0", C.c_void_p)]
+                ("log_every_t", C.c_int), ("n_log", C.c_int), ("d_log_x", C.c_void_p), ("d_log_x0", C.c_void_p),
+                ("split_kh", C.c_int), ("split_kw", C.c_int), ("split_sh", C.c_int), ("split_sw", C.c_int),
+                ("h_split_weight", C.POINTER(C.c_float))]
 
 
 class maa_vae_config(C.Structure):
@@ -106,6 +108,7 @@ EXPORTS = [
     "maa_resampler_forward", "maa_op_linear", "maa_op_conv", "maa_op_groupnorm", "maa_op_layernorm",
     "maa_op_attention", "maa_op_attention_ex", "maa_op_conv_transpose1d", "maa_op_snake_aa", "maa_op_bench_conv", "maa_calib",
     "maa_op_mrf_pair", "maa_op_groupnorm_ex", "maa_op_layernorm_ex", "maa_op_split32",
+    "maa_unet_forward_split", "maa_op_unfold", "maa_op_fold",
 ]
 
 _lib = None
@@ -188,6 +191,9 @@ def load():
         "maa_op_groupnorm_ex": [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, fp, fp, cf, ci, vp, ci, vp],
         "maa_op_layernorm_ex": [vp, vp, ci, ci, fp, fp, cf, vp, ci],
         "maa_op_split32": [vp, vp, ci, ci, cf, ci, vp],
+        "maa_unet_forward_split": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, fp, vp],
+        "maa_op_unfold": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp],
+        "maa_op_fold": [vp, vp, fp, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)

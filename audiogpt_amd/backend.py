@@ -231,6 +231,28 @@ class Context:
         L.check(self.lib.maa_op_split32(self.h, L.dptr(x), rows, Cc, float(slope), int(unpack), L.dptr(y)))
         return y
 
+    def op_unfold(self, x, ks, stride):
+        """maa_op_unfold: x [B, C, H, W] -> the crops [B * L, C, kh, kw] of split_input_params (torch.nn.Unfold's order)."""
+        x = _f32(x, self.device)
+        B, Cc, H, W = x.shape
+        (kh, kw), (sh, sw) = ks, stride
+        n = ((H - kh) // sh + 1) * ((W - kw) // sw + 1) if min(kh, kw, sh, sw) > 0 else 0
+        y = torch.empty(B * max(n, 0), Cc, kh, kw, device=self.device)
+        L.check(self.lib.maa_op_unfold(self.h, L.dptr(x), B, Cc, H, W, kh, kw, sh, sw, L.dptr(y)))
+        return y
+
+    def op_fold(self, crops, weight, size, ks, stride):
+        """maa_op_fold: crops [B * L, C, kh, kw], weight [kh * kw, L] -> [B, C, H, W] = fold(crops * weight) / fold(weight)."""
+        crops = _f32(crops, self.device)
+        (H, W), (kh, kw), (sh, sw) = size, ks, stride
+        wt, wp = L.host_f32(weight)
+        n = wt.shape[1]
+        assert wt.shape[0] == kh * kw and crops.shape[0] % n == 0 and tuple(crops.shape[2:]) == (kh, kw)
+        B, Cc = crops.shape[0] // n, crops.shape[1]
+        y = torch.empty(B, Cc, H, W, device=self.device)
+        L.check(self.lib.maa_op_fold(self.h, L.dptr(crops), wp, B, Cc, H, W, kh, kw, sh, sw, L.dptr(y)))
+        return y
+
     def op_conv_transpose1d(self, x, w, b, stride, leaky=0.0):
         x = _f32(x, self.device)
         B, Cin, Ln = x.shape
@@ -302,6 +324,39 @@ class UNet:
             L.check(ctx.lib.maa_unet_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
         self.h = h
         self._context = None
+        self._context_len = None
+
+    def split_plan(self, split, H, W, concat=False):
+        """The SplitPlan (ldm/split.py) of the reference's `split_input_params` dictionary -- or a plan already made -- for an
+        [*, *, H, W] latent on this UNet; None for None.  Raises MaaError for what the reference cannot compute."""
+        from .ldm import split as SP
+        if split is None or isinstance(split, SP.SplitPlan):
+            return split
+        return SP.plan(split, H, W, down=SP.unet_down_factor(self.cfg), conditioning_key="concat" if concat else "crossattn")
+
+    def forward_split(self, x, t, context, split):
+        """One model evaluation with split_input_params (maa_unet_forward_split; ddpm_audio.py:572-654): the UNet on the
+        overlapping crops of x [B, C, H, W] as one batch, stitched with the border-distance weighting.  The context's K/V are
+        projected once for the B samples."""
+        x = _f32(x, self.ctx.device)
+        B, _, H, W = x.shape
+        sp = self.split_plan(split, H, W, concat=not self.cfg["use_spatial_transformer"])
+        tf = t.to(device=self.ctx.device, dtype=torch.float32).contiguous()
+        cp = None
+        if context is not None:
+            context = _f32(context, self.ctx.device)
+            if context.dim() != 3 or context.shape[0] != B:
+                raise L.MaaError("forward_split: context must be [B=%d, L, context_dim], got %s" % (B, tuple(context.shape)))
+            if self._context_len != context.shape[1]:
+                self.set_context(context)          # (fixes the token count the C entry reads the context with)
+            cp = L.dptr(context)
+        out = torch.empty(B, self.cfg["out_channels"], H, W, device=self.ctx.device)
+        wp = C.cast(sp.weight.data_ptr(), C.POINTER(C.c_float))
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_unet_forward_split(self.ctx.h, self.h, L.dptr(x), L.dptr(tf), cp, B, H, W, sp.kh, sp.kw,
+                                                        sp.sh, sp.sw, wp, L.dptr(out)))
+        self._context = None          # the library's context is now the tiled one: a plain forward sets its own again
+        return out
 
     def set_context(self, context):
         """context [B, L, context_dim] on the device; K/V projections are cached for the next forwards."""
@@ -310,6 +365,7 @@ class UNet:
         B, Ln, _ = context.shape
         with self.ctx.lock:
             L.check(self.ctx.lib.maa_unet_set_context(self.ctx.h, self.h, L.dptr(context), B, Ln))
+        self._context_len = Ln
 
     def forward(self, x, t, context=None):
         """UNetModel.forward(x, timesteps, context) (openaimodel.py:711-744)."""
@@ -325,7 +381,7 @@ class UNet:
 
     __call__ = forward
 
-    def _ddim_args(self, what, x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep):
+    def _ddim_args(self, what, x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep, split=None):
         """maa_ddim_args for the latent x (on the device) and the S-step schedule, with the conditioning checked and kept alive in
         `keep`; `what` names the caller in the messages."""
         dev = self.ctx.device
@@ -369,36 +425,47 @@ class UNet:
         a.h_alphas = al.ctypes.data_as(C.POINTER(C.c_float))
         a.h_alphas_prev = ap.ctypes.data_as(C.POINTER(C.c_float))
         a.use_graph = int(use_graph)
+        sp = self.split_plan(split, H, W, concat=concat is not None)
+        if sp is not None:
+            # split_input_params (ldm/split.py): crop size, stride and the host weighting [kh * kw, L]
+            keep.append(sp)
+            a.split_kh, a.split_kw, a.split_sh, a.split_sw = sp.kh, sp.kw, sp.sh, sp.sw
+            a.h_split_weight = C.cast(sp.weight.data_ptr(), C.POINTER(C.c_float))
+        self._context_len = None          # (a loop sets the library's context itself: forward_split must not trust the old length)
         return a, B, Cc, H, W
 
     def ddim_sample(self, x_T, timesteps, alphas, alphas_prev, cond=None, uncond=None, scale=1.0, concat=None,
                     use_graph=True, mask=None, x0=None, noise_q=None, sqrt_ac=None, sqrt_1mac=None, sigmas=None,
-                    noise_p=None, temperature=1.0, log_every_t=None):
+                    noise_p=None, temperature=1.0, log_every_t=None, split=None):
         """Whole DDIM trajectory on the device (ddim.py:118-225).  Returns x_0, or (x_0, x_inter, pred_x0) when
         log_every_t is given (the two logs as [n_log, B, C, H, W] tensors, ddim.py:158-163).
+        split: the reference's `split_input_params` dictionary (or a SplitPlan of ldm/split.py): every model evaluation
+        runs on overlapping crops of the latent and is stitched (ddpm_audio.py:572-654); crossattn models only.
         mask / x0 / noise_q [S, B, C, H, W] / sqrt_ac, sqrt_1mac [S]: the mask blend of ddim.py:147-150;
         sigmas [S] / noise_p [S, B, C, H, W] / temperature: the eta > 0 noise term of ddim.py:210-225.  Noise tensors
         are in loop order (first step first)."""
         return self._sample("ddim_sample", self.ctx.lib.maa_ddim_sample, x_T, timesteps, alphas, alphas_prev, cond, uncond, scale,
-                            concat, use_graph, mask, x0, noise_q, sqrt_ac, sqrt_1mac, sigmas, noise_p, temperature, log_every_t)
+                            concat, use_graph, mask, x0, noise_q, sqrt_ac, sqrt_1mac, sigmas, noise_p, temperature, log_every_t,
+                            split)
 
     def plms_sample(self, x_T, timesteps, alphas, alphas_prev, cond=None, uncond=None, scale=1.0, concat=None,
-                    use_graph=True, mask=None, x0=None, noise_q=None, sqrt_ac=None, sqrt_1mac=None, log_every_t=None):
+                    use_graph=True, mask=None, x0=None, noise_q=None, sqrt_ac=None, sqrt_1mac=None, log_every_t=None, split=None):
         """Whole PLMS trajectory on the device (PLMSSampler.plms_sampling, plms.py:115-236) through maa_ldm_plms_sample:
         the pseudo improved Euler step, then Adams-Bashforth steps of order up to 4; S steps make S + 1 UNet evaluations.
         Arguments and return value as ddim_sample's with eta 0 (PLMS has no noise term): the same tables, conditioning,
         mask / x0 / noise_q [S, B, C, H, W] / sqrt_ac, sqrt_1mac [S] blend before each step's first evaluation, and the logs
-        of the final x_prev / pred_x0 of the logged steps."""
+        of the final x_prev / pred_x0 of the logged steps; split as ddim_sample's."""
         return self._sample("plms_sample", self.ctx.lib.maa_ldm_plms_sample, x_T, timesteps, alphas, alphas_prev, cond, uncond,
-                            scale, concat, use_graph, mask, x0, noise_q, sqrt_ac, sqrt_1mac, None, None, 1.0, log_every_t)
+                            scale, concat, use_graph, mask, x0, noise_q, sqrt_ac, sqrt_1mac, None, None, 1.0, log_every_t, split)
 
     def _sample(self, what, entry, x_T, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, mask, x0, noise_q,
-                sqrt_ac, sqrt_1mac, sigmas, noise_p, temperature, log_every_t):
+                sqrt_ac, sqrt_1mac, sigmas, noise_p, temperature, log_every_t, split=None):
         """ddim_sample / plms_sample: the maa_ddim_args of a whole trajectory, the C entry `entry` on them and the logs."""
         dev = self.ctx.device
         x = _f32(x_T, dev).clone()
         keep = []
-        a, B, Cc, H, W = self._ddim_args(what, x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep)
+        a, B, Cc, H, W = self._ddim_args(what, x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep,
+                                         split)
         S = a.S
 
         def host_table(v, name):
@@ -464,15 +531,16 @@ class UNet:
         return x
 
     def ddim_decode(self, x_latent, t_start, timesteps, alphas, alphas_prev, cond=None, uncond=None, scale=1.0, concat=None,
-                    use_graph=True, sigmas=None, noise_p=None, temperature=1.0):
-        """DDIMSampler.decode (ddim.py:243-261) on the device: the DDIM steps of indices t_start - 1 .. 0 of the S-step schedule
+                    use_graph=True, sigmas=None, noise_p=None, temperature=1.0, split=None):
+        """DDIMSampler.decode (ddim.py:243-261) on the device (split as ddim_sample's): the DDIM steps of indices t_start - 1 .. 0 of the S-step schedule
         (timesteps / alphas / alphas_prev as for ddim_sample) from x_latent; t_start = 0 returns a copy of x_latent.  Guidance and
         concat conditioning as for ddim_sample; sigmas [S] / noise_p [t_start, B, C, H, W] (loop order) / temperature: the eta > 0
         term.  With the same S, shapes and guidance as the last ddim_sample on this context the kept step graph is replayed."""
         dev = self.ctx.device
         x = _f32(x_latent, dev).clone()
         keep = []
-        a, B, Cc, H, W = self._ddim_args("ddim_decode", x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep)
+        a, B, Cc, H, W = self._ddim_args("ddim_decode", x, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, keep,
+                                         split)
         S = a.S
         t_start = int(t_start)
         if not 0 <= t_start <= S:

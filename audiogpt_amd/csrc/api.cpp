@@ -290,6 +290,18 @@ int maa_unet_forward(maa_ctx* ctx, maa_unet* u, const float* d_x, const float* d
     });
 }
 
+// (the arguments are checked before the context is bound: a malformed call fails the same way with or without a device)
+int maa_unet_forward_split(maa_ctx* ctx, maa_unet* u, const float* d_x, const float* d_t, const float* d_context, int B, int H, int W,
+                           int kh, int kw, int sh, int sw, const float* h_weight, float* d_out) {
+    return guarded([&] {
+        MAA_CHECK(u && d_x && d_t && h_weight && d_out, "bad forward_split arguments: null pointer");
+        MAA_CHECK(B > 0, "bad forward_split arguments: empty batch");
+        maa::split_check(H, W, kh, kw, sh, sw);
+        bind(ctx);
+        maa::unet_forward_split(ctx->c, *u->m, d_x, d_t, d_context, B, H, W, kh, kw, sh, sw, h_weight, d_out);
+    });
+}
+
 int maa_ddim_update(maa_ctx* ctx, const float* d_x, const float* d_eps_uncond, const float* d_eps_cond, float scale,
                     const float* d_coef, int64_t n, float* d_x_prev, float* d_pred_x0) {
     return guarded([&] {
@@ -774,6 +786,38 @@ int maa_op_split32(maa_ctx* ctx, const float* d_x, int rows, int C, float slope,
             maa::launch_split32_unpack(c, d_x, rows, C, d_y);
         else
             maa::launch_split32_pack(c, d_x, rows, C, d_y, slope);
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
+int maa_op_unfold(maa_ctx* ctx, const float* d_x, int B, int C, int H, int W, int kh, int kw, int sh, int sw, float* d_out) {
+    return guarded([&] {
+        MAA_CHECK(d_x && d_out && d_x != d_out, "bad op_unfold arguments: null pointer");
+        MAA_CHECK(B > 0 && C > 0, "bad op_unfold arguments: empty batch");
+        maa::split_check(H, W, kh, kw, sh, sw);
+        bind(ctx);
+        maa::launch_split_unfold(ctx->c, d_x, B, C, H, W, kh, kw, sh, sw, d_out);
+        MAA_HIP(hipStreamSynchronize(ctx->c.stream));
+    });
+}
+
+int maa_op_fold(maa_ctx* ctx, const float* d_crops, const float* h_weight, int B, int C, int H, int W, int kh, int kw, int sh, int sw,
+                float* d_out) {
+    return guarded([&] {
+        MAA_CHECK(d_crops && h_weight && d_out && d_crops != d_out, "bad op_fold arguments: null pointer");
+        MAA_CHECK(B > 0 && C > 0, "bad op_fold arguments: empty batch");
+        maa::split_check(H, W, kh, kw, sh, sw);
+        bind(ctx);
+        maa::Ctx& c = ctx->c;
+        const int L = maa::split_crops(H, W, kh, kw, sh, sw);
+        const size_t kk = (size_t)kh * kw, n_w = (kk * L + 63) / 64 * 64;
+        float* slab = static_cast<float*>(c.split_scratch.get((n_w + (size_t)H * W) * sizeof(float), c.stream));
+        std::vector<float> h_wT(kk * L);      // the kernels read the weighting as [L][kh * kw]
+        for (size_t p = 0; p < kk; ++p)
+            for (int l = 0; l < L; ++l) h_wT[(size_t)l * kk + p] = h_weight[p * L + l];
+        MAA_HIP(hipMemcpyAsync(slab, h_wT.data(), h_wT.size() * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        maa::launch_split_norm(c, slab, H, W, kh, kw, sh, sw, slab + n_w);
+        maa::launch_split_fold(c, d_crops, slab, slab + n_w, B, C, H, W, kh, kw, sh, sw, d_out);
         MAA_HIP(hipStreamSynchronize(c.stream));
     });
 }

@@ -41,13 +41,17 @@ struct Loop {
     Ctx& ctx;
     UNet& unet;
     const maa_ddim_args& a;
-    bool concat, cfg, masked, logging, emb_hoist, share;
+    bool concat, cfg, masked, logging, emb_hoist, share, split;
     int nB, Cin;
+    int crops, rows;                // split_input_params: crops per sample (1 without), UNet rows per step = nB * crops
+    long long per_crop, per_crop_in;      // elements of one crop row of the UNet's output / input
     long long per, per_in;          // latent elements per sample, UNet input elements per sample
     size_t emb_w;
-    std::vector<float> h_tab;       // (h_tab and h_step are read by async copies: they live until the loop's final synchronisation)
+    std::vector<float> h_tab;       // (h_tab, h_wT and h_step are read by async copies: they live until the loop's final synchronisation)
+    std::vector<float> h_wT;        // the split's weighting transposed, [L][kh * kw]
     int h_step;
     float *slab, *tab_t, *tab_coef, *cur_t, *cur_coef, *xin, *eps, *xs, *ccs, *emb_tab, *cur_emb;
+    float *wT = nullptr, *norm = nullptr, *zin = nullptr, *ecrop = nullptr;      // split: weighting, its fold, crop input, crop eps
     int* d_step;
     Ctx* lane2;
 
@@ -62,6 +66,15 @@ struct Loop {
         per = (long long)a.C * a.H * a.W;
         per_in = (long long)Cin * a.H * a.W;
         MAA_CHECK(unet.config().in_channels == Cin, "ddim: UNet in_channels does not match latent (+concat) channels");
+        // split_input_params (ddpm_audio.py:572-654): every model evaluation runs on overlapping crops of the latent
+        split = a.split_kh != 0 || a.split_kw != 0 || a.split_sh != 0 || a.split_sw != 0 || a.h_split_weight != nullptr;
+        MAA_CHECK(!split || (a.split_kh > 0 && a.split_kw > 0 && a.split_sh > 0 && a.split_sw > 0 && a.h_split_weight),
+                  "ddim: the split needs ks, stride and the weighting (all zero / NULL: no split)");
+        MAA_CHECK(!split || !concat, "ddim: a concat-conditioned model cannot be split (every crop would get the full-size concat tensor)");
+        crops = split ? split_crops(a.H, a.W, a.split_kh, a.split_kw, a.split_sh, a.split_sw) : 1;
+        rows = nB * crops;
+        per_crop = split ? (long long)a.C * a.split_kh * a.split_kw : per;
+        per_crop_in = split ? (long long)Cin * a.split_kh * a.split_kw : per_in;
 
         // ---- device state of the loop, in one slab the context keeps across calls: tables (one row per DDIM index), the
         // device step index, the step's timestep / coefficient slots, UNet input and output
@@ -94,11 +107,24 @@ struct Loop {
         // variant adds the sample's context to the embedding and keeps the per-forward computation): six launches leave every step
         emb_hoist = !unet.config().add_context_to_emb;
         emb_w = emb_hoist ? (size_t)unet.emb_width() : 0;
-        const size_t o_tab = 0, o_step = o_tab + up(h_tab.size()), o_t = o_step + 64, o_coef = o_t + up(nB),
+        // (the split's pieces follow the others: the weighting, its fold, the crop rows of the UNet's input and output; the
+        // timestep slots hold one per crop row)
+        const size_t kk = split ? (size_t)a.split_kh * a.split_kw : 0;
+        const size_t o_tab = 0, o_step = o_tab + up(h_tab.size()), o_t = o_step + 64, o_coef = o_t + up(rows),
                      o_xin = o_coef + 64, o_eps = o_xin + up((size_t)nB * per_in), o_x = o_eps + up((size_t)nB * per),
                      o_cc = o_x + up((size_t)a.B * per), o_embt = o_cc + up(n_cc), o_emb = o_embt + up((size_t)a.S * emb_w),
-                     total = o_emb + up(emb_w);
+                     o_wT = o_emb + up(emb_w), o_norm = o_wT + up(kk * crops), o_zin = o_norm + up(split ? (size_t)a.H * a.W : 0),
+                     o_ecrop = o_zin + up(split ? (size_t)rows * per_crop_in : 0),
+                     total = o_ecrop + up(split ? (size_t)rows * per_crop : 0);
         slab = static_cast<float*>(ctx.sampler_scratch.get(total * sizeof(float), ctx.stream));
+        if (split) {
+            wT = slab + o_wT, norm = slab + o_norm, zin = slab + o_zin, ecrop = slab + o_ecrop;
+            h_wT.resize(kk * crops);
+            for (size_t p = 0; p < kk; ++p)
+                for (int l = 0; l < crops; ++l) h_wT[(size_t)l * kk + p] = a.h_split_weight[p * crops + l];
+            MAA_HIP(hipMemcpyAsync(wT, h_wT.data(), h_wT.size() * 4, hipMemcpyHostToDevice, ctx.stream));
+            launch_split_norm(ctx, wT, a.H, a.W, a.split_kh, a.split_kw, a.split_sh, a.split_sw, norm);
+        }
         tab_t = slab + o_tab, tab_coef = slab + o_tab + a.S, cur_t = slab + o_t, cur_coef = slab + o_coef, xin = slab + o_xin,
         eps = slab + o_eps, xs = slab + o_x, ccs = slab + o_cc, emb_tab = slab + o_embt, cur_emb = slab + o_emb;
         // the trajectory runs on the slab's copy of the latent (and of the concat conditioning)
@@ -111,12 +137,12 @@ struct Loop {
 
         if (emb_hoist) unet.emb_table(ctx, tab_t, a.S, emb_tab);      // (tab_t: the S timesteps as floats, uploaded above)
 
-        // ---- conditioning: constant over the trajectory -> project K/V once
+        // ---- conditioning: constant over the trajectory -> project K/V once (split: once per sample, served to its crops)
         if (!concat && a.d_cond) {
             if (cfg)
-                unet.set_context_cfg(ctx, a.d_uncond, a.d_cond, a.B, a.L);
+                unet.set_context_cfg(ctx, a.d_uncond, a.d_cond, a.B, a.L, crops);
             else
-                unet.set_context(ctx, a.d_cond, nB, a.L);
+                unet.set_context(ctx, a.d_cond, nB, a.L, crops);
         }
 
         // Classifier-free guidance: the reference evaluates the model once on cat([x] * 2) (ddim.py:177-199); the two halves are
@@ -137,23 +163,35 @@ struct Loop {
     // the step's UNet input (cat([x] * 2) / cat([x, c]), the mask blend) and its timestep / coefficient / embedding slots
     void prepare() {
         launch_ddim_prepare(ctx, xs, concat ? ccs : nullptr, a.B, nB, per, per_in - per, tab_t, tab_coef, d_step, xin, cur_t,
-                            cur_coef, a.d_mask, a.d_x0, a.d_noise_q, a.S, emb_hoist ? emb_tab : nullptr, (int)emb_w, cur_emb);
+                            cur_coef, a.d_mask, a.d_x0, a.d_noise_q, a.S, emb_hoist ? emb_tab : nullptr, (int)emb_w, cur_emb, rows);
     }
 
-    // eps = UNet(xin, cur_t) over nB rows (with CFG: [uncond ; cond], on one stream or as two lanes)
+    // eps = UNet(xin, cur_t) over nB rows (with CFG: [uncond ; cond], on one stream or as two lanes).  With the split the UNet
+    // runs over the nB * crops crop rows of xin -- unfold keeps each half's rows together, so the halves, the shared prefix and
+    // the lanes are what they are without it -- and fold stitches its output into eps.
     void forward() {
+        const float* in = xin;
+        float* out = eps;
+        int h = a.H, w = a.W;
+        if (split) {
+            launch_split_unfold(ctx, xin, nB, Cin, a.H, a.W, a.split_kh, a.split_kw, a.split_sh, a.split_sw, zin);
+            in = zin, out = ecrop, h = a.split_kh, w = a.split_kw;
+        }
+        const int half = a.B * crops;      // UNet rows of one half of a guided step
         if (lane2) {
             MAA_HIP(hipEventRecord(ctx.ev_fork, ctx.stream));
             MAA_HIP(hipStreamWaitEvent(lane2->stream, ctx.ev_fork, 0));
             // (the conditional lane starts from the unconditional lane's layers before the first cross-attention: unet.cpp)
-            unet.forward(ctx, xin, cur_t, unet.context_ptr, a.B, a.H, a.W, eps, emb_hoist ? cur_emb : nullptr, 0, share ? 2 : 0);
-            unet.forward(*lane2, xin + (size_t)a.B * per_in, cur_t + a.B, unet.context_ptr, a.B, a.H, a.W, eps + (size_t)a.B * per,
-                         emb_hoist ? cur_emb : nullptr, a.B, share ? 3 : 0);
+            unet.forward(ctx, in, cur_t, unet.context_ptr, half, h, w, out, emb_hoist ? cur_emb : nullptr, 0, share ? 2 : 0);
+            unet.forward(*lane2, in + (size_t)half * per_crop_in, cur_t + half, unet.context_ptr, half, h, w,
+                         out + (size_t)half * per_crop, emb_hoist ? cur_emb : nullptr, half, share ? 3 : 0);
             MAA_HIP(hipEventRecord(ctx.ev_join, lane2->stream));
             MAA_HIP(hipStreamWaitEvent(ctx.stream, ctx.ev_join, 0));
         } else
             // (one stream: the halves of cat([x] * 2) share every layer before the first cross-attention -- unet.cpp `dup`)
-            unet.forward(ctx, xin, cur_t, unet.context_ptr, nB, a.H, a.W, eps, emb_hoist ? cur_emb : nullptr, -1, share ? 1 : 0);
+            unet.forward(ctx, in, cur_t, unet.context_ptr, rows, h, w, out, emb_hoist ? cur_emb : nullptr, -1, share ? 1 : 0);
+        if (split)
+            launch_split_fold(ctx, ecrop, wT, norm, nB, a.C, a.H, a.W, a.split_kh, a.split_kw, a.split_sh, a.split_sw, eps);
     }
 
     // Everything a captured step depends on besides the device-side state it reads: the model and its own buffers, the
@@ -185,7 +223,10 @@ struct Loop {
                                      // the second lane of a CFG step: its stream and workspace are part of the captured step
                                      (unsigned long long)reinterpret_cast<uintptr_t>(lane2 ? lane2->stream : nullptr),
                                      (unsigned long long)reinterpret_cast<uintptr_t>(lane2 ? lane2->ws.base() : nullptr),
-                                     (unsigned long long)(lane2 ? lane2->ws.capacity() : 0)})
+                                     (unsigned long long)(lane2 ? lane2->ws.capacity() : 0),
+                                     // the split: a step with it launches other kernels on other shapes than one without
+                                     (unsigned long long)a.split_kh, (unsigned long long)a.split_kw, (unsigned long long)a.split_sh,
+                                     (unsigned long long)a.split_sw, (unsigned long long)reinterpret_cast<uintptr_t>(wT)})
             k.push_back(v);
         return k;
     }
@@ -299,7 +340,7 @@ void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
         lp.prepare();
         lp.forward();
         launch_ldm_plms_euler_mid(ctx, lp.xin, lp.per, lp.per_in, a.B, lp.nB, lp.eps, eps_c, a.scale, lp.cur_coef, lp.xs, ring,
-                                  lp.tab_t, lp.cur_t, lp.emb_hoist ? lp.emb_tab : nullptr, (int)lp.emb_w, lp.cur_emb);
+                                  lp.tab_t, lp.cur_t, lp.emb_hoist ? lp.emb_tab : nullptr, (int)lp.emb_w, lp.cur_emb, lp.rows);
         lp.forward();
         launch_ldm_plms_euler_final(ctx, lp.eps, eps_c, a.scale, lp.cur_coef, n, lp.xs, ring, log_x, log_x0, lp.d_step);
     };
@@ -336,6 +377,37 @@ void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
     }
     MAA_HIP(hipMemcpyAsync(d_x, lp.xs, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx.stream));
     MAA_HIP(hipStreamSynchronize(ctx.stream));
+}
+
+// One evaluation of the model with split_input_params (ddpm_audio.py:572-654) outside a loop: what Loop::forward does per step,
+// on the caller's x / t / context.  Its device state lives in the context's split_scratch: [wT | norm | crop input | crop eps | t].
+void unet_forward_split(Ctx& ctx, UNet& unet, const float* d_x, const float* d_t, const float* d_context, int B, int H, int W, int kh,
+                        int kw, int sh, int sw, const float* h_weight, float* d_out) {
+    const maa_unet_config& uc = unet.config();
+    const int L = split_crops(H, W, kh, kw, sh, sw);
+    const size_t kk = (size_t)kh * kw;
+    const long long rows = (long long)B * L;
+    MAA_CHECK(rows <= (1 << 20), "forward_split: too many crop rows");
+    if (uc.use_spatial_transformer) {
+        MAA_CHECK(d_context && unet.context_len() > 0,
+                  "forward_split: this UNet needs d_context, [B, L, context_dim] with the token count L of an earlier maa_unet_set_context");
+        unet.set_context(ctx, d_context, B, unet.context_len(), L);
+    }
+    auto up = [](size_t n) { return (n + 63) / 64 * 64; };
+    const size_t o_wT = 0, o_norm = o_wT + up(kk * L), o_zin = o_norm + up((size_t)H * W),
+                 o_e = o_zin + up((size_t)rows * uc.in_channels * kk), o_t = o_e + up((size_t)rows * uc.out_channels * kk),
+                 total = o_t + up((size_t)rows);
+    float* slab = static_cast<float*>(ctx.split_scratch.get(total * sizeof(float), ctx.stream));
+    std::vector<float> h_wT(kk * L);
+    for (size_t p = 0; p < kk; ++p)
+        for (int l = 0; l < L; ++l) h_wT[(size_t)l * kk + p] = h_weight[p * L + l];
+    MAA_HIP(hipMemcpyAsync(slab + o_wT, h_wT.data(), h_wT.size() * 4, hipMemcpyHostToDevice, ctx.stream));
+    MAA_HIP(hipStreamSynchronize(ctx.stream));      // (h_wT goes out of scope; everything after is asynchronous)
+    launch_split_norm(ctx, slab + o_wT, H, W, kh, kw, sh, sw, slab + o_norm);
+    launch_repeat_rows(ctx, d_t, B, 1, L, slab + o_t);
+    launch_split_unfold(ctx, d_x, B, uc.in_channels, H, W, kh, kw, sh, sw, slab + o_zin);
+    unet.forward(ctx, slab + o_zin, slab + o_t, unet.context_ptr, (int)rows, kh, kw, slab + o_e);
+    launch_split_fold(ctx, slab + o_e, slab + o_wT, slab + o_norm, B, uc.out_channels, H, W, kh, kw, sh, sw, d_out);
 }
 
 // ddim.py:227-241.  The two coefficient tables go up once per call next to an error flag in the context's own slab; the flag is

@@ -154,6 +154,7 @@ struct Ctx {
     DevSlab encode_scratch;   // stochastic_encode's coefficient tables and error flag (apart from the loop's slab, whose address the step graph keeps)
     StepGraph plms_graph;     // the PLMS loop's captured Adams-Bashforth step (steps 1 .. S-1), kept apart from ddim_graph
     DevSlab plms_ring;        // the PLMS loop's ring of three e_t slabs (apart from sampler_scratch, which keeps DDIM's size)
+    DevSlab split_scratch;    // maa_unet_forward_split's weighting, norm, crop rows and their timesteps (apart from the loops' slab)
     Profiler* prof = nullptr;
     float* zeros = nullptr;   // 256 B zero page (device), source of masked tile loads
     int device = 0;
@@ -285,6 +286,16 @@ void launch_avgpool2(const Ctx& ctx, const float* x, int B, int H, int W, int C,
 void launch_upsample2(const Ctx& ctx, const float* x, int B, int H, int W, int C, float* out);
 // out[0 .. n) = out[n .. 2n) = x[0 .. n)   (n % 4 == 0): the two halves of a guided step's batch leave their shared prefix
 void launch_dup_half(const Ctx& ctx, const float* x, long long n, float* out);
+// split_input_params' crop-and-stitch around the UNet (split.hip; ddpm_audio.py:572-654).  split_check throws on a geometry the
+// kernels do not cover (ks larger than the latent, positions in no crop); split_crops = Ly * Lx.  wT: the weighting transposed,
+// [L][kh * kw]; norm [H, W] = its fold.  repeat_rows: src [rows][len] -> dst [rows * rep][len], every row rep times in a row.
+void split_check(int H, int W, int kh, int kw, int sh, int sw);
+int split_crops(int H, int W, int kh, int kw, int sh, int sw);
+void launch_split_unfold(const Ctx& ctx, const float* x, int nB, int C, int H, int W, int kh, int kw, int sh, int sw, float* out);
+void launch_split_norm(const Ctx& ctx, const float* wT, int H, int W, int kh, int kw, int sh, int sw, float* norm);
+void launch_split_fold(const Ctx& ctx, const float* e, const float* wT, const float* norm, int nB, int C, int H, int W, int kh,
+                       int kw, int sh, int sw, float* out);
+void launch_repeat_rows(const Ctx& ctx, const float* src, long long rows, long long len, int rep, float* dst);
 void launch_scale(const Ctx& ctx, const float* x, long long n, float s, float* out);
 // eps = eu + scale*(ec - eu); x0 = (x - somat*eps)/sqrt(a_t); x' = sqrt(a_prev)*x0 + sqrt(1-a_prev-sig^2)*eps
 // coef = device pointer to {a_t, a_prev, sigma, sqrt_one_minus_at}; eps_c may be null (no CFG)
@@ -298,7 +309,7 @@ void launch_ddim_prepare(const Ctx& ctx, const float* x, const float* concat, in
                          long long per_c, const float* tab_t, const float* tab_coef, const int* step, float* xin,
                          float* cur_t, float* cur_coef, const float* mask = nullptr, const float* x0 = nullptr,
                          const float* noise_q = nullptr, int S = 0, const float* emb_tab = nullptr, int emb_w = 0,
-                         float* cur_emb = nullptr);
+                         float* cur_emb = nullptr, int n_t = 0);
 // emb_tab [S][emb_w] / cur_emb [emb_w]: the step's precomputed ResBlock time-embedding row is copied into its fixed slot
 // the loop's update: x from the step's UNet input, optional sigma_t * noise * temperature, logged intermediates, index - 1
 void launch_ddim_step(const Ctx& ctx, const float* xin, long long per, long long per_in, const float* eps_u, const float* eps_c,
@@ -314,7 +325,7 @@ void launch_ldm_plms_step(const Ctx& ctx, const float* xin, long long per, long 
 // channels of all nB rows, cur_t [nB] / cur_emb to t_next = tab_t[max(idx - 1, 0)] (its hoisted embedding row when emb_tab)
 void launch_ldm_plms_euler_mid(const Ctx& ctx, float* xin, long long per, long long per_in, int B, int nB, const float* eps_u,
                                const float* eps_c, float scale, const float* coef, float* x_save, float* e_keep, const float* tab_t,
-                               float* cur_t, const float* emb_tab, int emb_w, float* cur_emb);
+                               float* cur_t, const float* emb_tab, int emb_w, float* cur_emb, int n_t = 0);
 // step 0 after its second evaluation: x = update(x, (e_keep + e_next) / 2) in place, logs, *step = idx - 1
 void launch_ldm_plms_euler_final(const Ctx& ctx, const float* eps_u, const float* eps_c, float scale, const float* coef, long long n,
                                  float* x, const float* e_keep, float* log_x, float* log_x0, int* step);

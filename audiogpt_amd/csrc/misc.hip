@@ -458,10 +458,11 @@ __global__ void ldm_plms_euler_mid_kernel(float* __restrict__ xin, long long per
                                           const float* __restrict__ eu, const float* __restrict__ ec, float scale,
                                           const float* __restrict__ coef, long long n, float* __restrict__ x_save,
                                           float* __restrict__ e_keep, const float* __restrict__ tab_t, float* __restrict__ cur_t,
-                                          const float* __restrict__ emb_tab, int emb_w, float* __restrict__ cur_emb) {
+                                          const float* __restrict__ emb_tab, int emb_w, float* __restrict__ cur_emb, int n_t) {
     const int idx = (int)coef[7];
     const int idx_next = idx > 0 ? idx - 1 : 0;
-    if (blockIdx.x == 0 && threadIdx.x < nB) cur_t[threadIdx.x] = tab_t[idx_next];
+    if (blockIdx.x == 0)      // (n_t = nB, or nB * L rows when the step evaluates the model on crops)
+        for (int k = threadIdx.x; k < n_t; k += blockDim.x) cur_t[k] = tab_t[idx_next];
     if (emb_tab)
         for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < emb_w; k += gridDim.x * blockDim.x)
             cur_emb[k] = emb_tab[(long long)idx_next * emb_w + k];
@@ -523,12 +524,12 @@ __global__ void ddim_prepare_kernel(const float* __restrict__ x, const float* __
                                     const float* __restrict__ tab_coef, const int* __restrict__ step,
                                     float* __restrict__ xin, float* __restrict__ cur_t, float* __restrict__ cur_coef,
                                     const float* __restrict__ mask, const float* __restrict__ x0, const float* __restrict__ noise_q,
-                                    int S, const float* __restrict__ emb_tab, int emb_w, float* __restrict__ cur_emb) {
+                                    int S, const float* __restrict__ emb_tab, int emb_w, float* __restrict__ cur_emb, int n_t) {
     const int idx = *step;
     if (emb_tab)
         for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < emb_w; i += gridDim.x * blockDim.x) cur_emb[i] = emb_tab[(long long)idx * emb_w + i];
     if (blockIdx.x == 0) {
-        if (threadIdx.x < nB) cur_t[threadIdx.x] = tab_t[idx];
+        for (int k = threadIdx.x; k < n_t; k += blockDim.x) cur_t[k] = tab_t[idx];      // (n_t = nB, or one slot per crop row)
         if (threadIdx.x < 8) cur_coef[threadIdx.x] = tab_coef[idx * 8 + threadIdx.x];
     }
     const float sq_ac = tab_coef[idx * 8 + 4], sq_1mac = tab_coef[idx * 8 + 5];
@@ -757,10 +758,10 @@ void launch_ddim_update(const Ctx& ctx, const float* x, const float* eps_u, cons
 void launch_ddim_prepare(const Ctx& ctx, const float* x, const float* concat, int B, int nB, long long per,
                          long long per_c, const float* tab_t, const float* tab_coef, const int* step, float* xin,
                          float* cur_t, float* cur_coef, const float* mask, const float* x0, const float* noise_q, int S,
-                         const float* emb_tab, int emb_w, float* cur_emb) {
+                         const float* emb_tab, int emb_w, float* cur_emb, int n_t) {
     MAA_CHECK(nB <= 256, "ddim: at most 256 UNet rows per step");
     MAA_LAUNCH1(ddim_prepare_kernel, (long long)nB * (per + per_c), x, concat, B, nB, per, per_c, tab_t, tab_coef, step,
-                xin, cur_t, cur_coef, mask, x0, noise_q, S, emb_tab, emb_w, cur_emb);
+                xin, cur_t, cur_coef, mask, x0, noise_q, S, emb_tab, emb_w, cur_emb, n_t > 0 ? n_t : nB);
 }
 void launch_ddim_step(const Ctx& ctx, const float* xin, long long per, long long per_in, const float* eps_u, const float* eps_c,
                       float scale, const float* coef, long long n, float* x_prev, const float* noise_p, float temperature, int S,
@@ -802,16 +803,17 @@ void launch_ldm_plms_step(const Ctx& ctx, const float* xin, long long per, long 
 }
 void launch_ldm_plms_euler_mid(const Ctx& ctx, float* xin, long long per, long long per_in, int B, int nB, const float* eps_u,
                                const float* eps_c, float scale, const float* coef, float* x_save, float* e_keep, const float* tab_t,
-                               float* cur_t, const float* emb_tab, int emb_w, float* cur_emb) {
+                               float* cur_t, const float* emb_tab, int emb_w, float* cur_emb, int n_t) {
     MAA_CHECK(per > 0 && B > 0 && (nB == B || nB == 2 * B) && nB <= 256, "plms: bad step shape");
+    if (n_t <= 0) n_t = nB;
     const long long n = (long long)B * per;
     const bool vec = per % 4 == 0 && per_in % 4 == 0 && al16(xin) && al16(eps_u) && al16(eps_c) && al16(x_save) && al16(e_keep);
     if (vec) {
         MAA_LAUNCH1(ldm_plms_euler_mid_kernel<4>, n / 4, xin, per, per_in, B, nB, eps_u, eps_c, scale, coef, n, x_save, e_keep, tab_t,
-                    cur_t, emb_tab, emb_w, cur_emb);
+                    cur_t, emb_tab, emb_w, cur_emb, n_t);
     } else {
         MAA_LAUNCH1(ldm_plms_euler_mid_kernel<1>, n, xin, per, per_in, B, nB, eps_u, eps_c, scale, coef, n, x_save, e_keep, tab_t,
-                    cur_t, emb_tab, emb_w, cur_emb);
+                    cur_t, emb_tab, emb_w, cur_emb, n_t);
     }
 }
 void launch_ldm_plms_euler_final(const Ctx& ctx, const float* eps_u, const float* eps_c, float scale, const float* coef, long long n,

@@ -11,10 +11,13 @@ public:
     // packed weight layout)
     UNet(const maa_unet_config& cfg, const StateDict& sd, int precision);
     ~UNet();
-    void set_context(Ctx& ctx, const float* d_context, int B, int L);
+    // rep > 1: the B samples are evaluated as B * rep rows, sample b's conditioning serving rows b * rep .. b * rep + rep - 1 (the
+    // crops of split_input_params); the K/V projections are still computed once per sample and copied on the device
+    void set_context(Ctx& ctx, const float* d_context, int B, int L, int rep = 1);
+    int context_len() const;      // tokens per sample of the last set_context (0: none yet)
     // classifier-free guidance: context rows [uncond (B) ; cond (B)] assembled in a buffer the UNet owns (it stays
     // valid for later forwards, e.g. the I2A time-embedding add), then set_context over 2B rows
-    void set_context_cfg(Ctx& ctx, const float* d_uncond, const float* d_cond, int B, int L);
+    void set_context_cfg(Ctx& ctx, const float* d_uncond, const float* d_cond, int B, int L, int rep = 1);
     // emb_row: optional, the ResBlocks' time-embedding row of this step from emb_table() (one row for all samples: every
     // sample of a DDIM step shares t); null: computed from t (and, I2A, the context) as the reference does per forward
     // batch_off >= 0: this call covers samples [batch_off, batch_off + B) of the batch set_context saw (one lane of a CFG
@@ -147,6 +150,10 @@ void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, floa
 // PLMSSampler.plms_sampling (plms.py:115-236) over the S-step schedule `a` describes (eta 0: no sigmas, no step noise)
 void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x);
 // DDIMSampler.stochastic_encode (ddim.py:227-241) with host tables of n_tab rows; checks every t[b] against n_tab
+// One model evaluation with split_input_params outside a loop (ddpm_audio.py:572-654): unfold, the UNet over B * L crop rows,
+// fold.  h_weight [kh * kw][L] on the host (get_weighting's table); d_context [B, context_len(), context_dim] or null
+void unet_forward_split(Ctx& ctx, UNet& unet, const float* d_x, const float* d_t, const float* d_context, int B, int H, int W, int kh,
+                        int kw, int sh, int sw, const float* h_weight, float* d_out);
 void ddim_stochastic_encode(Ctx& ctx, const float* d_x0_or_moments, bool from_moments, float scale_factor, const float* d_noise_post,
                             const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab, const float* d_noise, int B,
                             int C, int H, int W, float* d_out);

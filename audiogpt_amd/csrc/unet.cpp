@@ -85,6 +85,7 @@ struct UNet::Impl {
     int kv_rows = 0, kv_len = 0, kv_batch = 0;
     size_t kv_cap_rows = 0;
     DevSlab cfg_context;      // [uncond ; cond] rows of a CFG sample() call
+    DevSlab tiled_context;    // the context rows once per crop (set_context with rep > 1, add_context_to_emb only)
     // The shared prefix of a guided step run as two lanes (ddim.cpp): the unconditional lane computes the layers before the
     // first cross-attention as part of its own pass and leaves their four outputs where they are in ITS workspace (share 2);
     // the conditional lane starts at that cross-attention and reads them (share 3) -- `ready` orders the two streams, the
@@ -658,11 +659,14 @@ UNet::~UNet() { delete impl_; }
 const maa_unet_config& UNet::config() const { return impl_->cfg; }
 size_t UNet::weight_bytes() const { return impl_->ws.bytes(); }
 
-void UNet::set_context(Ctx& ctx, const float* context, int B, int L) {
+void UNet::set_context(Ctx& ctx, const float* context, int B, int L, int rep) {
     Impl& m = *impl_;
+    MAA_CHECK(rep >= 1, "set_context: rep must be at least 1");
     if (!m.cfg.use_spatial_transformer) return;
     PrecisionGuard pg(ctx, m.precision);
-    const size_t rows = (size_t)B * L;
+    // rep > 1 (split_input_params: every sample is evaluated as `rep` crops that share its conditioning): the projections are
+    // computed once, for the B samples, behind the cache's B * rep sample slots and copied into them rep times each
+    const size_t served = (size_t)B * rep * L, rows = rep > 1 ? served + (size_t)B * L : served;
     if (rows > m.kv_cap_rows) {
         MAA_HIP(hipStreamSynchronize(ctx.stream));      // the old caches may still be read by queued launches
         for (size_t i = 0; i < m.kv_cache.size(); ++i) {
@@ -675,13 +679,23 @@ void UNet::set_context(Ctx& ctx, const float* context, int B, int L) {
         m.kv_cap_rows = rows;
     }
     for (const STW& s : m.st)
-        for (const STBlockW& b : s.blocks)
-            linear_into(ctx, context, m.cfg.context_dim, (long long)rows, m.cfg.context_dim, b.kv2, nullptr, 0,
-                        m.kv_cache[b.kv_slot], 2 * s.heads * s.dh);
-    m.kv_batch = B;
+        for (const STBlockW& b : s.blocks) {
+            const size_t w = (size_t)2 * s.heads * s.dh;
+            float* kv = m.kv_cache[b.kv_slot] + (rep > 1 ? served * w : 0);
+            linear_into(ctx, context, m.cfg.context_dim, (long long)B * L, m.cfg.context_dim, b.kv2, nullptr, 0, kv, (int)w);
+            if (rep > 1) launch_repeat_rows(ctx, kv, B, (long long)L * w, rep, m.kv_cache[b.kv_slot]);
+        }
+    m.kv_batch = B * rep;
     m.kv_len = L;
     context_ptr = context;
+    if (rep > 1 && m.cfg.add_context_to_emb) {      // (I2A: the time embedding reads the sample's context row as well)
+        const long long len = (long long)L * m.cfg.context_dim;
+        float* tiled = static_cast<float*>(m.tiled_context.get((size_t)B * rep * len * sizeof(float), ctx.stream));
+        launch_repeat_rows(ctx, context, B, len, rep, tiled);
+        context_ptr = tiled;
+    }
 }
+int UNet::context_len() const { return impl_->kv_len; }
 
 void UNet::graph_key(std::vector<unsigned long long>& key) const {
     const Impl& m = *impl_;
@@ -693,13 +707,13 @@ void UNet::graph_key(std::vector<unsigned long long>& key) const {
     for (const float* p : m.kv_cache) key.push_back((unsigned long long)reinterpret_cast<uintptr_t>(p));
 }
 
-void UNet::set_context_cfg(Ctx& ctx, const float* d_uncond, const float* d_cond, int B, int L) {
+void UNet::set_context_cfg(Ctx& ctx, const float* d_uncond, const float* d_cond, int B, int L, int rep) {
     Impl& m = *impl_;
     const size_t half = (size_t)B * L * m.cfg.context_dim * sizeof(float);
     char* buf = static_cast<char*>(m.cfg_context.get(2 * half, ctx.stream));
     MAA_HIP(hipMemcpyAsync(buf, d_uncond, half, hipMemcpyDeviceToDevice, ctx.stream));
     MAA_HIP(hipMemcpyAsync(buf + half, d_cond, half, hipMemcpyDeviceToDevice, ctx.stream));
-    set_context(ctx, reinterpret_cast<const float*>(buf), 2 * B, L);
+    set_context(ctx, reinterpret_cast<const float*>(buf), 2 * B, L, rep);
 }
 
 void UNet::forward(Ctx& ctx, const float* x_nchw, const float* t, const float* context, int B, int H, int W,

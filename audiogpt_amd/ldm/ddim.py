@@ -60,6 +60,12 @@ class DDIMSampler(object):
         if verbose:
             print(f"Selected timesteps for ddim sampler: {steps}")
 
+    def _split(self):
+        """The model's `split_input_params` (ddpm_audio.py:572), if it has the attribute: the device loops then evaluate the
+        model on overlapping crops and stitch them, as the reference's apply_model does inside its sampling loop."""
+        get = getattr(self.model, "split_params", None)
+        return get() if get is not None else getattr(self.model, "split_input_params", None)
+
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0,
@@ -99,6 +105,8 @@ class DDIMSampler(object):
                                    unconditional_conditioning=unconditional_conditioning, noise_q=noise_q, noise_p=noise_p)
         key = self.model.conditioning_key
         kw = dict(scale=float(unconditional_guidance_scale), log_every_t=int(log_every_t), temperature=float(temperature))
+        if self._split() is not None:
+            kw["split"] = self._split()
         if key == "concat":
             kw["concat"] = conditioning          # cat([x, c], dim=1) inside the loop (ddpm.py:1404-1406)
         else:
@@ -159,6 +167,8 @@ class DDIMSampler(object):
             return x_latent
         noise_p = torch.stack([torch.randn(x.shape, device=self.device) for _ in range(n)])      # util.py:264-267, per step
         kw = dict(scale=float(unconditional_guidance_scale))
+        if self._split() is not None:
+            kw["split"] = self._split()
         if self.model.conditioning_key == "concat":
             kw["concat"] = cond
         else:

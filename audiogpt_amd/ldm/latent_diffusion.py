@@ -187,13 +187,28 @@ class LatentDiffusionAudio(object):
         return self.vae.decode(z.to(self.device), self.scale_factor)
 
     # ---- diffusion model ------------------------------------------------------------------------
+    def split_params(self):
+        """The `split_input_params` attribute as the reference reads it -- `hasattr(self, "split_input_params")`
+        (ddpm_audio.py:572) -- or None.  A concat-conditioned model with the attribute raises MaaError here, before anything
+        is launched (ldm/split.py: the reference fails in torch.cat)."""
+        if not hasattr(self, "split_input_params"):
+            return None
+        if self.conditioning_key == "concat":
+            from . import split as SP
+            SP.plan(self.split_input_params, 0, 0, conditioning_key="concat")          # raises
+        return self.split_input_params
+
     def apply_model(self, x_noisy, t, cond):
-        """ddpm_audio.py:561-570,657 + DiffusionWrapper (ddpm.py:1400-1409)."""
+        """ddpm_audio.py:561-570,657 + DiffusionWrapper (ddpm.py:1400-1409); with `split_input_params` set the crop-and-stitch
+        evaluation of :572-654 (maa_unet_forward_split)."""
         if isinstance(cond, dict):
             key = "c_concat" if self.conditioning_key == "concat" else "c_crossattn"
             cond = cond[key]
         if isinstance(cond, (list, tuple)):
             cond = torch.cat(list(cond), 1)
+        split = self.split_params()
+        if split is not None:
+            return self.unet.forward_split(x_noisy, t, cond, split)
         if self.conditioning_key == "concat":
             return self.unet(torch.cat([x_noisy.to(self.device), cond.to(self.device)], dim=1), t)
         return self.unet(x_noisy, t, cond)

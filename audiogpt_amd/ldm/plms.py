@@ -95,6 +95,8 @@ class PLMSSampler(object):
                 torch.randn(size, device=self.device)
         key = self.model.conditioning_key
         kw = dict(scale=float(unconditional_guidance_scale), log_every_t=int(log_every_t))
+        if DDIMSampler._split(self) is not None:          # the model's split_input_params (ddpm_audio.py:572)
+            kw["split"] = DDIMSampler._split(self)
         if key == "concat":
             kw["concat"] = conditioning          # cat([x, c], dim=1) inside the loop (ddpm.py:1404-1406)
         else:

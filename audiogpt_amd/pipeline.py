@@ -61,14 +61,30 @@ class MakeAnAudio:
         self.alphas_cumprod = alphas_cumprod_f32(self.ldm["timesteps"], self.ldm["linear_start"], self.ldm["linear_end"])
 
     # ---- stages ----------------------------------------------------------------------------------
-    def sample_latents(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim"):
+    # The widest latent the chain takes.  The VAE decoder's mid-block attention (vae.cpp run_attn: one head as wide as the block,
+    # 512, which the fused attention kernel does not take) runs as two batched GEMMs around a softmax over the [h w, h w] score
+    # matrix of each sample, held in the workspace with its rows padded to a multiple of 4; the contraction engines address a
+    # sample's matrix with 32-bit products of position and pitch (blocks.cpp attention_into, igemm_*.hip), so h w * pad4(h w)
+    # must stay below 2^31: h w <= 46340, i.e. w <= 4634 at the models' h = 10 (4634 * 8 frames * 256 / 16 kHz = 593 s).
+    MAX_LATENT_POSITIONS = 46340
+
+    def check_latent_size(self, h, w):
+        """Raises MaaError for a latent [*, *, h, w] larger than the VAE decoder's mid-block attention accepts
+        (MAX_LATENT_POSITIONS = 46340 positions: w <= 4634 at h = 10); nothing is launched."""
+        if int(h) * int(w) > self.MAX_LATENT_POSITIONS:
+            raise MaaError("latent %d x %d has %d positions; the VAE decoder's mid-block attention takes at most %d (w <= %d at "
+                           "h = %d)" % (h, w, int(h) * int(w), self.MAX_LATENT_POSITIONS, self.MAX_LATENT_POSITIONS // int(h), h))
+
+    def sample_latents(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim", split=None):
         """x_T -> x_0 over the S-step schedule: sampler "ddim" (DDIMSampler, S UNet evaluations) or "plms" (PLMSSampler,
-        S + 1 evaluations)."""
+        S + 1 evaluations).  split: the reference's `split_input_params` dictionary (ldm/split.py) for a latent wider than the
+        model was trained on -- every evaluation runs on overlapping crops of `ks` and is stitched (ddpm_audio.py:572-654)."""
         if sampler not in ("ddim", "plms"):
             raise MaaError('sampler must be "ddim" or "plms", got %r' % (sampler,))
         steps, a, ap = ddim_schedule(S, self.alphas_cumprod)
         run = self.unet.plms_sample if sampler == "plms" else self.unet.ddim_sample
-        return run(x_T, steps, a, ap, cond=cond, uncond=uncond, scale=scale, concat=concat, use_graph=use_graph)
+        kw = dict(split=split) if split is not None else {}
+        return run(x_T, steps, a, ap, cond=cond, uncond=uncond, scale=scale, concat=concat, use_graph=use_graph, **kw)
 
     def decode(self, z):
         """decode_first_stage then the tools' clamp((x+1)/2, 0, 1) (audio-chatgpt.py:175-176) -> [B,80,T]."""
@@ -77,29 +93,35 @@ class MakeAnAudio:
     def vocode(self, spec):
         return self.vocoder(spec)[:, 0]
 
-    def generate_here(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim"):
+    def generate_here(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim", split=None):
         """generate() on the CURRENT torch stream, which must be this replica's stream when it has one (the caller orders
         inputs and outputs against other streams itself: bench.py's worker threads)."""
-        z = self.sample_latents(x_T, cond, uncond, scale, S, concat, use_graph, sampler=sampler)
+        self.check_latent_size(x_T.shape[-2], x_T.shape[-1])
+        z = self.sample_latents(x_T, cond, uncond, scale, S, concat, use_graph, sampler=sampler, split=split)
         spec = self.decode(z)
         return self.vocode(spec), spec, z
 
-    def generate(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim"):
+    def generate(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim", split=None):
         """x_T [B,4,h,w] -> (wav [B, T*hop], spec [B,80,T], z [B,4,h,w]); all on the device.  With a private stream the
         work is ordered after the caller's current stream on entry and the caller's stream after it on return.
-        sampler: "ddim" or "plms" (sample_latents)."""
+        sampler: "ddim" or "plms" (sample_latents).
+        split: long-form generation -- the reference's `split_input_params` dictionary (sample_latents); the sampler evaluates the
+        UNet on crops of the training size, the VAE decode and the vocoder run on the whole width.  The widest latent the VAE's
+        mid-block attention accepts is h * w <= 46340 positions (w <= 4634 at h = 10, about 593 s of audio: MAX_LATENT_POSITIONS
+        above says why); a wider one raises MaaError before anything is launched."""
+        self.check_latent_size(x_T.shape[-2], x_T.shape[-1])
         if self.stream is None:
-            return self.generate_here(x_T, cond, uncond, scale, S, concat, use_graph, sampler=sampler)
+            return self.generate_here(x_T, cond, uncond, scale, S, concat, use_graph, sampler=sampler, split=split)
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            out = self.generate_here(x_T, cond, uncond, scale, S, concat, use_graph, sampler=sampler)
+            out = self.generate_here(x_T, cond, uncond, scale, S, concat, use_graph, sampler=sampler, split=split)
         cur.wait_stream(self.stream)
         for t in out:
             t.record_stream(cur)
         return out
 
-    def edit_here(self, mel, cond, uncond=None, scale=1.0, S=100, strength=0.5, noise=None, use_graph=True):
+    def edit_here(self, mel, cond, uncond=None, scale=1.0, S=100, strength=0.5, noise=None, use_graph=True, split=None):
         """Text-guided editing of an existing recording (SDEdit, Make-An-Audio's img2img form): the mel's latent is noised
         part of the way down an S-step DDIM schedule and denoised under `cond`.  mel [B, 1, 80, T] in [-1, 1] (as
         Inpaint.make_batch_sd forms it) -> (wav [B, T*hop], spec [B, 80, T], z [B, 4, 10, T/8]), all on the device, on the
@@ -110,7 +132,9 @@ class MakeAnAudio:
         index t_enc and the first denoising step is index t_enc - 1; strength must lie in [0, 1), so that t_enc < S (an
         S-step schedule has no index S); at t_enc = 0 the latent is noised at index 0 and no step runs.
         noise: None (the posterior noise, then the q_sample noise, drawn from the model's device generator) or the pair
-        (n_post, n_q), each [B, 4, h, w]."""
+        (n_post, n_q), each [B, 4, h, w].
+        split: the reference's `split_input_params` dictionary for a recording longer than the model's training size (the
+        denoising steps then run on overlapping crops, as generate's; the same width limit applies)."""
         if not self.has_encoder:
             raise MaaError("edit: the VAE has no encoder weights -- build MakeAnAudio with with_encoder=True (or a vae_sd with "
                            "encoder.* / quant_conv.*)")
@@ -120,6 +144,7 @@ class MakeAnAudio:
         mel = mel.detach().to(device=self.device, dtype=torch.float32).contiguous()
         if mel.dim() != 4 or mel.shape[1] != 1:
             raise MaaError("edit: mel must be [B, 1, n_mels, T], got %s" % (tuple(mel.shape),))
+        self.check_latent_size(mel.shape[2] // 8, mel.shape[3] // 8)
         moments = self.vae.encode_moments(mel)
         B, C2, h, w = moments.shape
         shape = (B, C2 // 2, h, w)
@@ -132,19 +157,20 @@ class MakeAnAudio:
         a_t = torch.from_numpy(a)
         z_enc = ddim_stochastic_encode(self.ctx, moments, t_enc, torch.sqrt(a_t), torch.sqrt(1.0 - a_t), n_q, moments=True,
                                        scale_factor=self.scale_factor, noise_post=n_post)
-        z = self.unet.ddim_decode(z_enc, t_enc, steps, a, ap, cond=cond, uncond=uncond, scale=scale, use_graph=use_graph)
+        kw = dict(split=split) if split is not None else {}
+        z = self.unet.ddim_decode(z_enc, t_enc, steps, a, ap, cond=cond, uncond=uncond, scale=scale, use_graph=use_graph, **kw)
         spec = self.decode(z)
         return self.vocode(spec), spec, z
 
-    def edit(self, mel, cond, uncond=None, scale=1.0, S=100, strength=0.5, noise=None, use_graph=True):
+    def edit(self, mel, cond, uncond=None, scale=1.0, S=100, strength=0.5, noise=None, use_graph=True, split=None):
         """edit_here with generate()'s stream ordering: with a private stream the work is ordered after the caller's current
         stream on entry and the caller's stream after it on return."""
         if self.stream is None:
-            return self.edit_here(mel, cond, uncond, scale, S, strength, noise, use_graph)
+            return self.edit_here(mel, cond, uncond, scale, S, strength, noise, use_graph, split=split)
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            out = self.edit_here(mel, cond, uncond, scale, S, strength, noise, use_graph)
+            out = self.edit_here(mel, cond, uncond, scale, S, strength, noise, use_graph, split=split)
         cur.wait_stream(self.stream)
         for t in out:
             t.record_stream(cur)

@@ -139,6 +139,19 @@ int maa_unet_set_context(maa_ctx* ctx, maa_unet* u, const float* d_context, int 
 int maa_unet_forward(maa_ctx* ctx, maa_unet* u, const float* d_x, const float* d_t, int B, int H, int W,
                      float* d_out);
 
+/* replaces: LatentDiffusion_audio.apply_model with `split_input_params` set (ldm/models/diffusion/ddpm_audio.py:572-654;
+ * get_fold_unfold :242-293, get_weighting :226-240, delta_border :212-224, meshgrid :205-210): one evaluation of the model on a
+ * latent wider than it was trained on.  d_x [B, Cin, H, W] is cut into the L = Ly * Lx crops of kh x kw every sh / sw positions
+ * (:250-251; Unfold's order, :582-585), the UNet runs on the B * L crops as one batch with d_t [B] repeated per crop, and
+ * d_out [B, Cout, H, W] = fold(eps * weighting) / fold(weighting) (:649-654).  h_weight [kh * kw][L]: the weighting, fp32 on the
+ * HOST.  d_context [B, L_tokens, context_dim] with the token count of the last maa_unet_set_context on this UNet (NULL for a UNet
+ * without cross-attention): its K/V are projected here, once for the B samples, and served to each sample's crops; afterwards the
+ * UNet's context is this one over B * L rows (a plain maa_unet_forward needs maa_unet_set_context again).  (H - kh) % sh == 0,
+ * (W - kw) % sw == 0 and stride <= ks are required: the reference divides 0 by 0 at a position no crop covers.  Synchronises the
+ * stream once, after the weighting's upload. */
+int maa_unet_forward_split(maa_ctx* ctx, maa_unet* u, const float* d_x, const float* d_t, const float* d_context, int B, int H, int W,
+                           int kh, int kw, int sh, int sw, const float* h_weight, float* d_out);
+
 /* ---- DDIM ---------------------------------------------------------------------------------------
  * replaces: DDIMSampler.p_sample_ddim's elementwise tail (ddim.py:199, 210-225), eta = 0 or with caller noise:
  *   e = eu + scale*(ec - eu) (ec may be NULL: no guidance);  x0 = (x - sqrt(1-a_t) e)/sqrt(a_t);
@@ -187,6 +200,14 @@ typedef struct maa_ddim_args {
     int n_log;
     float* d_log_x;
     float* d_log_x0;
+    /* split_input_params (LatentDiffusion_audio.apply_model, ldm/models/diffusion/ddpm_audio.py:572-654): every model evaluation
+     *   of the loop cuts the latent into crops of split_kh x split_kw every split_sh / split_sw positions (Ly * Lx = L of them,
+     *   :250-251), runs the UNet on the B * L crops (2 B * L with guidance) in one batch and stitches its outputs,
+     *   sum_l w[p, l] eps_l / sum_l w[p, l] over the crops covering a position.  h_split_weight [split_kh * split_kw][L]: the
+     *   reference's weighting (get_weighting, :226-240) as fp32 on the host.  The conditioning's K/V are still projected once per
+     *   sample.  All zero / NULL: no split.  Crossattn models only (a concat model with the split fails the call). */
+    int split_kh, split_kw, split_sh, split_sw;
+    const float* h_split_weight;
 } maa_ddim_args;
 int maa_ddim_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, float* d_x);
 
@@ -464,6 +485,14 @@ int maa_op_snake_aa(maa_ctx* ctx, const float* d_x, int B, int C, int L, const f
 int maa_op_mrf_pair(maa_ctx* ctx, const float* d_x, int B, int C, int L, const float* h_w1, const float* h_b1, int k1, int d1,
                     float slope1, const float* h_w2, const float* h_b2, int k2, int d2, float slope2, float out_scale,
                     int accumulate, float* d_out);
+/* The two passes around the UNet of maa_unet_forward_split on their own (ddpm_audio.py:582-585 and :649-654).
+ * unfold: d_x [B, C, H, W] -> d_out [B * L, C, kh, kw], row b * L + l the crop l = ly * Lx + lx of sample b: torch.nn.Unfold's
+ * columns as images, a copy. */
+int maa_op_unfold(maa_ctx* ctx, const float* d_x, int B, int C, int H, int W, int kh, int kw, int sh, int sw, float* d_out);
+/* fold: d_crops [B * L, C, kh, kw], h_weight [kh * kw][L] on the HOST -> d_out [B, C, H, W] = (sum_l w[p, l] crop_l[p]) /
+ * (sum_l w[p, l]) over the crops that cover a position, in ascending l; the divisor is summed in fp64 and rounded once. */
+int maa_op_fold(maa_ctx* ctx, const float* d_crops, const float* h_weight, int B, int C, int H, int W, int kh, int kw, int sh, int sw,
+                float* d_out);
 
 #ifdef __cplusplus
 }
