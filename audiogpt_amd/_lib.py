@@ -51,6 +51,14 @@ class maa_ddim_args(C.Structure):
                 ("h_split_weight", C.POINTER(C.c_float))]
 
 
+class maa_ddpm_args(C.Structure):
+    _fields_ = [("loop", maa_ddim_args), ("start", C.c_int), ("n", C.c_int), ("clip_denoised", C.c_int),
+                ("h_sqrt_recip_ac", C.POINTER(C.c_float)), ("h_sqrt_recipm1_ac", C.POINTER(C.c_float)),
+                ("h_coef1", C.POINTER(C.c_float)), ("h_coef2", C.POINTER(C.c_float)), ("h_logvar", C.POINTER(C.c_float)),
+                ("h_sqrt_ac", C.POINTER(C.c_float)), ("h_sqrt_1mac", C.POINTER(C.c_float)),
+                ("h_temperature", C.POINTER(C.c_float))]
+
+
 class maa_vae_config(C.Structure):
     _fields_ = [("ch", C.c_int), ("out_ch", C.c_int), ("in_channels", C.c_int), ("z_channels", C.c_int),
                 ("embed_dim", C.c_int), ("resolution", C.c_int), ("num_res_blocks", C.c_int), ("double_z", C.c_int),
@@ -98,7 +106,7 @@ EXPORTS = [
     "maa_last_error", "maa_version", "maa_ctx_create", "maa_ctx_destroy", "maa_ctx_synchronize",
     "maa_ctx_set_stream", "maa_ctx_set_precision", "maa_ctx_set_cfg_split", "maa_ctx_set_concurrency", "maa_ctx_reload_tuning", "maa_ctx_workspace_bytes", "maa_prof_begin", "maa_prof_end", "maa_unet_create", "maa_unet_destroy",
     "maa_unet_set_context", "maa_unet_forward", "maa_ddim_update", "maa_ddim_sample", "maa_ddim_stochastic_encode", "maa_ddim_decode",
-    "maa_ldm_plms_sample",
+    "maa_ldm_plms_sample", "maa_ddpm_sample", "maa_ddpm_update",
     "maa_vae_create",
     "maa_vae_destroy", "maa_vae_decode", "maa_vae_decode_spec", "maa_vae_encode_moments", "maa_vocoder_create", "maa_vocoder_destroy",
     "maa_vocoder_forward", "maa_vocoder_forward_f0", "maa_diffnet_create", "maa_diffnet_destroy", "maa_diffnet_forward",
@@ -149,6 +157,8 @@ def load():
         "maa_ddim_stochastic_encode": [vp, vp, ci, cf, vp, vp, fp, fp, ci, vp, ci, ci, ci, ci, vp],
         "maa_ddim_decode": [vp, vp, C.POINTER(maa_ddim_args), ci, vp],
         "maa_ldm_plms_sample": [vp, vp, C.POINTER(maa_ddim_args), vp],
+        "maa_ddpm_sample": [vp, vp, C.POINTER(maa_ddpm_args), vp],
+        "maa_ddpm_update": [vp, vp, vp, vp, fp, fp, fp, fp, fp, ci, vp, cf, ci, ci, ci, ci, ci, vp, vp],
         "maa_vae_create": [vp, C.POINTER(maa_vae_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
         "maa_vae_destroy": [vp],
         "maa_vae_decode": [vp, vp, vp, ci, ci, ci, cf, vp],

@@ -577,6 +577,158 @@ class UNet:
                                                  float(scale), L.dptr(coef), x.numel(), L.dptr(x_prev), L.dptr(pred)))
         return x_prev, pred
 
+    # the model's schedule buffers the ancestral chain reads, under the reference's names (ddpm.py:139-155)
+    DDPM_TABLES = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1", "posterior_mean_coef2",
+                   "posterior_log_variance_clipped")
+    DDPM_Q_TABLES = ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")
+
+    @staticmethod
+    def _ddpm_tables(what, tables, names, keep):
+        """Host fp32 copies of `tables[name]` (a mapping or an object with the buffers as attributes), all of one length."""
+        out = []
+        # (a model keeps host copies of its buffers, ldm/ddpm.py register_ancestral_schedule: no device read per call)
+        host = getattr(tables, "_ddpm_host_tables", None)
+        for name in names:
+            if host is not None and name in host:
+                v = host[name]
+            else:
+                v = tables[name] if isinstance(tables, dict) else getattr(tables, name)
+            t = np.ascontiguousarray(np.asarray(v.detach().cpu() if torch.is_tensor(v) else v), dtype=np.float32)
+            if t.ndim != 1 or t.size == 0 or (out and t.shape != out[0].shape):
+                raise L.MaaError("%s: %s must hold one fp32 value per DDPM timestep, got %s" % (what, name, t.shape))
+            out.append(t)
+        keep += out
+        return out
+
+    def ddpm_sample(self, x_T, tables, n=None, cond=None, uncond=None, scale=1.0, concat=None, mask=None, x0=None, noise_p=None,
+                    noise_q=None, temperature=1.0, clip_denoised=True, log_every_t=None, use_graph=True, split=None, start=None):
+        """The model's own ancestral (DDPM) chain on the device through maa_ddpm_sample (LatentDiffusion_audio.p_sample_loop /
+        progressive_denoising, ddpm_audio.py:779-884): the steps t = start .. start - n + 1 of the schedule `tables` describes, one
+        UNet evaluation and one fused kernel each.  start defaults to n - 1 (the reference's loop: t = n - 1 .. 0) and n to
+        the number of timesteps.
+        tables: the model's fp32 schedule buffers under the reference's names (DDPM_TABLES; with a mask DDPM_Q_TABLES too), a
+        mapping or an object carrying them, one row per DDPM timestep.
+        noise_p [n, B, C, H, W] (required): the steps' noise_like draws in loop order; mask / x0 / noise_q [n, B, C, H, W]: the
+        blend AFTER each step with q_sample(x0, t) of the step's own t (ddpm_audio.py:873-875).  temperature: a float or one
+        value per DDPM timestep (progressive_denoising's list, indexed by t).  clip_denoised: clamp x_recon to [-1, 1].
+        cond / uncond / scale / concat / split / use_graph as ddim_sample's; guidance (uncond with scale != 1) is an extension,
+        e = e_u + scale (e_c - e_u) -- the reference's chain evaluates the model once per step.
+        Returns x_0, or (x_0, x_log, x_recon_log) when log_every_t is given: the latent after the blend and the clamped
+        x_recon of every step with t % log_every_t == 0 or t == start, as [n_log, B, C, H, W] tensors in loop order."""
+        what = "ddpm_sample"
+        dev = self.ctx.device
+        x = _f32(x_T, dev).clone()
+        keep = []
+        tabs = self._ddpm_tables(what, tables, self.DDPM_TABLES, keep)
+        T = tabs[0].shape[0]
+        n = T if n is None else int(n)
+        start = n - 1 if start is None else int(start)
+        if not 1 <= n <= T or not n - 1 <= start < T:
+            raise L.MaaError("%s: n must lie in 1 .. %d and start in n - 1 .. %d, got n = %d, start = %d" % (what, T, T - 1, n, start))
+        la, B, Cc, H, W = self._ddim_args(what, x, np.arange(T), np.ones(T), np.ones(T), cond, uncond, scale, concat, use_graph,
+                                          keep, split)
+        a = L.maa_ddpm_args()
+        a.loop = la
+        a.start, a.n, a.clip_denoised = start, n, int(bool(clip_denoised))
+        fp = C.POINTER(C.c_float)
+        a.h_sqrt_recip_ac, a.h_sqrt_recipm1_ac, a.h_coef1, a.h_coef2, a.h_logvar = [t.ctypes.data_as(fp) for t in tabs]
+
+        def step_noise(v, name):
+            if v is None:
+                raise L.MaaError("%s: %s [n=%d, %d, %d, %d, %d] is needed" % (what, name, n, B, Cc, H, W))
+            t = _f32(v, dev)
+            if tuple(t.shape) != (n, B, Cc, H, W):
+                raise L.MaaError("%s: %s must be [n=%d, %d, %d, %d, %d], got %s" % (what, name, n, B, Cc, H, W, tuple(t.shape)))
+            keep.append(t)
+            return t.data_ptr()
+
+        a.loop.d_noise_p = step_noise(noise_p, "noise_p")
+        if mask is not None:
+            if x0 is None:
+                raise L.MaaError(what + ": mask needs x0")          # ddpm_audio.py:860
+            m = _f32(mask, dev).expand(B, Cc, H, W).contiguous()
+            z0 = _f32(x0, dev).expand(B, Cc, H, W).contiguous()
+            keep += [m, z0]
+            a.loop.d_mask, a.loop.d_x0 = m.data_ptr(), z0.data_ptr()
+            a.loop.d_noise_q = step_noise(noise_q, "noise_q")
+            qt = self._ddpm_tables(what, tables, self.DDPM_Q_TABLES, keep)
+            if qt[0].shape != (T,):
+                raise L.MaaError("%s: the q_sample tables must hold %d rows, got %s" % (what, T, qt[0].shape))
+            a.h_sqrt_ac, a.h_sqrt_1mac = [t.ctypes.data_as(fp) for t in qt]
+        if np.ndim(temperature) != 0:
+            tt = np.ascontiguousarray(np.asarray(temperature), dtype=np.float32)
+            if tt.ndim != 1 or tt.shape[0] <= start:
+                raise L.MaaError("%s: a temperature list is indexed by the timestep and must reach t = %d, got %s"
+                                 % (what, start, tt.shape))
+            tt = np.ascontiguousarray(np.concatenate([tt[:T], np.ones(max(0, T - tt.shape[0]), dtype=np.float32)]))
+            keep.append(tt)
+            a.h_temperature = tt.ctypes.data_as(fp)
+        elif float(temperature) != 1.0:
+            tt = np.full(T, float(temperature), dtype=np.float32)
+            keep.append(tt)
+            a.h_temperature = tt.ctypes.data_as(fp)
+        logs = None
+        if log_every_t is not None:
+            every = int(log_every_t)
+            if every <= 0:
+                raise L.MaaError(what + ": log_every_t must be positive")
+            n_log = sum(1 for t in range(start - n + 1, start + 1) if t % every == 0 or t == start)
+            # (one pair of log slabs per shape is kept by this model, as _sample's: their addresses are in the step graph's key)
+            cache = self.__dict__.setdefault("_log_slabs", {})
+            key = (n_log, B, Cc, H, W)
+            if key not in cache:
+                if len(cache) >= 4:
+                    cache.clear()
+                cache[key] = (torch.empty(n_log, B, Cc, H, W, device=dev), torch.empty(n_log, B, Cc, H, W, device=dev))
+            logs = cache[key]
+            a.loop.log_every_t, a.loop.n_log = every, n_log
+            a.loop.d_log_x, a.loop.d_log_x0 = logs[0].data_ptr(), logs[1].data_ptr()
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_ddpm_sample(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
+            if logs is not None:
+                if self.ctx._stream is not None:
+                    with torch.cuda.stream(self.ctx._stream):
+                        out = (logs[0].clone(), logs[1].clone())
+                    for t in out:
+                        t.record_stream(torch.cuda.current_stream(dev))
+                    torch.cuda.current_stream(dev).wait_stream(self.ctx._stream)
+                else:
+                    self.ctx.synchronize()
+                    out = (logs[0].clone(), logs[1].clone())
+                return x, out[0], out[1]
+        return x
+
+    def ddpm_update(self, x, eps, t, tables, noise, temperature=1.0, clip_denoised=True):
+        """One ancestral step outside the loop (p_sample's arithmetic, ddpm_audio.py:729-777) through maa_ddpm_update:
+        x_recon = sqrt_recip_ac[t] x - sqrt_recipm1_ac[t] eps (clamped when clip_denoised), the posterior mean, and
+        mean + (t != 0) exp(0.5 logvar[t]) (noise temperature).  t: an int or [B] integer timesteps, one per sample, each in
+        [0, num_timesteps).  Returns (x_prev, x_recon).  Used by p_sample and the host-hook loop."""
+        what = "ddpm_update"
+        dev = self.ctx.device
+        x, eps, noise = _f32(x, dev), _f32(eps, dev), _f32(noise, dev)
+        if x.dim() != 4 or eps.shape != x.shape or noise.shape != x.shape:
+            raise L.MaaError("%s: x, eps and noise must share one [B, C, H, W] shape, got %s / %s / %s"
+                             % (what, tuple(x.shape), tuple(eps.shape), tuple(noise.shape)))
+        B, Cc, H, W = x.shape
+        keep = []
+        tabs = self._ddpm_tables(what, tables, self.DDPM_TABLES, keep)
+        n_tab = tabs[0].shape[0]
+        th = np.asarray(t.detach().cpu() if torch.is_tensor(t) else t).reshape(-1)
+        if th.size == 1:
+            th = np.repeat(th, B)
+        if th.shape != (B,) or not np.issubdtype(th.dtype, np.integer):
+            raise L.MaaError("%s: t must hold one integer timestep per sample (B=%d), got %s %s" % (what, B, th.shape, th.dtype))
+        if th.min() < 0 or th.max() >= n_tab:
+            raise L.MaaError("%s: t must lie in [0, %d), got %s" % (what, n_tab, th.tolist()))
+        td = torch.from_numpy(th.astype(np.int32)).to(dev)
+        x_prev, x_recon = torch.empty_like(x), torch.empty_like(x)
+        fp = C.POINTER(C.c_float)
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_ddpm_update(self.ctx.h, L.dptr(x), L.dptr(eps), C.c_void_p(td.data_ptr()),
+                                                 *[tb.ctypes.data_as(fp) for tb in tabs], n_tab, L.dptr(noise), float(temperature),
+                                                 int(bool(clip_denoised)), B, Cc, H, W, L.dptr(x_prev), L.dptr(x_recon)))
+        return x_prev, x_recon
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.maa_unet_destroy(self.h)

@@ -53,19 +53,19 @@ LDM_T2A = dict(
     unet=UNET_T2A, vae=VAE_DDCONFIG, timesteps=1000,
     linear_start=0.00085, linear_end=0.0120,
     conditioning_key="crossattn", latent_shape=(4, 10, 78), scale_factor=1.0,
-    sample_rate=16000, hop=256,
+    sample_rate=16000, hop=256, log_every_t=200,
 )
 LDM_I2A = dict(
     unet=UNET_I2A, vae=VAE_DDCONFIG, timesteps=1000,
     linear_start=0.00085, linear_end=0.0120,
     conditioning_key="crossattn", latent_shape=(4, 10, 78), scale_factor=1.0,
-    sample_rate=16000, hop=256,
+    sample_rate=16000, hop=256, log_every_t=200,
 )
 LDM_INPAINT = dict(
     unet=UNET_INPAINT, vae=VAE_DDCONFIG, timesteps=1000,
     linear_start=0.0015, linear_end=0.0205,
     conditioning_key="concat", latent_shape=(4, 10, 106), scale_factor=1.0,
-    sample_rate=16000, hop=256,
+    sample_rate=16000, hop=256, log_every_t=100,
 )
 
 # ---------------------------------------------------------------- vocoders

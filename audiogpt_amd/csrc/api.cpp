@@ -153,6 +153,7 @@ int maa_ctx_reload_tuning(maa_ctx* ctx) {
         ctx->c.tune.load();
         ctx->c.ddim_graph.clear();      // a kept step graph was captured under the old knobs
         ctx->c.plms_graph.clear();
+        ctx->c.ddpm_graph.clear();
     });
 }
 int maa_ctx_synchronize(maa_ctx* ctx) {
@@ -185,6 +186,7 @@ int maa_ctx_set_concurrency(maa_ctx* ctx, int n) {
         if (ctx->c.kept_full() != (n >= 3)) {
             ctx->c.ddim_graph.clear();      // the kept step graphs were captured under the other arrangement's launches
             ctx->c.plms_graph.clear();
+            ctx->c.ddpm_graph.clear();
         }
         ctx->c.concurrency = n;
     });
@@ -349,6 +351,45 @@ int maa_ldm_plms_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, fl
                   "bad ldm_plms_sample arguments: ddim_eta must be 0 for PLMS (h_sigmas and d_noise_p must be NULL)");
         bind(ctx);
         maa::ldm_plms_sample(ctx->c, *u->m, *args, d_x);
+    });
+}
+// (as above: every argument error is reported before the context is bound and anything is launched)
+int maa_ddpm_sample(maa_ctx* ctx, maa_unet* u, const maa_ddpm_args* args, float* d_x) {
+    return guarded([&] {
+        MAA_CHECK(u && args && d_x, "bad ddpm_sample arguments: null pointer");
+        const maa_ddim_args& l = args->loop;
+        MAA_CHECK(l.S > 0 && l.B > 0 && l.C > 0 && l.H > 0 && l.W > 0, "bad ddpm_sample arguments: empty problem");
+        MAA_CHECK(args->n >= 1 && args->n <= l.S, "bad ddpm_sample arguments: the number of steps must lie in 1 .. num_timesteps");
+        MAA_CHECK(args->start >= args->n - 1 && args->start < l.S, "bad ddpm_sample arguments: steps outside the schedule");
+        MAA_CHECK(args->h_sqrt_recip_ac && args->h_sqrt_recipm1_ac && args->h_coef1 && args->h_coef2 && args->h_logvar,
+                  "bad ddpm_sample arguments: the posterior tables are missing");
+        MAA_CHECK(l.d_noise_p, "bad ddpm_sample arguments: the steps' noise is missing");
+        MAA_CHECK(!l.d_mask || (l.d_x0 && l.d_noise_q && args->h_sqrt_ac && args->h_sqrt_1mac),
+                  "bad ddpm_sample arguments: mask needs x0, its noise and the q_sample tables");
+        if (l.n_log > 0 || l.d_log_x || l.d_log_x0) {
+            MAA_CHECK(l.d_log_x && l.d_log_x0 && l.log_every_t > 0, "bad ddpm_sample arguments: intermediates need their buffers and log_every_t");
+            int n_logged = 0;
+            for (int t = args->start; t > args->start - args->n; --t) n_logged += (t % l.log_every_t == 0 || t == args->start);
+            MAA_CHECK(n_logged == l.n_log, "bad ddpm_sample arguments: n_log does not match log_every_t");
+        }
+        bind(ctx);
+        maa::ddpm_sample(ctx->c, *u->m, *args, d_x);
+    });
+}
+int maa_ddpm_update(maa_ctx* ctx, const float* d_x, const float* d_eps, const int32_t* d_t, const float* h_sqrt_recip_ac,
+                    const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_logvar, int n_tab,
+                    const float* d_noise, float temperature, int clip_denoised, int B, int C, int H, int W, float* d_x_prev,
+                    float* d_x_recon) {
+    return guarded([&] {
+        MAA_CHECK(d_x && d_eps && d_t && d_noise && d_x_prev && d_x_recon, "bad ddpm_update arguments: null pointer");
+        MAA_CHECK(h_sqrt_recip_ac && h_sqrt_recipm1_ac && h_coef1 && h_coef2 && h_logvar, "bad ddpm_update arguments: the posterior tables are missing");
+        MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "bad ddpm_update arguments: empty shape or table");
+        for (const float* out : {(const float*)d_x_prev, (const float*)d_x_recon})
+            MAA_CHECK(out != d_x && out != d_eps && out != d_noise, "bad ddpm_update arguments: the outputs may not alias the inputs");
+        MAA_CHECK(d_x_prev != d_x_recon, "bad ddpm_update arguments: the outputs may not alias each other");
+        bind(ctx);
+        maa::ddpm_update(ctx->c, d_x, d_eps, d_t, h_sqrt_recip_ac, h_sqrt_recipm1_ac, h_coef1, h_coef2, h_logvar, n_tab, d_noise,
+                         temperature, clip_denoised != 0, B, C, H, W, d_x_prev, d_x_recon);
     });
 }
 

@@ -379,6 +379,125 @@ void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
     MAA_HIP(hipStreamSynchronize(ctx.stream));
 }
 
+// LatentDiffusion_audio's ancestral chain (ddpm_audio.py:717-884: p_mean_variance, p_sample, p_sample_loop, progressive_denoising)
+// on the DDIM loop's state: the "schedule" Loop sees is the identity over the model's T DDPM timesteps (index = timestep, so the
+// hoisted embeddings are those of t = 0 .. T-1 whatever part of the chain a call runs), without mask, noise or logs -- those
+// belong to the step kernel here, which blends AFTER the update and reads its coefficients from a table of its own (Ctx::ddpm_tab,
+// one row per timestep) by the index in the step's coefficient slot.  Steps t = start .. start - n + 1; the first runs eager (it
+// sizes the workspace), then one step is captured into Ctx::ddpm_graph and replayed, kept across calls under the loop's key plus
+// everything the step kernel is launched with.
+void ddpm_sample(Ctx& ctx, UNet& unet, const maa_ddpm_args& a, float* d_x) {
+    const maa_ddim_args& u = a.loop;
+    const int T = u.S;
+    MAA_CHECK(T > 0 && u.B > 0 && u.C > 0 && u.H > 0 && u.W > 0, "ddpm: empty problem");
+    MAA_CHECK(a.n >= 1 && a.n <= T, "ddpm: the number of steps must lie in 1 .. num_timesteps");
+    MAA_CHECK(a.start >= a.n - 1 && a.start < T, "ddpm: steps outside the schedule");
+    MAA_CHECK(a.h_sqrt_recip_ac && a.h_sqrt_recipm1_ac && a.h_coef1 && a.h_coef2 && a.h_logvar, "ddpm: the posterior tables are missing");
+    MAA_CHECK(u.d_noise_p, "ddpm: the steps' noise is missing");
+    const bool masked = u.d_mask != nullptr;
+    MAA_CHECK(!masked || (u.d_x0 && u.d_noise_q && a.h_sqrt_ac && a.h_sqrt_1mac), "ddpm: mask needs x0, its noise and the q_sample tables");
+    const bool logging = u.n_log > 0;
+    MAA_CHECK(!logging || (u.d_log_x && u.d_log_x0 && u.log_every_t > 0), "ddpm: intermediates need their buffers and log_every_t");
+
+    std::vector<float> h_tab((size_t)T * DDPM_TAB_W, 0.f);
+    for (int t = 0; t < T; ++t) {
+        float* r = &h_tab[(size_t)t * DDPM_TAB_W];
+        r[0] = a.h_sqrt_recip_ac[t], r[1] = a.h_sqrt_recipm1_ac[t], r[2] = a.h_coef1[t], r[3] = a.h_coef2[t];
+        r[4] = t == 0 ? 0.f : std::exp(0.5f * a.h_logvar[t]);      // nonzero_mask * (0.5 * model_log_variance).exp(), fp32 as torch's
+        r[5] = a.h_temperature ? a.h_temperature[t] : 1.f;
+        r[6] = masked ? a.h_sqrt_ac[t] : 0.f;
+        r[7] = masked ? a.h_sqrt_1mac[t] : 0.f;
+        r[8] = -1.f;
+    }
+    int n_logged = 0;
+    for (int t = a.start; t > a.start - a.n; --t)                   // ddpm_audio.py:877 with timesteps - 1 = the first step run
+        if (logging && (t % u.log_every_t == 0 || t == a.start)) h_tab[(size_t)t * DDPM_TAB_W + 8] = (float)n_logged++;
+    MAA_CHECK(!logging || n_logged == u.n_log, "ddpm: n_log does not match log_every_t");
+
+    // what Loop sees: the identity schedule, no blend before the step, no noise term, no logs of its own
+    std::vector<int32_t> h_ts((size_t)T);
+    std::vector<float> h_one((size_t)T, 1.0f);
+    for (int t = 0; t < T; ++t) h_ts[t] = t;
+    maa_ddim_args la = u;
+    la.h_timesteps = h_ts.data(), la.h_alphas = la.h_alphas_prev = h_one.data();
+    la.d_mask = la.d_x0 = la.d_noise_q = la.d_noise_p = nullptr;
+    la.h_sqrt_ac = la.h_sqrt_1mac = la.h_sigmas = nullptr;
+    la.temperature = 1.0f;
+    la.log_every_t = la.n_log = 0;
+    la.d_log_x = la.d_log_x0 = nullptr;
+    Loop lp(ctx, unet, la, a.start, d_x);
+
+    float* tab = static_cast<float*>(ctx.ddpm_tab.get(h_tab.size() * sizeof(float), ctx.stream));
+    MAA_HIP(hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
+    const long long nel = (long long)u.B * lp.per;
+    float* log_x = logging ? u.d_log_x : nullptr;
+    float* log_x0 = logging ? u.d_log_x0 : nullptr;
+    auto step_body = [&]() {
+        lp.prepare();
+        lp.forward();
+        launch_ddpm_step(ctx, lp.xin, lp.per, lp.per_in, lp.eps, lp.cfg ? lp.eps + nel : nullptr, u.scale, lp.cur_coef, tab, nel, lp.xs,
+                         u.d_noise_p, a.start, a.clip_denoised != 0, u.d_mask, u.d_x0, u.d_noise_q, log_x, log_x0, lp.d_step);
+    };
+    auto key = [&]() {
+        std::vector<unsigned long long> k = lp.key(nullptr);
+        for (const void* p : {(const void*)tab, (const void*)u.d_noise_p, (const void*)u.d_mask, (const void*)u.d_x0,
+                              (const void*)u.d_noise_q, (const void*)log_x, (const void*)log_x0})
+            k.push_back((unsigned long long)reinterpret_cast<uintptr_t>(p));
+        k.push_back((unsigned long long)a.start);
+        k.push_back((unsigned long long)(a.clip_denoised != 0));
+        return k;
+    };
+
+    StepGraph& sg = ctx.ddpm_graph;
+    int first = 0;
+    if (u.use_graph && sg.exec && sg.key == key()) {
+        // the kept step: replay from the first step on
+    } else if (u.use_graph) {
+        sg.clear();
+        step_body();                      // first step eager: sizes the workspace before any capture
+        first = 1;
+        if (a.n > 1) capture_step(ctx, sg, step_body, key());
+    }
+    for (int i = first; i < a.n; ++i) {
+#ifdef MAA_ROCTX
+        char range[48];
+        std::snprintf(range, sizeof(range), "ddpm_step %d/%d t=%d", i + 1, a.n, a.start - i);
+#endif
+        MAA_RANGE_PUSH(range);
+        if (u.use_graph)
+            MAA_HIP(hipGraphLaunch(sg.exec, ctx.stream));
+        else
+            step_body();
+        MAA_RANGE_POP();
+    }
+    MAA_HIP(hipMemcpyAsync(d_x, lp.xs, (size_t)nel * 4, hipMemcpyDeviceToDevice, ctx.stream));
+    MAA_HIP(hipStreamSynchronize(ctx.stream));   // the host tables go out of scope; the call returns a finished latent
+}
+
+// p_sample's arithmetic for one step (ddpm_audio.py:748-777) with a timestep per sample: the five tables go up next to an error
+// flag in a slab of their own, as ddim_stochastic_encode's do.
+void ddpm_update(Ctx& ctx, const float* d_x, const float* d_eps, const int32_t* d_t, const float* h_sqrt_recip_ac,
+                 const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_logvar, int n_tab,
+                 const float* d_noise, float temperature, bool clip, int B, int C, int H, int W, float* d_x_prev, float* d_x_recon) {
+    MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "ddpm_update: empty problem");
+    char* slab = static_cast<char*>(ctx.ddpm_scratch.get(256 + 5 * (size_t)n_tab * sizeof(float), ctx.stream));
+    int* bad = reinterpret_cast<int*>(slab);
+    float* tab = reinterpret_cast<float*>(slab + 256);
+    std::vector<float> h_tab((size_t)5 * n_tab);
+    for (int t = 0; t < n_tab; ++t) {
+        float* r = &h_tab[(size_t)t * 5];
+        r[0] = h_sqrt_recip_ac[t], r[1] = h_sqrt_recipm1_ac[t], r[2] = h_coef1[t], r[3] = h_coef2[t];
+        r[4] = t == 0 ? 0.f : std::exp(0.5f * h_logvar[t]);
+    }
+    MAA_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx.stream));
+    MAA_HIP(hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
+    launch_ddpm_update(ctx, d_x, d_eps, d_t, tab, n_tab, d_noise, temperature, clip, B, (long long)C * H * W, d_x_prev, d_x_recon, bad);
+    int h_bad = 0;
+    MAA_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+    MAA_HIP(hipStreamSynchronize(ctx.stream));
+    MAA_CHECK(h_bad == 0, "ddpm_update: some t[b] lies outside [0, n_tab)");
+}
+
 // One evaluation of the model with split_input_params (ddpm_audio.py:572-654) outside a loop: what Loop::forward does per step,
 // on the caller's x / t / context.  Its device state lives in the context's split_scratch: [wT | norm | crop input | crop eps | t].
 void unet_forward_split(Ctx& ctx, UNet& unet, const float* d_x, const float* d_t, const float* d_context, int B, int H, int W, int kh,

@@ -154,6 +154,9 @@ struct Ctx {
     DevSlab encode_scratch;   // stochastic_encode's coefficient tables and error flag (apart from the loop's slab, whose address the step graph keeps)
     StepGraph plms_graph;     // the PLMS loop's captured Adams-Bashforth step (steps 1 .. S-1), kept apart from ddim_graph
     DevSlab plms_ring;        // the PLMS loop's ring of three e_t slabs (apart from sampler_scratch, which keeps DDIM's size)
+    StepGraph ddpm_graph;     // the ancestral (DDPM) loop's captured step, kept apart from DDIM's and PLMS's
+    DevSlab ddpm_tab;         // the ancestral loop's per-timestep table (its address is in ddpm_graph's key)
+    DevSlab ddpm_scratch;     // maa_ddpm_update's table and error flag
     DevSlab split_scratch;    // maa_unet_forward_split's weighting, norm, crop rows and their timesteps (apart from the loops' slab)
     Profiler* prof = nullptr;
     float* zeros = nullptr;   // 256 B zero page (device), source of masked tile loads
@@ -329,6 +332,16 @@ void launch_ldm_plms_euler_mid(const Ctx& ctx, float* xin, long long per, long l
 // step 0 after its second evaluation: x = update(x, (e_keep + e_next) / 2) in place, logs, *step = idx - 1
 void launch_ldm_plms_euler_final(const Ctx& ctx, const float* eps_u, const float* eps_c, float scale, const float* coef, long long n,
                                  float* x, const float* e_keep, float* log_x, float* log_x0, int* step);
+// LatentDiffusion_audio's ancestral chain (ddpm_audio.py:717-777), ddpm_* kernels.  The loop's step: tab [T][DDPM_TAB_W] per DDPM
+// timestep = {sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sd (0 at t = 0), temperature, sqrt_ac, sqrt_1mac, log slot (-1: none)};
+// t = coef[7] (the step's slot); noise_p / noise_q [.][n] indexed by start - t; the mask blend follows the step; *step = t - 1
+constexpr int DDPM_TAB_W = 9;
+void launch_ddpm_step(const Ctx& ctx, const float* xin, long long per, long long per_in, const float* eps_u, const float* eps_c,
+                      float scale, const float* coef, const float* tab, long long n, float* x_prev, const float* noise_p, int start,
+                      bool clip, const float* mask, const float* x0, const float* noise_q, float* log_x, float* log_x0, int* step);
+// one step with a timestep per sample (p_sample): tab [n_tab][5] = the first five above; *bad is set when some t[b] lies outside it
+void launch_ddpm_update(const Ctx& ctx, const float* x, const float* eps, const int* t, const float* tab, int n_tab, const float* noise,
+                        float temperature, bool clip, int B, long long per, float* x_prev, float* x_recon, int* bad);
 // DDIMSampler.stochastic_encode (ddim.py:227-241): out[b] = tab[t[b]] * x0[b] + tab[n_tab + t[b]] * noise[b] over [B, per];
 // moments / n_post instead of x0: x0 = scale_factor * (mean + exp(0.5 clamp(logvar, -30, 20)) * n_post) from the VAE moments
 // [B, 2, per]; t [B] device int32; *bad (device) is set when some t[b] lies outside [0, n_tab)

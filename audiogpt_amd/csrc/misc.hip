@@ -513,6 +513,99 @@ __global__ void ldm_plms_euler_final_kernel(const float* __restrict__ eu, const 
     }
 }
 
+// ---- LatentDiffusion_audio's ancestral chain (ddpm_audio.py:717-777, ddpm.py:214-227): one DDPM step over the latent.
+//   x_recon = sqrt_recip_ac[t] x - sqrt_recipm1_ac[t] e          predict_start_from_noise     (clamped to [-1, 1] when clip)
+//   mean    = coef1[t] x_recon + coef2[t] x                       q_posterior
+//   x'      = mean + sd[t] (z temperature)                        sd = exp(0.5 logvar_clipped[t]), 0 at t = 0 (no noise there)
+// Term order as torch's (-ffp-contract=off).  c = {sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sd, temperature}.
+template <int V>
+__device__ __forceinline__ void ddpm_update(const FVec<V>& x, const FVec<V>& e, const float* __restrict__ z, const float* c, bool clip,
+                                            FVec<V>& xp, FVec<V>& xr) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        float r = c[0] * x.v[k] - c[1] * e.v[k];
+        if (clip) r = fminf(fmaxf(r, -1.f), 1.f);
+        xr.v[k] = r;
+        xp.v[k] = c[2] * r + c[3] * x.v[k];
+    }
+    if (c[4] != 0.f) {      // (t = 0: the reference multiplies its draw by zero; it is not read here)
+        const FVec<V> zv = load_v<V>(z);
+#pragma unroll
+        for (int k = 0; k < V; ++k) xp.v[k] = xp.v[k] + c[4] * (zv.v[k] * c[5]);
+    }
+}
+
+// The device loop's step (csrc/ddim.cpp ddpm_sample): idx = the DDPM timestep in the step's coefficient slot (written by the
+// prepare kernel), tab [T][DDPM_TAB_W] = {the six of ddpm_update, sqrt_ac, sqrt_1mac, log slot} per timestep, v = start - idx the
+// visiting order that indexes the two noises.  x is read from the step's UNet input as ddim_step_kernel reads it.  The mask
+// blend comes AFTER the step with the step's own t (ddpm_audio.py:873-875; DDIM blends before): x' = q_sample(x0, t) mask +
+// (1 - mask) x'.  A logged step copies x' after the blend and x_recon after the clamp.  V = 4 needs per % 4 == per_in % 4 == 0.
+template <int V>
+__global__ void ddpm_step_kernel(const float* __restrict__ xin, long long per, long long per_in, const float* __restrict__ eu,
+                                 const float* __restrict__ ec, float scale, const float* __restrict__ coef,
+                                 const float* __restrict__ tab, long long n, float* __restrict__ x_prev,
+                                 const float* __restrict__ noise_p, int start, int clip, const float* __restrict__ mask,
+                                 const float* __restrict__ x0, const float* __restrict__ noise_q, float* __restrict__ log_x,
+                                 float* __restrict__ log_x0, int* __restrict__ step) {
+    const int idx = (int)coef[7];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *step = idx - 1;
+    float c[DDPM_TAB_W];
+#pragma unroll
+    for (int k = 0; k < DDPM_TAB_W; ++k) c[k] = tab[(long long)idx * DDPM_TAB_W + k];
+    const int slot = (int)c[8];
+    const long long v = start - idx;
+    const float* zp = noise_p + v * n;
+    const float* zq = noise_q ? noise_q + v * n : nullptr;
+    const long long nv = n / V;
+    for (long long iv = blockIdx.x * (long long)blockDim.x + threadIdx.x; iv < nv; iv += (long long)gridDim.x * blockDim.x) {
+        const long long i = iv * V;
+        const long long b = i / per;
+        const FVec<V> e = plms_eps<V>(eu, ec, scale, i);
+        const FVec<V> x = load_v<V>(xin + b * per_in + (i - b * per));
+        FVec<V> xp, xr;
+        ddpm_update<V>(x, e, zp + i, c, clip != 0, xp, xr);
+        if (mask) {
+            const FVec<V> m = load_v<V>(mask + i), o = load_v<V>(x0 + i), z = load_v<V>(zq + i);
+#pragma unroll
+            for (int k = 0; k < V; ++k) xp.v[k] = (c[6] * o.v[k] + c[7] * z.v[k]) * m.v[k] + (1.f - m.v[k]) * xp.v[k];
+        }
+        store_v<V>(x_prev + i, xp);
+        if (slot >= 0 && log_x) {
+            store_v<V>(log_x + (long long)slot * n + i, xp);
+            store_v<V>(log_x0 + (long long)slot * n + i, xr);
+        }
+    }
+}
+
+// One step outside the loop (p_sample, ddpm_audio.py:748-777): the timestep is t[b] per sample, tab [n_tab][5] = the first five
+// of ddpm_update.  An index outside [0, n_tab) raises *bad and writes zeros, as ddim_stochastic_encode_kernel.  x_prev / x_recon
+// may not alias x.
+template <int V>
+__global__ void ddpm_update_kernel(const float* __restrict__ x, const float* __restrict__ eps, const int* __restrict__ t,
+                                   const float* __restrict__ tab, int n_tab, const float* __restrict__ noise, float temperature,
+                                   int clip, long long per, long long n, float* __restrict__ x_prev, float* __restrict__ x_recon,
+                                   int* __restrict__ bad) {
+    const long long nv = n / V;
+    for (long long iv = blockIdx.x * (long long)blockDim.x + threadIdx.x; iv < nv; iv += (long long)gridDim.x * blockDim.x) {
+        const long long i = iv * V;
+        const int ti = t[i / per];
+        FVec<V> xp, xr;
+        if (ti < 0 || ti >= n_tab) {
+            *bad = 1;
+#pragma unroll
+            for (int k = 0; k < V; ++k) xp.v[k] = xr.v[k] = 0.f;
+        } else {
+            float c[6];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) c[k] = tab[(long long)ti * 5 + k];
+            c[5] = temperature;
+            ddpm_update<V>(load_v<V>(x + i), load_v<V>(eps + i), noise + i, c, clip != 0, xp, xr);
+        }
+        store_v<V>(x_prev + i, xp);
+        store_v<V>(x_recon + i, xr);
+    }
+}
+
 // UNet input and scalars of one DDIM step, with nothing from the host: idx = *step selects the row of the device
 // tables; xin[b'] = cat(x[b' % B], concat[b' % B]) for b' < nB (nB = 2B duplicates the latents for CFG in the order
 // [uncond ; cond], ddim.py:177-179; concat is the inpaint model's conditioning, ddpm.py:1404-1406).
@@ -824,6 +917,33 @@ void launch_ldm_plms_euler_final(const Ctx& ctx, const float* eps_u, const float
         MAA_LAUNCH1(ldm_plms_euler_final_kernel<4>, n / 4, eps_u, eps_c, scale, coef, n, x, e_keep, log_x, log_x0, step);
     } else {
         MAA_LAUNCH1(ldm_plms_euler_final_kernel<1>, n, eps_u, eps_c, scale, coef, n, x, e_keep, log_x, log_x0, step);
+    }
+}
+
+void launch_ddpm_step(const Ctx& ctx, const float* xin, long long per, long long per_in, const float* eps_u, const float* eps_c,
+                      float scale, const float* coef, const float* tab, long long n, float* x_prev, const float* noise_p, int start,
+                      bool clip, const float* mask, const float* x0, const float* noise_q, float* log_x, float* log_x0, int* step) {
+    MAA_CHECK(per > 0 && n > 0 && n % per == 0 && noise_p, "ddpm: empty problem");
+    MAA_CHECK(!mask || (x0 && noise_q), "ddpm: mask needs x0 and its noise");
+    const bool vec = per % 4 == 0 && per_in % 4 == 0 && al16(xin) && al16(eps_u) && al16(eps_c) && al16(x_prev) && al16(noise_p) &&
+                     al16(mask) && al16(x0) && al16(noise_q) && al16(log_x) && al16(log_x0);
+    if (vec) {
+        MAA_LAUNCH1(ddpm_step_kernel<4>, n / 4, xin, per, per_in, eps_u, eps_c, scale, coef, tab, n, x_prev, noise_p, start, (int)clip,
+                    mask, x0, noise_q, log_x, log_x0, step);
+    } else {
+        MAA_LAUNCH1(ddpm_step_kernel<1>, n, xin, per, per_in, eps_u, eps_c, scale, coef, tab, n, x_prev, noise_p, start, (int)clip, mask,
+                    x0, noise_q, log_x, log_x0, step);
+    }
+}
+void launch_ddpm_update(const Ctx& ctx, const float* x, const float* eps, const int* t, const float* tab, int n_tab, const float* noise,
+                        float temperature, bool clip, int B, long long per, float* x_prev, float* x_recon, int* bad) {
+    MAA_CHECK(B > 0 && per > 0 && n_tab > 0 && x && eps && t && tab && noise && x_prev && x_recon && bad, "ddpm_update: empty problem");
+    const long long n = (long long)B * per;
+    const bool vec = per % 4 == 0 && al16(x) && al16(eps) && al16(noise) && al16(x_prev) && al16(x_recon);
+    if (vec) {
+        MAA_LAUNCH1(ddpm_update_kernel<4>, n / 4, x, eps, t, tab, n_tab, noise, temperature, (int)clip, per, n, x_prev, x_recon, bad);
+    } else {
+        MAA_LAUNCH1(ddpm_update_kernel<1>, n, x, eps, t, tab, n_tab, noise, temperature, (int)clip, per, n, x_prev, x_recon, bad);
     }
 }
 

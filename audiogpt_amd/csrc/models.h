@@ -149,6 +149,12 @@ void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x);
 void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, float* d_x);
 // PLMSSampler.plms_sampling (plms.py:115-236) over the S-step schedule `a` describes (eta 0: no sigmas, no step noise)
 void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x);
+// LatentDiffusion_audio's ancestral chain (ddpm_audio.py:717-884): DDPM steps a.start .. a.start - a.n + 1 on the device
+void ddpm_sample(Ctx& ctx, UNet& unet, const maa_ddpm_args& a, float* d_x);
+// one such step with a timestep per sample and host tables of n_tab rows (p_sample); checks every t[b] against n_tab
+void ddpm_update(Ctx& ctx, const float* d_x, const float* d_eps, const int32_t* d_t, const float* h_sqrt_recip_ac,
+                 const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_logvar, int n_tab,
+                 const float* d_noise, float temperature, bool clip, int B, int C, int H, int W, float* d_x_prev, float* d_x_recon);
 // DDIMSampler.stochastic_encode (ddim.py:227-241) with host tables of n_tab rows; checks every t[b] against n_tab
 // One model evaluation with split_input_params outside a loop (ddpm_audio.py:572-654): unfold, the UNet over B * L crop rows,
 // fold.  h_weight [kh * kw][L] on the host (get_weighting's table); d_context [B, context_len(), context_dim] or null

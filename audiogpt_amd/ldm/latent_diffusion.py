@@ -5,6 +5,8 @@ Stands in for `ldm.models.diffusion.ddpm_audio.LatentDiffusion_audio` as used at
   .first_stage_model.embed_dim, .get_learned_conditioning, .cond_stage_model, .encode_first_stage,
   .get_first_stage_encoding, .decode_first_stage, .apply_model, .num_timesteps, .betas, .alphas_cumprod(_prev),
   .device, .load_state_dict(sd, strict=False), .to(device)
+and the model's own ancestral sampler (ddpm_audio.py:717-917; ldm/ddpm.py): register_schedule's posterior buffers,
+  .p_mean_variance, .p_sample, .p_sample_loop, .progressive_denoising, .sample, .sample_log, .log_every_t, .clip_denoised
 UNet and VAE run in libaudiogpt_mi355x; the conditioning encoders (CLAP text tower / OpenCLIP image tower,
 ldm/modules/encoders/modules.py:173-212, 315-350) are outside the hot path: the caller
 plugs one in as `cond_stage_model` (any object with `.encode(list[str])` / `.forward_img(img)`); without one a
@@ -19,6 +21,7 @@ from .. import config as C
 from .. import weights as WT
 from ..backend import Context, UNet, VAE, default_precision
 from ..pipeline import alphas_cumprod_f32, make_beta_schedule_linear
+from .ddpm import AncestralSampling
 
 
 class DiagonalGaussianDistribution(object):
@@ -87,7 +90,7 @@ class _FirstStage(object):
         return DiagonalGaussianDistribution(self._owner.vae.encode_moments(x))
 
 
-class LatentDiffusionAudio(object):
+class LatentDiffusionAudio(AncestralSampling):
     def __init__(self, ldm_config=None, device="cuda:0", state_dict=None, seeds=(0, 1), cond_stage_model=None,
                  precision=None, tokenizer=None, preprocess=None):
         self.cfg = ldm_config or C.LDM_T2A
@@ -106,6 +109,10 @@ class LatentDiffusionAudio(object):
         ac64 = np.cumprod(1.0 - betas, axis=0)
         self.sqrt_alphas_cumprod = torch.tensor(np.sqrt(ac64), dtype=torch.float32, device=self.device)
         self.sqrt_one_minus_alphas_cumprod = torch.tensor(np.sqrt(1.0 - ac64), dtype=torch.float32, device=self.device)
+        # the model's own ancestral sampler (ldm/ddpm.py): the rest of register_schedule's buffers, and what sample() reads
+        self.register_ancestral_schedule(self.num_timesteps, self.cfg["linear_start"], self.cfg["linear_end"])
+        self.log_every_t = int(self.cfg.get("log_every_t", 200))
+        self.channels, self.mel_dim, self.mel_length = self.cfg["latent_shape"]
         self.scale_factor = float(self.cfg.get("scale_factor", 1.0))
         self.unet = self.vae = None
         # conditioning encoder: the caller's; else the device towers when the checkpoint carries their weights

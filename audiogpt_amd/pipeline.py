@@ -1,4 +1,4 @@
-"""Make-An-Audio generation pipeline on one MI355X: DDIM or PLMS (UNet) -> VAE decode -> clamp -> vocoder.
+"""Make-An-Audio generation pipeline on one MI355X: DDIM, PLMS or ancestral DDPM (UNet) -> VAE decode -> clamp -> vocoder.
 
 This is the body of the reference's `T2A.txt2audio` / `I2A.img2audio` / `Inpaint.inpaint`
 (audio-chatgpt.py:158-183, 232-261, 500-528) between conditioning and waveform, run by
@@ -59,6 +59,7 @@ class MakeAnAudio:
         self.vocoder = Vocoder(self.ctx, self.vocoder_cfg, vocoder_sd)
         self.scale_factor = float(self.ldm.get("scale_factor", 1.0))
         self.alphas_cumprod = alphas_cumprod_f32(self.ldm["timesteps"], self.ldm["linear_start"], self.ldm["linear_end"])
+        self._ddpm_tables = None      # the ancestral sampler's schedule buffers, made on first use (sample_latents)
 
     # ---- stages ----------------------------------------------------------------------------------
     # The widest latent the chain takes.  The VAE decoder's mid-block attention (vae.cpp run_attn: one head as wide as the block,
@@ -77,13 +78,25 @@ class MakeAnAudio:
 
     def sample_latents(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim", split=None):
         """x_T -> x_0 over the S-step schedule: sampler "ddim" (DDIMSampler, S UNet evaluations) or "plms" (PLMSSampler,
-        S + 1 evaluations).  split: the reference's `split_input_params` dictionary (ldm/split.py) for a latent wider than the
+        S + 1 evaluations); or sampler "ddpm", the model's own ancestral chain (LatentDiffusion_audio.p_sample_loop) over all
+        `timesteps` (1000) DDPM steps with the model's clip_denoised=True -- S is ignored there.  Its per-step noise is drawn up
+        front from torch's global generator on the device, in the reference's order (ldm/ddpm.py): timesteps * B * C * H * W * 4
+        bytes, 100 MB for 8 T2A latents.  Guidance with "ddpm" is an extension (the reference's chain has none).
+        split: the reference's `split_input_params` dictionary (ldm/split.py) for a latent wider than the
         model was trained on -- every evaluation runs on overlapping crops of `ks` and is stitched (ddpm_audio.py:572-654)."""
-        if sampler not in ("ddim", "plms"):
-            raise MaaError('sampler must be "ddim" or "plms", got %r' % (sampler,))
+        if sampler not in ("ddim", "plms", "ddpm"):
+            raise MaaError('sampler must be "ddim", "plms" or "ddpm", got %r' % (sampler,))
+        kw = dict(split=split) if split is not None else {}
+        if sampler == "ddpm":
+            from .ldm.ddpm import schedule_buffers
+            if self._ddpm_tables is None:
+                self._ddpm_tables = schedule_buffers(self.ldm["timesteps"], self.ldm["linear_start"], self.ldm["linear_end"])
+            n = self.ldm["timesteps"]
+            noise_p = torch.stack([torch.randn(tuple(x_T.shape), device=self.device) for _ in range(n)])      # ddpm_audio.py:766
+            return self.unet.ddpm_sample(x_T, self._ddpm_tables, n, cond=cond, uncond=uncond, scale=scale, concat=concat,
+                                         noise_p=noise_p, use_graph=use_graph, **kw)
         steps, a, ap = ddim_schedule(S, self.alphas_cumprod)
         run = self.unet.plms_sample if sampler == "plms" else self.unet.ddim_sample
-        kw = dict(split=split) if split is not None else {}
         return run(x_T, steps, a, ap, cond=cond, uncond=uncond, scale=scale, concat=concat, use_graph=use_graph, **kw)
 
     def decode(self, z):
@@ -104,7 +117,7 @@ class MakeAnAudio:
     def generate(self, x_T, cond=None, uncond=None, scale=1.0, S=100, concat=None, use_graph=True, sampler="ddim", split=None):
         """x_T [B,4,h,w] -> (wav [B, T*hop], spec [B,80,T], z [B,4,h,w]); all on the device.  With a private stream the
         work is ordered after the caller's current stream on entry and the caller's stream after it on return.
-        sampler: "ddim" or "plms" (sample_latents).
+        sampler: "ddim", "plms" or "ddpm" -- the model's ancestral chain over all its timesteps; S is ignored (sample_latents).
         split: long-form generation -- the reference's `split_input_params` dictionary (sample_latents); the sampler evaluates the
         UNet on crops of the training size, the VAE decode and the vocoder run on the whole width.  The widest latent the VAE's
         mid-block attention accepts is h * w <= 46340 positions (w <= 4634 at h = 10, about 593 s of audio: MAX_LATENT_POSITIONS

@@ -237,6 +237,45 @@ int maa_ddim_decode(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, int t_
  * step replayed, kept on the context apart from maa_ddim_sample's.  (Not the DiffSinger maa_plms_sample below.) */
 int maa_ldm_plms_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, float* d_x);
 
+/* replaces: LatentDiffusion_audio's own ancestral chain -- p_mean_variance / p_sample / p_sample_loop / progressive_denoising
+ * (ldm/models/diffusion/ddpm_audio.py:717-884) -- on the device: the DDPM steps t = start, start - 1, ..., start - n + 1 of the
+ * model's num_timesteps-step schedule (p_sample_loop is start = n - 1), one UNet evaluation and one fused kernel each:
+ *   e       = eps                                   (eps_u + scale (eps_c - eps_u) with guidance: an extension, the reference's chain has none)
+ *   x_recon = h_sqrt_recip_ac[t] x - h_sqrt_recipm1_ac[t] e,  clamped to [-1, 1] when clip_denoised          (ddpm.py:214-218)
+ *   mean    = h_coef1[t] x_recon + h_coef2[t] x                                                               (ddpm.py:220-224)
+ *   x'      = mean + (t != 0) exp(0.5 h_logvar[t]) (noise_p[v] temperature[t]),  v = start - t                (ddpm_audio.py:766-777)
+ *   x'      = (h_sqrt_ac[t] x0 + h_sqrt_1mac[t] noise_q[v]) mask + (1 - mask) x'   with a mask, AFTER the step (ddpm_audio.py:873-875)
+ * `loop` carries what the loop shares with maa_ddim_sample: S = num_timesteps (the rows of every table below), B, C, H, W, the
+ * conditioning (d_cond / d_uncond / scale / L, or d_concat / Cc), use_graph, d_mask / d_x0 / d_noise_q [n][B, C, H, W], d_noise_p
+ * [n][B, C, H, W] (required; both in loop order, first step first), log_every_t / n_log / d_log_x / d_log_x0 and the split.  A step
+ * is logged when t % log_every_t == 0 or t == start: x' after the blend -> d_log_x, x_recon after the clamp -> d_log_x0; n_log must
+ * equal the number of such steps among the n run.  loop's h_timesteps / h_alphas / h_alphas_prev / h_sqrt_ac / h_sqrt_1mac / h_sigmas /
+ * temperature are not read.  The tables are the model's fp32 buffers (ddpm.py:115-155), one row per DDPM timestep, on the host;
+ * h_temperature [S] (progressive_denoising's per-timestep list) may be NULL: 1.  The first step runs eagerly and sizes the workspace,
+ * then one step is captured and replayed; the graph is kept on the context apart from maa_ddim_sample's and maa_ldm_plms_sample's. */
+typedef struct maa_ddpm_args {
+    maa_ddim_args loop;
+    int start, n;
+    int clip_denoised;
+    const float* h_sqrt_recip_ac;
+    const float* h_sqrt_recipm1_ac;
+    const float* h_coef1;
+    const float* h_coef2;
+    const float* h_logvar;          /* posterior_log_variance_clipped */
+    const float* h_sqrt_ac;         /* with a mask: sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod */
+    const float* h_sqrt_1mac;
+    const float* h_temperature;
+} maa_ddpm_args;
+int maa_ddpm_sample(maa_ctx* ctx, maa_unet* u, const maa_ddpm_args* args, float* d_x);
+/* The same arithmetic for ONE step with a timestep per sample (p_sample, ddpm_audio.py:748-777): d_t [B] device int32 indexes the
+ * five host tables of n_tab rows (checked as maa_ddim_stochastic_encode checks its indices); d_eps is the model's output (after any
+ * score corrector); d_x_prev = mean + (t != 0) exp(0.5 logvar[t]) (d_noise temperature), d_x_recon = the clamped prediction
+ * (return_x0).  Outputs may not alias the inputs.  Synchronises the context's stream. */
+int maa_ddpm_update(maa_ctx* ctx, const float* d_x, const float* d_eps, const int32_t* d_t, const float* h_sqrt_recip_ac,
+                    const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_logvar, int n_tab,
+                    const float* d_noise, float temperature, int clip_denoised, int B, int C, int H, int W, float* d_x_prev,
+                    float* d_x_recon);
+
 /* ---- VAE ----------------------------------------------------------------------------------------
  * ddconfig of ldm.models.autoencoder.AutoencoderKL (txt2audio_args.yaml:54-68) */
 typedef struct maa_vae_config {
