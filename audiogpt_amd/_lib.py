@@ -102,6 +102,14 @@ class maa_plms_args(C.Structure):
                 ("d_cond", C.c_void_p), ("h_alphas_cumprod", C.POINTER(C.c_float)), ("use_graph", C.c_int)]
 
 
+class maa_ds_ddpm_args(C.Structure):
+    _fields_ = [("B", C.c_int), ("T", C.c_int), ("start", C.c_int), ("n", C.c_int), ("timesteps", C.c_int),
+                ("clip_denoised", C.c_int), ("use_graph", C.c_int),
+                ("d_cond", C.c_void_p), ("d_noise", C.c_void_p),
+                ("h_sqrt_recip_ac", C.POINTER(C.c_float)), ("h_sqrt_recipm1_ac", C.POINTER(C.c_float)),
+                ("h_coef1", C.POINTER(C.c_float)), ("h_coef2", C.POINTER(C.c_float)), ("h_sigma", C.POINTER(C.c_float))]
+
+
 EXPORTS = [
     "maa_last_error", "maa_version", "maa_ctx_create", "maa_ctx_destroy", "maa_ctx_synchronize",
     "maa_ctx_set_stream", "maa_ctx_set_precision", "maa_ctx_set_cfg_split", "maa_ctx_set_concurrency", "maa_ctx_reload_tuning", "maa_ctx_workspace_bytes", "maa_prof_begin", "maa_prof_end", "maa_unet_create", "maa_unet_destroy",
@@ -110,7 +118,7 @@ EXPORTS = [
     "maa_vae_create",
     "maa_vae_destroy", "maa_vae_decode", "maa_vae_decode_spec", "maa_vae_encode_moments", "maa_vocoder_create", "maa_vocoder_destroy",
     "maa_vocoder_forward", "maa_vocoder_forward_f0", "maa_diffnet_create", "maa_diffnet_destroy", "maa_diffnet_forward",
-    "maa_plms_sample", "maa_encoder_create", "maa_encoder_destroy", "maa_encoder_text", "maa_encoder_image",
+    "maa_plms_sample", "maa_ds_ddpm_sample", "maa_ds_ddpm_update", "maa_encoder_create", "maa_encoder_destroy", "maa_encoder_text", "maa_encoder_image",
     "maa_encoder_text_cls", "maa_clap_audio_create", "maa_clap_audio_destroy", "maa_clap_audio_embed", "maa_clap_similarity",
     "maa_spectral_create", "maa_spectral_destroy", "maa_spectral_forward", "maa_resampler_create", "maa_resampler_destroy",
     "maa_resampler_forward", "maa_op_linear", "maa_op_conv", "maa_op_groupnorm", "maa_op_layernorm",
@@ -172,6 +180,8 @@ def load():
         "maa_diffnet_destroy": [vp],
         "maa_diffnet_forward": [vp, vp, vp, vp, vp, ci, ci, vp],
         "maa_plms_sample": [vp, vp, C.POINTER(maa_plms_args), vp],
+        "maa_ds_ddpm_sample": [vp, vp, C.POINTER(maa_ds_ddpm_args), vp],
+        "maa_ds_ddpm_update": [vp, vp, vp, vp, fp, fp, fp, fp, fp, ci, ci, ci, ci, ci, vp],
         "maa_encoder_create": [vp, C.POINTER(maa_encoder_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
         "maa_encoder_destroy": [vp],
         "maa_encoder_text": [vp, vp, vp, ci, ci, vp],

@@ -979,6 +979,70 @@ class DiffNet:
             L.check(self.ctx.lib.maa_plms_sample(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
         return x
 
+    @staticmethod
+    def _ddpm_tables(what, tables):
+        """The five host tables of the ancestral step, fp32 and of one length: (sqrt_recip_alphas_cumprod,
+        sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2, sigma)."""
+        if len(tables) != 5:
+            raise L.MaaError(what + ": tables = (sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, sigma), got %d" % len(tables))
+        tabs = [np.ascontiguousarray(np.asarray(t), dtype=np.float32).reshape(-1) for t in tables]
+        if tabs[0].shape[0] < 1 or any(t.shape[0] != tabs[0].shape[0] for t in tabs):
+            raise L.MaaError(what + ": the tables need one row per timestep each, got %s" % [t.shape[0] for t in tabs])
+        return tabs, [t.ctypes.data_as(C.POINTER(C.c_float)) for t in tabs]
+
+    def ddpm_sample(self, x, cond, tables, start, n, noise, clip_denoised=True, use_graph=True):
+        """The ancestral steps t = start, ..., start - n + 1 on the device through maa_ds_ddpm_sample (p_sample in the loop of
+        shallow_diffusion_tts.py:269-271): x [B, 1, M, T] at step `start` -> x after step start - n + 1 (a new tensor).
+        tables: see _ddpm_tables; noise [n, B, 1, M, T]: the steps' draws in loop order."""
+        what = "ds_ddpm_sample"
+        dev = self.ctx.device
+        x = _f32(x, dev).clone()
+        cond, noise = _f32(cond, dev), _f32(noise, dev)
+        if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != self.cfg["in_dims"]:
+            raise L.MaaError("%s: x %s is not [B, 1, %d, T]" % (what, tuple(x.shape), self.cfg["in_dims"]))
+        B, _, M, T = x.shape
+        if tuple(cond.shape) != (B, self.cfg["hidden_size"], T):
+            raise L.MaaError("%s: cond %s does not fit x %s: it must be [B, %d, T]"
+                             % (what, tuple(cond.shape), tuple(x.shape), self.cfg["hidden_size"]))
+        if B > 256:
+            raise L.MaaError("%s: at most 256 samples per call (got %d)" % (what, B))
+        start, n = int(start), int(n)
+        tabs, ptrs = self._ddpm_tables(what, tables)
+        if n < 1:
+            raise L.MaaError("%s: the number of steps n must be at least 1 (got %d)" % (what, n))
+        if start < 0 or start >= tabs[0].shape[0]:
+            raise L.MaaError("%s: start %d lies outside the schedule of %d timesteps" % (what, start, tabs[0].shape[0]))
+        if start - n + 1 < 0:
+            raise L.MaaError("%s: %d steps from t = %d run past t = 0" % (what, n, start))
+        if tuple(noise.shape) != (n,) + tuple(x.shape):
+            raise L.MaaError("%s: noise %s is not [n = %d] + x %s" % (what, tuple(noise.shape), n, tuple(x.shape)))
+        a = L.maa_ds_ddpm_args()
+        a.B, a.T, a.start, a.n, a.timesteps = B, T, start, n, int(tabs[0].shape[0])
+        a.clip_denoised, a.use_graph = int(bool(clip_denoised)), int(bool(use_graph))
+        a.d_cond, a.d_noise = cond.data_ptr(), noise.data_ptr()
+        a.h_sqrt_recip_ac, a.h_sqrt_recipm1_ac, a.h_coef1, a.h_coef2, a.h_sigma = ptrs
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_ds_ddpm_sample(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
+        return x
+
+    def ddpm_update(self, x, eps, t, tables, noise, clip_denoised=True):
+        """One ancestral step outside the loop through maa_ds_ddpm_update (p_sample's arithmetic after the denoiser,
+        shallow_diffusion_tts.py:134-166): x, eps, noise [B, 1, M, T], t [B] integer steps (one per sample) -> x_{t-1} (new)."""
+        what = "ds_ddpm_update"
+        dev = self.ctx.device
+        x = _f32(x, dev).clone()
+        eps, noise = _f32(eps, dev), _f32(noise, dev)
+        t = _f32(torch.as_tensor(t).reshape(-1), dev)
+        if x.dim() != 4 or x.shape[1] != 1 or eps.shape != x.shape or noise.shape != x.shape or t.shape[0] != x.shape[0]:
+            raise L.MaaError("%s: x %s / eps %s / noise %s / t %s do not fit each other"
+                             % (what, tuple(x.shape), tuple(eps.shape), tuple(noise.shape), tuple(t.shape)))
+        B, _, M, T = x.shape
+        tabs, ptrs = self._ddpm_tables(what, tables)
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_ds_ddpm_update(self.ctx.h, L.dptr(eps), L.dptr(t), L.dptr(noise), *ptrs, int(tabs[0].shape[0]),
+                                                    B, M, T, int(bool(clip_denoised)), L.dptr(x)))
+        return x
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.maa_diffnet_destroy(self.h)

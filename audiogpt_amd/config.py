@@ -95,7 +95,20 @@ HIFIGAN_NSF_24K = dict(HIFIGAN_16K, sampling_rate=24000, upsample_rates=(8, 4, 2
 # DiffSinger denoiser + PLMS loop of the T2S tool (egs_bases/svs/base.yaml:3-5, midi/e2e/opencpop/ds1000.yaml:22-36;
 # checkpoints/0831_opencpop_ds1000): oracle groundwork for SURVEY 8f/N2 only.
 DIFFSINGER_DS1000 = dict(in_dims=80, hidden_size=256, residual_layers=20, residual_channels=256, dilation_cycle_length=4,
-                         timesteps=1000, K_step=1000, max_beta=0.02, pndm_speedup=10)
+                         timesteps=1000, K_step=1000, max_beta=0.02, pndm_speedup=10, schedule_type="linear")
+
+# The configurations without pndm_speedup: the reference samples them with the ancestral chain, K_step p_sample steps
+# (shallow_diffusion_tts.py:269-271).  hidden_size 256 is the FastSpeech2 default they inherit; residual_layers / residual_channels /
+# dilation_cycle_length / timesteps come from egs_bases/svs/base.yaml:3-6.  spec_min / spec_max (80 values, in the same files)
+# belong to the checkpoint and are passed to GaussianDiffusion by the caller.
+# egs_bases/svs/popcs_ds_beta6.yaml:63-68 (DiffSinger on PopCS, shallow diffusion from the fs2 mel at t = 50)
+DIFFSINGER_POPCS_BETA6 = dict(in_dims=80, hidden_size=256, residual_layers=20, residual_channels=256, dilation_cycle_length=1,
+                              timesteps=100, K_step=51, max_beta=0.06, schedule_type="linear")
+# egs_bases/svs/lj_ds_beta6.yaml:36-41 (DiffSpeech on LJSpeech)
+DIFFSPEECH_LJ_BETA6 = dict(DIFFSINGER_POPCS_BETA6, K_step=71)
+# egs_bases/svs/midi/e2e/opencpop/ds100_adj_rel.yaml:22-32 and midi/e2e/popcs/ds100_adj_rel.yaml over popcs_ds_beta6.yaml: the
+# whole chain from Gaussian noise
+DIFFSINGER_DS100_ADJ_REL = dict(DIFFSINGER_POPCS_BETA6, dilation_cycle_length=4, K_step=100, gaussian_start=True)
 
 # BigVGAN's args.yml (vocoder/logs/bigv16k53w) does not ship with the reference
 # (SURVEY.md section 0.3); these are the generator defaults it is exercised with here.

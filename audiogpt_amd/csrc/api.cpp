@@ -497,6 +497,26 @@ int maa_plms_sample(maa_ctx* ctx, maa_diffnet* d, const maa_plms_args* args, flo
         d->m->plms_sample(ctx->c, *args, d_x);
     });
 }
+int maa_ds_ddpm_sample(maa_ctx* ctx, maa_diffnet* d, const maa_ds_ddpm_args* args, float* d_x) {
+    return guarded([&] {
+        bind(ctx);
+        MAA_CHECK(d && args && d_x, "bad ds_ddpm_sample arguments: null pointer");
+        d->m->ddpm_sample(ctx->c, *args, d_x);
+    });
+}
+int maa_ds_ddpm_update(maa_ctx* ctx, const float* d_eps, const float* d_t, const float* d_noise, const float* h_sqrt_recip_ac,
+                       const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_sigma,
+                       int timesteps, int B, int M, int T, int clip_denoised, float* d_x) {
+    return guarded([&] {
+        bind(ctx);
+        MAA_CHECK(d_eps && d_t && d_noise && d_x, "bad ds_ddpm_update arguments: null pointer");
+        MAA_CHECK(h_sqrt_recip_ac && h_sqrt_recipm1_ac && h_coef1 && h_coef2 && h_sigma,
+                  "bad ds_ddpm_update arguments: the posterior tables are missing");
+        MAA_CHECK(d_x != d_eps && d_x != d_noise, "bad ds_ddpm_update arguments: d_x is updated in place and may not alias the inputs");
+        maa::ds_ddpm_update(ctx->c, d_eps, d_t, d_noise, h_sqrt_recip_ac, h_sqrt_recipm1_ac, h_coef1, h_coef2, h_sigma, timesteps,
+                            B, M, T, clip_denoised != 0, d_x);
+    });
+}
 
 // ------------------------------------------------------------------------------------------ conditioning encoders
 int maa_encoder_create(maa_ctx* ctx, const maa_encoder_config* cfg, const maa_tensor* tensors, int n_tensors,

@@ -1,8 +1,9 @@
-// DiffSinger's denoiser (DiffNet) and the PLMS sampling loop on the device (the T2S tool's diffusion hot
+// DiffSinger's denoiser (DiffNet) and its two sampling loops on the device (the T2S tool's diffusion hot
 // loop, audio-chatgpt.py:298-339).
 //
 // Mirrors NeuralSeq/modules/diff/net.py:58-130 (ResidualBlock, DiffNet.forward) and
-// NeuralSeq/modules/diff/shallow_diffusion_tts.py:166-201, 262-269 (p_sample_plms and its loop with pndm_speedup).
+// NeuralSeq/modules/diff/shallow_diffusion_tts.py:166-201, 262-269 (p_sample_plms and its loop with pndm_speedup) and
+// :134-166, 269-271 (p_sample and the ancestral loop every configuration without pndm_speedup takes).
 // Layout: channels-last sequences [B, T, C]; a Conv1d(k = 1) is a plain GEMM over the B*T rows, the dilated k = 3 conv an
 // implicit GEMM.  Differences from a literal translation (same maths):
 //   * the 20 per-layer `diffusion_projection` Linears of the step embedding run as ONE GEMM per evaluation
@@ -15,6 +16,8 @@
 #include "models.h"
 
 #include <cmath>
+#include <cstdint>
+#include <vector>
 
 namespace maa {
 
@@ -29,6 +32,10 @@ void launch_ds_plms(const Ctx& ctx, float* x, const float* e, const float* e_pre
                     const float* ac, int interval, int* st, int mode, float* x_out);
 void launch_ds_plms_advance(const Ctx& ctx, int* st, int interval, float* t_slot, int B);
 void launch_ds_fill(const Ctx& ctx, float* p, int n, float v);
+void launch_ds_ddpm_step(const Ctx& ctx, float* x, const float* e, const float* noise, long long n, const float* tab,
+                         int timesteps, const int* st, int start, int n_steps, int clip);
+void launch_ds_ddpm_update(const Ctx& ctx, float* x, const float* e, const float* noise, int B, long long per, const float* t,
+                           const float* tab, int timesteps, int clip, int* bad);
 
 struct DiffNet::Impl {
     maa_diffnet_config cfg;
@@ -40,7 +47,7 @@ struct DiffNet::Impl {
     DevSlab cond_cache;       // conditioner projections of all layers for the current conditioning: [B*T, L * 2C]
     const float* cond_src = nullptr;
     int cond_B = 0, cond_T = 0;
-    DevSlab loop;             // PLMS loop state
+    DevSlab loop;             // state of the sampling loop that runs (PLMS or ancestral; each call writes all of its own)
 
     void build(const StateDict& sd) {
         const int L = cfg.residual_layers;
@@ -198,6 +205,51 @@ void DiffNet::forward(Ctx& ctx, const float* spec, const float* t, const float* 
     run_sized(ctx, [&] { m.forward(ctx, spec, t, B, T, out); });
 }
 
+namespace {
+
+// `count` more steps of a sampling loop whose first step has run eagerly (and sized the workspace): identical launches on identical
+// addresses, so one step is captured as a hipGraph and replayed; use_graph false runs the same body eagerly.  Ends synchronised.
+template <class F>
+void run_steps(Ctx& ctx, int count, bool use_graph, F&& step_body) {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    try {
+        for (int i = 0; i < count; ++i) {
+            if (!use_graph) {
+                ctx.ws.reset();
+                step_body();
+                continue;
+            }
+            if (!exec) {
+                ctx.ws.reset();
+                MAA_HIP(hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeRelaxed));
+                try {
+                    step_body();
+                } catch (...) {
+                    hipGraph_t dead = nullptr;
+                    (void)hipStreamEndCapture(ctx.stream, &dead);
+                    if (dead) (void)hipGraphDestroy(dead);
+                    throw;
+                }
+                MAA_HIP(hipStreamEndCapture(ctx.stream, &graph));
+                MAA_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+            }
+            MAA_HIP(hipGraphLaunch(exec, ctx.stream));
+        }
+        MAA_HIP(hipStreamSynchronize(ctx.stream));
+    } catch (...) {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        throw;
+    }
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
 void DiffNet::plms_sample(Ctx& ctx, const maa_plms_args& a, float* d_x) {
     Impl& m = *impl_;
     MAA_CHECK(a.B > 0 && a.T > 0 && a.K_step > 0 && a.interval > 0 && a.timesteps >= a.K_step && a.h_alphas_cumprod && a.d_cond,
@@ -239,39 +291,83 @@ void DiffNet::plms_sample(Ctx& ctx, const maa_plms_args& a, float* d_x) {
         launch_ds_plms(ctx, d_x, e, nullptr, hist, n, ac, a.interval, st, 0, nullptr);
         launch_ds_plms_advance(ctx, st, a.interval, t_slot, B);
     };
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    try {
-        for (int i = 1; i < nsteps; ++i) {
-            if (!a.use_graph) {
-                ctx.ws.reset();
-                step_body();
-                continue;
-            }
-            if (!exec) {
-                ctx.ws.reset();
-                MAA_HIP(hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeRelaxed));
-                try {
-                    step_body();
-                } catch (...) {
-                    hipGraph_t dead = nullptr;
-                    (void)hipStreamEndCapture(ctx.stream, &dead);
-                    if (dead) (void)hipGraphDestroy(dead);
-                    throw;
-                }
-                MAA_HIP(hipStreamEndCapture(ctx.stream, &graph));
-                MAA_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            }
-            MAA_HIP(hipGraphLaunch(exec, ctx.stream));
-        }
-        MAA_HIP(hipStreamSynchronize(ctx.stream));
-    } catch (...) {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
+    run_steps(ctx, nsteps - 1, a.use_graph != 0, step_body);
+}
+
+// The ancestral chain (shallow_diffusion_tts.py:269-271 / :320-321 over p_sample, :159-166).  Loop state in Impl::loop, which the
+// PLMS loop also uses (every call writes all of its own): the coefficient table [timesteps][5], {t, steps done, -}, the timestep
+// slot, eps.  The step reads t from the state and takes its noise at draw start - t of the caller's buffer, so the captured step
+// carries no host data; ds_plms_advance_kernel with interval 1 moves t and writes the next evaluation's timestep slot.
+void DiffNet::ddpm_sample(Ctx& ctx, const maa_ds_ddpm_args& a, float* d_x) {
+    Impl& m = *impl_;
+    const int B = a.B, T = a.T, M = m.cfg.in_dims;
+    MAA_CHECK(B > 0 && T > 0 && a.timesteps > 0, "ds_ddpm_sample: empty problem");
+    MAA_CHECK(a.n >= 1, "ds_ddpm_sample: the number of steps n must be at least 1");
+    MAA_CHECK(a.start >= 0 && a.start < a.timesteps, "ds_ddpm_sample: start lies outside the schedule (0 <= start < timesteps)");
+    MAA_CHECK(a.start - a.n + 1 >= 0, "ds_ddpm_sample: the steps run past t = 0 (start - n + 1 < 0)");
+    MAA_CHECK(a.h_sqrt_recip_ac && a.h_sqrt_recipm1_ac && a.h_coef1 && a.h_coef2 && a.h_sigma,
+              "ds_ddpm_sample: the posterior tables are missing");
+    MAA_CHECK(a.d_cond, "ds_ddpm_sample: the conditioning d_cond is missing");
+    MAA_CHECK(a.d_noise, "ds_ddpm_sample: the steps' noise d_noise is missing");
+    MAA_CHECK(B <= 256, "ds_ddpm_sample: at most 256 samples per call (the step-advance kernel is one workgroup)");
+    MAA_CHECK(M % 4 == 0, "ds_ddpm_sample: in_dims must be a multiple of 4 (16-byte accesses)");
+    MAA_CHECK(aligned16(d_x) && aligned16(a.d_noise), "ds_ddpm_sample: d_x and d_noise must be 16-byte aligned");
+    PrecisionGuard pg(ctx, m.precision);
+    const long long n = (long long)B * M * T;
+    m.set_cond(ctx, a.d_cond, B, T);
+    auto up = [](size_t k) { return (k + 63) / 64 * 64; };
+    const size_t o_tab = 0, o_st = o_tab + up((size_t)5 * a.timesteps), o_t = o_st + 64, o_e = o_t + up(B), total = o_e + up(n);
+    float* slab = static_cast<float*>(m.loop.get(total * sizeof(float), ctx.stream));
+    float *tab = slab + o_tab, *t_slot = slab + o_t, *e = slab + o_e;
+    int* st = reinterpret_cast<int*>(slab + o_st);
+    std::vector<float> h_tab((size_t)5 * a.timesteps);
+    for (int t = 0; t < a.timesteps; ++t) {
+        float* r = &h_tab[(size_t)t * 5];
+        r[0] = a.h_sqrt_recip_ac[t], r[1] = a.h_sqrt_recipm1_ac[t], r[2] = a.h_coef1[t], r[3] = a.h_coef2[t];
+        r[4] = t == 0 ? 0.f : a.h_sigma[t];                                  // nonzero_mask (:165)
     }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
+    const int h_st[3] = {a.start, 0, 0};
+    MAA_HIP(hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
+    MAA_HIP(hipMemcpyAsync(st, h_st, sizeof(h_st), hipMemcpyHostToDevice, ctx.stream));
+    MAA_HIP(hipStreamSynchronize(ctx.stream));      // (the host copies above may go out of scope on an error below)
+    const int clip = a.clip_denoised ? 1 : 0;
+    auto update = [&]() {
+        launch_ds_ddpm_step(ctx, d_x, e, a.d_noise, n, tab, a.timesteps, st, a.start, a.n, clip);
+        launch_ds_plms_advance(ctx, st, 1, t_slot, B);
+    };
+    // ---- first step: eager, sizes the workspace
+    launch_ds_fill(ctx, t_slot, B, (float)a.start);
+    run_sized(ctx, [&] { m.forward(ctx, d_x, t_slot, B, T, e); });
+    update();
+    // ---- remaining steps: one captured step, replayed
+    run_steps(ctx, a.n - 1, a.use_graph != 0, [&]() {
+        m.forward(ctx, d_x, t_slot, B, T, e);
+        update();
+    });
+}
+
+void ds_ddpm_update(Ctx& ctx, const float* d_eps, const float* d_t, const float* d_noise, const float* h_sqrt_recip_ac,
+                    const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_sigma, int timesteps,
+                    int B, int M, int T, bool clip, float* d_x) {
+    MAA_CHECK(B > 0 && M > 0 && T > 0 && timesteps > 0, "ds_ddpm_update: empty shape or table");
+    MAA_CHECK(M % 4 == 0, "ds_ddpm_update: M must be a multiple of 4 (16-byte accesses)");
+    MAA_CHECK(aligned16(d_x) && aligned16(d_eps) && aligned16(d_noise), "ds_ddpm_update: d_x, d_eps and d_noise must be 16-byte aligned");
+    char* slab = static_cast<char*>(ctx.ddpm_scratch.get(256 + 5 * (size_t)timesteps * sizeof(float), ctx.stream));
+    int* bad = reinterpret_cast<int*>(slab);
+    float* tab = reinterpret_cast<float*>(slab + 256);
+    std::vector<float> h_tab((size_t)5 * timesteps);
+    for (int t = 0; t < timesteps; ++t) {
+        float* r = &h_tab[(size_t)t * 5];
+        r[0] = h_sqrt_recip_ac[t], r[1] = h_sqrt_recipm1_ac[t], r[2] = h_coef1[t], r[3] = h_coef2[t];
+        r[4] = t == 0 ? 0.f : h_sigma[t];
+    }
+    MAA_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx.stream));
+    MAA_HIP(hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
+    launch_ds_ddpm_update(ctx, d_x, d_eps, d_noise, B, (long long)M * T, d_t, tab, timesteps, clip ? 1 : 0, bad);
+    int h_bad = 0;
+    MAA_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+    MAA_HIP(hipStreamSynchronize(ctx.stream));
+    MAA_CHECK(h_bad == 0, "ds_ddpm_update: some t[b] lies outside [0, timesteps)");
 }
 
 }  // namespace maa

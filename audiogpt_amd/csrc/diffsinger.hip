@@ -2,7 +2,8 @@
 //
 // Replaces (NeuralSeq/modules/diff/): net.py:31-44 SinusoidalPosEmb, diffusion.py:68-70 Mish, net.py:68-81 the gated
 // activation and the residual / skip bookkeeping of ResidualBlock, shallow_diffusion_tts.py:166-201 p_sample_plms
-// (get_x_pred and the 1st..4th-order pseudo linear multistep combinations of the noise history).
+// (get_x_pred and the 1st..4th-order pseudo linear multistep combinations of the noise history), :134-166 the ancestral step
+// (predict_start_from_noise, p_mean_variance's clamp, q_posterior's mean, p_sample).
 #include "maa_internal.h"
 
 namespace maa {
@@ -136,6 +137,56 @@ __global__ void ds_plms_advance_kernel(int* st, int interval, float* __restrict_
     if ((int)threadIdx.x < B) t_slot[threadIdx.x] = (float)max(tn, 0);
 }
 
+// One ancestral step of one element (shallow_diffusion_tts.py:134-166: predict_start_from_noise, the clamp of p_mean_variance,
+// q_posterior's mean, p_sample's `mean + nonzero_mask * (0.5 * logvar).exp() * noise`), in torch's term order.
+// r = one row of the table: {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2,
+// sigma}, sigma = 0 in row 0 (the nonzero_mask).  Shared by the loop's kernel and the single-step kernel: both round alike.
+__device__ __forceinline__ float ds_ddpm_one(float x, float e, float z, const float* __restrict__ r, int clip) {
+    float xr = r[0] * x - r[1] * e;
+    if (clip) xr = fminf(fmaxf(xr, -1.0f), 1.0f);
+    const float mean = r[2] * xr + r[3] * x;
+    return mean + r[4] * z;
+}
+
+__device__ __forceinline__ float4 ds_ddpm_four(float4 x, float4 e, float4 z, const float* __restrict__ r, int clip) {
+    return make_float4(ds_ddpm_one(x.x, e.x, z.x, r, clip), ds_ddpm_one(x.y, e.y, z.y, r, clip),
+                       ds_ddpm_one(x.z, e.z, z.z, r, clip), ds_ddpm_one(x.w, e.w, z.w, r, clip));
+}
+
+// The loop's step: t = st[0] (device state), the step's noise is draw k = start - t of the call's buffer [n_steps][n], so a
+// captured launch takes no host data.  n4 = n / 4 (n = B * M * T, M % 4 == 0).  A state outside the call's range writes nothing.
+__global__ void ds_ddpm_step_kernel(float4* x, const float4* __restrict__ e, const float4* __restrict__ noise, long long n4,
+                                    const float* __restrict__ tab, int timesteps, const int* __restrict__ st, int start,
+                                    int n_steps, int clip) {
+    const int t = st[0], k = start - t;
+    if (t < 0 || t >= timesteps || k < 0 || k >= n_steps) return;
+    float r[5];
+    for (int j = 0; j < 5; ++j) r[j] = tab[(long long)t * 5 + j];
+    const float4* z = noise + (long long)k * n4;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x)
+        x[i] = ds_ddpm_four(x[i], e[i], z[i], r, clip);
+}
+
+// p_sample's arithmetic for one step with a timestep per sample: t [B] (the integer step as float, as the denoiser takes it),
+// per4 = M * T / 4 vectors per sample.  A t[b] outside the table leaves its sample unchanged and raises *bad.
+__global__ void ds_ddpm_update_kernel(float4* x, const float4* __restrict__ e, const float4* __restrict__ noise, int B,
+                                      long long per4, const float* __restrict__ t, const float* __restrict__ tab,
+                                      int timesteps, int clip, int* __restrict__ bad) {
+    const long long n4 = (long long)B * per4;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / per4);
+        const float tf = t[b];
+        const int tb = (int)tf;
+        if (!(tf >= 0.0f) || tb >= timesteps) {
+            *bad = 1;
+            continue;
+        }
+        float r[5];
+        for (int j = 0; j < 5; ++j) r[j] = tab[(long long)tb * 5 + j];
+        x[i] = ds_ddpm_four(x[i], e[i], noise[i], r, clip);
+    }
+}
+
 __global__ void ds_fill_kernel(float* __restrict__ p, int n, float v) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -173,6 +224,17 @@ void launch_ds_plms_advance(const Ctx& ctx, int* st, int interval, float* t_slot
     MAA_CHECK(B <= 256, "plms: at most 256 samples per call");
     hipLaunchKernelGGL(ds_plms_advance_kernel, dim3(1), dim3(256), 0, ctx.stream, st, interval, t_slot, B);
     MAA_HIP(hipGetLastError());
+}
+// n must be a multiple of 4 and x / e / noise 16-byte aligned (checked by the callers, DiffNet::ddpm_sample and ds_ddpm_update)
+void launch_ds_ddpm_step(const Ctx& ctx, float* x, const float* e, const float* noise, long long n, const float* tab,
+                         int timesteps, const int* st, int start, int n_steps, int clip) {
+    DS_LAUNCH(ds_ddpm_step_kernel, n / 4, reinterpret_cast<float4*>(x), reinterpret_cast<const float4*>(e),
+              reinterpret_cast<const float4*>(noise), n / 4, tab, timesteps, st, start, n_steps, clip);
+}
+void launch_ds_ddpm_update(const Ctx& ctx, float* x, const float* e, const float* noise, int B, long long per, const float* t,
+                           const float* tab, int timesteps, int clip, int* bad) {
+    DS_LAUNCH(ds_ddpm_update_kernel, B * per / 4, reinterpret_cast<float4*>(x), reinterpret_cast<const float4*>(e),
+              reinterpret_cast<const float4*>(noise), B, per / 4, t, tab, timesteps, clip, bad);
 }
 void launch_ds_fill(const Ctx& ctx, float* p, int n, float v) {
     if (ctx.ws.dry) return;

@@ -82,6 +82,8 @@ public:
     ~DiffNet();
     void forward(Ctx& ctx, const float* spec, const float* t, const float* cond, int B, int T, float* out);
     void plms_sample(Ctx& ctx, const maa_plms_args& a, float* d_x);
+    // the ancestral chain (shallow_diffusion_tts.py:159-166, 269-271): steps a.start .. a.start - a.n + 1 on the device
+    void ddpm_sample(Ctx& ctx, const maa_ds_ddpm_args& a, float* d_x);
     const maa_diffnet_config& config() const;
 
 private:
@@ -155,6 +157,11 @@ void ddpm_sample(Ctx& ctx, UNet& unet, const maa_ddpm_args& a, float* d_x);
 void ddpm_update(Ctx& ctx, const float* d_x, const float* d_eps, const int32_t* d_t, const float* h_sqrt_recip_ac,
                  const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_logvar, int n_tab,
                  const float* d_noise, float temperature, bool clip, int B, int C, int H, int W, float* d_x_prev, float* d_x_recon);
+// DiffSinger's p_sample arithmetic for one step with a timestep per sample (shallow_diffusion_tts.py:134-166), d_x in place;
+// host tables of `timesteps` rows; checks every t[b] against them (csrc/diffnet.cpp)
+void ds_ddpm_update(Ctx& ctx, const float* d_eps, const float* d_t, const float* d_noise, const float* h_sqrt_recip_ac,
+                    const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_sigma, int timesteps,
+                    int B, int M, int T, bool clip, float* d_x);
 // DDIMSampler.stochastic_encode (ddim.py:227-241) with host tables of n_tab rows; checks every t[b] against n_tab
 // One model evaluation with split_input_params outside a loop (ddpm_audio.py:572-654): unfold, the UNet over B * L crop rows,
 // fold.  h_weight [kh * kw][L] on the host (get_weighting's table); d_context [B, context_len(), context_dim] or null

@@ -4,7 +4,9 @@ Inference subset of `GaussianDiffusion` (NeuralSeq/modules/diff/shallow_diffusio
 it (audio-chatgpt.py:298-339 -> NeuralSeq/inference/svs/ds_e2e.py): the FastSpeech2 front end (`self.fs2`) that turns
 phonemes into the conditioning `decoder_inp` and the coarse mel is outside the accelerated path and stays with the
 caller; what runs on the device is the part that costs the time -- `denoise_fn` (DiffNet, 20 gated dilated residual
-layers) inside the PLMS loop (`pndm_speedup`), K_step / pndm_speedup evaluations per utterance.
+layers) inside the sampling loop.  Both loops of forward(infer=True) are here: the PLMS loop (`pndm_speedup`, K_step /
+pndm_speedup evaluations per utterance, ds1000.yaml) and the ancestral chain every other shipped configuration takes
+(K_step p_sample steps: popcs_ds_beta6.yaml, lj_ds_beta6.yaml, ds100_adj_rel.yaml, ds60_rel.yaml, ds1000-10dil.yaml).
 
     gd = GaussianDiffusion(C.DIFFSINGER_DS1000, device="cuda:0", state_dict=ckpt_denoise_fn_sd, spec_min=..., spec_max=...)
     mel = gd.infer(fs2_mel [B, T, 80], cond [B, 256, T])          # == ret['mel_out'] of forward(..., infer=True)
@@ -16,34 +18,141 @@ from . import config as C
 from . import weights as WT
 from .backend import Context, DiffNet, default_precision
 
+# sample_ddpm's default cap on the steps' noise buffer: n * B * M * T * 4 bytes per device call
+NOISE_CAP_BYTES = 64 << 20
 
-def linear_beta_schedule(timesteps, max_beta):
-    """shallow_diffusion_tts.py:43-49."""
+
+def linear_beta_schedule(timesteps, max_beta=0.01):
+    """shallow_diffusion_tts.py:44-49."""
     return np.linspace(1e-4, max_beta, timesteps)
 
 
+def cosine_beta_schedule(timesteps, s=0.008):
+    """shallow_diffusion_tts.py:52-62 (https://openreview.net/forum?id=-NEXDKk8gZ)."""
+    steps = timesteps + 1
+    x = np.linspace(0, steps, steps)
+    alphas_cumprod = np.cos(((x / steps) + s) / (1 + s) * np.pi * 0.5) ** 2
+    alphas_cumprod = alphas_cumprod / alphas_cumprod[0]
+    betas = 1 - (alphas_cumprod[1:] / alphas_cumprod[:-1])
+    return np.clip(betas, a_min=0, a_max=0.999)
+
+
+def extract(a, t, x_shape):
+    """shallow_diffusion_tts.py:32-35."""
+    b = t.shape[0]
+    return a.gather(-1, t).reshape(b, *((1,) * (len(x_shape) - 1)))
+
+
+def noise_like(shape, device, repeat=False):
+    """shallow_diffusion_tts.py:38-41: one draw of `shape`, or one row drawn and repeated over the batch."""
+    if repeat:
+        return torch.randn((1, *shape[1:]), device=device).repeat(shape[0], *((1,) * (len(shape) - 1)))
+    return torch.randn(shape, device=device)
+
+
+# the buffers of __init__ (:103-123), in its order
+SCHEDULE_BUFFERS = ("betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod",
+                    "log_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod",
+                    "posterior_variance", "posterior_log_variance_clipped", "posterior_mean_coef1", "posterior_mean_coef2")
+
+
+def schedule_buffers(timesteps, schedule_type=None, max_beta=0.01, betas=None):
+    """The twelve schedule buffers of GaussianDiffusion.__init__ (:82-123) as fp32 numpy arrays: float64 numpy, rounded once.
+    betas given: used as they are; else schedule_type "linear" (1e-4 .. max_beta) or "cosine" (also when it is None: :85-88)."""
+    if betas is not None:
+        betas = betas.detach().cpu().numpy() if isinstance(betas, torch.Tensor) else np.asarray(betas)
+    elif schedule_type is None or schedule_type == "cosine":
+        betas = cosine_beta_schedule(timesteps)
+    elif schedule_type == "linear":
+        betas = linear_beta_schedule(timesteps, max_beta)
+    else:
+        raise KeyError("schedule_type %r: the reference has 'linear' and 'cosine'" % (schedule_type,))
+    alphas = 1. - betas
+    alphas_cumprod = np.cumprod(alphas, axis=0)
+    alphas_cumprod_prev = np.append(1., alphas_cumprod[:-1])
+    posterior_variance = betas * (1. - alphas_cumprod_prev) / (1. - alphas_cumprod)
+    b = dict(
+        betas=betas, alphas_cumprod=alphas_cumprod, alphas_cumprod_prev=alphas_cumprod_prev,
+        sqrt_alphas_cumprod=np.sqrt(alphas_cumprod), sqrt_one_minus_alphas_cumprod=np.sqrt(1. - alphas_cumprod),
+        log_one_minus_alphas_cumprod=np.log(1. - alphas_cumprod), sqrt_recip_alphas_cumprod=np.sqrt(1. / alphas_cumprod),
+        sqrt_recipm1_alphas_cumprod=np.sqrt(1. / alphas_cumprod - 1), posterior_variance=posterior_variance,
+        posterior_log_variance_clipped=np.log(np.maximum(posterior_variance, 1e-20)),
+        posterior_mean_coef1=betas * np.sqrt(alphas_cumprod_prev) / (1. - alphas_cumprod),
+        posterior_mean_coef2=(1. - alphas_cumprod_prev) * np.sqrt(alphas) / (1. - alphas_cumprod))
+    return {k: torch.tensor(b[k], dtype=torch.float32).numpy() for k in SCHEDULE_BUFFERS}
+
+
 class GaussianDiffusion(object):
+    """cfg keys beside the denoiser's: timesteps, K_step, schedule_type ("linear" with max_beta, or "cosine": the reference's
+    default when the key is absent), pndm_speedup (truthy: the PLMS loop; falsy or absent: the ancestral chain), gaussian_start.
+    betas: an explicit schedule, as the reference's constructor takes it.  ctx / denoise_fn: an existing Context / DiffNet to use."""
+
     def __init__(self, cfg=None, device="cuda:0", state_dict=None, spec_min=None, spec_max=None, ctx=None, precision=None,
-                 seed=7):
+                 seed=7, betas=None, denoise_fn=None):
         self.cfg = dict(cfg or C.DIFFSINGER_DS1000)
         self.ctx = ctx or Context(device, precision=precision or default_precision())
         self.device = self.ctx.device
         self.mel_bins = self.cfg["in_dims"]
-        self.num_timesteps = int(self.cfg["timesteps"])
         self.K_step = int(self.cfg["K_step"])
-        betas = linear_beta_schedule(self.num_timesteps, self.cfg["max_beta"])
-        ac = np.cumprod(1.0 - betas, axis=0)
-        to32 = lambda a: torch.tensor(a, dtype=torch.float32, device=self.device)   # noqa: E731  (:82-96: fp32 buffers)
-        self.betas, self.alphas_cumprod = to32(betas), to32(ac)
-        self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod = to32(np.sqrt(ac)), to32(np.sqrt(1.0 - ac))
+        host = schedule_buffers(int(self.cfg["timesteps"]), self.cfg.get("schedule_type"), self.cfg.get("max_beta", 0.01), betas)
+        self.num_timesteps = int(host["betas"].shape[0])
+        for k in SCHEDULE_BUFFERS:                                                         # (:101-123: fp32 buffers)
+            setattr(self, k, torch.from_numpy(host[k]).to(self.device))
+        # sigma of p_sample (:166), by torch in fp32 from the fp32 buffer; with the four coefficients, the step's host tables
+        sigma = (0.5 * torch.from_numpy(host["posterior_log_variance_clipped"])).exp().numpy()
+        self._ddpm_tables = (host["sqrt_recip_alphas_cumprod"], host["sqrt_recipm1_alphas_cumprod"], host["posterior_mean_coef1"],
+                             host["posterior_mean_coef2"], sigma)
+        self._alphas_cumprod_host = host["alphas_cumprod"]
         m = self.mel_bins
         self.spec_min = torch.as_tensor(spec_min if spec_min is not None else [-6.0] * m, dtype=torch.float32, device=self.device)[None, None, :m]
         self.spec_max = torch.as_tensor(spec_max if spec_max is not None else [1.5] * m, dtype=torch.float32, device=self.device)[None, None, :m]
-        sd = state_dict if state_dict is not None else WT.make_diffnet_state_dict(self.cfg, seed=seed)
-        sd = WT.strip_prefix(sd, "denoise_fn.") or sd
-        self.denoise_fn = DiffNet(self.ctx, self.cfg, sd)
+        if denoise_fn is None:
+            sd = state_dict if state_dict is not None else WT.make_diffnet_state_dict(self.cfg, seed=seed)
+            sd = WT.strip_prefix(sd, "denoise_fn.") or sd
+            denoise_fn = DiffNet(self.ctx, self.cfg, sd)
+        self.denoise_fn = denoise_fn
 
-    # ---- shallow_diffusion_tts.py:203-208, 279-283
+    def _t(self, t):
+        return torch.as_tensor(t, device=self.device).long().reshape(-1)
+
+    # ---- shallow_diffusion_tts.py:128-147
+    def q_mean_variance(self, x_start, t):
+        t = self._t(t)
+        mean = extract(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
+        variance = extract(1. - self.alphas_cumprod, t, x_start.shape)
+        log_variance = extract(self.log_one_minus_alphas_cumprod, t, x_start.shape)
+        return mean, variance, log_variance
+
+    def predict_start_from_noise(self, x_t, t, noise):
+        t = self._t(t)
+        return (extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t -
+                extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape) * noise)
+
+    def q_posterior(self, x_start, x_t, t):
+        t = self._t(t)
+        posterior_mean = (extract(self.posterior_mean_coef1, t, x_t.shape) * x_start +
+                          extract(self.posterior_mean_coef2, t, x_t.shape) * x_t)
+        posterior_variance = extract(self.posterior_variance, t, x_t.shape)
+        posterior_log_variance_clipped = extract(self.posterior_log_variance_clipped, t, x_t.shape)
+        return posterior_mean, posterior_variance, posterior_log_variance_clipped
+
+    # ---- :149-166: the denoiser, then the fused step kernel (maa_ds_ddpm_update)
+    @torch.no_grad()
+    def p_mean_variance(self, x, t, cond, clip_denoised: bool):
+        t = self._t(t)
+        noise_pred = self.denoise_fn(x, t, cond)
+        model_mean = self.denoise_fn.ddpm_update(x, noise_pred, t, self._ddpm_tables, torch.zeros_like(noise_pred), clip_denoised)
+        return (model_mean, extract(self.posterior_variance, t, model_mean.shape),
+                extract(self.posterior_log_variance_clipped, t, model_mean.shape))
+
+    @torch.no_grad()
+    def p_sample(self, x, t, cond, clip_denoised=True, repeat_noise=False):
+        t = self._t(t)
+        noise_pred = self.denoise_fn(x, t, cond)
+        noise = noise_like(tuple(noise_pred.shape), self.device, repeat_noise)
+        return self.denoise_fn.ddpm_update(x, noise_pred, t, self._ddpm_tables, noise, clip_denoised)
+
+    # ---- :203-208, 279-283
     def q_sample(self, x_start, t, noise=None):
         if noise is None:
             noise = torch.randn_like(x_start)
@@ -61,21 +170,83 @@ class GaussianDiffusion(object):
         """x [B, 1, M, T] at step K_step - 1 -> x_0."""
         K = self.K_step if K_step is None else int(K_step)
         iv = int(self.cfg["pndm_speedup"]) if interval is None else int(interval)
-        return self.denoise_fn.plms_sample(x, cond, self.alphas_cumprod.cpu().numpy(), K, iv, use_graph=use_graph)
+        return self.denoise_fn.plms_sample(x, cond, self._alphas_cumprod_host, K, iv, use_graph=use_graph)
 
+    # ---- :269-271 with :159-166, on the device
     @torch.no_grad()
-    def infer(self, fs2_mels, cond, noise=None, gaussian_start=False, mel2ph=None):
-        """The infer branch of forward (:244-276) after the FastSpeech2 front end: fs2_mels [B, T, M] (ret['mel_out'] of
-        fs2), cond [B, H, T] (ret['decoder_inp'].transpose(1, 2)) -> mel_out [B, T, M]; with mel2ph [B, T] (singing) the
-        frames that belong to no phoneme are zeroed (:273-274)."""
+    def sample_ddpm(self, x, cond, K_step=None, noise_p=None, clip_denoised=True, use_graph=True, noise_cap_bytes=NOISE_CAP_BYTES):
+        """The ancestral chain `for i in reversed(range(0, K_step)): x = p_sample(x, i, cond)`: x [B, 1, M, T] at step
+        K_step - 1 -> x_0.  noise_p [K_step, B, 1, M, T]: the steps' draws in loop order; None draws them as the reference's loop
+        does, one torch.randn of x's shape per step on the device from the global generator, the t = 0 draw included.
+
+        The chain runs as consecutive device calls of n steps each (maa_ds_ddpm_sample(start, n)), n the largest count whose
+        noise buffer n * B * M * T * 4 bytes stays within noise_cap_bytes (at least 1: a single step's draw is never split).
+        The device loop equals its consecutive parts bit for bit and the draws are made one step at a time either way, so
+        the cap changes neither the draws nor the result."""
+        K = self.K_step if K_step is None else int(K_step)
+        x = x.to(device=self.device, dtype=torch.float32)
+        shape = tuple(x.shape)
+        if noise_p is not None and tuple(noise_p.shape) != (K,) + shape:
+            raise ValueError("sample_ddpm: noise_p %s is not [K_step = %d] + x %s" % (tuple(noise_p.shape), K, shape))
+        chunk = max(1, int(noise_cap_bytes) // (4 * max(x.numel(), 1)))
+        done = 0
+        while done < K:
+            n = min(chunk, K - done)
+            if noise_p is not None:
+                z = noise_p[done:done + n]
+            else:
+                z = torch.empty((n,) + shape, dtype=torch.float32, device=self.device)
+                for k in range(n):
+                    z[k] = torch.randn(shape, device=self.device)
+            x = self.denoise_fn.ddpm_sample(x, cond, self._ddpm_tables, K - 1 - done, n, z, clip_denoised=clip_denoised,
+                                            use_graph=use_graph)
+            done += n
+        return x
+
+    def _ancestral(self):
+        return not self.cfg.get("pndm_speedup")
+
+    def _infer_x0(self, fs2_mels, cond, noise, gaussian_start, noise_start, noise_p, clip_denoised):
         fs2_mels = fs2_mels.to(device=self.device, dtype=torch.float32)
         x0 = self.norm_spec(fs2_mels).transpose(1, 2)[:, None, :, :]
         t = torch.tensor([self.K_step - 1], device=self.device).long()
         x = self.q_sample(x0, t, noise)
+        if gaussian_start is None:
+            gaussian_start = bool(self.cfg.get("gaussian_start"))
         if gaussian_start:
-            x = torch.randn((cond.shape[0], 1, self.mel_bins, cond.shape[2]), device=self.device)
-        x = self.sample_plms(x, cond)
-        out = self.denorm_spec(x[:, 0].transpose(1, 2))
+            shape = (cond.shape[0], 1, self.mel_bins, cond.shape[2])
+            x = torch.randn(shape, device=self.device) if noise_start is None else noise_start.to(self.device).reshape(shape)
+        if self._ancestral():
+            x = self.sample_ddpm(x, cond, noise_p=noise_p, clip_denoised=clip_denoised)
+        else:
+            x = self.sample_plms(x, cond)
+        return x[:, 0].transpose(1, 2)
+
+    @torch.no_grad()
+    def infer(self, fs2_mels, cond, noise=None, gaussian_start=None, mel2ph=None, noise_start=None, noise_p=None,
+              clip_denoised=True):
+        """The infer branch of forward (:244-276) after the FastSpeech2 front end: fs2_mels [B, T, M] (ret['mel_out'] of
+        fs2), cond [B, H, T] (ret['decoder_inp'].transpose(1, 2)) -> mel_out [B, T, M]; with mel2ph [B, T] (singing) the
+        frames that belong to no phoneme are zeroed (:273-274).  The loop is the PLMS one with a truthy cfg['pndm_speedup'], the
+        ancestral chain (sample_ddpm) otherwise.  gaussian_start: None takes cfg['gaussian_start'].
+
+        Draws, in the reference's order, each made on the device from torch's global generator unless given: `noise` of
+        q_sample (made even when gaussian_start discards its result), `noise_start` [B, 1, M, T] with gaussian_start, then --
+        ancestral chain only -- `noise_p` [K_step, B, 1, M, T], one draw per step in loop order."""
+        out = self.denorm_spec(self._infer_x0(fs2_mels, cond, noise, gaussian_start, noise_start, noise_p, clip_denoised))
         if mel2ph is not None:
             out = out * (torch.as_tensor(mel2ph).to(out.device) > 0).float()[:, :, None]
         return out
+
+
+class OfflineGaussianDiffusion(GaussianDiffusion):
+    """shallow_diffusion_tts.py:292-324: the coarse mel comes with the batch (ref_mels[1]) and the loop is always the ancestral
+    chain, whatever cfg['pndm_speedup'] says; mel2ph masks nothing here (:322-323)."""
+
+    def _ancestral(self):
+        return True
+
+    @torch.no_grad()
+    def infer(self, fs2_mels, cond, noise=None, gaussian_start=None, mel2ph=None, noise_start=None, noise_p=None,
+              clip_denoised=True):
+        return self.denorm_spec(self._infer_x0(fs2_mels, cond, noise, gaussian_start, noise_start, noise_p, clip_denoised))

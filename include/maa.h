@@ -355,6 +355,36 @@ typedef struct maa_plms_args {
     int use_graph;
 } maa_plms_args;
 int maa_plms_sample(maa_ctx* ctx, maa_diffnet* d, const maa_plms_args* args, float* d_x);
+/* replaces: the other branch of GaussianDiffusion.forward(infer=True) (shallow_diffusion_tts.py:269-271, hparams['pndm_speedup']
+ * unset) and OfflineGaussianDiffusion.forward (:320-321) with p_sample / p_mean_variance / predict_start_from_noise / q_posterior
+ * (:134-166): the ancestral steps t = start, start - 1, ..., start - n + 1 of the timesteps-step schedule on d_x
+ * [B, 1, in_dims, T] in place (the whole chain: start = K_step - 1, n = K_step), one DiffNet evaluation and one fused kernel each:
+ *   x_recon = h_sqrt_recip_ac[t] x - h_sqrt_recipm1_ac[t] eps, clamped to [-1, 1] when clip_denoised
+ *   x'      = h_coef1[t] x_recon + h_coef2[t] x + h_sigma[t] noise[start - t]
+ * The tables are the reference's fp32 buffers (:111-123), one row per timestep, on the host; h_sigma[t] =
+ * exp(0.5 posterior_log_variance_clipped[t]) as p_sample computes it, and row 0 of it is not read: t = 0 adds no noise
+ * (nonzero_mask).  d_noise [n][B, 1, in_dims, T]: the call's draws in loop order, first step first (the t = 0 draw is there and
+ * is multiplied by zero, as in the reference).  A call equals its consecutive parts bit for bit (start, n1 then start - n1, n - n1).
+ * The first step runs eagerly and sizes the workspace, then one step is captured and replayed (use_graph = 0: all eager).
+ * in_dims must be a multiple of 4, d_x and d_noise 16-byte aligned, B <= 256. */
+typedef struct maa_ds_ddpm_args {
+    int B, T, start, n, timesteps;
+    int clip_denoised, use_graph;
+    const float* d_cond;              /* [B, hidden_size, T] */
+    const float* d_noise;             /* [n][B, 1, in_dims, T] */
+    const float* h_sqrt_recip_ac;     /* host, [timesteps] each */
+    const float* h_sqrt_recipm1_ac;
+    const float* h_coef1;
+    const float* h_coef2;
+    const float* h_sigma;
+} maa_ds_ddpm_args;
+int maa_ds_ddpm_sample(maa_ctx* ctx, maa_diffnet* d, const maa_ds_ddpm_args* args, float* d_x);
+/* The same arithmetic for ONE step with a timestep per sample, after a maa_diffnet_forward (p_sample, :159-166): d_t [B] as the
+ * denoiser takes it (the integer step as float) indexes the five host tables of `timesteps` rows; a d_t[b] outside them fails the
+ * call.  d_x [B, 1, M, T] in place, d_eps the denoiser's output, d_noise [B, 1, M, T].  Synchronises the context's stream. */
+int maa_ds_ddpm_update(maa_ctx* ctx, const float* d_eps, const float* d_t, const float* d_noise, const float* h_sqrt_recip_ac,
+                       const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_sigma,
+                       int timesteps, int B, int M, int T, int clip_denoised, float* d_x);
 
 /* ---- conditioning encoders (the step before the sampler: text / image -> cross-attention context) ----------
  * kind 0: the CLAP text branch as FrozenCLAPEmbedder.encode runs it (ldm/modules/encoders/modules.py:204-211):
