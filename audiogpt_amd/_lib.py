@@ -197,8 +197,8 @@ def load():
         "maa_resampler_create": [vp, ci, ci, ci, ci, fp, C.POINTER(vp)],
         "maa_resampler_destroy": [vp],
         "maa_resampler_forward": [vp, vp, vp, ci, ci, vp],
-        "maa_op_linear": [vp, vp, ci, ci, fp, fp, ci, ci, vp],
-        "maa_op_conv": [vp, vp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci],
+        "maa_op_linear": [vp, vp, ci, ci, fp, fp, ci, ci, vp, vp, ci],
+        "maa_op_conv": [vp, vp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, vp, vp, ci],
         "maa_op_groupnorm": [vp, vp, ci, ci, ci, fp, fp, cf, ci, vp],
         "maa_op_layernorm": [vp, vp, ci, ci, fp, fp, cf, vp],
         "maa_op_attention": [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp],

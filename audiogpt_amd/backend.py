@@ -127,18 +127,26 @@ class Context:
             pass
 
     # ---- single operators (parity tests / kernel profiling) -------------------------------------
-    def op_linear(self, a, w, b=None, geglu=False):
+    def op_linear(self, a, w, b=None, geglu=False, res=None, split_out=False):
+        """a [M,K]; w [N,K]; res [M,N] is added to the result.  split_out: the [M,N] floats returned hold split32 rows (per 32 columns
+        32 bf16 hi, then 32 bf16 lo)."""
         a = _f32(a, self.device)
         M, K = a.shape
         N = w.shape[0]
         wt, wp = L.host_f32(w)
         bt, bp = L.host_f32(b) if b is not None else (None, None)
         y = torch.empty(M, N // 2 if geglu else N, device=self.device)
-        L.check(self.lib.maa_op_linear(self.h, L.dptr(a), M, K, wp, bp, N, int(geglu), L.dptr(y)))
+        r = _f32(res, self.device) if res is not None else None
+        assert r is None or tuple(r.shape) == tuple(y.shape)
+        L.check(self.lib.maa_op_linear(self.h, L.dptr(a), M, K, wp, bp, N, int(geglu), L.dptr(y),
+                                       L.dptr(r) if r is not None else None, int(split_out)))
         return y
 
-    def op_conv(self, x, w, b=None, stride=1, pad=0, dil=1, up=False, leaky=0.0, out_hw=None):
-        """x [B,Cin,H,W]; w [Cout,Cin,KH,KW]; returns [B,Cout,Ho,Wo]."""
+    def op_conv(self, x, w, b=None, stride=1, pad=0, dil=1, up=False, leaky=0.0, out_hw=None, rowadd=None, res=None,
+                split_out=False):
+        """x [B,Cin,H,W]; w [Cout,Cin,KH,KW]; returns [B,Cout,Ho,Wo].  rowadd [B,Cout] and res [B,Cout,Ho,Wo] are added to the
+        result.  split_out: returns the channels-last result [B,Ho,Wo,Cout] as split32 rows instead (see op_linear), as the
+        convolutions that feed a contraction write it."""
         x = _f32(x, self.device)
         B, Cin, H, W = x.shape
         Cout, _, KH, KW = w.shape
@@ -151,9 +159,14 @@ class Context:
             Ho, Wo = out_hw
         wt, wp = L.host_f32(w)
         bt, bp = L.host_f32(b) if b is not None else (None, None)
-        y = torch.empty(B, Cout, Ho, Wo, device=self.device)
+        y = torch.empty((B, Ho, Wo, Cout) if split_out else (B, Cout, Ho, Wo), device=self.device)
+        ra = _f32(rowadd, self.device) if rowadd is not None else None
+        r = _f32(res, self.device) if res is not None else None
+        assert ra is None or tuple(ra.shape) == (B, Cout)
+        assert r is None or tuple(r.shape) == (B, Cout, Ho, Wo)
         L.check(self.lib.maa_op_conv(self.h, L.dptr(x), B, Cin, H, W, wp, bp, Cout, KH, KW, stride, pad, dil,
-                                     int(up), float(leaky), L.dptr(y), Ho, Wo))
+                                     int(up), float(leaky), L.dptr(y), Ho, Wo, L.dptr(ra) if ra is not None else None,
+                                     L.dptr(r) if r is not None else None, int(split_out)))
         return y
 
     def op_groupnorm(self, x, gamma, beta, eps, silu=False):

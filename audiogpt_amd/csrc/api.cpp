@@ -650,10 +650,12 @@ static bool op_presplit(const maa::Ctx& c, int channels, bool other_prologue) {
 }
 
 int maa_op_linear(maa_ctx* ctx, const float* d_a, int M, int K, const float* h_w, const float* h_bias, int N,
-                  int geglu, float* d_y) {
+                  int geglu, float* d_y, const float* d_res, int c_split) {
     return guarded([&] {
         bind(ctx);
         MAA_CHECK(d_a && h_w && d_y && M > 0 && K > 0 && N > 0, "bad op_linear arguments");
+        MAA_CHECK(!c_split || N % 32 == 0, "op_linear: split32 output needs a multiple of 32 columns");
+        MAA_CHECK(!geglu || (!d_res && !c_split), "op_linear: GEGLU takes neither a residual nor split32 output here");
         OneShot s;
         s.add("w", h_w, {N, K});
         if (h_bias) s.add("b", h_bias, {N});
@@ -669,7 +671,7 @@ int maa_op_linear(maa_ctx* ctx, const float* d_a, int M, int K, const float* h_w
                 maa::launch_split32_pack(c, d_a, M, K, sp);
                 a = sp;
             }
-            maa::linear_into(c, a, K, M, K, pw, nullptr, 0, d_y, geglu ? N / 2 : N, geglu, 0, pre ? M : 0);
+            maa::linear_into(c, a, K, M, K, pw, d_res, N, d_y, geglu ? N / 2 : N, geglu, 0, pre ? M : 0, c_split);
         });
         MAA_HIP(hipStreamSynchronize(c.stream));
     });
@@ -677,10 +679,13 @@ int maa_op_linear(maa_ctx* ctx, const float* d_a, int M, int K, const float* h_w
 
 int maa_op_conv(maa_ctx* ctx, const float* d_x, int B, int Cin, int H, int W, const float* h_w, const float* h_bias,
                 int Cout, int KH, int KW, int stride, int pad, int dil, int upsample2, float leaky_slope, float* d_y,
-                int Ho, int Wo) {
+                int Ho, int Wo, const float* d_rowadd, const float* d_res, int c_split) {
     return guarded([&] {
         bind(ctx);
         MAA_CHECK(d_x && h_w && d_y, "bad op_conv arguments");
+        const bool extras = d_rowadd || d_res || c_split;
+        MAA_CHECK(!extras || !upsample2, "op_conv: row add, residual and split32 output are not combined with the upsample");
+        MAA_CHECK(!c_split || Cout % 32 == 0, "op_conv: split32 output needs a multiple of 32 channels");
         OneShot s;
         s.add("w", h_w, {Cout, Cin, KH, KW});
         if (h_bias) s.add("b", h_bias, {Cout});
@@ -699,7 +704,7 @@ int maa_op_conv(maa_ctx* ctx, const float* d_x, int B, int Cin, int H, int W, co
                 xs.split = true;
                 x = xs;
             }
-            if (x.split && Cout <= 4 && h_bias && KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1 && !upsample2 && c.tune.up2) {
+            if (x.split && Cout <= 4 && h_bias && KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1 && !upsample2 && !extras && c.tune.up2) {
                 maa::PackedW pn = ws.pack_narrow3x3(s.sd, "w", "b");      // the UNet's output convolution (unet.cpp forward_body)
                 if (maa::launch_narrow_conv3x3(c, x.p, Cin, B, H, W, Cin, pn.w, pn.bias, Cout, d_y)) return;
             }
@@ -714,6 +719,19 @@ int maa_op_conv(maa_ctx* ctx, const float* d_x, int B, int Cin, int H, int W, co
             if (leaky_slope != 0.f) {
                 o.a_act = 1;
                 o.a_slope = leaky_slope;
+            }
+            o.rowadd = d_rowadd;      // [B, Cout]: the time-embedding row of a ResBlock's first convolution
+            o.ld_rowadd = Cout;
+            if (d_res) {
+                maa::T4 r = maa::alloc_t(c, B, Ho, Wo, Cout);
+                maa::launch_nchw_to_nhwc(c, d_res, B, Cout, Ho * Wo, r.p);
+                o.res = r.p;
+            }
+            if (c_split) {             // the result stays channels-last: d_y = [B Ho Wo][Cout] split32 rows
+                o.c_split = 1;
+                y.p = d_y;
+                maa::conv_into(c, x, nullptr, pw, o, y);
+                return;
             }
             if (!(pw4.w && maa::conv_up2_into(c, x, pw4, y))) maa::conv_into(c, x, nullptr, pw, o, y);
             maa::launch_nhwc_to_nchw(c, y.p, B, Cout, Ho * Wo, d_y, Cout);

@@ -325,22 +325,25 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_dma2_kernel(const IGemm 
 }
 
 // Adds the S slabs of every 32x32 block in slice order (fixed: ((s0 + s1) + s2) + ...) and applies the epilogue.  A
-// workgroup has the thread geometry of the GEMM workgroup and finishes block (i, j) -- with GEGLU the value / gate pair
-// (j, j+1) -- of one tile, so every thread reads back exactly the registers its GEMM twin wrote.
-template <int JW>
-__global__ void splitk_reduce_kernel(const IGemm p, const float* __restrict__ part, int S, int tiles, int ntiles, int Nb,
-                                     int BM, int BN, int WGN, int MI, int NI) {
-    const int NTH = blockDim.x;
+// workgroup has the thread geometry of the GEMM workgroup (NTH threads, waves WGN abreast, MI x NI blocks per wave) and
+// finishes block (i, j) -- with GEGLU the value / gate pair (j, j+1) -- of one tile, so every thread reads back exactly the
+// registers its GEMM twin wrote.
+// (Tried and dropped, profiles/splitk_finish_ab.txt: the sum unrolled for S = 2 / 4 with every slab load and the epilogue's reads
+//  in flight as one group -- 12.5 -> 11.9 us alone, but 200 VGPRs, one workgroup per CU, and -0.2 % with three batches in flight.)
+template <int JW, int MI, int NI, int WGN, int NTH>
+__global__ __launch_bounds__(NTH) void splitk_reduce_kernel(const IGemm p, const float* __restrict__ part, int S, int tiles,
+                                                           int ntiles, int Nb) {
+    constexpr int njb = NI / JW, nblk = MI * njb;
+    constexpr int WTM = 32 * MI, WTN = 32 * NI;
+    constexpr int BM = WTM * (NTH / 64 / WGN), BN = WTN * WGN;
+    constexpr long long slab = (long long)(MI * NI * 4) * NTH * 4;       // floats per (slice, tile)
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int njb = NI / JW, nblk = MI * njb;
     const int wi = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);      // the blocks of a tile, and neighbouring tiles' rows, on one XCD
     const int tile = wi / nblk, blk = wi - tile * nblk;
     const int i = blk / njb, j = (blk - i * njb) * JW;
     const int mt = tile / ntiles, nt = tile - mt * ntiles;
     const int wm = wid / WGN, wn = wid - wm * WGN;
-    const int WTM = 32 * MI, WTN = 32 * NI;
     f32x16 acc[1][JW];
-    const long long slab = (long long)(MI * NI * 4) * NTH * 4;          // floats per (slice, tile)
 #pragma unroll
     for (int jj = 0; jj < JW; ++jj) {
         const float* src = part + (long long)tile * slab + ((long long)((i * NI + j + jj) * 4) * NTH + tid) * 4;
@@ -359,6 +362,22 @@ __global__ void splitk_reduce_kernel(const IGemm p, const float* __restrict__ pa
     }
     const int rpb = p.Hout * p.Wout;
     igemm_epilogue<1, JW>(p, acc, mt * BM + wm * WTM + i * 32, nt * BN + wn * WTN + j * 32, lane & 31, lane >> 5, 0, Nb, rpb);
+}
+
+// the reduce for one GEMM workgroup geometry
+template <int MI, int NI, int WGN, int NTH>
+void launch_reduce_geom(const Ctx& ctx, const IGemm& p, const float* part, int S, int tiles, int ntiles, int Nb) {
+    auto go = [&](auto kern, int blocks) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NTH), 0, ctx.stream, p, part, S, tiles, ntiles, Nb);
+    };
+    if (p.geglu) {
+        if constexpr (NI % 2 == 0)
+            go(splitk_reduce_kernel<2, MI, NI, WGN, NTH>, tiles * MI * (NI / 2));
+        else
+            MAA_CHECK(false, "split-K reduce: GEGLU needs value / gate block pairs inside a wave");
+        return;
+    }
+    go(splitk_reduce_kernel<1, MI, NI, WGN, NTH>, tiles * MI * NI);
 }
 
 template <int BM, int BN, int WGM, int WGN, int NS>
@@ -399,14 +418,16 @@ void launch_one(const Ctx& ctx, const IGemm& p, int Nb, int S, float* part) {
 
 void launch_splitk_reduce(const Ctx& ctx, const IGemm& p, const float* part, int S, int tiles, int ntiles, int Nb, int BM,
                           int BN, int WGN, int MI, int NI, int NTH) {
-    if (p.geglu && NI % 2 == 0) {
-        hipLaunchKernelGGL(splitk_reduce_kernel<2>, dim3((unsigned)(tiles * MI * (NI / 2))), dim3(NTH), 0, ctx.stream, p, part, S,
-                           tiles, ntiles, Nb, BM, BN, WGN, MI, NI);
-        return;
-    }
-    MAA_CHECK(!p.geglu, "split-K reduce: GEGLU needs value / gate block pairs inside a wave");
-    hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3((unsigned)(tiles * MI * NI)), dim3(NTH), 0, ctx.stream, p, part, S, tiles,
-                       ntiles, Nb, BM, BN, WGN, MI, NI);
+    MAA_CHECK(BM == 32 * MI * (NTH / 64 / WGN) && BN == 32 * NI * WGN, "split-K reduce: tile and wave geometry disagree");
+    // the workgroup geometries of the engines that write slabs: the reduce is compiled for each (a missing one is an error)
+    if (MI == 1 && NI == 5 && WGN == 1 && NTH == 512)             // igemm_pp / igemm_pp1, 256 x 160
+        launch_reduce_geom<1, 5, 1, 512>(ctx, p, part, S, tiles, ntiles, Nb);
+    else if (MI == 2 && NI == 2 && WGN == 2 && NTH == 512)        // igemm_pp / igemm_pp1, 256 x 128
+        launch_reduce_geom<2, 2, 2, 512>(ctx, p, part, S, tiles, ntiles, Nb);
+    else if (MI == 2 && NI == 2 && WGN == 2 && NTH == 256)        // igemm_dma2, 128 x 128
+        launch_reduce_geom<2, 2, 2, 256>(ctx, p, part, S, tiles, ntiles, Nb);
+    else
+        MAA_CHECK(false, "split-K reduce: no instantiation for this workgroup geometry");
 }
 
 // Which problems take this engine and with how many K slices: a function of the layer (K, packed N) only.

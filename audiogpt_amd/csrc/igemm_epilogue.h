@@ -57,7 +57,8 @@ __device__ __forceinline__ void store_split_pair(float* row, int n, float v) {
 
 // acc[MI][NI]: MI x NI fragments of 32x32 owned by this wave; (m_base, n_base) = first row / column of the wave.
 // PAIR: plain fp32 output whose columns pair up (even width, even pitch, 8-byte aligned base): see the store loop
-template <int MI, int NI, bool PAIR>
+// RSEL: a sample has >= 32 rows (or there is no row add), so the row add of a block's row is one of two samples'
+template <int MI, int NI, bool PAIR, bool RSEL>
 __device__ __forceinline__ void igemm_epilogue_impl(const IGemm& p, f32x16 (&acc)[MI][NI], int m_base, int n_base,
                                                     int lrow, int lk, long long coff, int Nb, int rpb) {
     float* cp = p.c + coff;
@@ -110,7 +111,7 @@ __device__ __forceinline__ void igemm_epilogue_impl(const IGemm& p, f32x16 (&acc
         // sample index of the block's rows for the per-sample row add: 32 consecutive rows span at most two samples when a
         // sample has >= 32 rows (one division per block instead of one per row)
         const int mb = m_base + i * 32;
-        const int b0 = mb / rpb;
+        const int b0 = (mb < p.M ? mb : p.M - 1) / rpb;      // (a block wholly past M reads the last sample's row, never one past it)
         const int nextb = (b0 + 1) * rpb;
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
@@ -127,11 +128,17 @@ __device__ __forceinline__ void igemm_epilogue_impl(const IGemm& p, f32x16 (&acc
                     mc[r] = m < p.M ? m : p.M - 1;
                     ra[r] = rs[r] = cv[r] = 0.f;
                 }
+                // (RSEL is a property of the instantiation: chosen per row at run time, even though rpb is wave-uniform, it compiled
+                // to a branch around every load -- 500 basic blocks -- and as two alternative loops to a wait for every load in
+                // flight where they join)
                 if (p.rowadd) {
+                    if constexpr (RSEL) {
+                        const float* ra0 = p.rowadd + (long long)b0 * p.ld_rowadd + n;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int bb = rpb >= 32 ? (mc[r] < nextb ? b0 : b0 + 1) : (int)(mc[r] / rpb);
-                        ra[r] = p.rowadd[(long long)bb * p.ld_rowadd + n];
+                        for (int r = 0; r < 16; ++r) ra[r] = ra0[mc[r] < nextb ? 0 : p.ld_rowadd];
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) ra[r] = p.rowadd[(long long)((int)mc[r] / rpb) * p.ld_rowadd + n];
                     }
                 }
                 if (resp) {
@@ -150,17 +157,29 @@ __device__ __forceinline__ void igemm_epilogue_impl(const IGemm& p, f32x16 (&acc
                     settle(rs[r]);
                     settle(cv[r]);
                 }
+                // (blocks without an activation, the UNet's, skip the per-element chain of scalar branches that chooses it)
                 float outv[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     float v = acc[i][j][r] * p.alpha + bias;
                     if (p.rowadd) v += ra[r];
                     if (resp) v += rs[r];
-                    if (p.act == 1) v = tanhf(v);
-                    else if (p.act == 2) v = fmaxf(v, 0.f);
-                    else if (p.act == 3) v = 0.5f * v * (1.f + fast_erff(v * 0.70710678118654752440f));
-                    else if (p.act == 4) v = v > 0.f ? v : v * p.act_slope;
-                    v *= p.out_scale;
+                    outv[r] = v;
+                }
+                if (p.act != 0) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float v = outv[r];
+                        if (p.act == 1) v = tanhf(v);
+                        else if (p.act == 2) v = fmaxf(v, 0.f);
+                        else if (p.act == 3) v = 0.5f * v * (1.f + fast_erff(v * 0.70710678118654752440f));
+                        else if (p.act == 4) v = v > 0.f ? v : v * p.act_slope;
+                        outv[r] = v;
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float v = outv[r] * p.out_scale;
                     if (p.accumulate && !p.c_split) v += cv[r];
                     outv[r] = v;
                 }
@@ -208,10 +227,15 @@ __device__ __forceinline__ void igemm_epilogue(const IGemm& p, f32x16 (&acc)[MI]
                                                int lk, long long coff, int Nb, int rpb) {
     const bool pair = !p.geglu && !p.c_split && p.c2 == nullptr && (p.N & 1) == 0 && (p.ldc & 1) == 0 && (coff & 1) == 0 &&
                       (reinterpret_cast<uintptr_t>(p.c) & 7) == 0;
-    if (pair)
-        igemm_epilogue_impl<MI, NI, true>(p, acc, m_base, n_base, lrow, lk, coff, Nb, rpb);
+    const bool rsel = !(p.rowadd && rpb < 32);       // (false: images of a few pixels, one division per row)
+    if (pair && rsel)
+        igemm_epilogue_impl<MI, NI, true, true>(p, acc, m_base, n_base, lrow, lk, coff, Nb, rpb);
+    else if (pair)
+        igemm_epilogue_impl<MI, NI, true, false>(p, acc, m_base, n_base, lrow, lk, coff, Nb, rpb);
+    else if (rsel)
+        igemm_epilogue_impl<MI, NI, false, true>(p, acc, m_base, n_base, lrow, lk, coff, Nb, rpb);
     else
-        igemm_epilogue_impl<MI, NI, false>(p, acc, m_base, n_base, lrow, lk, coff, Nb, rpb);
+        igemm_epilogue_impl<MI, NI, false, false>(p, acc, m_base, n_base, lrow, lk, coff, Nb, rpb);
 }
 
 }  // namespace maa

@@ -494,13 +494,17 @@ int maa_resampler_forward(maa_ctx* ctx, maa_resampler* r, const float* d_wav, in
 int maa_calib(maa_ctx* ctx, int kind, double* out_value);
 
 /* ---- single-operator entry points (parity tests and profiling of individual kernels) ------------ */
-/* y[M,N] = A[M,K] * W^T (+bias) with W given as torch Linear weight [N,K] on the HOST; A, y on device */
+/* y[M,N] = A[M,K] * W^T (+bias) with W given as torch Linear weight [N,K] on the HOST; A, y on device.
+ * The epilogue's other operands, as the models use them (null / 0 = absent): d_res [M,N] is added to the result;
+ * c_split != 0 writes y as split32 rows ([32 bf16 hi | 32 bf16 lo] per 32 columns, N % 32 == 0). */
 int maa_op_linear(maa_ctx* ctx, const float* d_a, int M, int K, const float* h_w, const float* h_bias, int N,
-                  int geglu, float* d_y);
-/* conv on channels-first tensors: d_x [B,Cin,H,W] (1-D: H = 1), torch weight [Cout,Cin,KH,KW] on the HOST */
+                  int geglu, float* d_y, const float* d_res, int c_split);
+/* conv on channels-first tensors: d_x [B,Cin,H,W] (1-D: H = 1), torch weight [Cout,Cin,KH,KW] on the HOST.
+ * d_rowadd [B,Cout] (a ResBlock's time-embedding row) and d_res [B,Cout,Ho,Wo] are added to the result; c_split != 0 leaves
+ * the result channels-last, d_y = [B Ho Wo][Cout] split32 rows (Cout % 32 == 0). */
 int maa_op_conv(maa_ctx* ctx, const float* d_x, int B, int Cin, int H, int W, const float* h_w, const float* h_bias,
                 int Cout, int KH, int KW, int stride, int pad, int dil, int upsample2, float leaky_slope,
-                float* d_y, int Ho, int Wo);
+                float* d_y, int Ho, int Wo, const float* d_rowadd, const float* d_res, int c_split);
 /* GroupNorm(32 groups)(+SiLU) on d_x [B,C,HW] */
 int maa_op_groupnorm(maa_ctx* ctx, const float* d_x, int B, int C, int HW, const float* h_gamma,
                      const float* h_beta, float eps, int silu, float* d_y);
