@@ -81,6 +81,12 @@ class maa_diffnet_config(C.Structure):
                 ("residual_channels", C.c_int), ("dilation_cycle_length", C.c_int)]
 
 
+class maa_pitch_extractor_config(C.Structure):
+    _fields_ = [("n_mel_bins", C.c_int), ("hidden_size", C.c_int), ("predictor_hidden", C.c_int), ("predictor_kernel", C.c_int),
+                ("conv_layers", C.c_int), ("ffn_padding_same", C.c_int), ("use_uv", C.c_int), ("pitch_norm", C.c_int),
+                ("f0_mean", C.c_float), ("f0_std", C.c_float)]
+
+
 class maa_encoder_config(C.Structure):
     _fields_ = [("kind", C.c_int), ("layers", C.c_int), ("width", C.c_int), ("heads", C.c_int), ("mlp_dim", C.c_int),
                 ("d_proj", C.c_int), ("vocab", C.c_int), ("max_positions", C.c_int), ("patch", C.c_int),
@@ -118,7 +124,9 @@ EXPORTS = [
     "maa_vae_create",
     "maa_vae_destroy", "maa_vae_decode", "maa_vae_decode_spec", "maa_vae_encode_moments", "maa_vocoder_create", "maa_vocoder_destroy",
     "maa_vocoder_forward", "maa_vocoder_forward_f0", "maa_diffnet_create", "maa_diffnet_destroy", "maa_diffnet_forward",
-    "maa_plms_sample", "maa_ds_ddpm_sample", "maa_ds_ddpm_update", "maa_encoder_create", "maa_encoder_destroy", "maa_encoder_text", "maa_encoder_image",
+    "maa_plms_sample", "maa_ds_ddpm_sample", "maa_ds_ddpm_update",
+    "maa_pitch_extractor_create", "maa_pitch_extractor_destroy", "maa_pitch_extractor_forward",
+    "maa_encoder_create", "maa_encoder_destroy", "maa_encoder_text", "maa_encoder_image",
     "maa_encoder_text_cls", "maa_clap_audio_create", "maa_clap_audio_destroy", "maa_clap_audio_embed", "maa_clap_similarity",
     "maa_spectral_create", "maa_spectral_destroy", "maa_spectral_forward", "maa_resampler_create", "maa_resampler_destroy",
     "maa_resampler_forward", "maa_op_linear", "maa_op_conv", "maa_op_groupnorm", "maa_op_layernorm",
@@ -182,6 +190,9 @@ def load():
         "maa_plms_sample": [vp, vp, C.POINTER(maa_plms_args), vp],
         "maa_ds_ddpm_sample": [vp, vp, C.POINTER(maa_ds_ddpm_args), vp],
         "maa_ds_ddpm_update": [vp, vp, vp, vp, fp, fp, fp, fp, fp, ci, ci, ci, ci, ci, vp],
+        "maa_pitch_extractor_create": [vp, C.POINTER(maa_pitch_extractor_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+        "maa_pitch_extractor_destroy": [vp],
+        "maa_pitch_extractor_forward": [vp, vp, vp, ci, ci, vp, vp, vp],
         "maa_encoder_create": [vp, C.POINTER(maa_encoder_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
         "maa_encoder_destroy": [vp],
         "maa_encoder_text": [vp, vp, vp, ci, ci, vp],

@@ -1068,6 +1068,70 @@ class DiffNet:
             pass
 
 
+def pe_config(cfg):
+    """maa_pitch_extractor_config of a PitchExtractor hparams dict (config.PITCH_EXTRACTOR); refuses what the library does not
+    build, with the reason, before any device is touched."""
+    pad = cfg.get("ffn_padding", "SAME")
+    if pad != "SAME":
+        raise L.MaaError("PitchExtractor: ffn_padding %r is not supported: only 'SAME' (kernel // 2 zeros on both sides) is built, "
+                         "the causal 'LEFT' padding (kernel - 1, 0) is not" % (pad,))
+    norm = cfg.get("pitch_norm", "log")
+    if norm not in ("log", "standard"):
+        raise L.MaaError("PitchExtractor: pitch_norm %r: the reference has 'log' and 'standard'" % (norm,))
+    if cfg.get("pitch_type", "frame") != "frame":
+        raise L.MaaError("PitchExtractor: pitch_type %r is not supported: only 'frame'" % (cfg.get("pitch_type"),))
+    c = L.maa_pitch_extractor_config()
+    c.n_mel_bins, c.hidden_size = int(cfg["n_mel_bins"]), int(cfg["hidden_size"])
+    c.predictor_hidden, c.predictor_kernel = int(cfg.get("predictor_hidden", -1)), int(cfg.get("predictor_kernel", 5))
+    c.conv_layers = int(cfg.get("conv_layers", 2))
+    c.ffn_padding_same = 1
+    c.use_uv = int(bool(cfg.get("use_uv", True)))          # (pitch_type == 'frame' holds here)
+    c.pitch_norm = 0 if norm == "log" else 1
+    c.f0_mean, c.f0_std = float(cfg.get("f0_mean", 0.0)), float(cfg.get("f0_std", 1.0))
+    return c
+
+
+class PitchExtractor:
+    """maa_pitch_extractor handle: DiffSinger's PitchExtractor (NeuralSeq/modules/fastspeech/pe.py:119-149), mel -> f0."""
+
+    def __init__(self, ctx, cfg, state_dict):
+        self.ctx, self.cfg = ctx, dict(cfg)
+        c = pe_config(self.cfg)
+        arr, n, keep = L.tensor_list(state_dict)
+        h = C.c_void_p()
+        with ctx.lock:
+            L.check(ctx.lib.maa_pitch_extractor_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
+        self.h = h
+
+    def forward(self, mel, return_hidden=False):
+        """mel [B, T, n_mel_bins] (an all-zero frame is padding) -> (pitch_pred [B, T, 2], f0 [B, T]) on the device; with
+        return_hidden also mel_hidden [B, T, hidden_size], the input of pitch_predictor."""
+        mel = _f32(mel, self.ctx.device)
+        if mel.dim() != 3 or mel.shape[2] != self.cfg["n_mel_bins"] or mel.shape[0] < 1 or mel.shape[1] < 1:
+            raise L.MaaError("PitchExtractor.forward: mel %s is not [B, T, %d]" % (tuple(mel.shape), self.cfg["n_mel_bins"]))
+        B, T, _ = mel.shape
+        pitch_pred = torch.empty(B, T, 2, device=self.ctx.device)
+        f0 = torch.empty(B, T, device=self.ctx.device)
+        hidden = torch.empty(B, T, self.cfg["hidden_size"], device=self.ctx.device) if return_hidden else None
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_pitch_extractor_forward(self.ctx.h, self.h, L.dptr(mel), B, T, L.dptr(pitch_pred), L.dptr(f0),
+                                                             L.dptr(hidden) if return_hidden else None))
+        return (pitch_pred, f0, hidden) if return_hidden else (pitch_pred, f0)
+
+    __call__ = forward
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.maa_pitch_extractor_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Encoder:
     """maa_encoder handle: a conditioning tower on the device.
 

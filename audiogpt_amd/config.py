@@ -110,6 +110,14 @@ DIFFSPEECH_LJ_BETA6 = dict(DIFFSINGER_POPCS_BETA6, K_step=71)
 # whole chain from Gaussian noise
 DIFFSINGER_DS100_ADJ_REL = dict(DIFFSINGER_POPCS_BETA6, dilation_cycle_length=4, K_step=100, gaussian_start=True)
 
+# PitchExtractor of the e2e singing configurations (pe_enable: true in midi/e2e/opencpop/ds1000.yaml, ds100_adj_rel.yaml,
+# ds1000-10dil.yaml, midi/e2e/popcs/ds100_adj_rel.yaml): egs_bases/svs/midi/pe.yaml (pitch_type frame, predictor_hidden -1,
+# conv_layers 2 = PitchExtractor's default) over the FastSpeech2 defaults of egs_bases/tts/fs2.yaml and base.yaml (hidden_size
+# 256, predictor_kernel 5, ffn_padding SAME, use_uv true, pitch_norm log).  f0_mean / f0_std are read with pitch_norm 'standard'
+# only.  checkpoints/0102_xiaoma_pe is not shipped.
+PITCH_EXTRACTOR = dict(n_mel_bins=80, hidden_size=256, predictor_hidden=-1, predictor_kernel=5, ffn_padding="SAME", conv_layers=2,
+                       pitch_type="frame", use_uv=True, pitch_norm="log", f0_mean=0.0, f0_std=1.0)
+
 # BigVGAN's args.yml (vocoder/logs/bigv16k53w) does not ship with the reference
 # (SURVEY.md section 0.3); these are the generator defaults it is exercised with here.
 BIGVGAN_16K = dict(

@@ -26,6 +26,9 @@ struct maa_vocoder {
 struct maa_diffnet {
     std::unique_ptr<maa::DiffNet> m;
 };
+struct maa_pitch_extractor {
+    std::unique_ptr<maa::PitchExtractor> m;
+};
 struct maa_encoder {
     std::unique_ptr<maa::Encoder> m;
 };
@@ -515,6 +518,48 @@ int maa_ds_ddpm_update(maa_ctx* ctx, const float* d_eps, const float* d_t, const
         MAA_CHECK(d_x != d_eps && d_x != d_noise, "bad ds_ddpm_update arguments: d_x is updated in place and may not alias the inputs");
         maa::ds_ddpm_update(ctx->c, d_eps, d_t, d_noise, h_sqrt_recip_ac, h_sqrt_recipm1_ac, h_coef1, h_coef2, h_sigma, timesteps,
                             B, M, T, clip_denoised != 0, d_x);
+    });
+}
+
+// ------------------------------------------------------------------------------------------ DiffSinger PitchExtractor
+int maa_pitch_extractor_create(maa_ctx* ctx, const maa_pitch_extractor_config* cfg, const maa_tensor* tensors, int n_tensors,
+                               maa_pitch_extractor** out) {
+    return guarded([&] {
+        MAA_CHECK(cfg && out, "bad pitch_extractor_create arguments: null pointer");
+        // (a configuration that cannot run is refused before the device is touched)
+        MAA_CHECK(cfg->ffn_padding_same != 0,
+                  "PitchExtractor: hparams['ffn_padding'] must be 'SAME' -- the causal 'LEFT' padding (kernel - 1, 0) is not built");
+        MAA_CHECK(cfg->n_mel_bins > 0 && cfg->n_mel_bins % 4 == 0 && cfg->hidden_size >= 16 && cfg->hidden_size % 16 == 0 &&
+                      cfg->conv_layers >= 0,
+                  "bad PitchExtractor config: n_mel_bins must be a multiple of 4, hidden_size a multiple of 16, conv_layers >= 0");
+        MAA_CHECK(cfg->predictor_hidden <= 1024 && (cfg->predictor_hidden <= 0 || cfg->predictor_hidden % 4 == 0) &&
+                      cfg->hidden_size <= 1024,
+                  "bad PitchExtractor config: predictor_hidden must be a multiple of 4 (or <= 0 for hidden_size), widths at most 1024");
+        MAA_CHECK(cfg->predictor_kernel >= 1 && cfg->predictor_kernel % 2 == 1,
+                  "bad PitchExtractor config: predictor_kernel must be odd ('SAME' padding keeps the length only then)");
+        MAA_CHECK(cfg->pitch_norm == 0 || cfg->pitch_norm == 1, "bad PitchExtractor config: pitch_norm is 0 ('log') or 1 ('standard')");
+        bind(ctx);
+        auto sd = to_state_dict(tensors, n_tensors);
+        auto* p = new maa_pitch_extractor;
+        try {
+            p->m.reset(new maa::PitchExtractor(*cfg, sd, ctx->c.dtype));
+        } catch (...) {
+            delete p;
+            throw;
+        }
+        *out = p;
+    });
+}
+int maa_pitch_extractor_destroy(maa_pitch_extractor* pe) {
+    return guarded([&] { delete pe; });
+}
+int maa_pitch_extractor_forward(maa_ctx* ctx, maa_pitch_extractor* pe, const float* d_mel, int B, int T, float* d_pitch_pred,
+                                float* d_f0, float* d_mel_hidden) {
+    return guarded([&] {
+        bind(ctx);
+        MAA_CHECK(pe && d_mel && d_pitch_pred && d_f0, "bad pitch_extractor_forward arguments: null pointer");
+        MAA_CHECK(B > 0 && T > 0 && (long long)B * T < (1LL << 31) / 1024, "bad pitch_extractor_forward arguments: B, T");
+        pe->m->forward(ctx->c, d_mel, B, T, d_pitch_pred, d_f0, d_mel_hidden);
     });
 }
 

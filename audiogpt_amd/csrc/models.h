@@ -91,6 +91,20 @@ private:
     Impl* impl_;
 };
 
+// DiffSinger's PitchExtractor (pitch_extractor.cpp, pitch.hip): the generated mel -> f0 for the NSF vocoder
+class PitchExtractor {
+public:
+    PitchExtractor(const maa_pitch_extractor_config& cfg, const StateDict& sd, int precision);
+    ~PitchExtractor();
+    // mel [B, T, n_mel_bins] -> pitch_pred [B, T, 2], f0 [B, T]; hidden_out (optional) [B, T, hidden_size]: pitch_predictor's input
+    void forward(Ctx& ctx, const float* mel, int B, int T, float* pitch_pred, float* f0, float* hidden_out);
+    const maa_pitch_extractor_config& config() const;
+
+private:
+    struct Impl;
+    Impl* impl_;
+};
+
 class Encoder {
 public:
     Encoder(const maa_encoder_config& cfg, const StateDict& sd, int precision);

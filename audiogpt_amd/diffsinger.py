@@ -10,12 +10,20 @@ pndm_speedup evaluations per utterance, ds1000.yaml) and the ancestral chain eve
 
     gd = GaussianDiffusion(C.DIFFSINGER_DS1000, device="cuda:0", state_dict=ckpt_denoise_fn_sd, spec_min=..., spec_max=...)
     mel = gd.infer(fs2_mel [B, T, 80], cond [B, 256, T])          # == ret['mel_out'] of forward(..., infer=True)
+
+The tail of the e2e singing pipeline (NeuralSeq/inference/svs/ds_e2e.py:36-45, every shipped e2e configuration sets
+`pe_enable`) runs on the device as well: `PitchExtractor` predicts f0 from the generated mel and the NSF HiFi-GAN takes both,
+so the mel never leaves the device between the diffusion and the waveform.
+
+    e2e = DiffSingerE2E(gd, hifigan.vocoder, pe=PitchExtractor(ctx=gd.ctx, state_dict=pe_ckpt_sd))
+    wav = e2e.infer(fs2_mel, cond)                                # [1, B * T * hop], run_vocoder's shape
 """
 import numpy as np
 import torch
 
 from . import config as C
 from . import weights as WT
+from . import backend
 from .backend import Context, DiffNet, default_precision
 
 # sample_ddpm's default cap on the steps' noise buffer: n * B * M * T * 4 bytes per device call
@@ -250,3 +258,69 @@ class OfflineGaussianDiffusion(GaussianDiffusion):
     def infer(self, fs2_mels, cond, noise=None, gaussian_start=None, mel2ph=None, noise_start=None, noise_p=None,
               clip_denoised=True):
         return self.denorm_spec(self._infer_x0(fs2_mels, cond, noise, gaussian_start, noise_start, noise_p, clip_denoised))
+
+
+class PitchExtractor(object):
+    """modules/fastspeech/pe.py:119-149 with the reference's call surface: `pe(mel_out)['f0_denorm_pred']`.  cfg: the hparams
+    it reads (config.PITCH_EXTRACTOR); state_dict: the checkpoint's (a `model.` prefix is stripped), seeded random weights when
+    None.  ctx: an existing Context, e.g. the diffusion's, so the stages share one stream."""
+
+    def __init__(self, cfg=None, device="cuda:0", state_dict=None, ctx=None, precision=None, seed=13):
+        self.cfg = dict(cfg or C.PITCH_EXTRACTOR)
+        backend.pe_config(self.cfg)                    # refuses an unsupported configuration before a context is made
+        self.ctx = ctx or Context(device, precision=precision or default_precision())
+        self.device = self.ctx.device
+        sd = state_dict if state_dict is not None else WT.make_pe_state_dict(self.cfg, seed=seed)
+        sd = WT.strip_prefix(sd, "model.") or sd
+        self.net = backend.PitchExtractor(self.ctx, self.cfg, sd)
+
+    @torch.no_grad()
+    def forward(self, mel_input=None):
+        """mel_input [B, T, n_mel_bins] -> {'pitch_pred' [B, T, 2], 'f0_denorm_pred' [B, T]}, device tensors."""
+        pitch_pred, f0 = self.net.forward(mel_input)
+        return {"pitch_pred": pitch_pred, "f0_denorm_pred": f0}
+
+    __call__ = forward
+
+    def eval(self):
+        return self
+
+    def to(self, *args, **kwargs):
+        return self
+
+
+class DiffSingerE2E(object):
+    """The tail of DiffSingerE2EInfer.forward_model (inference/svs/ds_e2e.py:36-45) with BaseSVSInfer.run_vocoder
+    (base_svs_infer.py:61-70): mel_out -> f0 (pe, when set) -> waveform.  diffusion: a GaussianDiffusion; vocoder: a
+    backend.Vocoder (forward / forward_f0) on the same device; use_nsf: hparams['use_nsf']."""
+
+    def __init__(self, diffusion, vocoder, pe=None, use_nsf=True):
+        self.diffusion, self.vocoder, self.pe, self.use_nsf = diffusion, vocoder, pe, bool(use_nsf)
+
+    @torch.no_grad()
+    def run_vocoder(self, c, f0=None, **draws):
+        """c [B, T, 80], f0 [B, T] or None -> [1, B * T * hop].  The NSF branch runs only with f0 given and use_nsf; draws:
+        SineGen's rand_ini / noise, passed to forward_f0."""
+        c = c.transpose(2, 1)
+        if f0 is not None and self.use_nsf:
+            y = self.vocoder.forward_f0(c, f0, **draws).reshape(-1)
+        else:
+            y = self.vocoder.forward(c).reshape(-1)
+        return y[None]
+
+    @torch.no_grad()
+    def mel_to_wav(self, mel_out, **draws):
+        f0 = self.pe(mel_out)["f0_denorm_pred"] if self.pe is not None else None
+        return self.run_vocoder(mel_out, f0=f0, **draws)
+
+    @torch.no_grad()
+    def infer(self, fs2_mels, cond, mel2ph=None, rand_ini=None, noise_sine=None, **kw):
+        """diffusion.infer(fs2_mels, cond, mel2ph=mel2ph, **kw) followed by mel_to_wav.  rand_ini / noise_sine: SineGen's two draws
+        (`noise` is q_sample's draw of diffusion.infer)."""
+        mel_out = self.diffusion.infer(fs2_mels, cond, mel2ph=mel2ph, **kw)
+        draws = {}
+        if rand_ini is not None:
+            draws["rand_ini"] = rand_ini
+        if noise_sine is not None:
+            draws["noise"] = noise_sine
+        return self.mel_to_wav(mel_out, **draws)

@@ -347,6 +347,39 @@ def make_diffnet_state_dict(cfg, seed=7):
     return sd
 
 
+def make_pe_state_dict(cfg, seed=13):
+    """PitchExtractor (NeuralSeq/modules/fastspeech/pe.py:119-133) in the reference key layout, bookkeeping entries included
+    (BatchNorm's num_batches_tracked, embed_positions._float_tensor): 59 keys at the defaults.  The BatchNorm running
+    statistics and affine and pos_embed_alpha are drawn away from their initial values, so a loader that skipped them shows."""
+    g, sd = _Gen(seed), {}
+    H, M, k = cfg["hidden_size"], cfg["n_mel_bins"], 5
+    Cp = cfg["predictor_hidden"] if cfg["predictor_hidden"] > 0 else H
+    kp = cfg["predictor_kernel"]
+    for i in range(3):
+        p, cin = f"mel_prenet.layers.{i}.", (M if i == 0 else H)
+        sd[p + "0.weight"], sd[p + "0.bias"] = g.weight((H, cin, k), 1.4), g.bias(H)
+        sd[p + "2.weight"], sd[p + "2.bias"] = g.gamma(H), g.beta(H)
+        sd[p + "2.running_mean"] = 0.3 + g.normal((H,), 0.3)
+        sd[p + "2.running_var"] = 0.5 + torch.rand((H,), generator=g.g, dtype=torch.float32)
+        sd[p + "2.num_batches_tracked"] = torch.tensor(1000 + i, dtype=torch.long)
+    sd["mel_prenet.out_proj.weight"], sd["mel_prenet.out_proj.bias"] = g.weight((H, H)), g.bias(H)
+    if cfg["conv_layers"] > 0:
+        sd["mel_encoder.in_proj.weight"], sd["mel_encoder.in_proj.bias"] = g.weight((H, H)), g.bias(H)
+        for i in range(cfg["conv_layers"]):
+            p = f"mel_encoder.conv.{i}."
+            sd[p + "conv.conv.weight"], sd[p + "conv.conv.bias"] = g.weight((H, H, k)), g.bias(H)
+            sd[p + "norm.weight"], sd[p + "norm.bias"] = g.gamma(H), g.beta(H)
+        sd["mel_encoder.out_proj.weight"], sd["mel_encoder.out_proj.bias"] = g.weight((H, H)), g.bias(H)
+    for i in range(5):
+        p, cin = f"pitch_predictor.conv.{i}.", (H if i == 0 else Cp)
+        sd[p + "1.weight"], sd[p + "1.bias"] = g.weight((Cp, cin, kp), 1.4), g.bias(Cp)
+        sd[p + "3.weight"], sd[p + "3.bias"] = g.gamma(Cp), g.beta(Cp)
+    sd["pitch_predictor.linear.weight"], sd["pitch_predictor.linear.bias"] = g.weight((2, Cp)), g.bias(2)
+    sd["pitch_predictor.embed_positions._float_tensor"] = torch.zeros(1, dtype=torch.float32)
+    sd["pitch_predictor.pos_embed_alpha"] = torch.tensor([0.7], dtype=torch.float32)
+    return sd
+
+
 # ----------------------------------------------------------------------------- conditioning encoders
 def make_clap_text_state_dict(cfg, seed=11):
     """`caption_encoder.`-relative keys of the CLAP checkpoint FrozenCLAPEmbedder loads (encoders/modules.py:179-183):

@@ -386,6 +386,29 @@ int maa_ds_ddpm_update(maa_ctx* ctx, const float* d_eps, const float* d_t, const
                        const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_sigma,
                        int timesteps, int B, int M, int T, int clip_denoised, float* d_x);
 
+/* ---- DiffSinger PitchExtractor (the e2e singing configurations' mel -> f0 between the diffusion and the NSF vocoder) ----
+ * NeuralSeq/modules/fastspeech/pe.py:119-149 with hparams hidden_size / predictor_hidden (<= 0: hidden_size) /
+ * predictor_kernel / ffn_padding / pitch_type / use_uv / pitch_norm / f0_mean / f0_std (egs_bases/svs/midi/pe.yaml) */
+typedef struct maa_pitch_extractor_config {
+    int n_mel_bins, hidden_size, predictor_hidden, predictor_kernel, conv_layers;
+    int ffn_padding_same;          /* hparams['ffn_padding'] == 'SAME'; anything else is refused */
+    int use_uv;                    /* pitch_type == 'frame' and use_uv: frames with a voicing logit > 0 get f0 = 0 */
+    int pitch_norm;                /* 0 'log' (f0 = 2 ** x), 1 'standard' (f0 = x * f0_std + f0_mean) */
+    float f0_mean, f0_std;
+} maa_pitch_extractor_config;
+typedef struct maa_pitch_extractor maa_pitch_extractor;
+/* tensors: the PitchExtractor state_dict (mel_prenet.layers.{i}.{0,2}.*, mel_prenet.out_proj.*, mel_encoder.{in_proj,out_proj}.*,
+ * mel_encoder.conv.{i}.{conv.conv,norm}.*, pitch_predictor.conv.{i}.{1,3}.*, pitch_predictor.linear.*,
+ * pitch_predictor.pos_embed_alpha); num_batches_tracked and embed_positions._float_tensor are accepted and ignored */
+int maa_pitch_extractor_create(maa_ctx* ctx, const maa_pitch_extractor_config* cfg, const maa_tensor* tensors, int n_tensors,
+                               maa_pitch_extractor** out);
+int maa_pitch_extractor_destroy(maa_pitch_extractor* pe);
+/* replaces: PitchExtractor.forward(mel_input) (pe.py:135-149): d_mel [B, T, n_mel_bins] (a frame of zeros is padding) ->
+ * d_pitch_pred [B, T, 2] (ret['pitch_pred']) and d_f0 [B, T] (ret['f0_denorm_pred'], 0 on unvoiced and padding frames).
+ * d_mel_hidden: null, or [B, T, hidden_size] receiving pitch_predictor's input.  Launches on the context's stream only. */
+int maa_pitch_extractor_forward(maa_ctx* ctx, maa_pitch_extractor* pe, const float* d_mel, int B, int T, float* d_pitch_pred,
+                                float* d_f0, float* d_mel_hidden);
+
 /* ---- conditioning encoders (the step before the sampler: text / image -> cross-attention context) ----------
  * kind 0: the CLAP text branch as FrozenCLAPEmbedder.encode runs it (ldm/modules/encoders/modules.py:204-211):
  *   transformers BertModel (bert-base-uncased, built by TextEncoder, CLAP/clap.py:41-45) on input_ids alone -- no
