@@ -32,8 +32,14 @@ constexpr int NT = 256;
 
 // TERMS = 3: bf16x3 (lo.hi, hi.lo, hi.hi); TERMS = 1: the context's plain-bf16 mode -- the operands are the hi halves of the
 // same split32 lines (hi = bf16(x) is exactly the rounding that mode asks for), one MFMA per k-step, the lo halves are never read
-template <int BM, int BN, int WGM, int WGN, int NS, int TERMS>
-__global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles, int Nb) {
+//
+// LINEAR: the 1x1 / Linear form (one tap, stride 1, no padding, no upsample, output grid = input grid: igemm_is_linear).  The A row
+// of output position m is a1 + m * lda1, so the prologue has no (sample, y, x) decode and no tap logic: every copy instruction's
+// source pointer is formed once and advanced by one chunk per issue.  The LDS image, the copy order, the vmcnt arithmetic and the
+// MFMA order are those of the convolution form.  EPI: the epilogue kind (igemm_epilogue.h); convolutions and every launch under
+// MAA_EPI=generic run <false, GENERIC>, the kernel as it was before the variants existed.
+template <int BM, int BN, int WGM, int WGN, int NS, int TERMS, bool LINEAR = false, Epi EPI = Epi::GENERIC>
+__global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles, int Nb, unsigned ntiles_rcp) {
     constexpr int WTM = BM / WGM, WTN = BN / WGN;
     constexpr int MI = WTM / 32, NI = WTN / 32;
     constexpr int ROWS = BM + BN;
@@ -46,7 +52,20 @@ __global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles
     const int tid = threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
     const int bid = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);      // consecutive tiles (N-tiles fastest) on one XCD: igemm_device.h
-    const int nt = bid % ntiles, mt = bid / ntiles;
+    int nt, mt;
+    if constexpr (LINEAR) {
+        // bid / ntiles without the division sequence: ntiles_rcp = min(floor(2^32 / ntiles), 2^32 - 1) from the launcher, so the
+        // high half of bid * ntiles_rcp is the quotient or one less (bid < 2^31); one conditional step settles it
+        mt = (int)__umulhi((unsigned)bid, ntiles_rcp);
+        nt = bid - mt * ntiles;
+        if (nt >= ntiles) {
+            nt -= ntiles;
+            ++mt;
+        }
+    } else {
+        nt = bid % ntiles;
+        mt = bid / ntiles;
+    }
     const int m0 = mt * BM, n0 = nt * BN;
 
     const int Ctot = p.C1;                     // single split32 source (checked by the launcher)
@@ -63,30 +82,45 @@ __global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles
     const char* a_slot[IPW];                   // a1 + this lane's slot offset (tap independent)
     const char* src[IPW];                      // A: row pointer under the current tap; B: weight row
     bool ok[IPW];
+    int adv[IPW];                              // LINEAR: bytes `src` moves per chunk (0: a masked row stays on the zero page)
+    if constexpr (LINEAR) {
 #pragma unroll
-    for (int j = 0; j < IPW; ++j) {
-        const int row = 8 * (wid * IPW + j) + (lane >> 3);
-        const int slot = (lane & 7) ^ ((row >> 1) & 7);
-        is_a[j] = 8 * (wid * IPW + j) < BM;
-        a_b[j] = -1;
-        a_iy0[j] = a_ix0[j] = 0;
-        a_slot[j] = reinterpret_cast<const char*>(p.a1) + slot * 16;
-        src[j] = zero;
-        ok[j] = false;
-        if (is_a[j]) {
-            const int m = m0 + row;
-            if (m < p.M) {
-                const int b = m / rpb;
-                const int rem = m - b * rpb;
-                const int oy = rem / p.Wout;
-                a_b[j] = b;
-                a_iy0[j] = oy * p.sh - p.ph;
-                a_ix0[j] = (rem - oy * p.Wout) * p.sw - p.pw;
+        for (int j = 0; j < IPW; ++j) {
+            const int row = 8 * (wid * IPW + j) + (lane >> 3);
+            const int slot = (lane & 7) ^ ((row >> 1) & 7);
+            const bool a = 8 * (wid * IPW + j) < BM;                  // wave-uniform
+            const int idx = a ? m0 + row : n0 + row - BM;
+            const bool live = idx < (a ? p.M : Nb);
+            const char* base = reinterpret_cast<const char*>(a ? p.a1 : p.b);
+            src[j] = live ? base + (long long)idx * (a ? p.lda1 : p.ldb) * 4 + slot * 16 : zero;
+            adv[j] = live ? BK * 4 : 0;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < IPW; ++j) {
+            const int row = 8 * (wid * IPW + j) + (lane >> 3);
+            const int slot = (lane & 7) ^ ((row >> 1) & 7);
+            is_a[j] = 8 * (wid * IPW + j) < BM;
+            a_b[j] = -1;
+            a_iy0[j] = a_ix0[j] = 0;
+            a_slot[j] = reinterpret_cast<const char*>(p.a1) + slot * 16;
+            src[j] = zero;
+            ok[j] = false;
+            if (is_a[j]) {
+                const int m = m0 + row;
+                if (m < p.M) {
+                    const int b = m / rpb;
+                    const int rem = m - b * rpb;
+                    const int oy = rem / p.Wout;
+                    a_b[j] = b;
+                    a_iy0[j] = oy * p.sh - p.ph;
+                    a_ix0[j] = (rem - oy * p.Wout) * p.sw - p.pw;
+                }
+            } else {
+                const int n = n0 + row - BM;
+                ok[j] = n < Nb;
+                src[j] = reinterpret_cast<const char*>(p.b) + (long long)(ok[j] ? n : 0) * p.ldb * 4 + slot * 16;
             }
-        } else {
-            const int n = n0 + row - BM;
-            ok[j] = n < Nb;
-            src[j] = reinterpret_cast<const char*>(p.b) + (long long)(ok[j] ? n : 0) * p.ldb * 4 + slot * 16;
         }
     }
     auto set_tap = [&](int tap) {
@@ -105,8 +139,24 @@ __global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles
     };
     int g_tap = 0, g_ci = 0;
     bool past = false;                          // chunks beyond K: everything masked (keeps the vmcnt arithmetic uniform)
+    int left = (p.K + BK - 1) / BK;             // LINEAR: chunks of K not issued yet
     auto issue = [&](int stage) {
         char* sbase = smem + stage * STAGE + wid * (IPW * 1024);
+        if constexpr (LINEAR) {
+#pragma unroll
+            for (int j = 0; j < IPW; ++j) {
+                __builtin_amdgcn_global_load_lds((gptr_t)src[j], (lptr_t)(sbase + j * 1024), 16, 0, 0);
+                src[j] += adv[j];
+            }
+            if (--left == 0) {                  // chunks beyond K: the zero page (keeps the vmcnt arithmetic uniform)
+#pragma unroll
+                for (int j = 0; j < IPW; ++j) {
+                    src[j] = zero;
+                    adv[j] = 0;
+                }
+            }
+            return;
+        }
         const int k0 = g_tap * Ctot + g_ci;
 #pragma unroll
         for (int j = 0; j < IPW; ++j) {
@@ -195,7 +245,7 @@ __global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles
     // (the NS-2 younger chunks may stay in flight), barrier (everybody's copies of chunk c are in LDS, and everybody is
     // done reading chunk c-1), refill the stage chunk c-1 used with chunk c+NS-1, then read + multiply chunk c.
     const int nchunks = (p.K + BK - 1) / BK;
-    set_tap(0);
+    if constexpr (!LINEAR) set_tap(0);
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s) issue(s);
     int st = 0, st_fill = NS - 1;
@@ -209,26 +259,50 @@ __global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles
     }
     wait_vmcnt<0>();        // no copy may land in LDS after this workgroup has given it back
 
-    igemm_epilogue<MI, NI>(p, acc, m0 + wm * WTM, n0 + wn * WTN, lrow, lk, 0, Nb, rpb);
+    if constexpr (EPI == Epi::GENERIC)
+        igemm_epilogue<MI, NI>(p, acc, m0 + wm * WTM, n0 + wn * WTN, lrow, lk, 0, Nb, rpb);
+    else
+        igemm_epilogue_fast<MI, NI, EPI>(p, acc, m0 + wm * WTM, n0 + wn * WTN, lrow, lk, Nb);
 }
 
-template <int BM, int BN, int WGM, int WGN, int NS, int TERMS>
+template <int BM, int BN, int WGM, int WGN, int NS, int TERMS, bool LINEAR, Epi EPI>
 void launch_terms(const Ctx& ctx, const IGemm& p, int Nb) {
     const int ncols = p.N * (p.geglu ? 2 : 1);
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (ncols + BN - 1) / BN;
     dim3 grid((unsigned)((long long)mtiles * ntiles));
     constexpr size_t lds = (size_t)NS * (BM + BN) * 128;
-    auto kern = igemm_dma_kernel<BM, BN, WGM, WGN, NS, TERMS>;
+    auto kern = igemm_dma_kernel<BM, BN, WGM, WGN, NS, TERMS, LINEAR, EPI>;
     ensure_dynamic_lds(reinterpret_cast<const void*>(kern), ctx.device, (int)lds);
-    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, ctx.stream, p, ntiles, Nb);
+    const unsigned long long rcp = (1ULL << 32) / (unsigned)ntiles;      // (the linear form's tile decode)
+    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, ctx.stream, p, ntiles, Nb, (unsigned)(rcp > 0xFFFFFFFFULL ? 0xFFFFFFFFULL : rcp));
 }
 
+template <int BM, int BN, int WGM, int WGN, int NS, bool LINEAR, Epi EPI>
+void launch_kind(const Ctx& ctx, const IGemm& p, int Nb) {
+    if (ctx.dtype == 2)
+        launch_terms<BM, BN, WGM, WGN, NS, 1, LINEAR, EPI>(ctx, p, Nb);
+    else
+        launch_terms<BM, BN, WGM, WGN, NS, 3, LINEAR, EPI>(ctx, p, Nb);
+}
+
+// The 1x1 / Linear form: the A row of output position m is a1 + m * lda1 and K is one pass over its channels.
+bool igemm_is_linear(const IGemm& p) {
+    return p.KH == 1 && p.KW == 1 && p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 && p.up == 0 && p.a2 == nullptr && p.C2 == 0 &&
+           p.K == p.C1 && p.Hin == p.Hout && p.Win == p.Wout;
+}
+
+// A linear whose epilogue is one of the fast kinds runs the linear form with that kind; everything else -- convolutions, linears
+// with a row add, an activation, an accumulate, a second output, a scale -- and every launch under MAA_EPI=generic runs the
+// convolution form with the generic epilogue.  Bit-identical either way (tests/test_gpu_linear_variants.py).
 template <int BM, int BN, int WGM, int WGN, int NS>
 void launch_one(const Ctx& ctx, const IGemm& p, int Nb) {
-    if (ctx.dtype == 2)
-        launch_terms<BM, BN, WGM, WGN, NS, 1>(ctx, p, Nb);
-    else
-        launch_terms<BM, BN, WGM, WGN, NS, 3>(ctx, p, Nb);
+    const Epi kind = ctx.tune.epi_generic || !igemm_is_linear(p) ? Epi::GENERIC : igemm_epi_kind(p);
+    if (kind == Epi::PLAIN) return launch_kind<BM, BN, WGM, WGN, NS, true, Epi::PLAIN>(ctx, p, Nb);
+    if (kind == Epi::SPLIT) return launch_kind<BM, BN, WGM, WGN, NS, true, Epi::SPLIT>(ctx, p, Nb);
+    if constexpr ((BN / WGN / 32) % 2 == 0) {      // (GEGLU pairs a value block with a gate block of the same wave: igemm_plan gives it the 128-wide tile)
+        if (kind == Epi::GEGLU) return launch_kind<BM, BN, WGM, WGN, NS, true, Epi::GEGLU>(ctx, p, Nb);
+    }
+    launch_kind<BM, BN, WGM, WGN, NS, false, Epi::GENERIC>(ctx, p, Nb);
 }
 
 }  // namespace

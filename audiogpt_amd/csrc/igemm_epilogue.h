@@ -43,16 +43,20 @@ __device__ __forceinline__ void settle(float& x) { asm volatile("" : "+v"(x)); }
 // even / odd column pair swap one half each (DPP quad_perm [1,0,3,2]) so that the even lane stores both hi halves and the odd
 // lane both lo halves -- ONE 4-byte store per lane and element instead of two 2-byte stores.  Both lanes of a pair must be
 // active (n even <-> lane even; callers guarantee N % 2 == 0 and a row condition that is uniform over the pair).
-__device__ __forceinline__ void store_split_pair(float* row, int n, float v) {
+// (split_pair_word: the 4-byte word the lane stores -- both hi halves of the pair on the even lane, both lo halves on the odd one)
+__device__ __forceinline__ unsigned split_pair_word(bool even, float v) {
     const __bf16 h = (__bf16)v;
     const unsigned hb = __builtin_bit_cast(unsigned short, h);
     const __bf16 l = (__bf16)(v - __builtin_bit_cast(float, hb << 16));
     const unsigned lb = __builtin_bit_cast(unsigned short, l);
-    const bool even = (n & 1) == 0;
     const unsigned mine = even ? lb : hb;                                  // what the partner stores
     const unsigned theirs = (unsigned)__builtin_amdgcn_update_dpp(0, (int)mine, 0xB1, 0xF, 0xF, false);
+    return even ? (hb | (theirs << 16)) : (theirs | (lb << 16));
+}
+__device__ __forceinline__ void store_split_pair(float* row, int n, float v) {
+    const bool even = (n & 1) == 0;
     unsigned* o = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(row) + (n >> 5) * 64 + ((n & 31) & ~1) + (even ? 0 : 32));
-    *o = even ? (hb | (theirs << 16)) : (theirs | (lb << 16));
+    *o = split_pair_word(even, v);
 }
 
 // acc[MI][NI]: MI x NI fragments of 32x32 owned by this wave; (m_base, n_base) = first row / column of the wave.
@@ -236,6 +240,178 @@ __device__ __forceinline__ void igemm_epilogue(const IGemm& p, f32x16 (&acc)[MI]
         igemm_epilogue_impl<MI, NI, false, true>(p, acc, m_base, n_base, lrow, lk, coff, Nb, rpb);
     else
         igemm_epilogue_impl<MI, NI, false, false>(p, acc, m_base, n_base, lrow, lk, coff, Nb, rpb);
+}
+
+// ------------------------------------------------------------------------------------------ epilogue kinds fixed at compile time
+// The function above carries every feature as a run-time flag and decides it per 32x32 block; what a transformer linear needs of it
+// is a few hundred instructions.  A launcher that knows its IGemm picks one of these kinds (igemm_epi_kind) and the kernel is
+// instantiated with it; GENERIC is the function above and takes everything the other kinds do not.  The arithmetic of the fast
+// kinds is the generic expression with the absent terms left out -- alpha == 1 and out_scale == 1 are conditions of every fast
+// kind, x * 1.0f is exact and the build has -ffp-contract=off -- so a launch returns the same bits under either.
+//   PLAIN   acc + bias (+ residual), fp32 pair stores           q / k / v, to_out, proj_in / proj_out, ff.net.2
+//   SPLIT   the same, written as split32 lines (c_split)
+//   GEGLU   value * gelu(gate), fp32 or split32 output          ff.net.0
+enum class Epi : int { GENERIC = 0, PLAIN = 1, SPLIT = 2, GEGLU = 3 };
+
+// Kind of a launch whose output starts at p.c (Z == 1).  The fast kinds address a 32x32 block as one 64-bit base plus 32-bit
+// offsets of up to 32 rows, hence the pitch limits.
+inline Epi igemm_epi_kind(const IGemm& p) {
+    const bool pitches = p.ldc > 0 && p.ldc < (1 << 24) && p.ldr >= 0 && p.ldr < (1 << 24);
+    if (!pitches || p.Z != 1 || p.M <= 0 || p.alpha != 1.f || p.out_scale != 1.f || p.rowadd || p.act != 0 || p.accumulate || p.c2)
+        return Epi::GENERIC;
+    if (p.geglu) return p.res ? Epi::GENERIC : Epi::GEGLU;
+    if (p.c_split) return (p.N & 1) == 0 ? Epi::SPLIT : Epi::GENERIC;
+    const bool pair = (p.N & 1) == 0 && (p.ldc & 1) == 0 && (reinterpret_cast<uintptr_t>(p.c) & 7) == 0;
+    return pair ? Epi::PLAIN : Epi::GENERIC;
+}
+
+__device__ __forceinline__ constexpr unsigned frag_row(int r) { return (unsigned)((r & 3) + 8 * (r >> 2)); }
+
+// One wave's blocks.  FULL: the wave's MI x NI blocks lie wholly inside M and N (no row clamps, no guards); otherwise the guarded
+// form, whose reads come from clamped rows as in the generic function.  (mb0, nb0) are wave-uniform; a block is addressed as a
+// uniform base + this lane's 32-bit offset, and the offset of a fragment row is a uniform multiple of the pitch on top of the
+// lane's own (4 lk) * pitch + column, formed once.  All reads of a block are issued before its first store (settle).
+template <int MI, int NI, Epi KIND, bool FULL, bool RES>
+__device__ __forceinline__ void igemm_epilogue_fast_body(const IGemm& p, f32x16 (&acc)[MI][NI], int mb0, int nb0, int lrow, int lk,
+                                                         int Nb) {
+    const bool even = (lrow & 1) == 0;
+    const unsigned ldc = (unsigned)p.ldc, ldr = (unsigned)p.ldr;
+    const unsigned lane_f32 = 4u * lk * ldc + lrow;                                   // fp32 element (row 4 lk, column lrow)
+    const unsigned lane_pair = (4u * lk + (even ? 0u : 1u)) * ldc + (lrow & ~1);      // pair store: even lane the even row, odd lane the odd row
+    const unsigned lane_split = 4u * lk * ldc + (lrow >> 1) + (even ? 0u : 16u);      // split32 word: hi pairs | lo pairs of the 32 columns
+    const unsigned lane_res = 4u * lk * ldr + lrow;
+    if constexpr (KIND == Epi::GEGLU) {
+        // packed columns: [32 value | 32 gate] per group of 64; output column = group*32 + j
+        static_assert(NI % 2 == 0, "GEGLU pairs a value block with a gate block");
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+            const int mb = mb0 + i * 32;
+            if (!FULL && mb >= p.M) break;
+#pragma unroll
+            for (int j = 0; j < NI; j += 2) {
+                const int cb = nb0 + j * 32, ob = (cb >> 6) * 32;
+                const int cpk = cb + lrow;
+                if (FULL || (cpk + 32 < Nb && ob + lrow < p.N)) {
+                    float bv = p.bias ? p.bias[cpk] : 0.f;
+                    float bg = p.bias ? p.bias[cpk + 32] : 0.f;
+                    settle(bv);
+                    settle(bg);
+                    float outv[16];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float val = acc[i][j][r] + bv;
+                        const float g = acc[i][j + 1][r] + bg;
+                        const float gl = 0.5f * g * (1.f + fast_erff(g * 0.70710678118654752440f));
+                        outv[r] = val * gl;
+                    }
+                    float* blk = p.c + ((long long)mb * ldc + ob);
+                    if (p.c_split) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const unsigned w = split_pair_word(even, outv[r]);
+                            if (FULL || mb + (int)frag_row(r) + 4 * lk < p.M) reinterpret_cast<unsigned*>(blk)[lane_split + frag_row(r) * ldc] = w;
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (FULL || mb + (int)frag_row(r) + 4 * lk < p.M) blk[lane_f32 + frag_row(r) * ldc] = outv[r];
+                    }
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+            const int mb = mb0 + i * 32;
+            if (!FULL && mb >= p.M) break;
+            const unsigned last = (unsigned)(p.M - 1 - mb);        // (guarded form) last row of the block that exists
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+                const int nb = nb0 + j * 32;
+                if (FULL || nb + lrow < p.N) {
+                    float bias = p.bias ? p.bias[nb + lrow] : 0.f;
+                    float rs[16];
+                    if constexpr (RES) {
+                        const float* rb = p.res + ((long long)mb * ldr + nb);
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            if constexpr (FULL) {
+                                rs[r] = rb[lane_res + frag_row(r) * ldr];
+                            } else {
+                                const unsigned row = frag_row(r) + 4u * lk;
+                                rs[r] = rb[(row < last ? row : last) * ldr + lrow];
+                            }
+                        }
+                    }
+                    settle(bias);
+                    float outv[16];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float v = acc[i][j][r] + bias;
+                        if constexpr (RES) {
+                            settle(rs[r]);
+                            v += rs[r];
+                        }
+                        outv[r] = v;
+                    }
+                    float* blk = p.c + ((long long)mb * ldc + nb);
+                    if constexpr (KIND == Epi::PLAIN) {
+                        // two columns per lane, as in the generic function's PAIR form
+#pragma unroll
+                        for (int rp = 0; rp < 8; ++rp) {
+                            const float keep = even ? outv[2 * rp] : outv[2 * rp + 1];
+                            const float give = even ? outv[2 * rp + 1] : outv[2 * rp];
+                            const float got = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, give), 0xB1, 0xF, 0xF, false));
+                            const f32x2 v2 = even ? f32x2{keep, got} : f32x2{got, keep};
+                            if (FULL || mb + (int)frag_row(2 * rp) + 4 * lk + (even ? 0 : 1) < p.M)
+                                *reinterpret_cast<f32x2*>(blk + (lane_pair + frag_row(2 * rp) * ldc)) = v2;
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const unsigned w = split_pair_word(even, outv[r]);
+                            if (FULL || mb + (int)frag_row(r) + 4 * lk < p.M) reinterpret_cast<unsigned*>(blk)[lane_split + frag_row(r) * ldc] = w;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// (m_base, n_base) = first row / column of the wave, as for igemm_epilogue.  One wave-uniform decision per tile: a wave wholly
+// past M or N has nothing to write; one wholly inside takes the unguarded body.
+template <int MI, int NI, Epi KIND>
+__device__ __forceinline__ void igemm_epilogue_fast(const IGemm& p, f32x16 (&acc)[MI][NI], int m_base, int n_base, int lrow, int lk,
+                                                    int Nb) {
+    static_assert(KIND != Epi::GENERIC, "the generic kind is igemm_epilogue");
+    const int mb0 = __builtin_amdgcn_readfirstlane(m_base), nb0 = __builtin_amdgcn_readfirstlane(n_base);
+    if (mb0 >= p.M) return;
+    bool full = mb0 + MI * 32 <= p.M;
+    if constexpr (KIND == Epi::GEGLU) {
+        // every lane's guard (cpk + 32 < Nb, output column < N) holds iff the last lane's of the last block pair does
+        const int cpk = nb0 + (NI - 2) * 32 + 31;
+        if (nb0 + 32 >= Nb) return;
+        full = full && cpk + 32 < Nb && (cpk >> 6) * 32 + 31 < p.N;
+        if (full)
+            igemm_epilogue_fast_body<MI, NI, KIND, true, false>(p, acc, mb0, nb0, lrow, lk, Nb);
+        else
+            igemm_epilogue_fast_body<MI, NI, KIND, false, false>(p, acc, mb0, nb0, lrow, lk, Nb);
+    } else {
+        if (nb0 >= p.N) return;
+        full = full && nb0 + NI * 32 <= p.N;
+        if (p.res) {
+            if (full)
+                igemm_epilogue_fast_body<MI, NI, KIND, true, true>(p, acc, mb0, nb0, lrow, lk, Nb);
+            else
+                igemm_epilogue_fast_body<MI, NI, KIND, false, true>(p, acc, mb0, nb0, lrow, lk, Nb);
+        } else {
+            if (full)
+                igemm_epilogue_fast_body<MI, NI, KIND, true, false>(p, acc, mb0, nb0, lrow, lk, Nb);
+            else
+                igemm_epilogue_fast_body<MI, NI, KIND, false, false>(p, acc, mb0, nb0, lrow, lk, Nb);
+        }
+    }
 }
 
 }  // namespace maa

@@ -123,6 +123,7 @@ struct Tuning {
     bool no_dma = false;                    // MAA_NO_DMA: every bf16 contraction on the register-staged engine (bit-identity tests)
     int halo = 2;                           // MAA_HALO = "off": the narrow vocoder stages through the implicit GEMM; "single": their MRF pairs as two halo launches; default: fused pairs (bit-identity tests)
     bool cfg_shared = true;                 // MAA_CFG_SHARED=0: a guided DDIM step on one stream evaluates both halves of cat([x] * 2) in full (rounds 1-6a) instead of computing the layers before the first cross-attention once
+    bool epi_generic = false;               // MAA_EPI=generic: every launch of the LDS-DMA engine on the convolution form with the generic epilogue, not the linear form / compile-time epilogue kinds (A/B arm, bit-identity tests)
     bool gn_two_pass = false;               // MAA_GN_TWO_PASS=1: GroupNorm as the statistics + apply launches everywhere (the VAE's large images always take them; tests)
     void load();
 };

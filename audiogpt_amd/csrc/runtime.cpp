@@ -147,6 +147,7 @@ void Tuning::load() {
     const std::string hs = get_s("MAA_HALO");
     halo = hs == "off" ? 0 : hs == "single" ? 1 : 2;
     gn_two_pass = get_s("MAA_GN_TWO_PASS") == "1";
+    epi_generic = get_s("MAA_EPI") == "generic";
     // a stale override in an older round's format ("2,2,0,1": tile, stages ...) is refused here, when the context is created
     // (last, so that every other knob is in place), not by a check in the middle of a forward pass
     if (!dma2.empty() && dma2 != "off") {

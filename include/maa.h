@@ -79,7 +79,7 @@ int maa_ctx_set_cfg_split(maa_ctx* ctx, int mode);
  * lanes part. */
 int maa_ctx_set_concurrency(maa_ctx* ctx, int n);
 /* The test / A-B knobs of the environment (MAA_PP, MAA_PP1, MAA_PP_S, MAA_PP_TILE_MAJOR, MAA_UP2, MAA_DMA2, MAA_NO_DMA, MAA_HALO,
- * MAA_OP_PRESPLIT, MAA_GN_TWO_PASS) are parsed in one place, when a context is created; this parses them again
+ * MAA_OP_PRESPLIT, MAA_GN_TWO_PASS, MAA_EPI) are parsed in one place, when a context is created; this parses them again
  * (and drops the step graph the sampler keeps).  A malformed MAA_DMA2 value fails here (and in maa_ctx_create) with a message
  * naming the variable.  For tests and A/B runs; a -DMAA_NO_TUNING build ignores the environment. */
 int maa_ctx_reload_tuning(maa_ctx* ctx);

@@ -20,7 +20,9 @@ q = "select %s, %s, %s count(*), sum(%s) from counters_collection group by %s, %
 rows = list(cur.execute(q))
 agg = {}
 for k, c, g, n, v in rows:
-    k = k.replace("maa::(anonymous namespace)::", "").replace("void ", "").split("(")[0][:64]
+    # cut the parameter list, not a template argument written with a cast ("igemm_dma_kernel<..., true, (maa::Epi)1>(maa::IGemm, ...)")
+    k = k.replace("maa::(anonymous namespace)::", "").replace("void ", "")
+    k = (k[:k.find(">(") + 1] if ">(" in k else k.split("(")[0])[:64]
     agg.setdefault((k, g), {})[c] = (n, v)
 def key(item):
     d = item[1]

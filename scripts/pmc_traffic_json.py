@@ -20,6 +20,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 path, prec, steps, out = sys.argv[1], sys.argv[2], int(sys.argv[3]), sys.argv[4]
 section_name = sys.argv[sys.argv.index("--section") + 1] if "--section" in sys.argv else None
 LABELS = {  # bench.py / maa_prof label -> (rocprof kernel prefixes, prefix whose launch count is the label's)
+    # (prefixes stop before the trailing template arguments: igemm_dma_kernel<64, 64, 2, 2, 2, 3> and its linear-form / epilogue-kind
+    #  instantiations igemm_dma_kernel<64, 64, 2, 2, 2, 3, true, (maa::Epi)1> are one row)
     "igemm_dma_bf16x3<64x64>": (["igemm_dma_kernel<64, 64"], "igemm_dma_kernel<64, 64"),
     "igemm_dma_bf16x3<128x64>": (["igemm_dma_kernel<128, 64"], "igemm_dma_kernel<128, 64"),
     "igemm_dma_bf16x3<128x128>": (["igemm_dma_kernel<128, 128"], "igemm_dma_kernel<128, 128"),

@@ -10,6 +10,8 @@ rows = list(db.execute("select name, grid_x, grid_y, count(*), sum(duration), av
 tot = sum(r[4] for r in rows)
 print("total kernel time %.3f ms (/%g = %.3f ms)" % (tot / 1e6, div, tot / 1e6 / div))
 for name, gx, gy, n, s, a, mn in rows[:60]:
-    name = name.replace("maa::(anonymous namespace)::", "").replace("void ", "").split("(")[0]
-    print("%-52s grid %8d x %4d  n %7.1f  avg %9.2f us  min %9.2f us  total %9.3f ms (%5.1f%%)" % (
-        name[:52], gx // 256, gy, n / div, a / 1e3, mn / 1e3, s / 1e6 / div, 100.0 * s / tot))
+    # cut the parameter list, not a template argument written with a cast ("igemm_dma_kernel<..., true, (maa::Epi)1>(maa::IGemm, ...)")
+    name = name.replace("maa::(anonymous namespace)::", "").replace("void ", "")
+    name = name[:name.find(">(") + 1] if ">(" in name else name.split("(")[0]
+    print("%-60s grid %8d x %4d  n %7.1f  avg %9.2f us  min %9.2f us  total %9.3f ms (%5.1f%%)" % (
+        name[:60], gx // 256, gy, n / div, a / 1e3, mn / 1e3, s / 1e6 / div, 100.0 * s / tot))
