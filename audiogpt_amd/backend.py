@@ -471,6 +471,43 @@ class UNet:
         return self._sample("plms_sample", self.ctx.lib.maa_ldm_plms_sample, x_T, timesteps, alphas, alphas_prev, cond, uncond,
                             scale, concat, use_graph, mask, x0, noise_q, sqrt_ac, sqrt_1mac, None, None, 1.0, log_every_t, split)
 
+    def _step_noise(self, what, v, name, dim, shape, keep):
+        """The device pointer of the per-step draws `v`, which must be [dim = shape[0], B, C, H, W] (`dim`: how the messages
+        call the leading dimension); the tensor is kept alive in `keep`."""
+        t = _f32(v, self.ctx.device)
+        if tuple(t.shape) != tuple(shape):
+            raise L.MaaError("%s: %s must be [%s=%d, %d, %d, %d, %d], got %s" % ((what, name, dim) + tuple(shape) + (tuple(t.shape),)))
+        keep.append(t)
+        return t.data_ptr()
+
+    def _log_slabs(self, n_log, B, Cc, H, W):
+        """The kept pair of [n_log, B, C, H, W] log slabs.  They are part of the captured step (their addresses are in the step
+        graph's key, csrc/ddim.cpp): one pair per shape is kept by this model (four shapes at most) and the caller gets copies, so
+        that a second call replays the kept graph whatever the caching allocator would have handed out for fresh tensors."""
+        cache = self.__dict__.setdefault("_log_slab_cache", {})
+        key = (n_log, B, Cc, H, W)
+        if key not in cache:
+            if len(cache) >= 4:
+                cache.clear()
+            cache[key] = (torch.empty(*key, device=self.ctx.device), torch.empty(*key, device=self.ctx.device))
+        return cache[key]
+
+    def _copy_logs(self, logs):
+        """Copies of the log slabs, taken under the context's lock: the slabs are shared by every call on this model, so they are
+        copied out before the lock is released, ordered behind the context's own stream (a private torch stream: copy on it; a
+        library-created blocking stream orders against torch's default stream by itself, but a caller on another stream must
+        wait, so drain it)."""
+        dev = self.ctx.device
+        if self.ctx._stream is None:
+            self.ctx.synchronize()
+            return logs[0].clone(), logs[1].clone()
+        with torch.cuda.stream(self.ctx._stream):
+            out = (logs[0].clone(), logs[1].clone())
+        for t in out:
+            t.record_stream(torch.cuda.current_stream(dev))
+        torch.cuda.current_stream(dev).wait_stream(self.ctx._stream)
+        return out
+
     def _sample(self, what, entry, x_T, timesteps, alphas, alphas_prev, cond, uncond, scale, concat, use_graph, mask, x0, noise_q,
                 sqrt_ac, sqrt_1mac, sigmas, noise_p, temperature, log_every_t, split=None):
         """ddim_sample / plms_sample: the maa_ddim_args of a whole trajectory, the C entry `entry` on them and the logs."""
@@ -489,11 +526,7 @@ class UNet:
             return t.ctypes.data_as(C.POINTER(C.c_float))
 
         def step_noise(v, name):
-            t = _f32(v, dev)
-            if tuple(t.shape) != (S, B, Cc, H, W):
-                raise L.MaaError("%s: %s must be [S=%d, %d, %d, %d, %d], got %s" % (what, name, S, B, Cc, H, W, tuple(t.shape)))
-            keep.append(t)
-            return t.data_ptr()
+            return self._step_noise(what, v, name, "S", (S, B, Cc, H, W), keep)
 
         if mask is not None:
             if x0 is None or noise_q is None or sqrt_ac is None or sqrt_1mac is None:
@@ -513,34 +546,13 @@ class UNet:
         logs = None
         if log_every_t is not None:
             n_log = sum(1 for i in range(S) if i % int(log_every_t) == 0 or i == S - 1)
-            # the log slabs are part of the captured step (their addresses are in the step graph's key, csrc/ddim.cpp): one pair
-            # per shape is kept by this model and the caller gets copies, so that a second sample() call replays the kept graph
-            # whatever the caching allocator would have handed out for fresh tensors
-            cache = self.__dict__.setdefault("_log_slabs", {})
-            key = (n_log, B, Cc, H, W)
-            if key not in cache:
-                if len(cache) >= 4:
-                    cache.clear()
-                cache[key] = (torch.empty(n_log, B, Cc, H, W, device=dev), torch.empty(n_log, B, Cc, H, W, device=dev))
-            logs = cache[key]
+            logs = self._log_slabs(n_log, B, Cc, H, W)
             a.log_every_t, a.n_log = int(log_every_t), n_log
             a.d_log_x, a.d_log_x0 = logs[0].data_ptr(), logs[1].data_ptr()
         with self.ctx.lock:
             L.check(entry(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
             if logs is not None:
-                # the slabs are shared by every call on this model: copy them out before the lock is released, ordered behind the
-                # context's own stream (a private torch stream: copy on it; a library-created blocking stream orders against
-                # torch's default stream by itself, but a caller on another stream must wait, so drain it)
-                if self.ctx._stream is not None:
-                    with torch.cuda.stream(self.ctx._stream):
-                        out = (logs[0].clone(), logs[1].clone())
-                    for t in out:
-                        t.record_stream(torch.cuda.current_stream(dev))
-                    torch.cuda.current_stream(dev).wait_stream(self.ctx._stream)
-                else:
-                    self.ctx.synchronize()
-                    out = (logs[0].clone(), logs[1].clone())
-                return x, out[0], out[1]
+                return (x,) + self._copy_logs(logs)
         return x
 
     def ddim_decode(self, x_latent, t_start, timesteps, alphas, alphas_prev, cond=None, uncond=None, scale=1.0, concat=None,
@@ -649,11 +661,7 @@ class UNet:
         def step_noise(v, name):
             if v is None:
                 raise L.MaaError("%s: %s [n=%d, %d, %d, %d, %d] is needed" % (what, name, n, B, Cc, H, W))
-            t = _f32(v, dev)
-            if tuple(t.shape) != (n, B, Cc, H, W):
-                raise L.MaaError("%s: %s must be [n=%d, %d, %d, %d, %d], got %s" % (what, name, n, B, Cc, H, W, tuple(t.shape)))
-            keep.append(t)
-            return t.data_ptr()
+            return self._step_noise(what, v, name, "n", (n, B, Cc, H, W), keep)
 
         a.loop.d_noise_p = step_noise(noise_p, "noise_p")
         if mask is not None:
@@ -686,29 +694,13 @@ class UNet:
             if every <= 0:
                 raise L.MaaError(what + ": log_every_t must be positive")
             n_log = sum(1 for t in range(start - n + 1, start + 1) if t % every == 0 or t == start)
-            # (one pair of log slabs per shape is kept by this model, as _sample's: their addresses are in the step graph's key)
-            cache = self.__dict__.setdefault("_log_slabs", {})
-            key = (n_log, B, Cc, H, W)
-            if key not in cache:
-                if len(cache) >= 4:
-                    cache.clear()
-                cache[key] = (torch.empty(n_log, B, Cc, H, W, device=dev), torch.empty(n_log, B, Cc, H, W, device=dev))
-            logs = cache[key]
+            logs = self._log_slabs(n_log, B, Cc, H, W)
             a.loop.log_every_t, a.loop.n_log = every, n_log
             a.loop.d_log_x, a.loop.d_log_x0 = logs[0].data_ptr(), logs[1].data_ptr()
         with self.ctx.lock:
             L.check(self.ctx.lib.maa_ddpm_sample(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
             if logs is not None:
-                if self.ctx._stream is not None:
-                    with torch.cuda.stream(self.ctx._stream):
-                        out = (logs[0].clone(), logs[1].clone())
-                    for t in out:
-                        t.record_stream(torch.cuda.current_stream(dev))
-                    torch.cuda.current_stream(dev).wait_stream(self.ctx._stream)
-                else:
-                    self.ctx.synchronize()
-                    out = (logs[0].clone(), logs[1].clone())
-                return x, out[0], out[1]
+                return (x,) + self._copy_logs(logs)
         return x
 
     def ddpm_update(self, x, eps, t, tables, noise, temperature=1.0, clip_denoised=True):

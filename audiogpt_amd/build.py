@@ -7,7 +7,7 @@ next to this file so that it travels with the repo snapshot to the GPU box.
 
 Diagnostic variants (tracing rows) are separate libraries beside the product one -- they never
 replace it; load one with AUDIOGPT_AMD_LIB=<path>:
-    MAA_BUILD_ROCTX=1      libaudiogpt_mi355x_roctx.so      per-DDIM-step roctx ranges (csrc/ddim.cpp) for rocprofv3 --marker-trace
+    MAA_BUILD_ROCTX=1      libaudiogpt_mi355x_roctx.so      per-step roctx ranges of the sampling loops (run_steps, csrc/runtime.cpp) for rocprofv3 --marker-trace
     MAA_BUILD_NO_TUNING=1  libaudiogpt_mi355x_notuning.so   deployment build: the MAA_* test / A-B switches compiled out (runtime.cpp)
 """
 import os
@@ -25,7 +25,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-W
          "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form"]
 LINK = []
 VARIANT = ""
-if os.environ.get("MAA_BUILD_ROCTX") == "1":      # per-DDIM-step roctx ranges (csrc/ddim.cpp) for rocprofv3 --marker-trace
+if os.environ.get("MAA_BUILD_ROCTX") == "1":      # per-step roctx ranges of the sampling loops (run_steps, csrc/runtime.cpp)
     FLAGS = FLAGS + ["-DMAA_ROCTX"]
     LINK = ["-L/opt/rocm/lib", "-lroctx64"]
     VARIANT += "_roctx"

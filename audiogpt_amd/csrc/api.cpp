@@ -154,9 +154,7 @@ int maa_ctx_reload_tuning(maa_ctx* ctx) {
     return guarded([&] {
         bind(ctx);
         ctx->c.tune.load();
-        ctx->c.ddim_graph.clear();      // a kept step graph was captured under the old knobs
-        ctx->c.plms_graph.clear();
-        ctx->c.ddpm_graph.clear();
+        ctx->c.drop_step_graphs();      // captured under the old knobs
     });
 }
 int maa_ctx_synchronize(maa_ctx* ctx) {
@@ -186,11 +184,7 @@ int maa_ctx_set_concurrency(maa_ctx* ctx, int n) {
     return guarded([&] {
         bind(ctx);
         MAA_CHECK(n >= -1 && n != 0, "concurrency: -1 (guess from the live contexts) or the number of contexts kept in flight (>= 1)");
-        if (ctx->c.kept_full() != (n >= 3)) {
-            ctx->c.ddim_graph.clear();      // the kept step graphs were captured under the other arrangement's launches
-            ctx->c.plms_graph.clear();
-            ctx->c.ddpm_graph.clear();
-        }
+        if (ctx->c.kept_full() != (n >= 3)) ctx->c.drop_step_graphs();      // captured under the other arrangement's launches
         ctx->c.concurrency = n;
     });
 }
@@ -327,9 +321,8 @@ int maa_ddim_stochastic_encode(maa_ctx* ctx, const float* d_x0_or_moments, int f
                                const float* d_noise_post, const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab,
                                const float* d_noise, int B, int C, int H, int W, float* d_out) {
     return guarded([&] {
-        MAA_CHECK(d_x0_or_moments && d_t && h_sqrt_a && h_sqrt_1ma && d_noise && d_out, "bad stochastic_encode arguments: null pointer");
-        MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "bad stochastic_encode arguments: empty shape or table");
-        MAA_CHECK(!from_moments || d_noise_post, "bad stochastic_encode arguments: the moments need their posterior noise");
+        maa::check_stochastic_encode_args(d_x0_or_moments, from_moments != 0, d_noise_post, d_t, h_sqrt_a, h_sqrt_1ma, n_tab, d_noise, B, C,
+                                          H, W, d_out);
         bind(ctx);
         maa::ddim_stochastic_encode(ctx->c, d_x0_or_moments, from_moments != 0, scale_factor, d_noise_post, d_t, h_sqrt_a, h_sqrt_1ma,
                                     n_tab, d_noise, B, C, H, W, d_out);
@@ -337,21 +330,14 @@ int maa_ddim_stochastic_encode(maa_ctx* ctx, const float* d_x0_or_moments, int f
 }
 int maa_ddim_decode(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, int t_start, float* d_x) {
     return guarded([&] {
-        MAA_CHECK(u && args && d_x && args->h_timesteps && args->h_alphas && args->h_alphas_prev, "bad ddim_decode arguments");
-        MAA_CHECK(args->S > 0 && args->B > 0, "bad ddim_decode arguments: empty problem");
-        MAA_CHECK(t_start >= 0 && t_start <= args->S, "bad ddim_decode arguments: t_start must lie in [0, S]");
-        MAA_CHECK(!args->d_mask && !args->d_x0 && !args->d_noise_q, "bad ddim_decode arguments: decode takes no mask / x0");
-        MAA_CHECK(args->n_log == 0 && !args->d_log_x && !args->d_log_x0, "bad ddim_decode arguments: decode logs no intermediates");
+        maa::check_ddim_decode_args(u, args, t_start, d_x);
         bind(ctx);
         maa::ddim_decode(ctx->c, *u->m, *args, t_start, d_x);
     });
 }
 int maa_ldm_plms_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, float* d_x) {
     return guarded([&] {
-        MAA_CHECK(u && args && d_x && args->h_timesteps && args->h_alphas && args->h_alphas_prev, "bad ldm_plms_sample arguments");
-        MAA_CHECK(args->S > 0 && args->B > 0, "bad ldm_plms_sample arguments: empty problem");
-        MAA_CHECK(!args->h_sigmas && !args->d_noise_p,
-                  "bad ldm_plms_sample arguments: ddim_eta must be 0 for PLMS (h_sigmas and d_noise_p must be NULL)");
+        maa::check_ldm_plms_args(u, args, d_x);
         bind(ctx);
         maa::ldm_plms_sample(ctx->c, *u->m, *args, d_x);
     });
@@ -359,22 +345,7 @@ int maa_ldm_plms_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, fl
 // (as above: every argument error is reported before the context is bound and anything is launched)
 int maa_ddpm_sample(maa_ctx* ctx, maa_unet* u, const maa_ddpm_args* args, float* d_x) {
     return guarded([&] {
-        MAA_CHECK(u && args && d_x, "bad ddpm_sample arguments: null pointer");
-        const maa_ddim_args& l = args->loop;
-        MAA_CHECK(l.S > 0 && l.B > 0 && l.C > 0 && l.H > 0 && l.W > 0, "bad ddpm_sample arguments: empty problem");
-        MAA_CHECK(args->n >= 1 && args->n <= l.S, "bad ddpm_sample arguments: the number of steps must lie in 1 .. num_timesteps");
-        MAA_CHECK(args->start >= args->n - 1 && args->start < l.S, "bad ddpm_sample arguments: steps outside the schedule");
-        MAA_CHECK(args->h_sqrt_recip_ac && args->h_sqrt_recipm1_ac && args->h_coef1 && args->h_coef2 && args->h_logvar,
-                  "bad ddpm_sample arguments: the posterior tables are missing");
-        MAA_CHECK(l.d_noise_p, "bad ddpm_sample arguments: the steps' noise is missing");
-        MAA_CHECK(!l.d_mask || (l.d_x0 && l.d_noise_q && args->h_sqrt_ac && args->h_sqrt_1mac),
-                  "bad ddpm_sample arguments: mask needs x0, its noise and the q_sample tables");
-        if (l.n_log > 0 || l.d_log_x || l.d_log_x0) {
-            MAA_CHECK(l.d_log_x && l.d_log_x0 && l.log_every_t > 0, "bad ddpm_sample arguments: intermediates need their buffers and log_every_t");
-            int n_logged = 0;
-            for (int t = args->start; t > args->start - args->n; --t) n_logged += (t % l.log_every_t == 0 || t == args->start);
-            MAA_CHECK(n_logged == l.n_log, "bad ddpm_sample arguments: n_log does not match log_every_t");
-        }
+        maa::check_ddpm_sample_args(u, args, d_x);
         bind(ctx);
         maa::ddpm_sample(ctx->c, *u->m, *args, d_x);
     });
@@ -384,12 +355,8 @@ int maa_ddpm_update(maa_ctx* ctx, const float* d_x, const float* d_eps, const in
                     const float* d_noise, float temperature, int clip_denoised, int B, int C, int H, int W, float* d_x_prev,
                     float* d_x_recon) {
     return guarded([&] {
-        MAA_CHECK(d_x && d_eps && d_t && d_noise && d_x_prev && d_x_recon, "bad ddpm_update arguments: null pointer");
-        MAA_CHECK(h_sqrt_recip_ac && h_sqrt_recipm1_ac && h_coef1 && h_coef2 && h_logvar, "bad ddpm_update arguments: the posterior tables are missing");
-        MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "bad ddpm_update arguments: empty shape or table");
-        for (const float* out : {(const float*)d_x_prev, (const float*)d_x_recon})
-            MAA_CHECK(out != d_x && out != d_eps && out != d_noise, "bad ddpm_update arguments: the outputs may not alias the inputs");
-        MAA_CHECK(d_x_prev != d_x_recon, "bad ddpm_update arguments: the outputs may not alias each other");
+        maa::check_ddpm_update_args(d_x, d_eps, d_t, h_sqrt_recip_ac, h_sqrt_recipm1_ac, h_coef1, h_coef2, h_logvar, n_tab, d_noise, B, C, H,
+                                    W, d_x_prev, d_x_recon);
         bind(ctx);
         maa::ddpm_update(ctx->c, d_x, d_eps, d_t, h_sqrt_recip_ac, h_sqrt_recipm1_ac, h_coef1, h_coef2, h_logvar, n_tab, d_noise,
                          temperature, clip_denoised != 0, B, C, H, W, d_x_prev, d_x_recon);
@@ -936,9 +903,7 @@ int maa_op_fold(maa_ctx* ctx, const float* d_crops, const float* h_weight, int B
         const int L = maa::split_crops(H, W, kh, kw, sh, sw);
         const size_t kk = (size_t)kh * kw, n_w = (kk * L + 63) / 64 * 64;
         float* slab = static_cast<float*>(c.split_scratch.get((n_w + (size_t)H * W) * sizeof(float), c.stream));
-        std::vector<float> h_wT(kk * L);      // the kernels read the weighting as [L][kh * kw]
-        for (size_t p = 0; p < kk; ++p)
-            for (int l = 0; l < L; ++l) h_wT[(size_t)l * kk + p] = h_weight[p * L + l];
+        const std::vector<float> h_wT = maa::split_weight_transposed(h_weight, kk, L);
         MAA_HIP(hipMemcpyAsync(slab, h_wT.data(), h_wT.size() * sizeof(float), hipMemcpyHostToDevice, c.stream));
         maa::launch_split_norm(c, slab, H, W, kh, kw, sh, sw, slab + n_w);
         maa::launch_split_fold(c, d_crops, slab, slab + n_w, B, C, H, W, kh, kw, sh, sw, d_out);

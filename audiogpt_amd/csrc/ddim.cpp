@@ -17,17 +17,6 @@
 #include <cstdio>
 #include <cstring>
 
-// Per-DDIM-step range markers for rocprofv3 --marker-trace (tracing): compiled in by
-// `MAA_BUILD_ROCTX=1 python -m audiogpt_amd.build --force` (-DMAA_ROCTX, links libroctx64); the default build has none.
-#ifdef MAA_ROCTX
-#include <roctracer/roctx.h>
-#define MAA_RANGE_PUSH(name) roctxRangePushA(name)
-#define MAA_RANGE_POP() roctxRangePop()
-#else
-#define MAA_RANGE_PUSH(name) ((void)0)
-#define MAA_RANGE_POP() ((void)0)
-#endif
-
 namespace maa {
 
 namespace {
@@ -119,9 +108,7 @@ struct Loop {
         slab = static_cast<float*>(ctx.sampler_scratch.get(total * sizeof(float), ctx.stream));
         if (split) {
             wT = slab + o_wT, norm = slab + o_norm, zin = slab + o_zin, ecrop = slab + o_ecrop;
-            h_wT.resize(kk * crops);
-            for (size_t p = 0; p < kk; ++p)
-                for (int l = 0; l < crops; ++l) h_wT[(size_t)l * kk + p] = a.h_split_weight[p * crops + l];
+            h_wT = split_weight_transposed(a.h_split_weight, kk, crops);
             MAA_HIP(hipMemcpyAsync(wT, h_wT.data(), h_wT.size() * 4, hipMemcpyHostToDevice, ctx.stream));
             launch_split_norm(ctx, wT, a.H, a.W, a.split_kh, a.split_kw, a.split_sh, a.split_sw, norm);
         }
@@ -194,6 +181,13 @@ struct Loop {
             launch_split_fold(ctx, ecrop, wT, norm, nB, a.C, a.H, a.W, a.split_kh, a.split_kw, a.split_sh, a.split_sw, eps);
     }
 
+    // the loop's tail: the slab's latent back to the caller's, synchronised (the host tables go out of scope; the call returns a
+    // finished latent)
+    void finish(float* d_x) {
+        MAA_HIP(hipMemcpyAsync(d_x, xs, (size_t)a.B * per * 4, hipMemcpyDeviceToDevice, ctx.stream));
+        MAA_HIP(hipStreamSynchronize(ctx.stream));
+    }
+
     // Everything a captured step depends on besides the device-side state it reads: the model and its own buffers, the
     // shapes, the guidance scale, the slab (every slot's offset is a function of the numbers listed) and the workspace.
     // (The workspace base / capacity go in AFTER the first eager step, which may grow it.)
@@ -232,23 +226,6 @@ struct Loop {
     }
 };
 
-// Captures one call of `body` on the context's stream into sg (instantiated) under `key`.
-template <class F>
-void capture_step(Ctx& ctx, StepGraph& sg, F&& body, std::vector<unsigned long long> key) {
-    MAA_HIP(hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeRelaxed));
-    try {
-        body();
-    } catch (...) {
-        hipGraph_t dead = nullptr;
-        (void)hipStreamEndCapture(ctx.stream, &dead);
-        if (dead) (void)hipGraphDestroy(dead);
-        throw;
-    }
-    MAA_HIP(hipStreamEndCapture(ctx.stream, &sg.graph));
-    MAA_HIP(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
-    sg.key = std::move(key);
-}
-
 // The loop body of sample() and decode(): n_steps steps of the S-step schedule `a` describes, from DDIM index `start` down to
 // start - n_steps + 1.  sample() is (S - 1, S); decode(t_start) is (t_start - 1, t_start).  The start only sets the device step
 // index before the first step, so it is not part of the step graph's key: a decode with the same S, shapes, guidance and buffers
@@ -267,47 +244,72 @@ void ddim_run(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int start, int n_ste
                          lp.logging ? a.d_log_x : nullptr, lp.logging ? a.d_log_x0 : nullptr, lp.d_step);
     };
 
-    StepGraph& sg = ctx.ddim_graph;
-    int first = 0;
-    if (a.use_graph && sg.exec && sg.key == lp.key(noise_p)) {
-        // same step as the last call's: replay from the first step on (the workspace the graph was captured over is still
-        // this context's, at the same address and size)
-    } else if (a.use_graph) {
-        sg.clear();
-        step_body();                      // first step eager: sizes the workspace before any capture
-        first = 1;
-        if (n_steps > 1) capture_step(ctx, sg, step_body, lp.key(noise_p));
-    }
-    for (int i = first; i < n_steps; ++i) {
-#ifdef MAA_ROCTX
-        char range[48];
-        std::snprintf(range, sizeof(range), "ddim_step %d/%d t=%d", i + 1, n_steps, (int)a.h_timesteps[start - i]);
-#endif
-        MAA_RANGE_PUSH(range);
-        if (a.use_graph)
-            MAA_HIP(hipGraphLaunch(sg.exec, ctx.stream));
-        else
-            step_body();
-        MAA_RANGE_POP();
-    }
-    MAA_HIP(hipMemcpyAsync(d_x, lp.xs, (size_t)a.B * lp.per * 4, hipMemcpyDeviceToDevice, ctx.stream));
-    MAA_HIP(hipStreamSynchronize(ctx.stream));   // the host tables go out of scope; the call returns a finished latent
+    run_steps(ctx, ctx.ddim_graph, n_steps, a.use_graph != 0, false, [&] { return lp.key(noise_p); }, step_body,
+              [&](int i, char* buf, size_t len) { std::snprintf(buf, len, "ddim_step %d/%d t=%d", i + 1, n_steps, (int)a.h_timesteps[start - i]); });
+    lp.finish(d_x);
 }
 
 }  // namespace
 
 void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) { ddim_run(ctx, unet, a, a.S - 1, a.S, a.d_noise_p, d_x); }
 
+// ---- The argument checks of the entry points below that touch no device: api.cpp runs them before it binds the context, so a
+// malformed call fails the same way with or without a device; the functions they guard do not repeat them.
+void check_ddim_decode_args(const void* unet, const maa_ddim_args* a, int t_start, const float* d_x) {
+    MAA_CHECK(unet && a && d_x && a->h_timesteps && a->h_alphas && a->h_alphas_prev, "bad ddim_decode arguments");
+    MAA_CHECK(a->S > 0 && a->B > 0, "bad ddim_decode arguments: empty problem");
+    MAA_CHECK(t_start >= 0 && t_start <= a->S, "bad ddim_decode arguments: t_start must lie in [0, S]");
+    MAA_CHECK(!a->d_mask && !a->d_x0 && !a->d_noise_q && !a->h_sqrt_ac && !a->h_sqrt_1mac,
+              "bad ddim_decode arguments: decode takes no mask / x0 (ddim.py:243-245)");
+    MAA_CHECK(a->n_log == 0 && !a->d_log_x && !a->d_log_x0, "bad ddim_decode arguments: decode logs no intermediates");
+}
+void check_ldm_plms_args(const void* unet, const maa_ddim_args* a, const float* d_x) {
+    MAA_CHECK(unet && a && d_x && a->h_timesteps && a->h_alphas && a->h_alphas_prev, "bad ldm_plms_sample arguments");
+    MAA_CHECK(a->S > 0 && a->B > 0, "bad ldm_plms_sample arguments: empty problem");
+    MAA_CHECK(!a->h_sigmas && !a->d_noise_p,
+              "bad ldm_plms_sample arguments: ddim_eta must be 0 for PLMS (h_sigmas and d_noise_p must be NULL)");
+}
+void check_ddpm_sample_args(const void* unet, const maa_ddpm_args* a, const float* d_x) {
+    MAA_CHECK(unet && a && d_x, "bad ddpm_sample arguments: null pointer");
+    const maa_ddim_args& l = a->loop;
+    MAA_CHECK(l.S > 0 && l.B > 0 && l.C > 0 && l.H > 0 && l.W > 0, "bad ddpm_sample arguments: empty problem");
+    MAA_CHECK(a->n >= 1 && a->n <= l.S, "bad ddpm_sample arguments: the number of steps must lie in 1 .. num_timesteps");
+    MAA_CHECK(a->start >= a->n - 1 && a->start < l.S, "bad ddpm_sample arguments: steps outside the schedule");
+    MAA_CHECK(a->h_sqrt_recip_ac && a->h_sqrt_recipm1_ac && a->h_coef1 && a->h_coef2 && a->h_logvar,
+              "bad ddpm_sample arguments: the posterior tables are missing");
+    MAA_CHECK(l.d_noise_p, "bad ddpm_sample arguments: the steps' noise is missing");
+    MAA_CHECK(!l.d_mask || (l.d_x0 && l.d_noise_q && a->h_sqrt_ac && a->h_sqrt_1mac),
+              "bad ddpm_sample arguments: mask needs x0, its noise and the q_sample tables");
+    if (l.n_log > 0 || l.d_log_x || l.d_log_x0) {
+        MAA_CHECK(l.d_log_x && l.d_log_x0 && l.log_every_t > 0, "bad ddpm_sample arguments: intermediates need their buffers and log_every_t");
+        int n_logged = 0;      // ddpm_audio.py:877 with timesteps - 1 = the first step run
+        for (int t = a->start; t > a->start - a->n; --t) n_logged += (t % l.log_every_t == 0 || t == a->start);
+        MAA_CHECK(n_logged == l.n_log, "bad ddpm_sample arguments: n_log does not match log_every_t");
+    }
+}
+void check_ddpm_update_args(const float* d_x, const float* d_eps, const int32_t* d_t, const float* h_sqrt_recip_ac,
+                            const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_logvar, int n_tab,
+                            const float* d_noise, int B, int C, int H, int W, const float* d_x_prev, const float* d_x_recon) {
+    MAA_CHECK(d_x && d_eps && d_t && d_noise && d_x_prev && d_x_recon, "bad ddpm_update arguments: null pointer");
+    MAA_CHECK(h_sqrt_recip_ac && h_sqrt_recipm1_ac && h_coef1 && h_coef2 && h_logvar, "bad ddpm_update arguments: the posterior tables are missing");
+    MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "bad ddpm_update arguments: empty shape or table");
+    for (const float* out : {d_x_prev, d_x_recon})
+        MAA_CHECK(out != d_x && out != d_eps && out != d_noise, "bad ddpm_update arguments: the outputs may not alias the inputs");
+    MAA_CHECK(d_x_prev != d_x_recon, "bad ddpm_update arguments: the outputs may not alias each other");
+}
+void check_stochastic_encode_args(const float* d_x0_or_moments, bool from_moments, const float* d_noise_post, const int32_t* d_t,
+                                  const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab, const float* d_noise, int B, int C, int H,
+                                  int W, const float* d_out) {
+    MAA_CHECK(d_x0_or_moments && d_t && h_sqrt_a && h_sqrt_1ma && d_noise && d_out, "bad stochastic_encode arguments: null pointer");
+    MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "bad stochastic_encode arguments: empty shape or table");
+    MAA_CHECK(!from_moments || d_noise_post, "bad stochastic_encode arguments: the moments need their posterior noise");
+}
+
 // ddim.py:243-261: decode runs p_sample_ddim over timesteps[:t_start] flipped, i.e. DDIM indices t_start - 1 .. 0 with the tables
 // of the whole schedule -- the tail of sample()'s loop.  Its caller's noise holds t_start draws (first step first); the step kernel
 // reads draw S - 1 - idx of its pointer, so the pointer handed over starts S - t_start draws before the caller's buffer (only
 // draws S - t_start .. S - 1 of it, the caller's 0 .. t_start - 1, are ever read).
 void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, float* d_x) {
-    MAA_CHECK(a.S > 0 && a.B > 0, "ddim_decode: empty problem");
-    MAA_CHECK(t_start >= 0 && t_start <= a.S, "ddim_decode: t_start must lie in [0, S]");
-    MAA_CHECK(!a.d_mask && !a.d_x0 && !a.d_noise_q && !a.h_sqrt_ac && !a.h_sqrt_1mac,
-              "ddim_decode: decode has no mask / x0 (ddim.py:243-245)");
-    MAA_CHECK(a.n_log == 0 && !a.d_log_x && !a.d_log_x0, "ddim_decode: decode logs no intermediates");
     if (t_start == 0) return;                          // the reference's loop is empty: x_latent comes back unchanged
     const float* noise_p = nullptr;
     if (a.h_sigmas && a.d_noise_p) {
@@ -327,8 +329,6 @@ void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, floa
 // replayed: its launches are the same for every step (the ring slot and the order follow from the device index).  The graph is
 // kept across calls under the DDIM loop's key plus the ring's address, apart from the DDIM graph.
 void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
-    MAA_CHECK(a.S > 0 && a.B > 0, "plms: empty problem");
-    MAA_CHECK(!a.h_sigmas && !a.d_noise_p, "plms: ddim_eta must be 0 for PLMS (no sigmas, no step noise)");
     Loop lp(ctx, unet, a, a.S - 1, d_x);
     const long long n = (long long)a.B * lp.per;
     float* ring = static_cast<float*>(ctx.plms_ring.get((size_t)3 * n * sizeof(float), ctx.stream));
@@ -350,33 +350,19 @@ void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
         launch_ldm_plms_step(ctx, lp.xin, lp.per, lp.per_in, lp.eps, eps_c, a.scale, lp.cur_coef, n, lp.xs, ring, a.S, log_x, log_x0,
                              lp.d_step);
     };
+    auto key = [&]() {
+        std::vector<unsigned long long> k = lp.key(nullptr);
+        k.push_back((unsigned long long)reinterpret_cast<uintptr_t>(ring));
+        return k;
+    };
 
     MAA_RANGE_PUSH("plms_step 1 (Euler pair)");
     euler_step();
     MAA_RANGE_POP();
-    StepGraph& sg = ctx.plms_graph;
-    if (a.use_graph && a.S > 1) {
-        std::vector<unsigned long long> key = lp.key(nullptr);      // (after step 0: the workspace is sized)
-        key.push_back((unsigned long long)reinterpret_cast<uintptr_t>(ring));
-        if (!(sg.exec && sg.key == key)) {
-            sg.clear();
-            capture_step(ctx, sg, ab_step, std::move(key));
-        }
-    }
-    for (int i = 1; i < a.S; ++i) {
-#ifdef MAA_ROCTX
-        char range[48];
-        std::snprintf(range, sizeof(range), "plms_step %d/%d t=%d", i + 1, a.S, (int)a.h_timesteps[a.S - 1 - i]);
-#endif
-        MAA_RANGE_PUSH(range);
-        if (a.use_graph)
-            MAA_HIP(hipGraphLaunch(sg.exec, ctx.stream));
-        else
-            ab_step();
-        MAA_RANGE_POP();
-    }
-    MAA_HIP(hipMemcpyAsync(d_x, lp.xs, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx.stream));
-    MAA_HIP(hipStreamSynchronize(ctx.stream));
+    // (the Euler pair has sized the workspace; the runner's step i is the loop's step i + 1)
+    run_steps(ctx, ctx.plms_graph, a.S - 1, a.use_graph != 0, true, key, ab_step,
+              [&](int i, char* buf, size_t len) { std::snprintf(buf, len, "plms_step %d/%d t=%d", i + 2, a.S, (int)a.h_timesteps[a.S - 2 - i]); });
+    lp.finish(d_x);
 }
 
 // LatentDiffusion_audio's ancestral chain (ddpm_audio.py:717-884: p_mean_variance, p_sample, p_sample_loop, progressive_denoising)
@@ -389,21 +375,14 @@ void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x) {
 void ddpm_sample(Ctx& ctx, UNet& unet, const maa_ddpm_args& a, float* d_x) {
     const maa_ddim_args& u = a.loop;
     const int T = u.S;
-    MAA_CHECK(T > 0 && u.B > 0 && u.C > 0 && u.H > 0 && u.W > 0, "ddpm: empty problem");
-    MAA_CHECK(a.n >= 1 && a.n <= T, "ddpm: the number of steps must lie in 1 .. num_timesteps");
-    MAA_CHECK(a.start >= a.n - 1 && a.start < T, "ddpm: steps outside the schedule");
-    MAA_CHECK(a.h_sqrt_recip_ac && a.h_sqrt_recipm1_ac && a.h_coef1 && a.h_coef2 && a.h_logvar, "ddpm: the posterior tables are missing");
-    MAA_CHECK(u.d_noise_p, "ddpm: the steps' noise is missing");
     const bool masked = u.d_mask != nullptr;
-    MAA_CHECK(!masked || (u.d_x0 && u.d_noise_q && a.h_sqrt_ac && a.h_sqrt_1mac), "ddpm: mask needs x0, its noise and the q_sample tables");
     const bool logging = u.n_log > 0;
-    MAA_CHECK(!logging || (u.d_log_x && u.d_log_x0 && u.log_every_t > 0), "ddpm: intermediates need their buffers and log_every_t");
 
-    std::vector<float> h_tab((size_t)T * DDPM_TAB_W, 0.f);
+    // nonzero_mask * (0.5 * model_log_variance).exp(), fp32 as torch's
+    std::vector<float> h_tab = posterior_rows(a.h_sqrt_recip_ac, a.h_sqrt_recipm1_ac, a.h_coef1, a.h_coef2, T,
+                                              [&](int t) { return std::exp(0.5f * a.h_logvar[t]); }, DDPM_TAB_W);
     for (int t = 0; t < T; ++t) {
         float* r = &h_tab[(size_t)t * DDPM_TAB_W];
-        r[0] = a.h_sqrt_recip_ac[t], r[1] = a.h_sqrt_recipm1_ac[t], r[2] = a.h_coef1[t], r[3] = a.h_coef2[t];
-        r[4] = t == 0 ? 0.f : std::exp(0.5f * a.h_logvar[t]);      // nonzero_mask * (0.5 * model_log_variance).exp(), fp32 as torch's
         r[5] = a.h_temperature ? a.h_temperature[t] : 1.f;
         r[6] = masked ? a.h_sqrt_ac[t] : 0.f;
         r[7] = masked ? a.h_sqrt_1mac[t] : 0.f;
@@ -412,7 +391,6 @@ void ddpm_sample(Ctx& ctx, UNet& unet, const maa_ddpm_args& a, float* d_x) {
     int n_logged = 0;
     for (int t = a.start; t > a.start - a.n; --t)                   // ddpm_audio.py:877 with timesteps - 1 = the first step run
         if (logging && (t % u.log_every_t == 0 || t == a.start)) h_tab[(size_t)t * DDPM_TAB_W + 8] = (float)n_logged++;
-    MAA_CHECK(!logging || n_logged == u.n_log, "ddpm: n_log does not match log_every_t");
 
     // what Loop sees: the identity schedule, no blend before the step, no noise term, no logs of its own
     std::vector<int32_t> h_ts((size_t)T);
@@ -447,31 +425,9 @@ void ddpm_sample(Ctx& ctx, UNet& unet, const maa_ddpm_args& a, float* d_x) {
         k.push_back((unsigned long long)(a.clip_denoised != 0));
         return k;
     };
-
-    StepGraph& sg = ctx.ddpm_graph;
-    int first = 0;
-    if (u.use_graph && sg.exec && sg.key == key()) {
-        // the kept step: replay from the first step on
-    } else if (u.use_graph) {
-        sg.clear();
-        step_body();                      // first step eager: sizes the workspace before any capture
-        first = 1;
-        if (a.n > 1) capture_step(ctx, sg, step_body, key());
-    }
-    for (int i = first; i < a.n; ++i) {
-#ifdef MAA_ROCTX
-        char range[48];
-        std::snprintf(range, sizeof(range), "ddpm_step %d/%d t=%d", i + 1, a.n, a.start - i);
-#endif
-        MAA_RANGE_PUSH(range);
-        if (u.use_graph)
-            MAA_HIP(hipGraphLaunch(sg.exec, ctx.stream));
-        else
-            step_body();
-        MAA_RANGE_POP();
-    }
-    MAA_HIP(hipMemcpyAsync(d_x, lp.xs, (size_t)nel * 4, hipMemcpyDeviceToDevice, ctx.stream));
-    MAA_HIP(hipStreamSynchronize(ctx.stream));   // the host tables go out of scope; the call returns a finished latent
+    run_steps(ctx, ctx.ddpm_graph, a.n, u.use_graph != 0, false, key, step_body,
+              [&](int i, char* buf, size_t len) { std::snprintf(buf, len, "ddpm_step %d/%d t=%d", i + 1, a.n, a.start - i); });
+    lp.finish(d_x);
 }
 
 // p_sample's arithmetic for one step (ddpm_audio.py:748-777) with a timestep per sample: the five tables go up next to an error
@@ -479,23 +435,11 @@ void ddpm_sample(Ctx& ctx, UNet& unet, const maa_ddpm_args& a, float* d_x) {
 void ddpm_update(Ctx& ctx, const float* d_x, const float* d_eps, const int32_t* d_t, const float* h_sqrt_recip_ac,
                  const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_logvar, int n_tab,
                  const float* d_noise, float temperature, bool clip, int B, int C, int H, int W, float* d_x_prev, float* d_x_recon) {
-    MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "ddpm_update: empty problem");
-    char* slab = static_cast<char*>(ctx.ddpm_scratch.get(256 + 5 * (size_t)n_tab * sizeof(float), ctx.stream));
-    int* bad = reinterpret_cast<int*>(slab);
-    float* tab = reinterpret_cast<float*>(slab + 256);
-    std::vector<float> h_tab((size_t)5 * n_tab);
-    for (int t = 0; t < n_tab; ++t) {
-        float* r = &h_tab[(size_t)t * 5];
-        r[0] = h_sqrt_recip_ac[t], r[1] = h_sqrt_recipm1_ac[t], r[2] = h_coef1[t], r[3] = h_coef2[t];
-        r[4] = t == 0 ? 0.f : std::exp(0.5f * h_logvar[t]);
-    }
-    MAA_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx.stream));
-    MAA_HIP(hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
-    launch_ddpm_update(ctx, d_x, d_eps, d_t, tab, n_tab, d_noise, temperature, clip, B, (long long)C * H * W, d_x_prev, d_x_recon, bad);
-    int h_bad = 0;
-    MAA_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
-    MAA_HIP(hipStreamSynchronize(ctx.stream));
-    MAA_CHECK(h_bad == 0, "ddpm_update: some t[b] lies outside [0, n_tab)");
+    FlaggedTable ft(ctx, ctx.ddpm_scratch, posterior_rows(h_sqrt_recip_ac, h_sqrt_recipm1_ac, h_coef1, h_coef2, n_tab,
+                                                         [&](int t) { return std::exp(0.5f * h_logvar[t]); }));
+    launch_ddpm_update(ctx, d_x, d_eps, d_t, ft.tab, n_tab, d_noise, temperature, clip, B, (long long)C * H * W, d_x_prev, d_x_recon,
+                       ft.bad);
+    ft.check("ddpm_update: some t[b] lies outside [0, n_tab)");
 }
 
 // One evaluation of the model with split_input_params (ddpm_audio.py:572-654) outside a loop: what Loop::forward does per step,
@@ -517,9 +461,7 @@ void unet_forward_split(Ctx& ctx, UNet& unet, const float* d_x, const float* d_t
                  o_e = o_zin + up((size_t)rows * uc.in_channels * kk), o_t = o_e + up((size_t)rows * uc.out_channels * kk),
                  total = o_t + up((size_t)rows);
     float* slab = static_cast<float*>(ctx.split_scratch.get(total * sizeof(float), ctx.stream));
-    std::vector<float> h_wT(kk * L);
-    for (size_t p = 0; p < kk; ++p)
-        for (int l = 0; l < L; ++l) h_wT[(size_t)l * kk + p] = h_weight[p * L + l];
+    const std::vector<float> h_wT = split_weight_transposed(h_weight, kk, L);
     MAA_HIP(hipMemcpyAsync(slab + o_wT, h_wT.data(), h_wT.size() * 4, hipMemcpyHostToDevice, ctx.stream));
     MAA_HIP(hipStreamSynchronize(ctx.stream));      // (h_wT goes out of scope; everything after is asynchronous)
     launch_split_norm(ctx, slab + o_wT, H, W, kh, kw, sh, sw, slab + o_norm);
@@ -529,29 +471,18 @@ void unet_forward_split(Ctx& ctx, UNet& unet, const float* d_x, const float* d_t
     launch_split_fold(ctx, slab + o_e, slab + o_wT, slab + o_norm, B, uc.out_channels, H, W, kh, kw, sh, sw, d_out);
 }
 
-// ddim.py:227-241.  The two coefficient tables go up once per call next to an error flag in the context's own slab; the flag is
-// read back after the launch (the call synchronises the stream: the host tables and the caller's t are its inputs).
+// ddim.py:227-241.  The two coefficient tables, A (n_tab) then B (n_tab), go up once per call next to an error flag in the context's
+// own slab; the flag is read back after the launch (the call synchronises the stream: the host tables and the caller's t are its inputs).
 void ddim_stochastic_encode(Ctx& ctx, const float* d_x0_or_moments, bool from_moments, float scale_factor, const float* d_noise_post,
                             const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab, const float* d_noise, int B,
                             int C, int H, int W, float* d_out) {
-    MAA_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && n_tab > 0, "stochastic_encode: empty problem");
-    MAA_CHECK(!from_moments || d_noise_post, "stochastic_encode: the moments need their posterior noise");
-    const long long per = (long long)C * H * W;
-    // [flag | pad to 256 B | A (n_tab) | B (n_tab)]
-    char* slab = static_cast<char*>(ctx.encode_scratch.get(256 + 2 * (size_t)n_tab * sizeof(float), ctx.stream));
-    int* bad = reinterpret_cast<int*>(slab);
-    float* tab = reinterpret_cast<float*>(slab + 256);
-    std::vector<float> h_tab((size_t)2 * n_tab);
-    std::memcpy(h_tab.data(), h_sqrt_a, (size_t)n_tab * sizeof(float));
-    std::memcpy(h_tab.data() + n_tab, h_sqrt_1ma, (size_t)n_tab * sizeof(float));
-    MAA_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx.stream));
-    MAA_HIP(hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
+    std::vector<float> h_tab(h_sqrt_a, h_sqrt_a + n_tab);
+    h_tab.insert(h_tab.end(), h_sqrt_1ma, h_sqrt_1ma + n_tab);
+    FlaggedTable ft(ctx, ctx.encode_scratch, std::move(h_tab));
     launch_ddim_stochastic_encode(ctx, from_moments ? nullptr : d_x0_or_moments, from_moments ? d_x0_or_moments : nullptr,
-                                  scale_factor, from_moments ? d_noise_post : nullptr, d_t, tab, n_tab, d_noise, B, per, d_out, bad);
-    int h_bad = 0;
-    MAA_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
-    MAA_HIP(hipStreamSynchronize(ctx.stream));
-    MAA_CHECK(h_bad == 0, "stochastic_encode: some t[b] lies outside [0, n_tab)");
+                                  scale_factor, from_moments ? d_noise_post : nullptr, d_t, ft.tab, n_tab, d_noise, B,
+                                  (long long)C * H * W, d_out, ft.bad);
+    ft.check("stochastic_encode: some t[b] lies outside [0, n_tab)");
 }
 
 }  // namespace maa

@@ -207,45 +207,6 @@ void DiffNet::forward(Ctx& ctx, const float* spec, const float* t, const float* 
 
 namespace {
 
-// `count` more steps of a sampling loop whose first step has run eagerly (and sized the workspace): identical launches on identical
-// addresses, so one step is captured as a hipGraph and replayed; use_graph false runs the same body eagerly.  Ends synchronised.
-template <class F>
-void run_steps(Ctx& ctx, int count, bool use_graph, F&& step_body) {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    try {
-        for (int i = 0; i < count; ++i) {
-            if (!use_graph) {
-                ctx.ws.reset();
-                step_body();
-                continue;
-            }
-            if (!exec) {
-                ctx.ws.reset();
-                MAA_HIP(hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeRelaxed));
-                try {
-                    step_body();
-                } catch (...) {
-                    hipGraph_t dead = nullptr;
-                    (void)hipStreamEndCapture(ctx.stream, &dead);
-                    if (dead) (void)hipGraphDestroy(dead);
-                    throw;
-                }
-                MAA_HIP(hipStreamEndCapture(ctx.stream, &graph));
-                MAA_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            }
-            MAA_HIP(hipGraphLaunch(exec, ctx.stream));
-        }
-        MAA_HIP(hipStreamSynchronize(ctx.stream));
-    } catch (...) {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-    }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-}
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -285,13 +246,15 @@ void DiffNet::plms_sample(Ctx& ctx, const maa_plms_args& a, float* d_x) {
     launch_ds_plms(ctx, d_x, e, e2, hist, n, ac, a.interval, st, 2, nullptr);
     launch_ds_plms_advance(ctx, st, a.interval, t_slot, B);
 
-    // ---- remaining steps: identical launches on identical addresses -> one hipGraph, replayed
-    auto step_body = [&]() {
+    // ---- remaining steps: identical launches on identical addresses -> one hipGraph, captured for this call and replayed
+    StepGraph sg;
+    run_steps(ctx, sg, nsteps - 1, a.use_graph != 0, true, [] { return std::vector<unsigned long long>(); }, [&]() {
+        ctx.ws.reset();
         m.forward(ctx, d_x, t_slot, B, T, e);          // (workspace already sized by the eager evaluations above)
         launch_ds_plms(ctx, d_x, e, nullptr, hist, n, ac, a.interval, st, 0, nullptr);
         launch_ds_plms_advance(ctx, st, a.interval, t_slot, B);
-    };
-    run_steps(ctx, nsteps - 1, a.use_graph != 0, step_body);
+    });
+    MAA_HIP(hipStreamSynchronize(ctx.stream));      // (sg is dropped after it)
 }
 
 // The ancestral chain (shallow_diffusion_tts.py:269-271 / :320-321 over p_sample, :159-166).  Loop state in Impl::loop, which the
@@ -320,12 +283,8 @@ void DiffNet::ddpm_sample(Ctx& ctx, const maa_ds_ddpm_args& a, float* d_x) {
     float* slab = static_cast<float*>(m.loop.get(total * sizeof(float), ctx.stream));
     float *tab = slab + o_tab, *t_slot = slab + o_t, *e = slab + o_e;
     int* st = reinterpret_cast<int*>(slab + o_st);
-    std::vector<float> h_tab((size_t)5 * a.timesteps);
-    for (int t = 0; t < a.timesteps; ++t) {
-        float* r = &h_tab[(size_t)t * 5];
-        r[0] = a.h_sqrt_recip_ac[t], r[1] = a.h_sqrt_recipm1_ac[t], r[2] = a.h_coef1[t], r[3] = a.h_coef2[t];
-        r[4] = t == 0 ? 0.f : a.h_sigma[t];                                  // nonzero_mask (:165)
-    }
+    const std::vector<float> h_tab = posterior_rows(a.h_sqrt_recip_ac, a.h_sqrt_recipm1_ac, a.h_coef1, a.h_coef2, a.timesteps,
+                                                    [&](int t) { return a.h_sigma[t]; });      // (row 0: nonzero_mask, :165)
     const int h_st[3] = {a.start, 0, 0};
     MAA_HIP(hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
     MAA_HIP(hipMemcpyAsync(st, h_st, sizeof(h_st), hipMemcpyHostToDevice, ctx.stream));
@@ -339,11 +298,14 @@ void DiffNet::ddpm_sample(Ctx& ctx, const maa_ds_ddpm_args& a, float* d_x) {
     launch_ds_fill(ctx, t_slot, B, (float)a.start);
     run_sized(ctx, [&] { m.forward(ctx, d_x, t_slot, B, T, e); });
     update();
-    // ---- remaining steps: one captured step, replayed
-    run_steps(ctx, a.n - 1, a.use_graph != 0, [&]() {
+    // ---- remaining steps: one step, captured for this call, replayed
+    StepGraph sg;
+    run_steps(ctx, sg, a.n - 1, a.use_graph != 0, true, [] { return std::vector<unsigned long long>(); }, [&]() {
+        ctx.ws.reset();
         m.forward(ctx, d_x, t_slot, B, T, e);
         update();
     });
+    MAA_HIP(hipStreamSynchronize(ctx.stream));      // (sg is dropped after it)
 }
 
 void ds_ddpm_update(Ctx& ctx, const float* d_eps, const float* d_t, const float* d_noise, const float* h_sqrt_recip_ac,
@@ -352,22 +314,10 @@ void ds_ddpm_update(Ctx& ctx, const float* d_eps, const float* d_t, const float*
     MAA_CHECK(B > 0 && M > 0 && T > 0 && timesteps > 0, "ds_ddpm_update: empty shape or table");
     MAA_CHECK(M % 4 == 0, "ds_ddpm_update: M must be a multiple of 4 (16-byte accesses)");
     MAA_CHECK(aligned16(d_x) && aligned16(d_eps) && aligned16(d_noise), "ds_ddpm_update: d_x, d_eps and d_noise must be 16-byte aligned");
-    char* slab = static_cast<char*>(ctx.ddpm_scratch.get(256 + 5 * (size_t)timesteps * sizeof(float), ctx.stream));
-    int* bad = reinterpret_cast<int*>(slab);
-    float* tab = reinterpret_cast<float*>(slab + 256);
-    std::vector<float> h_tab((size_t)5 * timesteps);
-    for (int t = 0; t < timesteps; ++t) {
-        float* r = &h_tab[(size_t)t * 5];
-        r[0] = h_sqrt_recip_ac[t], r[1] = h_sqrt_recipm1_ac[t], r[2] = h_coef1[t], r[3] = h_coef2[t];
-        r[4] = t == 0 ? 0.f : h_sigma[t];
-    }
-    MAA_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx.stream));
-    MAA_HIP(hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
-    launch_ds_ddpm_update(ctx, d_x, d_eps, d_noise, B, (long long)M * T, d_t, tab, timesteps, clip ? 1 : 0, bad);
-    int h_bad = 0;
-    MAA_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
-    MAA_HIP(hipStreamSynchronize(ctx.stream));
-    MAA_CHECK(h_bad == 0, "ds_ddpm_update: some t[b] lies outside [0, timesteps)");
+    FlaggedTable ft(ctx, ctx.ddpm_scratch, posterior_rows(h_sqrt_recip_ac, h_sqrt_recipm1_ac, h_coef1, h_coef2, timesteps,
+                                                         [&](int t) { return h_sigma[t]; }));
+    launch_ds_ddpm_update(ctx, d_x, d_eps, d_noise, B, (long long)M * T, d_t, ft.tab, timesteps, clip ? 1 : 0, ft.bad);
+    ft.check("ds_ddpm_update: some t[b] lies outside [0, timesteps)");
 }
 
 }  // namespace maa

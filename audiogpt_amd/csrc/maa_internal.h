@@ -5,10 +5,15 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#ifdef MAA_ROCTX
+#include <roctracer/roctx.h>
+#endif
 
 namespace maa {
 
@@ -97,9 +102,12 @@ struct DevSlab {
     DevSlab& operator=(const DevSlab&) = delete;
 };
 
-// The captured DDIM step of the last sample() call on a context, kept across calls: a call whose step would launch the
-// same kernels on the same addresses with the same arguments (same model, shapes, guidance, buffers) replays it instead
-// of capturing and instantiating again.  `key` lists everything the step's launches depend on.
+// One captured step of a sampling loop: a hipGraph, its instantiation and `key`, which lists everything the step's launches
+// depend on (model, shapes, guidance, buffers, workspace).  The UNet loops (DDIM sample / decode, LDM-PLMS, the ancestral DDPM
+// chain) keep theirs in the context across calls -- Ctx::ddim_graph, plms_graph, ddpm_graph: a call whose step would launch the
+// same kernels on the same addresses with the same arguments replays it instead of capturing and instantiating again.  The two
+// DiffNet loops (DiffSinger's PLMS and ancestral chains) hand run_steps a local one with an empty key: captured per call,
+// dropped when the call returns.
 struct StepGraph {
     std::vector<unsigned long long> key;
     hipGraph_t graph = nullptr;
@@ -110,9 +118,43 @@ struct StepGraph {
     StepGraph(const StepGraph&) = delete;
     StepGraph& operator=(const StepGraph&) = delete;
 };
+struct Ctx;
+// Range markers for rocprofv3 --marker-trace (tracing): compiled in by
+// `MAA_BUILD_ROCTX=1 python -m audiogpt_amd.build --force` (-DMAA_ROCTX, links libroctx64); the default build has none.
+#ifdef MAA_ROCTX
+#define MAA_RANGE_PUSH(name) roctxRangePushA(name)
+#define MAA_RANGE_POP() roctxRangePop()
+#else
+#define MAA_RANGE_PUSH(name) ((void)0)
+#define MAA_RANGE_POP() ((void)0)
+#endif
+using StepLabel = std::function<void(int i, char* buf, size_t len)>;      // writes the range label of a runner's step i (from 0)
+// The host driver of every sampling loop: n more steps, each one call of `body` -- identical launches on identical addresses
+// whatever the step -- on the context's stream; the caller synchronises.
+//   use_graph false: body() n times.
+//   sg holds a step and sg.key == key(): n launches of it (no eager step, no capture).
+//   otherwise: sg is cleared; unless `sized` (the caller's own eager work has sized the workspace) body() runs once eagerly,
+//     which counts as a step; key() is taken after it (the workspace may have grown); if steps remain, one body() is captured
+//     (relaxed mode) into sg under that key and launched for each of them.
+// label (optional): called under -DMAA_ROCTX only, for the range around each step of the final loop.
+void run_steps(Ctx& ctx, StepGraph& sg, int n, bool use_graph, bool sized, const std::function<std::vector<unsigned long long>()>& key,
+               const std::function<void()>& body, const StepLabel& label = nullptr);
+// A one-shot entry's host table next to a device error flag, [flag | pad to 256 B | table] in `slab`: the constructor clears the
+// flag and uploads the table on the context's stream; check(), after the caller's launch, reads the flag back, synchronises and
+// throws `msg` if a kernel set it.  (Keeps the host table until then: the upload reads it.)
+struct FlaggedTable {
+    FlaggedTable(Ctx& ctx, DevSlab& slab, std::vector<float> h_tab);
+    void check(const char* msg);
+    int* bad;
+    float* tab;
+
+private:
+    Ctx& ctx_;
+    std::vector<float> h_tab_;
+};
 
 // Test / A-B switches: every one of them is parsed in Tuning::load (runtime.cpp) -- the only place the library reads the
-// environment -- when a context is created and again by maa_ctx_reload_tuning; a kept DDIM graph is dropped on reload.
+// environment -- when a context is created and again by maa_ctx_reload_tuning; the kept step graphs are dropped on reload.
 struct Tuning {
     std::string dma2;                       // MAA_DMA2 = "off" | "0,4,1,S[,kmin[,kmax]]": the split-K LDS-DMA engine's policy override
     std::string pp, pp1;                    // MAA_PP / MAA_PP1 = "off" | "bn,S": tile width / K slices of the ping-pong engine (3x3 form, 1x1 form)
@@ -157,6 +199,11 @@ struct Ctx {
     DevSlab plms_ring;        // the PLMS loop's ring of three e_t slabs (apart from sampler_scratch, which keeps DDIM's size)
     StepGraph ddpm_graph;     // the ancestral (DDPM) loop's captured step, kept apart from DDIM's and PLMS's
     DevSlab ddpm_tab;         // the ancestral loop's per-timestep table (its address is in ddpm_graph's key)
+    void drop_step_graphs() {   // every kept step graph: they were captured under other knobs / another arrangement's launches
+        ddim_graph.clear();
+        plms_graph.clear();
+        ddpm_graph.clear();
+    }
     DevSlab ddpm_scratch;     // maa_ddpm_update's table and error flag
     DevSlab split_scratch;    // maa_unet_forward_split's weighting, norm, crop rows and their timesteps (apart from the loops' slab)
     Profiler* prof = nullptr;
@@ -295,6 +342,7 @@ void launch_dup_half(const Ctx& ctx, const float* x, long long n, float* out);
 // [L][kh * kw]; norm [H, W] = its fold.  repeat_rows: src [rows][len] -> dst [rows * rep][len], every row rep times in a row.
 void split_check(int H, int W, int kh, int kw, int sh, int sw);
 int split_crops(int H, int W, int kh, int kw, int sh, int sw);
+std::vector<float> split_weight_transposed(const float* h_weight, size_t kk, int L);      // [kh * kw][L] (get_weighting's table) -> wT (runtime.cpp)
 void launch_split_unfold(const Ctx& ctx, const float* x, int nB, int C, int H, int W, int kh, int kw, int sh, int sw, float* out);
 void launch_split_norm(const Ctx& ctx, const float* wT, int H, int W, int kh, int kw, int sh, int sw, float* norm);
 void launch_split_fold(const Ctx& ctx, const float* e, const float* wT, const float* norm, int nB, int C, int H, int W, int kh,

@@ -159,15 +159,38 @@ private:
     Impl* impl_;
 };
 
+// ---- shared by the samplers' host code (ddim.cpp, diffnet.cpp)
+// n rows of `width` >= 5 floats, the rest zero: {sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, fifth(t)} of the posterior at
+// timestep t, the fifth column -- the noise's scale, exp(0.5 logvar[t]) or sigma[t] -- 0 in row 0 (the reference's nonzero_mask)
+template <class F>
+std::vector<float> posterior_rows(const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* coef1, const float* coef2, int n,
+                                  F&& fifth, int width = 5) {
+    std::vector<float> tab((size_t)n * width, 0.f);
+    for (int t = 0; t < n; ++t) {
+        float* r = &tab[(size_t)t * width];
+        r[0] = sqrt_recip_ac[t], r[1] = sqrt_recipm1_ac[t], r[2] = coef1[t], r[3] = coef2[t];
+        r[4] = t == 0 ? 0.f : fifth(t);
+    }
+    return tab;
+}
 void ddim_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x);
+// check_*_args, each declared above the entry it guards: every argument check of that entry that touches no device (api.cpp
+// calls it before it binds the context; a malformed call fails the same way with or without a device).  The entries themselves
+// do not repeat them.  `unet` is the caller's handle, tested against null only.
 // DDIMSampler.decode (ddim.py:243-261): DDIM indices t_start - 1 .. 0 of the S-step schedule `a` describes; d_noise_p holds t_start
 // draws in loop order
+void check_ddim_decode_args(const void* unet, const maa_ddim_args* a, int t_start, const float* d_x);
 void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, float* d_x);
 // PLMSSampler.plms_sampling (plms.py:115-236) over the S-step schedule `a` describes (eta 0: no sigmas, no step noise)
+void check_ldm_plms_args(const void* unet, const maa_ddim_args* a, const float* d_x);
 void ldm_plms_sample(Ctx& ctx, UNet& unet, const maa_ddim_args& a, float* d_x);
 // LatentDiffusion_audio's ancestral chain (ddpm_audio.py:717-884): DDPM steps a.start .. a.start - a.n + 1 on the device
+void check_ddpm_sample_args(const void* unet, const maa_ddpm_args* a, const float* d_x);
 void ddpm_sample(Ctx& ctx, UNet& unet, const maa_ddpm_args& a, float* d_x);
 // one such step with a timestep per sample and host tables of n_tab rows (p_sample); checks every t[b] against n_tab
+void check_ddpm_update_args(const float* d_x, const float* d_eps, const int32_t* d_t, const float* h_sqrt_recip_ac,
+                            const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_logvar, int n_tab,
+                            const float* d_noise, int B, int C, int H, int W, const float* d_x_prev, const float* d_x_recon);
 void ddpm_update(Ctx& ctx, const float* d_x, const float* d_eps, const int32_t* d_t, const float* h_sqrt_recip_ac,
                  const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_logvar, int n_tab,
                  const float* d_noise, float temperature, bool clip, int B, int C, int H, int W, float* d_x_prev, float* d_x_recon);
@@ -176,11 +199,14 @@ void ddpm_update(Ctx& ctx, const float* d_x, const float* d_eps, const int32_t* 
 void ds_ddpm_update(Ctx& ctx, const float* d_eps, const float* d_t, const float* d_noise, const float* h_sqrt_recip_ac,
                     const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_sigma, int timesteps,
                     int B, int M, int T, bool clip, float* d_x);
-// DDIMSampler.stochastic_encode (ddim.py:227-241) with host tables of n_tab rows; checks every t[b] against n_tab
 // One model evaluation with split_input_params outside a loop (ddpm_audio.py:572-654): unfold, the UNet over B * L crop rows,
 // fold.  h_weight [kh * kw][L] on the host (get_weighting's table); d_context [B, context_len(), context_dim] or null
 void unet_forward_split(Ctx& ctx, UNet& unet, const float* d_x, const float* d_t, const float* d_context, int B, int H, int W, int kh,
                         int kw, int sh, int sw, const float* h_weight, float* d_out);
+// DDIMSampler.stochastic_encode (ddim.py:227-241) with host tables of n_tab rows; checks every t[b] against n_tab
+void check_stochastic_encode_args(const float* d_x0_or_moments, bool from_moments, const float* d_noise_post, const int32_t* d_t,
+                                  const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab, const float* d_noise, int B, int C, int H,
+                                  int W, const float* d_out);
 void ddim_stochastic_encode(Ctx& ctx, const float* d_x0_or_moments, bool from_moments, float scale_factor, const float* d_noise_post,
                             const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab, const float* d_noise, int B,
                             int C, int H, int W, float* d_out);

@@ -200,6 +200,71 @@ void StepGraph::clear() {
     key.clear();
 }
 
+void run_steps(Ctx& ctx, StepGraph& sg, int n, bool use_graph, bool sized, const std::function<std::vector<unsigned long long>()>& key,
+               const std::function<void()>& body, const StepLabel& label) {
+    if (n <= 0) return;                   // nothing to run: a kept graph stays
+    int i = 0;
+    if (use_graph && !(sg.exec && sg.key == key())) {
+        sg.clear();
+        if (!sized) {
+            body();                       // first step eager: sizes the workspace before any capture
+            i = 1;
+        }
+        if (i < n) {
+            std::vector<unsigned long long> k = key();      // (after the eager step: the workspace may have grown)
+            MAA_HIP(hipStreamBeginCapture(ctx.stream, hipStreamCaptureModeRelaxed));
+            try {
+                body();
+            } catch (...) {
+                hipGraph_t dead = nullptr;
+                (void)hipStreamEndCapture(ctx.stream, &dead);
+                if (dead) (void)hipGraphDestroy(dead);
+                throw;
+            }
+            MAA_HIP(hipStreamEndCapture(ctx.stream, &sg.graph));
+            MAA_HIP(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
+            sg.key = std::move(k);
+        }
+    }
+    // (a kept step whose key matched is replayed from the first step on: the workspace it was captured over is still this
+    // context's, at the same address and size)
+    for (; i < n; ++i) {
+#ifdef MAA_ROCTX
+        char range[48] = "";
+        if (label) label(i, range, sizeof(range));
+#endif
+        if (label) MAA_RANGE_PUSH(range);
+        if (use_graph)
+            MAA_HIP(hipGraphLaunch(sg.exec, ctx.stream));
+        else
+            body();
+        if (label) MAA_RANGE_POP();
+    }
+}
+
+FlaggedTable::FlaggedTable(Ctx& ctx, DevSlab& slab, std::vector<float> h_tab) : ctx_(ctx), h_tab_(std::move(h_tab)) {
+    char* p = static_cast<char*>(slab.get(256 + h_tab_.size() * sizeof(float), ctx.stream));
+    bad = reinterpret_cast<int*>(p);
+    tab = reinterpret_cast<float*>(p + 256);
+    MAA_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx.stream));
+    MAA_HIP(hipMemcpyAsync(tab, h_tab_.data(), h_tab_.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
+}
+void FlaggedTable::check(const char* msg) {
+    int h_bad = 0;
+    MAA_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx_.stream));
+    MAA_HIP(hipStreamSynchronize(ctx_.stream));
+    MAA_CHECK(h_bad == 0, msg);
+}
+
+
+std::vector<float> split_weight_transposed(const float* h_weight, size_t kk, int L) {
+    std::vector<float> h_wT(kk * L);
+    for (size_t p = 0; p < kk; ++p)
+        for (int l = 0; l < L; ++l) h_wT[(size_t)l * kk + p] = h_weight[p * L + l];
+    return h_wT;
+}
+
+
 // ------------------------------------------------------------------------------------------ per-device launch state
 namespace {
 std::mutex g_launch_mu;
