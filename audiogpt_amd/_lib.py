@@ -116,6 +116,18 @@ class maa_ds_ddpm_args(C.Structure):
                 ("h_coef1", C.POINTER(C.c_float)), ("h_coef2", C.POINTER(C.c_float)), ("h_sigma", C.POINTER(C.c_float))]
 
 
+class maa_igemm_ex_args(C.Structure):
+    _fields_ = [("d_x1", C.c_void_p), ("ld1", C.c_int), ("C1", C.c_int), ("d_x2", C.c_void_p), ("ld2", C.c_int), ("C2", C.c_int),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int),
+                ("h_w", C.POINTER(C.c_float)), ("h_bias", C.POINTER(C.c_float)), ("Cout", C.c_int), ("KH", C.c_int), ("KW", C.c_int),
+                ("stride", C.c_int), ("pad_w", C.c_int), ("pad_h", C.c_int), ("dil", C.c_int), ("up", C.c_int),
+                ("a_leaky", C.c_float), ("presplit", C.c_int),
+                ("alpha", C.c_float), ("d_rowadd", C.c_void_p), ("ld_rowadd", C.c_int), ("d_res", C.c_void_p), ("ldr", C.c_int),
+                ("act", C.c_int), ("act_slope", C.c_float), ("out_scale", C.c_float),
+                ("accumulate", C.c_int), ("geglu", C.c_int), ("c_split", C.c_int),
+                ("d_c", C.c_void_p), ("ldc", C.c_int), ("d_c2", C.c_void_p), ("ldc2", C.c_int), ("c2_slope", C.c_float)]
+
+
 EXPORTS = [
     "maa_last_error", "maa_version", "maa_ctx_create", "maa_ctx_destroy", "maa_ctx_synchronize",
     "maa_ctx_set_stream", "maa_ctx_set_precision", "maa_ctx_set_cfg_split", "maa_ctx_set_concurrency", "maa_ctx_reload_tuning", "maa_ctx_workspace_bytes", "maa_prof_begin", "maa_prof_end", "maa_unet_create", "maa_unet_destroy",
@@ -131,7 +143,7 @@ EXPORTS = [
     "maa_spectral_create", "maa_spectral_destroy", "maa_spectral_forward", "maa_resampler_create", "maa_resampler_destroy",
     "maa_resampler_forward", "maa_op_linear", "maa_op_conv", "maa_op_groupnorm", "maa_op_layernorm",
     "maa_op_attention", "maa_op_attention_ex", "maa_op_conv_transpose1d", "maa_op_snake_aa", "maa_op_bench_conv", "maa_calib",
-    "maa_op_mrf_pair", "maa_op_groupnorm_ex", "maa_op_layernorm_ex", "maa_op_split32",
+    "maa_op_mrf_pair", "maa_op_groupnorm_ex", "maa_op_layernorm_ex", "maa_op_split32", "maa_op_igemm_ex",
     "maa_unet_forward_split", "maa_op_unfold", "maa_op_fold",
 ]
 
@@ -220,6 +232,7 @@ def load():
         "maa_calib": [vp, ci, C.POINTER(C.c_double)],
         "maa_op_mrf_pair": [vp, vp, ci, ci, ci, fp, fp, ci, ci, cf, fp, fp, ci, ci, cf, cf, ci, vp],
         "maa_op_groupnorm_ex": [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, fp, fp, cf, ci, vp, ci, vp],
+        "maa_op_igemm_ex": [vp, C.POINTER(maa_igemm_ex_args)],
         "maa_op_layernorm_ex": [vp, vp, ci, ci, fp, fp, cf, vp, ci],
         "maa_op_split32": [vp, vp, ci, ci, cf, ci, vp],
         "maa_unet_forward_split": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, fp, vp],

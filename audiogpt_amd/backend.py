@@ -225,6 +225,31 @@ class Context:
                                              int(groups), gp, bp, float(eps), int(silu), ptr(out), int(out_split), ptr(raw)))
         return out
 
+    def op_igemm_ex(self, x1, ld1, C1, x2, ld2, C2, B, H, W, Ho, Wo, w, bias, c, ldc, stride=1, pad_w=0, pad_h=-1, dil=1, up=0,
+                    a_leaky=0.0, presplit=0, alpha=1.0, rowadd=None, ld_rowadd=0, res=None, ldr=0, act=0, act_slope=0.0,
+                    out_scale=1.0, accumulate=0, geglu=0, c_split=0, c2=None, ldc2=0, c2_slope=1.0):
+        """maa_op_igemm_ex: the library's internal contraction call (conv_into -> launch_igemm) with every field of its descriptor, on
+        channels-last device tensors the caller has laid out (x1 / x2 / rowadd / res / c / c2 are fp32 device tensors, possibly views
+        into wider buffers; pitches in floats; x2 None with C2 = 0 for one source).  w [Cout, C1+C2, KH, KW] (geglu: [2 inner, K]) and
+        bias come from the host.  Writes into `c` (and `c2`); nothing is allocated, copied or checked beyond what the C entry point
+        checks."""
+        for t in (x1, x2, rowadd, res, c, c2):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32), (t.device, t.dtype)
+        wt, wp = L.host_f32(w)
+        bt, bp = L.host_f32(bias) if bias is not None else (None, None)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        KH, KW = (1, 1) if wt.dim() == 2 else (int(wt.shape[2]), int(wt.shape[3]))
+        assert wt.shape[1] == C1 + C2 and (bt is None or bt.numel() == wt.shape[0])
+        a = L.maa_igemm_ex_args(
+            d_x1=ptr(x1), ld1=int(ld1), C1=int(C1), d_x2=ptr(x2), ld2=int(ld2), C2=int(C2), B=int(B), H=int(H), W=int(W), Ho=int(Ho),
+            Wo=int(Wo), h_w=wp, h_bias=bp, Cout=int(wt.shape[0]), KH=KH, KW=KW, stride=int(stride), pad_w=int(pad_w), pad_h=int(pad_h),
+            dil=int(dil), up=int(up), a_leaky=float(a_leaky), presplit=int(presplit), alpha=float(alpha), d_rowadd=ptr(rowadd),
+            ld_rowadd=int(ld_rowadd), d_res=ptr(res), ldr=int(ldr), act=int(act), act_slope=float(act_slope),
+            out_scale=float(out_scale), accumulate=int(accumulate), geglu=int(geglu), c_split=int(c_split), d_c=ptr(c), ldc=int(ldc),
+            d_c2=ptr(c2), ldc2=int(ldc2), c2_slope=float(c2_slope))
+        L.check(self.lib.maa_op_igemm_ex(self.h, C.byref(a)))
+        return c
+
     def op_layernorm_ex(self, x, gamma, beta, eps=1e-5, out_split=0):
         """LayerNorm over the last dim of x [rows, C]; out_split = 1: the result as split32 rows in an fp32-typed tensor."""
         x = _f32(x, self.device)

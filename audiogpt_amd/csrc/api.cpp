@@ -752,6 +752,91 @@ int maa_op_conv(maa_ctx* ctx, const float* d_x, int B, int Cin, int H, int W, co
     });
 }
 
+int maa_op_igemm_ex(maa_ctx* ctx, const maa_igemm_ex_args* a) {
+    return guarded([&] {
+        // (what does not need the device comes first: the argument checks can be tested without one)
+        MAA_CHECK(a && a->d_x1 && a->h_w && a->d_c, "bad op_igemm_ex arguments: null pointer");
+        MAA_CHECK(a->B > 0 && a->H > 0 && a->W > 0 && a->Ho > 0 && a->Wo > 0 && a->C1 > 0 && a->C2 >= 0 && a->Cout > 0 && a->KH > 0 &&
+                      a->KW > 0 && a->stride > 0 && a->dil > 0 && a->pad_w >= 0 && a->pad_h >= -1,
+                  "bad op_igemm_ex sizes");
+        MAA_CHECK((long long)a->B * a->Ho * a->Wo < (1ll << 31) && (long long)a->KH * a->KW * (a->C1 + a->C2) < (1ll << 31), "bad op_igemm_ex sizes");
+        MAA_CHECK((a->C2 == 0) == (a->d_x2 == nullptr), "op_igemm_ex: a second source needs both d_x2 and C2");
+        MAA_CHECK(!a->geglu || (a->h_bias && a->KH == 1 && a->KW == 1 && a->Cout % 2 == 0), "op_igemm_ex: GEGLU is a biased linear of 2 * inner columns");
+        const int N = a->geglu ? a->Cout / 2 : a->Cout, Ctot = a->C1 + a->C2;
+        MAA_CHECK(a->ld1 >= a->C1 && (a->C2 == 0 || a->ld2 >= a->C2) && a->ldc >= N && (!a->d_res || a->ldr >= N) &&
+                      (!a->d_c2 || a->ldc2 >= N) && (!a->d_rowadd || a->ld_rowadd >= N),
+                  "op_igemm_ex: a pitch is smaller than its width");
+        MAA_CHECK(!a->presplit || (a->C2 == 0 && a->C1 % 32 == 0 && a->ld1 == a->C1),
+                  "op_igemm_ex: presplit takes one dense source of whole 32-channel lines");
+        bind(ctx);
+        maa::Ctx& c = ctx->c;
+        MAA_CHECK(!a->presplit || c.dtype != 0, "op_igemm_ex: presplit needs a bf16 mode");
+        OneShot s;
+        if (a->geglu)
+            s.add("w", a->h_w, {a->Cout, Ctot});
+        else
+            s.add("w", a->h_w, {a->Cout, Ctot, a->KH, a->KW});
+        if (a->h_bias) s.add("b", a->h_bias, {a->Cout});
+        maa::WeightStore ws(c.dtype != 0);
+        maa::PackedW pw = a->geglu ? ws.pack_geglu(s.sd, "w", "b") : ws.pack_conv(s.sd, "w", a->h_bias ? "b" : "", a->KH, a->KW);
+        maa::run_sized(c, [&] {
+            maa::T4 x1, x2, y;
+            x1.p = const_cast<float*>(a->d_x1);
+            x1.B = a->B;
+            x1.H = a->H;
+            x1.W = a->W;
+            x1.C = a->C1;
+            x1.ld = a->ld1;
+            x2 = x1;
+            x2.p = const_cast<float*>(a->d_x2);
+            x2.C = a->C2;
+            x2.ld = a->ld2;
+            maa::ConvOpt o;
+            if (a->a_leaky != 0.f) {
+                o.a_act = 1;
+                o.a_slope = a->a_leaky;
+            }
+            if (a->presplit) {      // the slope goes into the packed rows: the engines that take split32 A apply no activation
+                float* xs = c.ws.alloc_f((size_t)a->B * a->H * a->W * a->C1);
+                maa::launch_split32_pack(c, a->d_x1, (long long)a->B * a->H * a->W, a->C1, xs, a->a_leaky != 0.f ? a->a_leaky : 1.f);
+                x1.p = xs;
+                x1.ld = 0;
+                x1.split = true;
+                o.a_act = 0;
+            }
+            y.p = a->d_c;
+            y.B = a->B;
+            y.H = a->Ho;
+            y.W = a->Wo;
+            y.C = N;
+            o.KH = a->KH;
+            o.KW = a->KW;
+            o.stride = a->stride;
+            o.pad = a->pad_w;
+            o.pad_h = a->pad_h;
+            o.dil = a->dil;
+            o.up = a->up ? 1 : 0;
+            o.alpha = a->alpha;
+            o.rowadd = a->d_rowadd;
+            o.ld_rowadd = a->ld_rowadd;
+            o.res = a->d_res;
+            o.ldr = a->ldr;
+            o.act = a->act;
+            o.act_slope = a->act_slope;
+            o.out_scale = a->out_scale;
+            o.accumulate = a->accumulate ? 1 : 0;
+            o.geglu = a->geglu ? 1 : 0;
+            o.c_split = a->c_split ? 1 : 0;
+            o.ldc = a->ldc;
+            o.c2 = a->d_c2;
+            o.ldc2 = a->ldc2;
+            o.c2_slope = a->c2_slope;
+            maa::conv_into(c, x1, a->d_x2 ? &x2 : nullptr, pw, o, y);
+        });
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
 int maa_calib(maa_ctx* ctx, int kind, double* out_value) {
     return guarded([&] {
         bind(ctx);

@@ -10,7 +10,7 @@ void conv_into(Ctx& ctx, const T4& x1, const T4* x2, const PackedW& w, const Con
     if (x2) {
         MAA_CHECK(x2->B == x1.B && x2->H == x1.H && x2->W == x1.W, "concat sources differ in shape");
         p.a2 = x2->p;
-        p.lda2 = x2->C;
+        p.lda2 = x2->ld ? x2->ld : x2->C;
         p.C2 = x2->C;
     }
     p.Hin = x1.H;
@@ -39,11 +39,12 @@ void conv_into(Ctx& ctx, const T4& x1, const T4* x2, const PackedW& w, const Con
     MAA_CHECK(p.K == w.K, "conv weight K mismatch");
     p.N = o.geglu ? w.N : out.C;
     MAA_CHECK(p.N <= w.N, "conv weight N mismatch");
+    p.alpha = o.alpha;
     p.bias = w.bias;
     p.rowadd = o.rowadd;
     p.ld_rowadd = o.ld_rowadd;
     p.res = o.res;
-    p.ldr = out.C;
+    p.ldr = o.ldr ? o.ldr : out.C;
     p.act = o.act;
     p.act_slope = o.act_slope;
     p.out_scale = o.out_scale;
@@ -51,9 +52,9 @@ void conv_into(Ctx& ctx, const T4& x1, const T4* x2, const PackedW& w, const Con
     p.geglu = o.geglu;
     p.c_split = o.c_split;
     p.c = out.p;
-    p.ldc = out.C;
+    p.ldc = o.ldc ? o.ldc : out.C;
     p.c2 = o.c2;
-    p.ldc2 = out.C;
+    p.ldc2 = o.ldc2 ? o.ldc2 : out.C;
     p.c2_slope = o.c2_slope;
     launch_igemm(ctx, p);
 }

@@ -41,6 +41,8 @@ struct ConvOpt {
     int c_split = 0;              // write the output as split32 lines
     float* c2 = nullptr;          // second output: leaky-relu(c2_slope) of the result as split32 lines (output's shape)
     float c2_slope = 1.f;
+    float alpha = 1.f;            // IGemm::alpha
+    int ldr = 0, ldc = 0, ldc2 = 0;      // row pitches of res / the output / c2 in floats; 0 = dense (the output's C)
 };
 
 // out = conv(x1 ++ x2) with packed weight `w`; output spatial size given by (Ho, Wo)

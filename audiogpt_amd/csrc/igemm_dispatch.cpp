@@ -168,6 +168,11 @@ int fit_slices(int nchunks, int S) {
 
 IGemmPlan igemm_plan(const Ctx& ctx, const IGemm& p) {
     IGemmPlan pl;
+    // (no model asks for both: the epilogue reads no accumulate target when it writes split32 lines, so the sum would be dropped)
+    MAA_CHECK(!(p.accumulate && p.c_split), "split32 output cannot accumulate");
+    // (likewise the GEGLU branch of the epilogue is value * gelu(gate) of alpha * acc + bias and nothing else)
+    MAA_CHECK(!p.geglu || (!p.rowadd && !p.res && p.act == 0 && p.out_scale == 1.f && !p.accumulate && !p.c2),
+              "GEGLU takes no row add, residual, activation, output scale, accumulate or second output");
     // precision mode of the context: 1 = bf16x3 split, 2 = plain bf16 operands; problems the bf16 engines cannot take run on the
     // exact-fp32 kernel.  (The bf16 part also runs in the workspace dry run: its split-K slabs come from the arena.)
     if (ctx.dtype != 0 && plan_bf16(ctx, p, pl)) return pl;
@@ -175,6 +180,7 @@ IGemmPlan igemm_plan(const Ctx& ctx, const IGemm& p) {
     if (ctx.ws.dry) return pl;
     MAA_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "empty igemm");
     MAA_CHECK(!p.c_split, "split32 output asked of a problem only the fp32 engine can take");
+    MAA_CHECK(!p.c2, "second (split32) output asked of a problem only the fp32 engine can take");      // (its epilogue writes none)
     const int taps = p.KH * p.KW, Ctot = p.C1 + p.C2;
     MAA_CHECK(p.K <= taps * Ctot && p.K > (taps - 1) * Ctot, "igemm K mismatch");
     MAA_CHECK(p.a_act == 0 || p.a_act == 1, "igemm A activation");

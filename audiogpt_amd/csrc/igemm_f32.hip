@@ -304,7 +304,7 @@ __global__ __launch_bounds__(NT) void igemm_f32_kernel(const IGemm p, int ntiles
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
         const int mb = m0 + wm * WTM + i * 32;
-        const int b0 = mb / rpb;
+        const int b0 = (mb < p.M ? mb : p.M - 1) / rpb;      // (a block wholly past M reads the last sample's row, never one past it)
         const int nextb = (b0 + 1) * rpb;
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
@@ -352,6 +352,7 @@ __global__ __launch_bounds__(NT) void igemm_f32_kernel(const IGemm p, int ntiles
                     if (p.act == 1) v = tanhf(v);
                     else if (p.act == 2) v = fmaxf(v, 0.f);
                     else if (p.act == 3) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+                    else if (p.act == 4) v = v > 0.f ? v : v * p.act_slope;
                     v *= p.out_scale;
                     if (p.accumulate) v += cv[r];
                     outv[r] = v;

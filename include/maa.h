@@ -554,6 +554,50 @@ int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const 
 int maa_op_groupnorm_ex(maa_ctx* ctx, const float* d_x1, int ld1, int C1, const float* d_x2, int ld2, int C2, int B, int HW,
                         int groups, const float* h_gamma, const float* h_beta, float eps, int silu, float* d_y, int out_split,
                         float* d_raw);
+/* One contraction exactly as the models issue it (tests of the implicit-GEMM engines and their shared epilogue): the library's
+ * internal convolution call, with every field of its descriptor, on channels-last DEVICE buffers the caller has laid out.  No
+ * layout kernels run in between and nothing the caller sees is allocated.
+ *   A: d_x1 [B,H,W,*] (row pitch ld1 >= C1 floats, channels 0 .. C1) and the optional d_x2 (pitch ld2 >= C2; NULL with C2 = 0)
+ *      holding channels C1 .. C1+C2; read through a nearest-2x upsample with up = 1; a_leaky != 0: leaky-relu(a_leaky) of A.
+ *      presplit = 1 (bf16 modes, one dense source, C1 % 32 == 0): x1 is first packed into split32 rows, the slope included, the
+ *      form the normalisations hand to the LDS-DMA engines.
+ *   B: h_w, torch weight [Cout, C1+C2, KH, KW] on the HOST and h_bias [Cout] or NULL, packed as the models pack them; geglu = 1:
+ *      h_w [Cout = 2 inner, C1+C2] (KH = KW = 1, bias required) packed value / gate interleaved, the output has N = inner columns.
+ *   geometry: stride, dil, pad_w, pad_h (-1: pad_w when KH > 1, else 0); the output is [B,Ho,Wo] positions, taps outside the
+ *      source read zero.
+ *   epilogue: v = act(alpha * acc + bias + rowadd[b] + res) * out_scale, c = v (+ c with accumulate = 1); d_rowadd [B, *] with
+ *      pitch ld_rowadd, d_res pitch ldr, act 0 none / 1 tanh / 2 relu / 3 gelu(erf) / 4 leaky-relu(act_slope); geglu: v = value *
+ *      gelu(gate) of (alpha * acc + bias).  d_c [B Ho Wo, *] has pitch ldc >= N and is written as fp32 rows, or with c_split = 1
+ *      (N % 32 == 0) as split32 rows; d_c2 (or NULL; N % 32 == 0, pitch ldc2) receives leaky-relu(c, c2_slope) as split32 rows.
+ * Checked here: null pointers, positive sizes, the presplit preconditions and pitches no smaller than the widths; everything
+ * else is the dispatch's own decision (and error). */
+typedef struct {
+    const float* d_x1;
+    int ld1, C1;
+    const float* d_x2;
+    int ld2, C2;
+    int B, H, W, Ho, Wo;
+    const float* h_w;
+    const float* h_bias;
+    int Cout, KH, KW;
+    int stride, pad_w, pad_h, dil, up;
+    float a_leaky;
+    int presplit;
+    float alpha;
+    const float* d_rowadd;
+    int ld_rowadd;
+    const float* d_res;
+    int ldr;
+    int act;
+    float act_slope, out_scale;
+    int accumulate, geglu, c_split;
+    float* d_c;
+    int ldc;
+    float* d_c2;
+    int ldc2;
+    float c2_slope;
+} maa_igemm_ex_args;
+int maa_op_igemm_ex(maa_ctx* ctx, const maa_igemm_ex_args* args);
 /* maa_op_layernorm with the kernels' out_split argument (1: d_y [rows,C] as split32 rows, C % 32 == 0) */
 int maa_op_layernorm_ex(maa_ctx* ctx, const float* d_x, int rows, int C, const float* h_gamma, const float* h_beta, float eps,
                         float* d_y, int out_split);

@@ -75,3 +75,45 @@ def test_normalisation_test_entries_are_bound_and_reject_null(lib_path):
     assert lib.maa_op_layernorm_ex(None, None, 1, 4, None, None, 1e-5, None, 0) < 0
     assert lib.maa_op_split32(None, None, 1, 32, 1.0, 0, None) < 0
     assert len(lib.maa_last_error()) > 0
+
+
+def test_contraction_test_entry_is_bound_and_rejects_null(lib_path):
+    """maa_op_igemm_ex (tests/test_gpu_igemm_ops.py) is declared, exported, bound with the header's argument count and a structure
+    that has the header's fields in the header's order, and fails with a message on null arguments, on a pitch below its width and
+    on presplit outside its preconditions -- all checked before the context is touched."""
+    from audiogpt_amd import _lib
+    lib = _lib.load()
+    raw = open(os.path.join(ROOT, "include", "maa.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    name = "maa_op_igemm_ex"
+    assert name in _lib.EXPORTS and name in _declared_symbols()
+    decl = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
+    assert len(getattr(lib, name).argtypes) == len(decl.split(",")), name
+    body = re.search(r"typedef struct \{([^}]*)\} maa_igemm_ex_args;", src).group(1)
+    fields = []
+    for stmt in body.split(";"):
+        stmt = stmt.strip()
+        if stmt:
+            fields += [f.strip().lstrip("*").strip() for f in re.sub(r"^(const\s+)?(float|int)\s*\*?", "", stmt).split(",")]
+    assert fields == [f[0] for f in _lib.maa_igemm_ex_args._fields_]
+    assert lib.maa_op_igemm_ex(None, None) < 0 and b"null pointer" in lib.maa_last_error()
+    import numpy as np
+    buf = np.zeros(64, np.float32)
+    fp = buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+    def args(**kw):      # a 1x1 convolution 32 -> 32 on a 1x1 image; the buffer stands in for device memory and is never read
+        d = dict(d_x1=buf.ctypes.data, ld1=32, C1=32, B=1, H=1, W=1, Ho=1, Wo=1, h_w=fp, Cout=32, KH=1, KW=1, stride=1, dil=1,
+                 pad_h=-1, alpha=1.0, out_scale=1.0, d_c=buf.ctypes.data, ldc=32)
+        d.update(kw)
+        return ctypes.byref(_lib.maa_igemm_ex_args(**d))
+
+    assert lib.maa_op_igemm_ex(None, args()) < 0 and b"null context" in lib.maa_last_error()      # past every argument check
+    for bad in (dict(ldc=31), dict(ld1=31), dict(d_res=buf.ctypes.data, ldr=16), dict(d_c2=buf.ctypes.data, ldc2=0),
+                dict(d_rowadd=buf.ctypes.data, ld_rowadd=8), dict(d_x2=buf.ctypes.data, C2=8, ld2=4)):
+        assert lib.maa_op_igemm_ex(None, args(**bad)) < 0 and b"pitch" in lib.maa_last_error(), bad
+    for bad in (dict(B=0), dict(Cout=0), dict(stride=0), dict(pad_h=-2)):
+        assert lib.maa_op_igemm_ex(None, args(**bad)) < 0 and b"sizes" in lib.maa_last_error(), bad
+    assert lib.maa_op_igemm_ex(None, args(C2=8)) < 0 and b"second source" in lib.maa_last_error()
+    assert lib.maa_op_igemm_ex(None, args(geglu=1)) < 0 and b"GEGLU" in lib.maa_last_error()
+    for bad in (dict(C1=16, ld1=16), dict(ld1=64), dict(d_x2=buf.ctypes.data, C2=32, ld2=32)):
+        assert lib.maa_op_igemm_ex(None, args(presplit=1, **bad)) < 0 and b"presplit" in lib.maa_last_error(), bad
