@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void halo_conv1d_kernel(const HaloArgs a) {
                 }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm0();
 
         f32x16 acc[MI][NI];
 #pragma unroll
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void halo_pair_kernel(const HaloPairArgs a) {
                 }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm0();
 
         f32x16 acc[MI][NI];
         auto zero_acc = [&]() __attribute__((always_inline)) {
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(256) void halo_pair_kernel(const HaloPairArgs a) {
                 tap = 0;
                 cb = 0;
                 dil = a.d2;
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wait_lgkm0();
             }
             wait_vmcnt<(NSB - 2) * IPW>();
             __builtin_amdgcn_s_barrier();          // chunk c of the weights is in LDS (and, at c = 0 / n1, the whole image)

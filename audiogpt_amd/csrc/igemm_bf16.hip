@@ -221,12 +221,7 @@ __global__ __launch_bounds__(NT) void igemm_bf16_kernel(const IGemm p, int ntile
     };
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WGN, wn = wid - wm * WGN;
@@ -250,25 +245,7 @@ __global__ __launch_bounds__(NT) void igemm_bf16_kernel(const IGemm p, int ntile
                 bh[j] = *reinterpret_cast<const bf16x8*>(base + b_row + j * 32 * LDK + ch);
                 if constexpr (TERMS == 3) bl[j] = *reinterpret_cast<const bf16x8*>(base + PLANE_ELEMS + b_row + j * 32 * LDK + ch);
             }
-            // term-major order: the three products of one accumulator are separated by the other accumulators'
-            // MFMAs (same per-accumulator order lo.hi, hi.lo, hi.hi, so results do not depend on the tile shape)
-            if constexpr (TERMS == 3) {
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NI; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NI; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+            mma_kstep<TERMS>(acc, ah, al, bh, bl);
         }
     };
 

@@ -84,7 +84,8 @@ bool plan_bf16(const Ctx& ctx, const IGemm& p, IGemmPlan& pl) {
     if (p.a_split && p.b_split && pl.cfg < 3 && !ctx.tune.no_dma) {
         if (!igemm_pp_takes(ctx, p, pl) && !igemm_pp1_takes(ctx, p, pl) && !igemm_dma2_takes(ctx, p, pl)) igemm_dma_takes(ctx, p, pl);
     }
-    if (pl.S > 1) {      // slabs of the split-K engines: S fp32 copies of every tile, borrowed from the arena for the two launches
+    if (pl.S > 1) {      // slabs of the split-K engines: S fp32 copies of every tile (slab_floats, igemm_device.h: one float per tile
+                         // element), borrowed from the arena for the two launches; the engine's launcher checks this size against its tile
         const int bm = pl.engine == IGemmPlan::DMA2 ? 128 : 256, bn = pl.engine == IGemmPlan::DMA2 ? 128 : pl.bn;
         const long long tiles = (long long)((p.M + bm - 1) / bm) * ((ncols + bn - 1) / bn);
         pl.slab_floats = (size_t)(tiles * pl.S * bm * bn);

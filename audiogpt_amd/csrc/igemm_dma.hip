@@ -17,8 +17,8 @@
 // the 16 lanes of a ds_read_b128 group hold rows {0-3, 12-15, 20-27} (+4, +32 ...), whose (row & 1, (row >> 1) & 7)
 // pairs are all distinct, i.e. 16 different 16-byte slots of the 256-byte bank row.
 //
-// The arithmetic (per accumulator: lo.hi, hi.lo, hi.hi per 16-deep k-step, k ascending) is the register kernel's, so
-// both engines return bit-identical results; MAA_NO_DMA=1 routes everything through the register kernel (tests).
+// The arithmetic is the register kernel's (mma_kstep, igemm_device.h; k ascending), so both engines return bit-identical
+// results; MAA_NO_DMA=1 routes everything through the register kernel (tests).
 #include "igemm_epilogue.h"
 
 #include <cstdio>
@@ -177,18 +177,15 @@ __global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles
     };
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int wm = wid / WGN, wn = wid - wm * WGN;
     const int lrow = lane & 31, lk = lane >> 5;
     const int swz = (lrow >> 1) & 7;           // tile offsets are multiples of 32 rows
     const int a_row = (wm * WTM + lrow) * 128, b_row = (BM + wn * WTN + lrow) * 128;
-    int slot_off[2][2];                        // [plane][k-step] -> byte offset of this lane's 16-byte operand piece
+    // [plane][k-step] -> byte offset of this lane's 16-byte operand piece: frag_slot_offsets' table (igemm_device.h), written out
+    // because through the helper the 128x128 linear form allocates two more VGPRs (profiles/pp_refactor_isa_table.txt)
+    int slot_off[2][2];
 #pragma unroll
     for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
@@ -204,40 +201,10 @@ __global__ __launch_bounds__(NT) void igemm_dma_kernel(const IGemm p, int ntiles
         for (int k0 = 0; k0 < 2; k0 += G) {
             bf16x8 ah[G][MI], bh[G][NI], al[G][MI], bl[G][NI];
 #pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const int ks = k0 + g;
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-                    if constexpr (TERMS == 3) al[g][i] = *reinterpret_cast<const bf16x8*>(base + a_row + i * 4096 + slot_off[1][ks]);
-#pragma unroll
-                for (int j = 0; j < NI; ++j) bh[g][j] = *reinterpret_cast<const bf16x8*>(base + b_row + j * 4096 + slot_off[0][ks]);
-#pragma unroll
-                for (int i = 0; i < MI; ++i) ah[g][i] = *reinterpret_cast<const bf16x8*>(base + a_row + i * 4096 + slot_off[0][ks]);
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    if constexpr (TERMS == 3) bl[g][j] = *reinterpret_cast<const bf16x8*>(base + b_row + j * 4096 + slot_off[1][ks]);
-            }
+            for (int g = 0; g < G; ++g) read_frags_kstep<TERMS>(base, a_row, b_row, slot_off, k0 + g, ah[g], al[g], bh[g], bl[g]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int g = 0; g < G; ++g) {
-                if constexpr (TERMS == 3) {
-#pragma unroll
-                    for (int i = 0; i < MI; ++i)
-#pragma unroll
-                        for (int j = 0; j < NI; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[g][i], bh[g][j], acc[i][j], 0, 0, 0);
-#pragma unroll
-                    for (int i = 0; i < MI; ++i)
-#pragma unroll
-                        for (int j = 0; j < NI; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[g][i], bl[g][j], acc[i][j], 0, 0, 0);
-                }
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NI; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[g][i], bh[g][j], acc[i][j], 0, 0, 0);
-            }
+            for (int g = 0; g < G; ++g) mma_kstep<TERMS>(acc, ah[g], al[g], bh[g], bl[g]);
         }
     };
 

@@ -14,8 +14,8 @@
 //
 // Numerical contract: S depends on the layer only (K and the packed N, never on M), so a sample's result does not
 // depend on the batch it was computed in (tests: batch invariance, prompt sharding).  Within a slice the products are
-// issued exactly as in igemm_bf16.hip / igemm_dma.hip (per accumulator lo.hi, hi.lo, hi.hi per 16-deep k-step, k
-// ascending); with S = 1 the result is bit-identical to those engines.
+// issued exactly as in igemm_bf16.hip / igemm_dma.hip (mma_kstep, igemm_device.h; k ascending); with S = 1 the result is
+// bit-identical to those engines.
 //
 // LDS image, swizzle and the DMA addressing are those of igemm_dma.hip (stage = [BM + BN rows][128 B], 16-byte slot s
 // of row r stored at slot s ^ ((r >> 1) & 7), permutation applied to the copy's SOURCE address and to the ds_read_b128
@@ -183,57 +183,19 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_dma2_kernel(const IGemm 
     };
 
     f32x16 acc[MI][NI];
-    auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    };
-    zero_acc();
+    zero_acc(acc);
 
     const int wm = wid / WGN, wn = wid - wm * WGN;
     const int lrow = lane & 31, lk = lane >> 5;
-    const int swz = (lrow >> 1) & 7;           // tile offsets are multiples of 32 rows
     const int a_row = (wm * WTM + lrow) * 128, b_row = (BM + wn * WTN + lrow) * 128;
     int slot_off[2][2];                        // [plane][k-step] -> byte offset of this lane's 16-byte operand piece
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) slot_off[pl][ks] = ((pl * 4 + ks * 2 + lk) ^ swz) << 4;
+    frag_slot_offsets(lrow, lk, slot_off);
 
     struct Frags {
         bf16x8 ah[MI], al[MI], bh[NI], bl[NI];
     };
     auto read_frags = [&](const char* base, int ks, Frags& f) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-            if constexpr (TERMS == 3) f.al[i] = *reinterpret_cast<const bf16x8*>(base + a_row + i * 4096 + slot_off[1][ks]);
-#pragma unroll
-        for (int j = 0; j < NI; ++j) f.bh[j] = *reinterpret_cast<const bf16x8*>(base + b_row + j * 4096 + slot_off[0][ks]);
-#pragma unroll
-        for (int i = 0; i < MI; ++i) f.ah[i] = *reinterpret_cast<const bf16x8*>(base + a_row + i * 4096 + slot_off[0][ks]);
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-            if constexpr (TERMS == 3) f.bl[j] = *reinterpret_cast<const bf16x8*>(base + b_row + j * 4096 + slot_off[1][ks]);
-    };
-    // the 3 MI NI MFMAs of one k-step; term-major, so the three products of an accumulator are MI NI - 1 MFMAs apart
-    auto mma = [&](const Frags& f) __attribute__((always_inline)) {
-        if constexpr (TERMS == 3) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.al[i], f.bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[i], f.bl[j], acc[i][j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[i], f.bh[j], acc[i][j], 0, 0, 0);
+        read_frags_kstep<TERMS>(base, a_row, b_row, slot_off, ks, f.ah, f.al, f.bh, f.bl);
     };
 
     // ---- the item whose chunks are being multiplied
@@ -250,20 +212,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_dma2_kernel(const IGemm 
         if (part == nullptr) {
             igemm_epilogue<MI, NI>(p, acc, mt * BM + wm * WTM, nt * BN + wn * WTN, lrow, lk, 0, Nb, rpb);
         } else {
-            // slab of this (slice, tile): [MI NI blocks][4 register quads][NTH threads][4 floats] -- every store
-            // instruction of a wave writes 1 KB contiguous
-            float* pp = part + ((long long)item * (MI * NI * 4) * NTH + tid) * 4;
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-                        *reinterpret_cast<f32x4*>(pp + (long long)((i * NI + j) * 4 + q) * NTH * 4) = v;
-                    }
+            store_slab<MI, NI, NTH>(part, item, tid, acc);
         }
-        zero_acc();
+        zero_acc(acc);
         c_w += w_step;
         if (c_w >= w_cnt) return false;
         c_rem = item_chunks(c_w);
@@ -294,13 +245,13 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_dma2_kernel(const IGemm 
             const int st_fill = st == 0 ? NS - 1 : st - 1;
             read_frags(cur, 1, f1);
             __builtin_amdgcn_sched_barrier(0);
-            mma(f0);
+            mma_kstep<TERMS>(acc, f0.ah, f0.al, f0.bh, f0.bl);
             __builtin_amdgcn_sched_barrier(0);
             wait_vmcnt<(NS - 3) * IPW>();          // this wave's copies of chunk c+1 have landed
             __builtin_amdgcn_s_barrier();          // B(c+1): everybody's have, and everybody consumed chunk c-1
             read_frags(smem + st_next * STAGE, 0, f0);      // (past the last chunk: zeros, never multiplied)
             __builtin_amdgcn_sched_barrier(0);
-            // MFMAs of k-step 1 interleaved with the IPW copies
+            // MFMAs of k-step 1 in mma_kstep's order (igemm_device.h), each followed by one of the IPW copies
             static_for<0, TERMS * MI * NI>([&](auto xc) {
                 constexpr int x = decltype(xc)::value;
                 constexpr int t = x / (MI * NI) + (3 - TERMS), i = (x % (MI * NI)) / NI, j = x % NI;
@@ -336,7 +287,7 @@ __global__ __launch_bounds__(NTH) void splitk_reduce_kernel(const IGemm p, const
     constexpr int njb = NI / JW, nblk = MI * njb;
     constexpr int WTM = 32 * MI, WTN = 32 * NI;
     constexpr int BM = WTM * (NTH / 64 / WGN), BN = WTN * WGN;
-    constexpr long long slab = (long long)(MI * NI * 4) * NTH * 4;       // floats per (slice, tile)
+    static_assert(slab_floats(MI, NI, NTH) == (long long)BM * BN, "a slab holds one float per tile element");
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wi = xcd_contiguous((int)blockIdx.x, (int)gridDim.x);      // the blocks of a tile, and neighbouring tiles' rows, on one XCD
     const int tile = wi / nblk, blk = wi - tile * nblk;
@@ -346,14 +297,14 @@ __global__ __launch_bounds__(NTH) void splitk_reduce_kernel(const IGemm p, const
     f32x16 acc[1][JW];
 #pragma unroll
     for (int jj = 0; jj < JW; ++jj) {
-        const float* src = part + (long long)tile * slab + ((long long)((i * NI + j + jj) * 4) * NTH + tid) * 4;
+        const float* src = slab_thread<MI, NI, NTH>(part, tile, tid) + slab_quad<NTH>(i * NI + j + jj, 0);
         f32x4 v[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const f32x4*>(src + (long long)q * NTH * 4);
+        for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const f32x4*>(src + slab_quad<NTH>(0, q));
         for (int s = 1; s < S; ++s) {
-            const float* sp = src + (long long)s * tiles * slab;
+            const float* sp = src + (long long)s * tiles * slab_floats(MI, NI, NTH);      // the same tile, slice s
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] += *reinterpret_cast<const f32x4*>(sp + (long long)q * NTH * 4);
+            for (int q = 0; q < 4; ++q) v[q] += *reinterpret_cast<const f32x4*>(sp + slab_quad<NTH>(0, q));
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -381,7 +332,7 @@ void launch_reduce_geom(const Ctx& ctx, const IGemm& p, const float* part, int S
 }
 
 template <int BM, int BN, int WGM, int WGN, int NS>
-void launch_one(const Ctx& ctx, const IGemm& p, int Nb, int S, float* part) {
+void launch_one(const Ctx& ctx, const IGemm& p, int Nb, int S, float* part, size_t part_floats) {
     constexpr int NW = WGM * WGN, NTH = 64 * NW;
     constexpr int MI = BM / WGM / 32, NI = BN / WGN / 32;
     const int ncols = p.N * (p.geglu ? 2 : 1);
@@ -391,6 +342,7 @@ void launch_one(const Ctx& ctx, const IGemm& p, int Nb, int S, float* part) {
     const int cps = (nchunks + S - 1) / S;
     const int Seff = (nchunks + cps - 1) / cps;            // slices that have at least one chunk
     MAA_CHECK(Seff == S, "split-K plan leaves an empty slice");
+    MAA_CHECK(S == 1 || part_floats == (size_t)((long long)tiles * S * slab_floats(MI, NI, NTH)), "igemm_dma2: the plan's slab size is not this tile's");
     MAA_CHECK(!p.geglu || NI % 2 == 0, "GEGLU needs value / gate block pairs inside a wave");
     constexpr size_t lds = (size_t)NS * (BM + BN) * 128;
     static_assert(lds <= 163840, "LDS per workgroup");
@@ -461,7 +413,7 @@ bool igemm_dma2_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl) {
 // `part`: pl.slab_floats floats when pl.S > 1
 void launch_igemm_dma2(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
     MAA_CHECK(pl.S == 1 || part != nullptr, "igemm_dma2: split-K needs its slab workspace");
-    launch_one<128, 128, 2, 2, 4>(ctx, p, pl.Nb, pl.S, part);      // 4 waves of 64x64, four LDS stages, in-wave pipelined loop
+    launch_one<128, 128, 2, 2, 4>(ctx, p, pl.Nb, pl.S, part, pl.slab_floats);      // 4 waves of 64x64, four LDS stages, in-wave pipelined loop
 }
 
 }  // namespace maa

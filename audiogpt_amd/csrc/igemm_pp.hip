@@ -17,15 +17,7 @@
 //     matrix pipe of a SIMD always has one wave feeding it and the partner's memory phase costs it nothing
 //     (MI355X_MICROARCH.md, "Two waves per SIMD": matrix beside memory is the complementary pairing).
 //
-// Tick t: group g reads chunk q at tick 2 q + g and multiplies it at tick 2 q + g + 1.  The weights of chunk q live in slot
-// q % 3 of a 3-slot ring and are needed during ticks 2 q .. 2 q + 1; the pieces of chunk q + 2 are issued into the slot chunk
-// q - 1 has left, half by group 0 at tick 2 q, half by group 1 at tick 2 q + 1, and every wave ends a memory phase with
-// s_waitcnt vmcnt(NP) -- everything but the NP pieces it has just issued has landed -- so a piece has two ticks (~1600
-// cycles) to arrive.  A is double-buffered by channel chunk: the pieces of chunk c + 1 are issued one per wave and memory
-// phase over taps 0..7 of chunk c.  Every wave issues exactly NP pieces per memory phase (pieces that do not exist copy the
-// zero page into a dump line) so the vmcnt arithmetic is the same constant everywhere.
-//
-// Numerical contract: per accumulator the products of a k-step are issued lo.hi, hi.lo, hi.hi like the other engines, but
+// Numerical contract: the k-step is the other engines' (mma_kstep, igemm_device.h), but
 // the k-steps run (channel chunk, tap, k) instead of (tap, channel, k): results differ from the other engines in the last
 // bits; which engine a layer takes is a function of the layer (taps, W, C, N), never of M, and so is the number of K
 // slices -- a sample's result does not depend on its batch.
@@ -42,7 +34,34 @@ namespace {
 constexpr int BM = 256;         // output rows per workgroup
 constexpr int NSB = 3;          // weight ring
 
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// The two-group schedule of both kernels: pp_lead_in, then per chunk j < NQ one pp_tick and the kernel's own step to the next chunk.
+// Tick t: group g reads chunk q at tick 2 q + g (`load(q)`: its fragments into
+// registers, its share of the LDS-DMA pieces on their way) and multiplies it at tick 2 q + g + 1 (`mma()`); group 1 runs one tick
+// behind group 0 and every wave passes 2 NQ barriers, each between two sched_barriers.  The weights of chunk q live in slot
+// q % 3 of a 3-slot ring and are needed during ticks 2 q .. 2 q + 1; the pieces of chunk q + 2 are issued into the slot chunk
+// q - 1 has left, half by group 0 at tick 2 q, half by group 1 at tick 2 q + 1, and every wave ends a memory phase with
+// s_waitcnt vmcnt(NP) -- everything but the NP pieces it has just issued has landed -- so a piece has two ticks (~1600
+// cycles) to arrive.  The halo kernel's A is double-buffered by channel chunk: the pieces of chunk c + 1 are issued one per wave
+// and memory phase over taps 0..7 of chunk c.  Every wave issues exactly NP pieces per memory phase (pieces that do not exist copy
+// the zero page into a dump line) so the vmcnt arithmetic is the same constant everywhere.
+__device__ __forceinline__ void pp_lead_in(int grp) {
+    if (grp == 1) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+template <class Load, class Mma>
+__device__ __forceinline__ void pp_tick(int grp, int j, int NQ, Load&& load, Mma&& mma) {
+    load(j);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    mma();
+    __builtin_amdgcn_sched_barrier(0);
+    if (!(grp == 1 && j == NQ - 1)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
 
 struct PPArgs {
     int W, H;            // image width / height (stride 1, "same" padding: output = input geometry; 1-D: H = 1, W = L)
@@ -129,12 +148,12 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
     const unsigned zaddr = (unsigned)(sZ - smem);
     // B: row n of the slot at n * 128, slot swizzle by the row (tile offsets are multiples of 32 rows)
     const int b_row = (wn * (32 * NI) + lrow) * 128;
-    const int b_swz = (lrow >> 1) & 7;
     int b_off[2][2];
+    frag_slot_offsets(lrow, lk, b_off);
 #pragma unroll
     for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) b_off[pl][ks] = b_row + (((pl * 4 + ks * 2 + lk) ^ b_swz) << 4);
+        for (int ks = 0; ks < 2; ++ks) b_off[pl][ks] += b_row;
 
     // ---- copies.  Lane i of a piece moves the 16 bytes of slot (i & 7) ^ swizzle(line) of line 8 piece + (i >> 3).
     // Every source address is valid memory whatever happens to its destination: weight rows and A positions are clamped
@@ -317,25 +336,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
 
     auto mma_phase = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            if constexpr (TERMS == 3) {
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int jn = 0; jn < NI; ++jn)
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ks][i], bh[ks][jn], acc[i][jn], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int jn = 0; jn < NI; ++jn)
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks][i], bl[ks][jn], acc[i][jn], 0, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int jn = 0; jn < NI; ++jn)
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks][i], bh[ks][jn], acc[i][jn], 0, 0, 0);
-        }
+        for (int ks = 0; ks < 2; ++ks) mma_kstep<TERMS>(acc, ah[ks], al[ks], bh[ks], bl[ks]);
     };
 
     setup_item(w_cur);
@@ -343,12 +344,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
     for (;;) {
         wait_vmcnt<0>();
         __syncthreads();                 // this item's first chunks are in LDS (and, first time, the zero line)
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        zero_acc(acc);
         a_o = 0;
         a_on8 = a_pieces;                // (the ring is longer than a chunk)
         ci = c_begin;
@@ -356,21 +352,9 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
         slot2 = t2 = NSB - 1;
         boff2 = (long long)(NSB - 1) * C4 + (long long)c_begin * 128;
 
-        // ---- ticks.  Group 1 runs one tick behind group 0; every wave passes 2 NQ barriers.
-        if (grp == 1) {
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        pp_lead_in(grp);
         for (int j = 0; j < NQ; ++j) {
-            load_phase(j);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            mma_phase();
-            __builtin_amdgcn_sched_barrier(0);
-            if (!(grp == 1 && j == NQ - 1)) __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
+            pp_tick(grp, j, NQ, load_phase, mma_phase);
             advance();
         }
         // Every fragment read of this item is done (a wave gets here through the barrier that follows group 1's last memory
@@ -392,17 +376,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IGemm p, const PPAr
         if constexpr (OUT == 1) {
             igemm_epilogue<MI, NI>(p, acc, row_base, col_base, lrow, lk, UP2 ? (long long)e_phase * p.M * p.ldc : 0LL, q.Nb, rpb);
         } else {
-            // slab of this (slice, tile): [MI NI blocks][4 register quads][512 threads][4 floats]
-            float* pp = q.part + ((long long)e_slab * (MI * NI * 4) * 512 + tid) * 4;
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int jn = 0; jn < NI; ++jn)
-#pragma unroll
-                    for (int qd = 0; qd < 4; ++qd) {
-                        const f32x4 v = {acc[i][jn][4 * qd], acc[i][jn][4 * qd + 1], acc[i][jn][4 * qd + 2], acc[i][jn][4 * qd + 3]};
-                        *reinterpret_cast<f32x4*>(pp + (long long)((i * NI + jn) * 4 + qd) * 512 * 4) = v;
-                    }
+            store_slab<MI, NI, 512>(q.part, e_slab, tid, acc);
         }
         if (!more) break;
         w_cur = w_next;
@@ -448,34 +422,43 @@ int pp_ring_lines(const PPGeom& g, int bn) {
     return cap <= room ? cap : 0;
 }
 
-template <int MI, int NI, int GWM, int GWN, int NPA, int TERMS>
-void launch_npa_terms(const Ctx& ctx, const IGemm& p, const PPArgs& q, int items, size_t lds) {
-    auto go = [&](auto kern) {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(kern), ctx.device, 163840);
-        hipLaunchKernelGGL(kern, dim3((unsigned)items), dim3(512), lds, ctx.stream, p, q);
-    };
-    const bool persist = q.items > items, slab = q.part != nullptr;      // (more items than workgroups: persistent)
-    if (persist && slab) go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, true, 2, TERMS>);
-    else if (persist) go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, true, 1, TERMS>);
-    else if (slab) go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, false, 2, TERMS>);
-    else go(igemm_pp_kernel<MI, NI, GWM, GWN, NPA, false, 1, TERMS>);
+// What both halo forms ask of the operands: one split32 source of whole 32-channel chunks against split32 [N][K] weights
+bool pp_operands_ok(const IGemm& p) {
+    return p.a_split && p.b_split && p.b_nk && p.C2 == 0 && p.C1 % BK == 0 && p.Z == 1 && p.a_act == 0 && !p.geglu;
+}
+// Tile width: `forced` (MAA_PP) when it is one; else 160 where it divides N (320, 640, 960, 1280) and its rings fit: no padded columns
+// at N = 320, and at N = 640 four K slices of 4 x 13 tiles make one round of 208 workgroups (profiles/r3_pp_bench_v4_ring.txt); else
+// 128.  A 160 whose rings do not fit falls back to 128; 0: neither fits.
+template <class Fits>
+int pp_tile_width(int N, Fits&& fits, int forced = 0) {
+    int bn = forced == 128 || forced == 160 ? forced : (N % 160 == 0 && fits(160)) ? 160 : 128;
+    if (!fits(bn)) bn = bn == 160 && fits(128) ? 128 : 0;
+    return bn;
 }
 
-template <int MI, int NI, int GWM, int GWN, int NPA>
-void launch_npa(const Ctx& ctx, const IGemm& p, const PPArgs& q, int items, size_t lds) {
-    if (ctx.dtype == 2)
-        launch_npa_terms<MI, NI, GWM, GWN, NPA, 1>(ctx, p, q, items, lds);
+// The two tiles: 256 x 128 = per group 2 x 2 waves of 2 x 2 fragments, 256 x 160 = 4 x 1 waves of 1 x 5.  f(PPTile<...>{})
+template <int MI_, int NI_, int GWM_, int GWN_>
+struct PPTile {
+    static constexpr int MI = MI_, NI = NI_, GWM = GWM_, GWN = GWN_, BN = GWN_ * NI_ * 32;
+};
+template <class F>
+void with_pp_tile(int bn, F&& f) {
+    if (bn == 128)
+        f(PPTile<2, 2, 2, 2>{});
     else
-        launch_npa_terms<MI, NI, GWM, GWN, NPA, 3>(ctx, p, q, items, lds);
+        f(PPTile<1, 5, 4, 1>{});
+}
+// f(std::true_type or std::false_type): a runtime flag as a template argument
+template <class F>
+void with_bool(bool b, F&& f) {
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
 }
 
-template <int MI, int NI, int GWM, int GWN>
-void launch_one(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
-    const int Nb = pl.Nb;
-    constexpr int BN = GWN * NI * 32;
-    const int ncols = p.N;
-    const int mtiles = (p.M + BM - 1) / BM, ntiles = (ncols + BN - 1) / BN;
-    const PPGeom g = pp_geom(p);
+// The kernel's arguments for S K slices of BN-wide tiles (the UP2 form overrides its own fields)
+PPArgs pp_args(const IGemm& p, const PPGeom& g, int BN, int Nb, int S, float* part, int tile_major) {
     PPArgs q;
     q.W = p.Win;
     q.H = p.Hin;
@@ -490,95 +473,87 @@ void launch_one(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part
     q.padflat = g.padflat;
     q.NLp = g.NLp;
     q.CAPl = pp_ring_lines(g, BN);
-    q.ntiles = ntiles;
-    q.tiles = mtiles * ntiles;
+    q.ntiles = (p.N + BN - 1) / BN;
+    q.tiles = (p.M + BM - 1) / BM * q.ntiles;
+    q.items = q.tiles * S;
     q.nci = p.C1 / BK;
-    q.cps = (q.nci + pl.S - 1) / pl.S;
+    q.cps = (q.nci + S - 1) / S;
     q.Nb = Nb;
-    q.part = pl.S > 1 ? part : nullptr;
-    q.S = pl.S;
-    // slice-major items (rounds 3 - 4, again since round 6): an XCD's contiguous eighth of the items is part of ONE K slice, so its
-    // L2 streams 1 / S of the packed weights; tile-major (round 5's default) gave it a few tiles with ALL their slices and every L2
-    // streamed the whole weight tensor: FETCH_SIZE x 3.4 at the 5 x 39 level for the same run time (profiles/r5/r5_bf16x3_pmc_fetch_write.txt)
-    q.tile_major = ctx.tune.pp_tile_major && pl.S > 1 ? 1 : 0;
+    q.part = S > 1 ? part : nullptr;
+    q.S = S;
+    q.tile_major = tile_major;
     q.tiles_pp = q.tiles;
     q.b_phase = 0;
-    MAA_CHECK((q.nci + q.cps - 1) / q.cps == pl.S, "igemm_pp: K split leaves an empty slice");
+    return q;
+}
+
+// One launch: LDS size, grid, and the instantiation for the runtime (npa, terms, persistent, slab)
+template <class T, bool UP2>
+void pp_launch(const Ctx& ctx, const IGemm& p, const PPArgs& q, int npa) {
     MAA_CHECK(q.CAPl > 0, "igemm_pp: the A ring does not fit beside the weight ring");
-    const size_t lds = (size_t)q.CAPl * 128 + (size_t)NSB * BN * 128 + 128 + 1024;
+    const size_t lds = (size_t)q.CAPl * 128 + (size_t)NSB * T::BN * 128 + 128 + 1024;
     MAA_CHECK(lds <= 163840, "igemm_pp: LDS per workgroup");
-    q.items = q.tiles * pl.S;
-    const int cus = device_cu_count(ctx.device);
     // persistent: one workgroup per CU holds the LDS.  (Round 6, profiles/r6_call4_grid_cap_ab.txt: capping the grid at half the
     // items -- two items per persistent workgroup, the second's first copies under the first's stores, the other CUs left to
     // the other contexts' kernels -- is 1 % slower with three batches in flight and 9 % slower with one.)
-    const int grid = q.items < cus ? q.items : cus;
-    if (g.npa == 1)
-        launch_npa<MI, NI, GWM, GWN, 1>(ctx, p, q, grid, lds);
-    else
-        launch_npa<MI, NI, GWM, GWN, 3>(ctx, p, q, grid, lds);
-    if (pl.S > 1) launch_splitk_reduce(ctx, p, part, pl.S, q.tiles, ntiles, Nb, BM, BN, GWN, MI, NI, 512);
-}
-
-// Upsample + 3x3 convolution as four 2x2 phase convolutions in one launch (see the kernel's UP2 note).  `p` describes ONE phase:
-// KH = KW = 2, the low-resolution geometry (Hin = Hout, Win = Wout), M = B H W, K = 4 C1, c = the phase-major plane buffer
-// [4][M][ldc]; b_phase = floats between the phases' packed weights.
-template <int MI, int NI, int GWM, int GWN>
-void launch_up2(const Ctx& ctx, const IGemm& p, int Nb, long long b_phase) {
-    constexpr int BN = GWN * NI * 32;
-    const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.N + BN - 1) / BN;
-    const PPGeom g = pp_geom(p);
-    PPArgs q;
-    q.W = p.Win;
-    q.H = p.Hin;
-    q.T = g.T;
-    q.KW = g.KW;
-    q.rowstep = g.rowstep;
-    q.colstep = g.colstep;
-    q.dh = p.dh;
-    q.dw = p.dw;
-    q.ph = 1;
-    q.pw = 1;
-    q.padflat = p.Win + 1;
-    q.NLp = g.NLp;
-    q.CAPl = pp_ring_lines(g, BN);
-    q.ntiles = ntiles;
-    q.tiles_pp = mtiles * ntiles;
-    q.tiles = 4 * q.tiles_pp;
-    q.nci = p.C1 / BK;
-    q.cps = q.nci;
-    q.Nb = Nb;
-    q.part = nullptr;
-    q.S = 1;
-    q.tile_major = 0;
-    q.b_phase = b_phase;
-    MAA_CHECK(q.CAPl > 0, "igemm_pp up2: the A ring does not fit beside the weight ring");
-    const size_t lds = (size_t)q.CAPl * 128 + (size_t)NSB * BN * 128 + 128 + 1024;
-    MAA_CHECK(lds <= 163840, "igemm_pp up2: LDS per workgroup");
-    q.items = q.tiles;
     const int cus = device_cu_count(ctx.device);
     const int grid = q.items < cus ? q.items : cus;
     auto go = [&](auto kern) {
         ensure_dynamic_lds(reinterpret_cast<const void*>(kern), ctx.device, 163840);
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, ctx.stream, p, q);
     };
-    const bool one = ctx.dtype == 2;
-    if (g.npa == 1) {
-        if (one) go(igemm_pp_kernel<MI, NI, GWM, GWN, 1, true, 1, 1, true>);
-        else go(igemm_pp_kernel<MI, NI, GWM, GWN, 1, true, 1, 3, true>);
-    } else {
-        if (one) go(igemm_pp_kernel<MI, NI, GWM, GWN, 3, true, 1, 1, true>);
-        else go(igemm_pp_kernel<MI, NI, GWM, GWN, 3, true, 1, 3, true>);
-    }
+    with_bool(ctx.dtype != 2, [&](auto x3) {
+        constexpr int TERMS = decltype(x3)::value ? 3 : 1;
+        if constexpr (UP2) {
+            // a 2x2 kernel has NLp >= 272, so pp_geom's need = (NLp / 8 + 23) / 24 >= 2: npa is 3 (or 0: not taken), never 1
+            MAA_CHECK(npa == 3, "igemm_pp up2: three A pieces per memory phase");
+            go(igemm_pp_kernel<T::MI, T::NI, T::GWM, T::GWN, 3, true, 1, TERMS, true>);
+        } else {
+            const bool persist = q.items > grid, slab = q.part != nullptr;      // (more items than workgroups: persistent)
+            with_bool(npa != 1, [&](auto n3) {
+                constexpr int NPA = decltype(n3)::value ? 3 : 1;
+                if (persist && slab) go(igemm_pp_kernel<T::MI, T::NI, T::GWM, T::GWN, NPA, true, 2, TERMS>);
+                else if (persist) go(igemm_pp_kernel<T::MI, T::NI, T::GWM, T::GWN, NPA, true, 1, TERMS>);
+                else if (slab) go(igemm_pp_kernel<T::MI, T::NI, T::GWM, T::GWN, NPA, false, 2, TERMS>);
+                else go(igemm_pp_kernel<T::MI, T::NI, T::GWM, T::GWN, NPA, false, 1, TERMS>);
+            });
+        }
+    });
+}
+
+template <class T>
+void launch_one(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part, T) {
+    const PPGeom g = pp_geom(p);
+    // slice-major items (rounds 3 - 4, again since round 6): an XCD's contiguous eighth of the items is part of ONE K slice, so its
+    // L2 streams 1 / S of the packed weights; tile-major (round 5's default) gave it a few tiles with ALL their slices and every L2
+    // streamed the whole weight tensor: FETCH_SIZE x 3.4 at the 5 x 39 level for the same run time (profiles/r5/r5_bf16x3_pmc_fetch_write.txt)
+    const PPArgs q = pp_args(p, g, T::BN, pl.Nb, pl.S, part, ctx.tune.pp_tile_major && pl.S > 1 ? 1 : 0);
+    MAA_CHECK((q.nci + q.cps - 1) / q.cps == pl.S, "igemm_pp: K split leaves an empty slice");
+    MAA_CHECK(pl.S == 1 || pl.slab_floats == (size_t)(q.items * slab_floats(T::MI, T::NI, 512)), "igemm_pp: the plan's slab size is not this tile's");
+    pp_launch<T, false>(ctx, p, q, g.npa);
+    if (pl.S > 1) launch_splitk_reduce(ctx, p, part, pl.S, q.tiles, q.ntiles, pl.Nb, BM, T::BN, T::GWN, T::MI, T::NI, 512);
+}
+
+// Upsample + 3x3 convolution as four 2x2 phase convolutions in one launch (see the kernel's UP2 note).  `p` describes ONE phase:
+// KH = KW = 2, the low-resolution geometry (Hin = Hout, Win = Wout), M = B H W, K = 4 C1, c = the phase-major plane buffer
+// [4][M][ldc]; b_phase = floats between the phases' packed weights.
+template <class T>
+void launch_up2(const Ctx& ctx, const IGemm& p, int Nb, long long b_phase, T) {
+    const PPGeom g = pp_geom(p);
+    PPArgs q = pp_args(p, g, T::BN, Nb, 1, nullptr, 0);
+    q.ph = q.pw = 1;      // (the kernel derives each phase's from its parity)
+    q.padflat = p.Win + 1;
+    q.tiles = q.items = 4 * q.tiles_pp;
+    q.b_phase = b_phase;
+    pp_launch<T, true>(ctx, p, q, g.npa);
 }
 
 
 // ------------------------------------------------------------------------------------------ 1x1 / Linear
 // The same two-group schedule for plain row-major contractions (q/k/v, to_out, proj_in/out, the GEGLU projection, ff.net.2):
 // no halo -- a chunk's A tile is its 256 rows' lines -- so A and the weights share one 3-slot ring [256 + BN lines] and a
-// wave issues NP1 = 4 + NPB pieces per memory phase.  Products are issued per accumulator in the order of the other engines
-// (k ascending; lo.hi, hi.lo, hi.hi per k-step): without a K split the result is bit-identical to theirs, with S slices to
-// the second engine's S-slice result.
+// wave issues NP1 = 4 + NPB pieces per memory phase.  The k-steps are the other engines' in their order (k ascending): without a
+// K split the result is bit-identical to theirs, with S slices to the second engine's S-slice result.
 struct PP1Args {
     int ntiles, tiles;   // N tiles, M tiles x N tiles
     int nchunks, cps;    // 32-deep chunks in all, per K slice
@@ -614,13 +589,9 @@ __global__ __launch_bounds__(512) void igemm_pp1_kernel(const IGemm p, const PP1
     const char* const zero = reinterpret_cast<const char*>(p.zeros);
 
     // fragment offsets inside a stage (tile offsets are multiples of 32 rows: the swizzle depends on lrow only)
-    const int swz = (lrow >> 1) & 7;
     const int a_row = (grp * 128 + wm * (32 * MI) + lrow) * 128, b_row = (BM + wn * (32 * NI) + lrow) * 128;
     int s_off[2][2];
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) s_off[pl][ks] = ((pl * 4 + ks * 2 + lk) ^ swz) << 4;
+    frag_slot_offsets(lrow, lk, s_off);
 
     // copies: piece = 8 rows x 128 B; this wave's pieces of a chunk are A rows 8 (grp 16 + k 4 + wq) .. and weight rows
     // 8 (grp BPG + k 4 + wq) ..; running per-lane source pointers, one 128-byte step per chunk
@@ -666,15 +637,11 @@ __global__ __launch_bounds__(512) void igemm_pp1_kernel(const IGemm p, const PP1
     __syncthreads();
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
     bf16x8 ah[2][MI], al[2][MI], bh[2][NI], bl[2][NI];
 
-    auto load_phase = [&](int j, int slot) __attribute__((always_inline)) {
+    int slot = 0;       // ring slot of the chunk being read
+    auto load_phase = [&](int j) __attribute__((always_inline)) {
         const char* const st = smem + slot * STAGE;
 #pragma unroll
         for (int i = 0; i < MI; ++i)
@@ -698,42 +665,12 @@ __global__ __launch_bounds__(512) void igemm_pp1_kernel(const IGemm p, const PP1
     };
     auto mma_phase = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            if constexpr (TERMS == 3) {
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int jn = 0; jn < NI; ++jn)
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ks][i], bh[ks][jn], acc[i][jn], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int jn = 0; jn < NI; ++jn)
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks][i], bl[ks][jn], acc[i][jn], 0, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int jn = 0; jn < NI; ++jn)
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks][i], bh[ks][jn], acc[i][jn], 0, 0, 0);
-        }
+        for (int ks = 0; ks < 2; ++ks) mma_kstep<TERMS>(acc, ah[ks], al[ks], bh[ks], bl[ks]);
     };
 
-    if (grp == 1) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    int slot = 0;
+    pp_lead_in(grp);
     for (int j = 0; j < NQ; ++j) {
-        load_phase(j, slot);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        mma_phase();
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(grp == 1 && j == NQ - 1)) __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        pp_tick(grp, j, NQ, load_phase, mma_phase);
         if (++slot == NSB) slot = 0;
     }
     wait_vmcnt<0>();
@@ -743,23 +680,14 @@ __global__ __launch_bounds__(512) void igemm_pp1_kernel(const IGemm p, const PP1
     if (q.part == nullptr) {
         igemm_epilogue<MI, NI>(p, acc, row_base, col_base, lrow, lk, 0, q.Nb, rpb);
     } else {
-        float* pp = q.part + ((long long)item * (MI * NI * 4) * 512 + tid) * 4;
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int jn = 0; jn < NI; ++jn)
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    const f32x4 v = {acc[i][jn][4 * qd], acc[i][jn][4 * qd + 1], acc[i][jn][4 * qd + 2], acc[i][jn][4 * qd + 3]};
-                    *reinterpret_cast<f32x4*>(pp + (long long)((i * NI + jn) * 4 + qd) * 512 * 4) = v;
-                }
+        store_slab<MI, NI, 512>(q.part, item, tid, acc);
     }
 }
 
-template <int MI, int NI, int GWM, int GWN>
-void launch_one1(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
+template <class T>
+void launch_one1(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part, T) {
+    constexpr int MI = T::MI, NI = T::NI, BN = T::BN;
     const int Nb = pl.Nb;
-    constexpr int BN = GWN * NI * 32;
     const int ncols = p.N * (p.geglu ? 2 : 1);
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (ncols + BN - 1) / BN;
     PP1Args q;
@@ -770,6 +698,7 @@ void launch_one1(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* par
     q.Nb = Nb;
     q.part = pl.S > 1 ? part : nullptr;
     MAA_CHECK((q.nchunks + q.cps - 1) / q.cps == pl.S, "igemm_pp: K split leaves an empty slice");
+    MAA_CHECK(pl.S == 1 || pl.slab_floats == (size_t)(q.tiles * pl.S * slab_floats(MI, NI, 512)), "igemm_pp1: the plan's slab size is not this tile's");
     MAA_CHECK(!p.geglu || NI % 2 == 0, "GEGLU needs value / gate block pairs inside a wave");
     constexpr size_t lds = (size_t)NSB * (BM + BN) * 128 + 1024;
     static_assert(lds <= 163840, "LDS per workgroup");
@@ -779,10 +708,10 @@ void launch_one1(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* par
         hipLaunchKernelGGL(kern, dim3((unsigned)items), dim3(512), lds, ctx.stream, p, q);
     };
     if (ctx.dtype == 2)
-        go(igemm_pp1_kernel<MI, NI, GWM, GWN, 1>);
+        go(igemm_pp1_kernel<MI, NI, T::GWM, T::GWN, 1>);
     else
-        go(igemm_pp1_kernel<MI, NI, GWM, GWN, 3>);
-    if (pl.S > 1) launch_splitk_reduce(ctx, p, part, pl.S, q.tiles, ntiles, Nb, BM, BN, GWN, MI, NI, 512);
+        go(igemm_pp1_kernel<MI, NI, T::GWM, T::GWN, 3>);
+    if (pl.S > 1) launch_splitk_reduce(ctx, p, part, pl.S, q.tiles, ntiles, Nb, BM, BN, T::GWN, MI, NI, 512);
 }
 }  // namespace
 
@@ -795,28 +724,18 @@ bool igemm_pp_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl) {
     if (!(T >= 3 && T <= 32 && p.sh == 1 && p.sw == 1 && p.up == 0)) return false;
     if (!(2 * p.ph == p.dh * (p.KH - 1) && 2 * p.pw == p.dw * (p.KW - 1))) return false;          // "same" padding, odd kernels
     if (!(p.KH == 1 || p.dh * p.Win >= (p.KW - 1) * p.dw)) return false;                         // tap offsets ascend with t
-    if (!(p.a_split && p.b_split && p.b_nk && p.C2 == 0 && p.C1 % BK == 0 && p.Z == 1 && p.a_act == 0 && !p.geglu)) return false;
+    if (!pp_operands_ok(p)) return false;
     if (p.Hout != p.Hin || p.Wout != p.Win || p.K != T * p.C1 || p.N < 64) return false;
     const PPGeom g = pp_geom(p);
     if (g.npa == 0) return false;
-    auto fits = [&](int bn) { return pp_ring_lines(g, bn) > 0; };
     const int nci = p.C1 / BK;
     int bn = 0, S = 0;
     if (!ctx.tune.pp.empty()) {
         if (ctx.tune.pp[0] == 'o') return false;
         std::sscanf(ctx.tune.pp.c_str(), "%d,%d", &bn, &S);
     }
-    if (bn != 128 && bn != 160) {
-        // 160-wide tiles where they divide N (320, 640, 960, 1280): no padded columns at N = 320, and at N = 640 four K slices
-        // of 4 x 13 tiles make one round of 208 workgroups (profiles/r3_pp_bench_v4_ring.txt); else 128
-        bn = (p.N % 160 == 0 && fits(160)) ? 160 : 128;
-    }
-    if (!fits(bn)) {
-        if (bn == 160 && fits(128))
-            bn = 128;
-        else
-            return false;
-    }
+    bn = pp_tile_width(p.N, [&](int w) { return pp_ring_lines(g, w) > 0; }, bn);
+    if (bn == 0) return false;
     if (S <= 0) {
         if (p.KH == 1) {
             S = 1;      // the vocoders' layers: tens of thousands of rows, thousands of tiles
@@ -837,10 +756,7 @@ bool igemm_pp_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl) {
 void launch_igemm_pp(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
     MAA_CHECK(pl.bn == 128 || pl.bn == 160, "igemm_pp: problem not planned for this engine");
     MAA_CHECK(pl.S == 1 || part != nullptr, "igemm_pp: split-K needs its slab workspace");
-    if (pl.bn == 128)
-        launch_one<2, 2, 2, 2>(ctx, p, pl, part);
-    else
-        launch_one<1, 5, 4, 1>(ctx, p, pl, part);
+    with_pp_tile(pl.bn, [&](auto tile) { launch_one(ctx, p, pl, part, tile); });
 }
 
 
@@ -849,21 +765,18 @@ void launch_igemm_pp(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float*
 bool launch_igemm_pp_up2(const Ctx& ctx, const IGemm& p, int Nb, long long b_phase) {
     if (ctx.dtype == 0 || (!ctx.tune.pp.empty() && ctx.tune.pp[0] == 'o')) return false;
     if (!(p.KH == 2 && p.KW == 2 && p.sh == 1 && p.sw == 1 && p.dh == 1 && p.dw == 1 && p.up == 0)) return false;
-    if (!(p.a_split && p.b_split && p.b_nk && p.C2 == 0 && p.C1 % BK == 0 && p.Z == 1 && p.a_act == 0 && !p.geglu)) return false;
+    if (!pp_operands_ok(p)) return false;
     if (p.Hout != p.Hin || p.Wout != p.Win || p.K != 4 * p.C1 || p.N < 64 || p.C1 / BK < 1) return false;
     const PPGeom g = pp_geom(p);
     if (g.npa == 0) return false;
-    int bn = (p.N % 160 == 0 && pp_ring_lines(g, 160) > 0) ? 160 : 128;
-    if (pp_ring_lines(g, bn) <= 0) return false;
+    const int bn = pp_tile_width(p.N, [&](int w) { return pp_ring_lines(g, w) > 0; });
+    if (bn == 0) return false;
     if (ctx.ws.dry) return true;
     const int terms = ctx.dtype == 2 ? 1 : 3;
     const char* name = terms == 1 ? (bn == 160 ? "igemm_pp_up2_bf16<256x160>" : "igemm_pp_up2_bf16<256x128>")
                                   : (bn == 160 ? "igemm_pp_up2_bf16x3<256x160>" : "igemm_pp_up2_bf16x3<256x128>");
     ProfScope prof(ctx, name, 2.0 * 4.0 * p.M * (double)p.N * p.K, 4.0 * (4.0 * p.K * p.N + 4.0 * p.M * p.N));
-    if (bn == 128)
-        launch_up2<2, 2, 2, 2>(ctx, p, Nb, b_phase);
-    else
-        launch_up2<1, 5, 4, 1>(ctx, p, Nb, b_phase);
+    with_pp_tile(bn, [&](auto tile) { launch_up2(ctx, p, Nb, b_phase, tile); });
     MAA_HIP(hipGetLastError());
     return true;
 }
@@ -902,10 +815,7 @@ bool igemm_pp1_takes(const Ctx& ctx, const IGemm& p, IGemmPlan& pl) {
 void launch_igemm_pp1(const Ctx& ctx, const IGemm& p, const IGemmPlan& pl, float* part) {
     MAA_CHECK(pl.bn == 128 || pl.bn == 160, "igemm_pp1: problem not planned for this engine");
     MAA_CHECK(pl.S == 1 || part != nullptr, "igemm_pp1: split-K needs its slab workspace");
-    if (pl.bn == 128)
-        launch_one1<2, 2, 2, 2>(ctx, p, pl, part);
-    else
-        launch_one1<1, 5, 4, 1>(ctx, p, pl, part);
+    with_pp_tile(pl.bn, [&](auto tile) { launch_one1(ctx, p, pl, part, tile); });
 }
 
 }  // namespace maa
