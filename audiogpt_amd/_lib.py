@@ -87,6 +87,14 @@ class maa_pitch_extractor_config(C.Structure):
                 ("f0_mean", C.c_float), ("f0_std", C.c_float)]
 
 
+class maa_fs2_config(C.Structure):
+    _fields_ = [(k, C.c_int) for k in (
+        "vocab_size", "hidden_size", "enc_layers", "dec_layers", "num_heads", "enc_ffn_kernel_size", "dec_ffn_kernel_size",
+        "dur_predictor_layers", "dur_predictor_kernel", "predictor_hidden", "audio_num_mel_bins",
+        "ffn_padding_same", "ffn_act_gelu", "dur_loss_mse", "rel_pos", "use_pos_embed", "encoder_fft", "decoder_fft",
+        "use_pitch_embed", "use_energy_embed", "use_spk_id", "use_spk_embed", "use_bert")]
+
+
 class maa_encoder_config(C.Structure):
     _fields_ = [("kind", C.c_int), ("layers", C.c_int), ("width", C.c_int), ("heads", C.c_int), ("mlp_dim", C.c_int),
                 ("d_proj", C.c_int), ("vocab", C.c_int), ("max_positions", C.c_int), ("patch", C.c_int),
@@ -138,13 +146,14 @@ EXPORTS = [
     "maa_vocoder_forward", "maa_vocoder_forward_f0", "maa_diffnet_create", "maa_diffnet_destroy", "maa_diffnet_forward",
     "maa_plms_sample", "maa_ds_ddpm_sample", "maa_ds_ddpm_update",
     "maa_pitch_extractor_create", "maa_pitch_extractor_destroy", "maa_pitch_extractor_forward",
+    "maa_fs2_create", "maa_fs2_destroy", "maa_fs2_encode", "maa_fs2_length_regulate", "maa_fs2_decode",
     "maa_encoder_create", "maa_encoder_destroy", "maa_encoder_text", "maa_encoder_image",
     "maa_encoder_text_cls", "maa_clap_audio_create", "maa_clap_audio_destroy", "maa_clap_audio_embed", "maa_clap_similarity",
     "maa_spectral_create", "maa_spectral_destroy", "maa_spectral_forward", "maa_resampler_create", "maa_resampler_destroy",
     "maa_resampler_forward", "maa_op_linear", "maa_op_conv", "maa_op_groupnorm", "maa_op_layernorm",
     "maa_op_attention", "maa_op_attention_ex", "maa_op_conv_transpose1d", "maa_op_snake_aa", "maa_op_bench_conv", "maa_calib",
     "maa_op_mrf_pair", "maa_op_groupnorm_ex", "maa_op_layernorm_ex", "maa_op_split32", "maa_op_igemm_ex",
-    "maa_unet_forward_split", "maa_op_unfold", "maa_op_fold",
+    "maa_unet_forward_split", "maa_op_unfold", "maa_op_fold", "maa_op_attention_masked",
 ]
 
 _lib = None
@@ -205,6 +214,11 @@ def load():
         "maa_pitch_extractor_create": [vp, C.POINTER(maa_pitch_extractor_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
         "maa_pitch_extractor_destroy": [vp],
         "maa_pitch_extractor_forward": [vp, vp, vp, ci, ci, vp, vp, vp],
+        "maa_fs2_create": [vp, C.POINTER(maa_fs2_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+        "maa_fs2_destroy": [vp],
+        "maa_fs2_encode": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
+        "maa_fs2_length_regulate": [vp, vp, vp, ci, ci, ci, vp],
+        "maa_fs2_decode": [vp, vp, vp, vp, ci, ci, ci, vp, vp],
         "maa_encoder_create": [vp, C.POINTER(maa_encoder_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
         "maa_encoder_destroy": [vp],
         "maa_encoder_text": [vp, vp, vp, ci, ci, vp],
@@ -226,6 +240,7 @@ def load():
         "maa_op_layernorm": [vp, vp, ci, ci, fp, fp, cf, vp],
         "maa_op_attention": [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp],
         "maa_op_attention_ex": [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, ci],
+        "maa_op_attention_masked": [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, ci, vp],
         "maa_op_conv_transpose1d": [vp, vp, ci, ci, ci, fp, fp, ci, ci, ci, cf, vp],
         "maa_op_snake_aa": [vp, vp, ci, ci, ci, fp, fp, ci, vp],
         "maa_op_bench_conv": [vp, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)],

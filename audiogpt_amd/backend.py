@@ -211,6 +211,20 @@ class Context:
                                              int(out_split), int(causal)))
         return out
 
+    def op_attention_masked(self, q, ldq, hsq, k, ldk, hsk, v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, out, ldo, key_mask,
+                            out_split=0, causal=0):
+        """maa_op_attention_masked: op_attention_ex with MultiheadAttention's key_padding_mask, key_mask [B, Nk] fp32 on the
+        device, non-zero = hidden from every query of its sample."""
+        for t in (q, k, v, out, key_mask):
+            assert t.is_cuda and t.dtype == torch.float32, (t.device, t.dtype)
+        assert key_mask.is_contiguous() and tuple(key_mask.shape) == (B, Nk), tuple(key_mask.shape)
+        L.check(self.lib.maa_op_attention_masked(self.h, C.c_void_p(q.data_ptr()), int(ldq), int(hsq),
+                                                 C.c_void_p(k.data_ptr()), int(ldk), int(hsk),
+                                                 C.c_void_p(v.data_ptr()), int(ldv), int(hsv), int(B), int(heads), int(dh),
+                                                 int(Nq), int(Nk), float(alpha), C.c_void_p(out.data_ptr()), int(ldo),
+                                                 int(out_split), int(causal), C.c_void_p(key_mask.data_ptr())))
+        return out
+
     def op_groupnorm_ex(self, x1, ld1, C1, x2, ld2, C2, B, HW, groups, gamma, beta, eps, silu, out, out_split=0, raw=None):
         """maa_op_groupnorm_ex: the library's internal GroupNorm call on channels-last device tensors the caller has laid out
         (x1 / x2 / out / raw are fp32 device tensors, possibly views into wider buffers; pitches in floats; x2 None with C2 = 0 for
@@ -1140,6 +1154,118 @@ class PitchExtractor:
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.maa_pitch_extractor_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fs2_config(cfg):
+    """maa_fs2_config of a FastSpeech2MIDI hparams dict (config.FASTSPEECH2_MIDI); refuses what the library does not build, with
+    the reason, before any device is touched."""
+    for k in ("use_pitch_embed", "use_energy_embed", "use_spk_id", "use_spk_embed", "use_bert"):
+        if cfg.get(k, False):
+            raise L.MaaError("FastSpeech2MIDI: %s is not supported: no shipped e2e singing configuration sets it and its branch "
+                             "is not built" % k)
+    for k in ("rel_pos", "use_pos_embed"):
+        if not cfg.get(k, k == "use_pos_embed"):
+            raise L.MaaError("FastSpeech2MIDI: %s must be true: the encoder's positions are RelPositionalEncoding, the only form "
+                             "built" % k)
+    pad = cfg.get("ffn_padding", "SAME")
+    if pad != "SAME":
+        raise L.MaaError("FastSpeech2MIDI: ffn_padding %r is not supported: only 'SAME' (kernel // 2 zeros on both sides) is built, "
+                         "the causal 'LEFT' padding (kernel - 1, 0) is not" % (pad,))
+    if cfg.get("ffn_act", "gelu") != "gelu":
+        raise L.MaaError("FastSpeech2MIDI: ffn_act %r is not supported: only 'gelu' is built into the FFN's epilogue" % (cfg.get("ffn_act"),))
+    if cfg.get("dur_loss", "mse") != "mse":
+        raise L.MaaError("FastSpeech2MIDI: dur_loss %r is not supported: only 'mse' (round(exp(x) - 1)) is built" % (cfg.get("dur_loss"),))
+    for k in ("encoder_type", "decoder_type"):
+        if cfg.get(k, "fft") != "fft":
+            raise L.MaaError("FastSpeech2MIDI: %s %r is not supported: only 'fft' (FFTBlocks) is built" % (k, cfg.get(k)))
+    H, nh = int(cfg["hidden_size"]), int(cfg["num_heads"])
+    if nh < 1 or H != 128 * nh:
+        raise L.MaaError("FastSpeech2MIDI: hidden_size %d / num_heads %d is not 128, the only head width the masked attention is "
+                         "built and tested for" % (H, nh))
+    c = L.maa_fs2_config()
+    for k in ("vocab_size", "hidden_size", "enc_layers", "dec_layers", "num_heads", "enc_ffn_kernel_size", "dec_ffn_kernel_size",
+              "audio_num_mel_bins"):
+        setattr(c, k, int(cfg[k]))
+    c.dur_predictor_layers, c.dur_predictor_kernel = int(cfg.get("dur_predictor_layers", 5)), int(cfg.get("dur_predictor_kernel", 3))
+    c.predictor_hidden = int(cfg.get("predictor_hidden", -1))
+    c.ffn_padding_same = c.ffn_act_gelu = c.dur_loss_mse = c.rel_pos = c.use_pos_embed = c.encoder_fft = c.decoder_fft = 1
+    return c
+
+
+class FastSpeech2MIDI:
+    """maa_fs2 handle: DiffSinger's FastSpeech2MIDI front end (NeuralSeq/modules/diffsinger_midi/fs2.py:46-118).  Integer tensors
+    cross the boundary as int32; nothing here reads the device."""
+
+    def __init__(self, ctx, cfg, state_dict):
+        self.ctx, self.cfg = ctx, dict(cfg)
+        c = fs2_config(self.cfg)
+        arr, n, keep = L.tensor_list(state_dict)
+        h = C.c_void_p()
+        with ctx.lock:
+            L.check(ctx.lib.maa_fs2_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
+        self.h = h
+
+    def _i32(self, t):
+        return torch.as_tensor(t).to(device=self.ctx.device, dtype=torch.int32).contiguous()
+
+    @staticmethod
+    def _p(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    def encode(self, txt_tokens, pitch_midi, midi_dur=None, is_slur=None):
+        """[B, T] tokens and note features -> (encoder_out [B, T, H], xs [B, T], dur int32 [B, T], totals int32 [B])."""
+        tok, midi = self._i32(txt_tokens), self._i32(pitch_midi)
+        B, T = tok.shape
+        dur_f = _f32(midi_dur, self.ctx.device) if midi_dur is not None else None
+        slur = self._i32(is_slur) if is_slur is not None else None
+        for name, t in (("pitch_midi", midi), ("midi_dur", dur_f), ("is_slur", slur)):
+            if t is not None and tuple(t.shape) != (B, T):
+                raise L.MaaError("FastSpeech2MIDI.encode: %s %s is not txt_tokens' [%d, %d]" % (name, tuple(t.shape), B, T))
+        dev = self.ctx.device
+        enc = torch.empty(B, T, self.cfg["hidden_size"], device=dev)
+        xs = torch.empty(B, T, device=dev)
+        dur = torch.empty(B, T, dtype=torch.int32, device=dev)
+        totals = torch.empty(B, dtype=torch.int32, device=dev)
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_fs2_encode(self.ctx.h, self.h, self._p(tok), self._p(midi), self._p(dur_f), self._p(slur), B, T,
+                                                self._p(enc), self._p(xs), self._p(dur), self._p(totals)))
+        return enc, xs, dur, totals
+
+    def length_regulate(self, dur, T_mel):
+        """dur int32 [B, T] -> mel2ph int32 [B, T_mel]."""
+        dur = self._i32(dur)
+        B, T = dur.shape
+        mel2ph = torch.empty(B, int(T_mel), dtype=torch.int32, device=self.ctx.device)
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_fs2_length_regulate(self.ctx.h, self.h, self._p(dur), B, T, int(T_mel), self._p(mel2ph)))
+        return mel2ph
+
+    def decode(self, encoder_out, mel2ph, skip_decoder=False):
+        """encoder_out [B, T, H], mel2ph [B, T_mel] -> (decoder_inp [B, T_mel, H], mel_out [B, T_mel, mel bins] or None)."""
+        enc = _f32(encoder_out, self.ctx.device)
+        m2p = self._i32(mel2ph)
+        B, T, _ = enc.shape
+        if m2p.dim() != 2 or m2p.shape[0] != B or m2p.shape[1] < 1:
+            raise L.MaaError("FastSpeech2MIDI.decode: mel2ph %s is not [%d, T_mel]" % (tuple(m2p.shape), B))
+        T_mel = int(m2p.shape[1])
+        dev = self.ctx.device
+        dec_inp = torch.empty(B, T_mel, self.cfg["hidden_size"], device=dev)
+        mel = None if skip_decoder else torch.empty(B, T_mel, self.cfg["audio_num_mel_bins"], device=dev)
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_fs2_decode(self.ctx.h, self.h, self._p(enc), self._p(m2p), B, T, T_mel, self._p(dec_inp),
+                                                self._p(mel)))
+        return dec_inp, mel
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.maa_fs2_destroy(self.h)
             self.h = None
 
     def __del__(self):

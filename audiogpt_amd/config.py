@@ -118,6 +118,17 @@ DIFFSINGER_DS100_ADJ_REL = dict(DIFFSINGER_POPCS_BETA6, dilation_cycle_length=4,
 PITCH_EXTRACTOR = dict(n_mel_bins=80, hidden_size=256, predictor_hidden=-1, predictor_kernel=5, ffn_padding="SAME", conv_layers=2,
                        pitch_type="frame", use_uv=True, pitch_norm="log", f0_mean=0.0, f0_std=1.0)
 
+# FastSpeech2MIDI of the e2e singing configurations (midi/e2e/opencpop/ds1000.yaml, ds1000-10dil.yaml, ds100_adj_rel.yaml,
+# midi/e2e/popcs/ds100_adj_rel.yaml): the hparams modules/diffsinger_midi/fs2.py and modules/fastspeech/fs2.py read, with the values
+# those files resolve to over egs_bases/tts/fs2.yaml and base.yaml (rel_pos true in the e2e files; use_pitch_embed false there: the
+# pitch comes from the extractor after the diffusion).  vocab_size = len(phone_encoder) of the checkpoint's dictionary -- a
+# placeholder here, the dictionary is not shipped; index 0 is the padding token.
+FASTSPEECH2_MIDI = dict(vocab_size=64, hidden_size=256, enc_layers=4, dec_layers=4, num_heads=2, enc_ffn_kernel_size=9,
+                        dec_ffn_kernel_size=9, dur_predictor_layers=5, dur_predictor_kernel=3, predictor_hidden=-1,
+                        audio_num_mel_bins=80, ffn_padding="SAME", ffn_act="gelu", dur_loss="mse", rel_pos=True, use_pos_embed=True,
+                        encoder_type="fft", decoder_type="fft", use_pitch_embed=False, use_energy_embed=False, use_spk_id=False,
+                        use_spk_embed=False, use_bert=False)
+
 # BigVGAN's args.yml (vocoder/logs/bigv16k53w) does not ship with the reference
 # (SURVEY.md section 0.3); these are the generator defaults it is exercised with here.
 BIGVGAN_16K = dict(

@@ -29,6 +29,9 @@ struct maa_diffnet {
 struct maa_pitch_extractor {
     std::unique_ptr<maa::PitchExtractor> m;
 };
+struct maa_fs2 {
+    std::unique_ptr<maa::FastSpeech2MIDI> m;
+};
 struct maa_encoder {
     std::unique_ptr<maa::Encoder> m;
 };
@@ -530,6 +533,75 @@ int maa_pitch_extractor_forward(maa_ctx* ctx, maa_pitch_extractor* pe, const flo
     });
 }
 
+// ------------------------------------------------------------------------------------------ DiffSinger FastSpeech2MIDI
+int maa_fs2_create(maa_ctx* ctx, const maa_fs2_config* cfg, const maa_tensor* tensors, int n_tensors, maa_fs2** out) {
+    return guarded([&] {
+        MAA_CHECK(cfg && out, "bad fs2_create arguments: null pointer");
+        // (a configuration that cannot run is refused before the device is touched)
+        MAA_CHECK(!cfg->use_pitch_embed, "FastSpeech2MIDI: hparams['use_pitch_embed'] is not built -- no shipped e2e singing configuration sets it");
+        MAA_CHECK(!cfg->use_energy_embed, "FastSpeech2MIDI: hparams['use_energy_embed'] is not built -- no shipped e2e singing configuration sets it");
+        MAA_CHECK(!cfg->use_spk_id && !cfg->use_spk_embed,
+                  "FastSpeech2MIDI: hparams['use_spk_id'] / ['use_spk_embed'] are not built -- no shipped e2e singing configuration sets them");
+        MAA_CHECK(!cfg->use_bert, "FastSpeech2MIDI: hparams['use_bert'] is not built -- no shipped e2e singing configuration sets it");
+        MAA_CHECK(cfg->rel_pos != 0 && cfg->use_pos_embed != 0,
+                  "FastSpeech2MIDI: hparams['rel_pos'] and ['use_pos_embed'] must be true -- only RelPositionalEncoding is built for the encoder");
+        MAA_CHECK(cfg->ffn_padding_same != 0,
+                  "FastSpeech2MIDI: hparams['ffn_padding'] must be 'SAME' -- the causal 'LEFT' padding (kernel - 1, 0) is not built");
+        MAA_CHECK(cfg->ffn_act_gelu != 0, "FastSpeech2MIDI: hparams['ffn_act'] must be 'gelu' -- the only activation built into the FFN's epilogue here");
+        MAA_CHECK(cfg->dur_loss_mse != 0, "FastSpeech2MIDI: hparams['dur_loss'] must be 'mse' -- out2dur's other branches are not built");
+        MAA_CHECK(cfg->encoder_fft != 0 && cfg->decoder_fft != 0, "FastSpeech2MIDI: hparams['encoder_type'] / ['decoder_type'] must be 'fft'");
+        MAA_CHECK(cfg->num_heads > 0 && cfg->hidden_size == 128 * cfg->num_heads,
+                  "FastSpeech2MIDI: hidden_size / num_heads must be 128 -- the only head width the masked attention is built and tested for");
+        MAA_CHECK(cfg->vocab_size > 0 && cfg->enc_layers >= 0 && cfg->dec_layers >= 0 && cfg->hidden_size <= 1024 &&
+                      cfg->audio_num_mel_bins > 0 && cfg->audio_num_mel_bins % 4 == 0,
+                  "bad FastSpeech2MIDI config: vocab_size > 0, layer counts >= 0, hidden_size <= 1024, audio_num_mel_bins a multiple of 4");
+        MAA_CHECK(cfg->enc_ffn_kernel_size >= 1 && cfg->enc_ffn_kernel_size % 2 == 1 && cfg->dec_ffn_kernel_size >= 1 &&
+                      cfg->dec_ffn_kernel_size % 2 == 1 && cfg->dur_predictor_kernel >= 1 && cfg->dur_predictor_kernel % 2 == 1,
+                  "bad FastSpeech2MIDI config: the FFN and predictor kernels must be odd ('SAME' padding keeps the length only then)");
+        MAA_CHECK(cfg->dur_predictor_layers >= 1 && cfg->predictor_hidden <= 1024 && (cfg->predictor_hidden <= 0 || cfg->predictor_hidden % 4 == 0),
+                  "bad FastSpeech2MIDI config: dur_predictor_layers >= 1, predictor_hidden a multiple of 4 (or <= 0 for hidden_size), at most 1024");
+        bind(ctx);
+        auto sd = to_state_dict(tensors, n_tensors);
+        auto* p = new maa_fs2;
+        try {
+            p->m.reset(new maa::FastSpeech2MIDI(*cfg, sd, ctx->c.dtype));
+        } catch (...) {
+            delete p;
+            throw;
+        }
+        *out = p;
+    });
+}
+int maa_fs2_destroy(maa_fs2* fs2) {
+    return guarded([&] { delete fs2; });
+}
+int maa_fs2_encode(maa_ctx* ctx, maa_fs2* fs2, const int* d_tokens, const int* d_pitch_midi, const float* d_midi_dur,
+                   const int* d_is_slur, int B, int T, float* d_encoder_out, float* d_xs, int* d_dur, int* d_totals) {
+    return guarded([&] {
+        MAA_CHECK(ctx && fs2 && d_tokens && d_pitch_midi && d_encoder_out && d_xs && d_dur && d_totals, "bad fs2_encode arguments: null pointer");
+        MAA_CHECK(B > 0 && T > 0 && (long long)B * T < (1LL << 31) / 4096, "bad fs2_encode arguments: B, T");
+        bind(ctx);
+        fs2->m->encode(ctx->c, d_tokens, d_pitch_midi, d_midi_dur, d_is_slur, B, T, d_encoder_out, d_xs, d_dur, d_totals);
+    });
+}
+int maa_fs2_length_regulate(maa_ctx* ctx, maa_fs2* fs2, const int* d_dur, int B, int T, int T_mel, int* d_mel2ph) {
+    return guarded([&] {
+        MAA_CHECK(ctx && fs2 && d_dur && d_mel2ph, "bad fs2_length_regulate arguments: null pointer");
+        MAA_CHECK(B > 0 && T > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_length_regulate arguments: B, T, T_mel");
+        bind(ctx);
+        fs2->m->length_regulate(ctx->c, d_dur, B, T, T_mel, d_mel2ph);
+    });
+}
+int maa_fs2_decode(maa_ctx* ctx, maa_fs2* fs2, const float* d_encoder_out, const int* d_mel2ph, int B, int T, int T_mel,
+                   float* d_decoder_inp, float* d_mel_out) {
+    return guarded([&] {
+        MAA_CHECK(ctx && fs2 && d_encoder_out && d_mel2ph && d_decoder_inp, "bad fs2_decode arguments: null pointer");
+        MAA_CHECK(B > 0 && T > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_decode arguments: B, T, T_mel");
+        bind(ctx);
+        fs2->m->decode(ctx->c, d_encoder_out, d_mel2ph, B, T, T_mel, d_decoder_inp, d_mel_out);
+    });
+}
+
 // ------------------------------------------------------------------------------------------ conditioning encoders
 int maa_encoder_create(maa_ctx* ctx, const maa_encoder_config* cfg, const maa_tensor* tensors, int n_tensors,
                        maa_encoder** out) {
@@ -905,6 +977,24 @@ int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const 
         maa::run_sized(c, [&] {
             maa::attention_into(c, d_q, ldq, hsq, d_k, ldk, hsk, d_v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, d_y, ldo,
                                 out_split, causal);
+        });
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
+int maa_op_attention_masked(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const float* d_k, int ldk, int hsk,
+                            const float* d_v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
+                            float* d_y, int ldo, int out_split, int causal, const float* d_key_mask) {
+    return guarded([&] {
+        MAA_CHECK(ctx && d_q && d_k && d_v && d_y && d_key_mask, "bad op_attention_masked arguments");
+        MAA_CHECK(B > 0 && heads > 0 && dh > 0 && Nq > 0 && Nk > 0, "bad op_attention_masked sizes");
+        MAA_CHECK(ldq >= dh && ldk >= dh && ldv >= dh && hsq >= 0 && hsk >= 0 && hsv >= 0 && ldo >= heads * dh,
+                  "bad op_attention_masked strides");
+        bind(ctx);
+        maa::Ctx& c = ctx->c;
+        maa::run_sized(c, [&] {
+            maa::attention_into(c, d_q, ldq, hsq, d_k, ldk, hsk, d_v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, d_y, ldo,
+                                out_split, causal, d_key_mask);
         });
         MAA_HIP(hipStreamSynchronize(c.stream));
     });

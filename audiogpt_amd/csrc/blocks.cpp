@@ -171,10 +171,11 @@ void linear_into(Ctx& ctx, const float* a, int lda, long long rows, int K, const
 
 void attention_into(Ctx& ctx, const float* q, int ldq, int hsq, const float* k, int ldk, int hsk, const float* v,
                     int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha, float* out, int ldo,
-                    int out_split, int causal) {
+                    int out_split, int causal, const float* key_mask) {
     MAA_CHECK(!causal || Nq == Nk, "causal attention needs Nq == Nk");
+    MAA_CHECK(!causal || !key_mask, "attention takes a causal mask or a key mask, not both");
     if (launch_flash_attention(ctx, q, ldq, hsq, k, ldk, hsk, v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, out, ldo,
-                               out_split, causal))
+                               out_split, causal, key_mask))
         return;
     MAA_CHECK(!out_split, "split32 attention output needs the fused kernel");
     const size_t mk = ctx.ws.mark();
@@ -202,7 +203,10 @@ void attention_into(Ctx& ctx, const float* q, int ldq, int hsq, const float* k, 
     p.c = S;
     p.ldc = ldS;
     launch_igemm(ctx, p);
-    launch_softmax(ctx, S, (long long)B * heads * Nq, Nk, ldS, causal ? Nq : 0);
+    if (key_mask)
+        launch_softmax_masked(ctx, S, (long long)B * heads * Nq, Nk, ldS, key_mask, (long long)heads * Nq);
+    else
+        launch_softmax(ctx, S, (long long)B * heads * Nq, Nk, ldS, causal ? Nq : 0);
     IGemm r;
     r.a1 = S;
     r.lda1 = ldS;

@@ -74,8 +74,10 @@ void linear_into(Ctx& ctx, const float* a, int lda, long long rows, int K, const
 //   out: [B, Nq, heads*dh] dense
 void attention_into(Ctx& ctx, const float* q, int ldq, int hsq, const float* k, int ldk, int hsk, const float* v,
                     int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha, float* out, int ldo,
-                    int out_split = 0, int causal = 0);
+                    int out_split = 0, int causal = 0, const float* key_mask = nullptr);
 // causal: query i attends to keys 0 .. i only (Nq == Nk)
+// key_mask [B, Nk]: a key whose entry is non-zero is hidden from every query of its sample (MultiheadAttention's key_padding_mask,
+//   weight exactly 0); a sample with no visible key is written as zeros.  Not together with causal.
 // out_split: write split32 rows (only where flash_attention_covers(ctx, dh))
 
 // In the bf16 modes a normalisation whose only consumer is a bf16-engine contraction writes bf16 hi/lo planes

@@ -14,6 +14,8 @@
 //                  the k-slot -> key map of the MFMA is free as long as A and B agree, so P never moves between
 //                  lanes; the running rescale exp(m_old - m_new) is one scalar per lane.
 // O^T is transposed through LDS at the end so that the output rows are written as contiguous runs of d.
+// The MASKED instantiations (d = 128) add MultiheadAttention's key_padding_mask for DiffSinger's FastSpeech2 blocks
+// (modules/commons/common_layers.py:541-587 with :165-293); the others are unchanged by it.
 #include "igemm_device.h"
 #include "maa_internal.h"
 
@@ -36,6 +38,7 @@ struct FlashArgs {
     int qtiles;                   // 128-query tiles per (sample, head)
     long long o_bs;
     const float* zeros;
+    const float* key_mask;        // MASKED kernels: [B, Nk], non-zero = the key is hidden from every query of its sample
 };
 
 namespace {
@@ -61,7 +64,11 @@ __device__ __forceinline__ bf16x8 as_bf16x8(const Frag& f) { return __builtin_bi
 // (round 6: five-wave workgroups of 160 query rows where that takes fewer waves -- 780 tokens: 5 x 5 waves instead of 7 x 4 with
 // three of them empty, each K / V tile staged for five waves -- measured 0.6 % SLOWER end to end, two workgroups per CU instead of
 // three: profiles/r6_call12_flash5_ab.txt)
-template <int DH, int TERMS>
+// MASKED (key_padding_mask of the FastSpeech2 blocks, d = 128): a hidden key is a score of -inf before the running maximum, so
+// its weight is exactly 0 whatever its logit.  The mask belongs to the sample, not the query: a tile whose 32 keys are all hidden
+// (or past Nk) is skipped by every wave, and in a tile that is not, every query sees a key -- the maximum is finite whenever
+// it is used, and exp2(-inf - -inf) never arises.  A sample with no visible key keeps l = 0 and is written as zeros.
+template <int DH, int TERMS, bool MASKED = false>
 __global__ __launch_bounds__(NT, 1) void flash_attn_kernel(const FlashArgs a) {
     constexpr int DK = (DH + 15) / 16 * 16;      // head dim padded to the MFMA k-step
     constexpr int DM = (DH + 31) / 32 * 32;      // rows of O^T
@@ -205,6 +212,21 @@ __global__ __launch_bounds__(NT, 1) void flash_attn_kernel(const FlashArgs a) {
         }
     };
 
+    // bit r: this lane's key r of tile kt (kt*32 + (r&3) + 8*(r>>2) + 4*lh) is hidden or past Nk; fetched a tile ahead like K / V
+    auto load_hidden = [&](int kt) {
+        unsigned hbits = 0u;
+        if constexpr (MASKED) {
+            const float* mp = a.key_mask + (long long)b * a.Nk;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = kt * KT + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const float mv = key < a.Nk ? mp[key] : 1.f;
+                hbits |= mv != 0.f ? 1u << r : 0u;
+            }
+        }
+        return hbits;
+    };
+
     f32x16 oacc[MB];
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
@@ -213,6 +235,7 @@ __global__ __launch_bounds__(NT, 1) void flash_attn_kernel(const FlashArgs a) {
     float m_run = -INFINITY, l_run = 0.f;
 
     const int ntiles = (a.Nk + KT - 1) / KT;
+    [[maybe_unused]] unsigned hid_next = load_hidden(0);
     load_tile(0);
     __syncthreads();          // zero fill complete
     store_tile(0);
@@ -223,8 +246,14 @@ __global__ __launch_bounds__(NT, 1) void flash_attn_kernel(const FlashArgs a) {
         load_tile(kt + 1);                         // past the end: every element masked -> zeros
         const unsigned short* base = smem + buf * BUF;
         const unsigned short* vt = base + PL * K_PLANE;
+        [[maybe_unused]] const unsigned hid = hid_next;
+        bool tile_live = true;
+        if constexpr (MASKED) {
+            hid_next = load_hidden(kt + 1);
+            tile_live = !__all(hid == 0xffffu);      // the two halves of a wave hold all 32 keys: workgroup-uniform
+        }
 
-        if (wave_live) {      // a wave whose 32 query rows all lie past Nq (the 780 = 6 x 128 + 12 tail) only helps stage K / V
+        if (wave_live && tile_live) {      // a wave whose 32 query rows all lie past Nq (the 780 = 6 x 128 + 12 tail) only helps stage K / V
             // ---- S^T = K_tile . Q^T
             f32x16 sacc;
     #pragma unroll
@@ -245,7 +274,13 @@ __global__ __launch_bounds__(NT, 1) void flash_attn_kernel(const FlashArgs a) {
             // mask needs the per-key test (uniform branch)
             float p[16];
             float mt = -INFINITY;
-            if (!a.causal && (kt + 1) * KT <= a.Nk) {
+            if constexpr (MASKED) {
+    #pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    p[r] = (hid >> r) & 1u ? -INFINITY : sacc[r];
+                    mt = fmaxf(mt, p[r]);
+                }
+            } else if (!a.causal && (kt + 1) * KT <= a.Nk) {
     #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     p[r] = sacc[r];
@@ -324,7 +359,8 @@ __global__ __launch_bounds__(NT, 1) void flash_attn_kernel(const FlashArgs a) {
 
     // ---- normalise and transpose O^T through LDS (wave-private 32 x (DM+1) floats), then write rows of d
     float* ot = reinterpret_cast<float*>(smem) + wid * 32 * (DM + 1);
-    const float inv = 1.f / l_run;
+    float inv = 1.f / l_run;
+    if constexpr (MASKED) inv = l_run > 0.f ? inv : 0.f;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -357,13 +393,13 @@ __global__ __launch_bounds__(NT, 1) void flash_attn_kernel(const FlashArgs a) {
     }
 }
 
-template <int DH, int TERMS>
+template <int DH, int TERMS, bool MASKED = false>
 void launch_dh(const Ctx& ctx, const FlashArgs& a, int B) {
     constexpr int DK = (DH + 15) / 16 * 16, DM = (DH + 31) / 32 * 32, PL = TERMS == 1 ? 1 : 2;
     constexpr size_t kv = (size_t)2 * PL * (KT * (DK + 8) + DM * (KT + 4)) * sizeof(unsigned short);
     constexpr size_t tr = (size_t)4 * 32 * (DM + 1) * sizeof(float);
     constexpr size_t lds = kv > tr ? kv : tr;
-    auto kern = flash_attn_kernel<DH, TERMS>;
+    auto kern = flash_attn_kernel<DH, TERMS, MASKED>;
     ensure_dynamic_lds(reinterpret_cast<const void*>(kern), ctx.device, (int)lds);
     dim3 grid((unsigned)(a.qtiles * B * a.heads));
     hipLaunchKernelGGL(kern, grid, dim3(NT), lds, ctx.stream, a);
@@ -375,11 +411,12 @@ bool flash_attention_covers(const Ctx& ctx, int dh) {
     return ctx.dtype != 0 && (dh == 32 || dh == 40 || dh == 64 || dh == 80);
 }
 
-// false: shape not covered (head dim other than 32 / 40 / 64 / 80, unaligned rows) -> caller uses the GEMM path
+// false: shape not covered (head dim other than 32 / 40 / 64 / 80 -- with a key mask: other than 128 --, unaligned rows) -> caller
+// uses the GEMM path
 bool launch_flash_attention(const Ctx& ctx, const float* q, int ldq, int hsq, const float* k, int ldk, int hsk,
                             const float* v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
-                            float* out, int ldo, int out_split, int causal) {
-    if (!flash_attention_covers(ctx, dh)) return false;
+                            float* out, int ldo, int out_split, int causal, const float* key_mask) {
+    if (key_mask ? ctx.dtype == 0 || dh != 128 || causal : !flash_attention_covers(ctx, dh)) return false;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (ldq % 4 || ldk % 4 || ldv % 4 || hsq % 4 || hsk % 4 || hsv % 4 || !al16(q) || !al16(k) || !al16(v)) return false;
     if (ctx.ws.dry) return true;
@@ -406,11 +443,20 @@ bool launch_flash_attention(const Ctx& ctx, const float* q, int ldq, int hsq, co
     a.causal = causal;
     a.o_bs = (long long)Nq * ldo;
     a.zeros = ctx.zeros;
+    a.key_mask = key_mask;
     a.qtiles = (Nq + 127) / 128;
     const double flops = 4.0 * B * heads * (double)Nq * Nk * dh;
     const double bytes = 4.0 * B * heads * ((double)2 * Nq * dh + 2.0 * Nk * dh);
     ProfScope prof(ctx, "flash_attention", flops, bytes);
     const int terms = ctx.dtype == 1 ? 3 : 1;
+    if (key_mask) {
+        if (terms == 3)
+            launch_dh<128, 3, true>(ctx, a, B);
+        else
+            launch_dh<128, 1, true>(ctx, a, B);
+        MAA_HIP(hipGetLastError());
+        return true;
+    }
 #define MAA_FLASH(DHV)                                 \
     if (terms == 3)                                    \
         launch_dh<DHV, 3>(ctx, a, B);                  \

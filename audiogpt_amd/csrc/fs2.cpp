@@ -1,0 +1,292 @@
+// DiffSinger's FastSpeech2MIDI on the device: tokens + note features -> encoder_out and durations (encode), durations -> mel2ph
+// (length_regulate), encoder_out + mel2ph -> decoder_inp and the coarse mel (decode): what DiffSingerE2EInfer.forward_model
+// runs before the diffusion (NeuralSeq/inference/svs/ds_e2e.py, modules/diff/shallow_diffusion_tts.py:244-251).
+//
+// Mirrors NeuralSeq/modules/diffsinger_midi/fs2.py:11-118 (FastspeechMIDIEncoder, FastSpeech2MIDI), modules/fastspeech/fs2.py:22-72,
+// 140-163,222-226 (FastSpeech2: add_dur, run_decoder), modules/fastspeech/tts_modules.py:59-143 (DurationPredictor), :179-214
+// (LengthRegulator), :276-384 (FFTBlocks, FastspeechEncoder, FastspeechDecoder), modules/commons/common_layers.py:485-587
+// (TransformerFFNLayer, EncSALayer) with :165-293 (MultiheadAttention, bias = False) and espnet_positional_embedding.py:14-45,89-113.
+// Layout: channels-last rows [B*T, C]; the FFN's Conv1d(H, 4H, k) and the predictor's Conv1d are implicit GEMMs over the rows with
+// zero padding per sample, GELU / ReLU their epilogue; in_proj / out_proj / ffn_2 / mel_out are plain GEMMs; the attention is the
+// masked kernel at head width 128.  What lies between is fs2.hip and the row kernels shared with the pitch extractor.
+//   * ffn_1's `* kernel_size ** -0.5` sits between its bias and the GELU: alpha of the GEMM, with the bias scaled once on the host
+//   * a padding row is NOT zero where in_proj and ffn_1 read it: LayerNorm of a zero row is its bias, and through the k-wide
+//     convolution that reaches the live neighbours, as in the reference.  Rows are masked where the reference masks them, no earlier
+//   * one FFTBlocks serves the encoder (mask = token 0) and the decoder (mask = an all-zero decoder_inp row, found on the device)
+// The three entry points issue launches on the context's stream only: no device-to-host copy, no synchronisation.  T_mel sizes
+// decode's outputs, so the caller reads the B totals between encode and decode -- the one read per utterance.
+#include "models.h"
+
+#include <cmath>
+#include <vector>
+
+namespace maa {
+
+void launch_fs2_embed(const Ctx& ctx, const int* tok, const int* midi, const float* midi_dur, const int* slur, const float* E, int vocab,
+                      const float* Mi, const float* dw, const float* db, const float* S, const float* pe, float scale, int B, int T, int H,
+                      float* x, float* nonpad, float* hidden);
+void launch_fs2_hidden(const Ctx& ctx, const float* nonpad, long long n, float* hidden);
+void launch_fs2_dur_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
+                         const float* w, const float* bias, const float* nonpad, float* xs, int* dur);
+void launch_fs2_length(Ctx& ctx, const int* dur, int B, int T, int* totals, int T_mel, int* mel2ph);
+void launch_fs2_expand(const Ctx& ctx, const float* enc, const int* mel2ph, int B, int T, int T_mel, int H, float* out, float* tgt);
+
+namespace {
+
+constexpr int FS2_REL_MAX_LEN = 5000, FS2_TABLE_INIT = 2000, FS2_MIDI_ROWS = 300;
+constexpr float FS2_EPS = 1e-5f;
+
+// RelPositionalEncoding's table (espnet_positional_embedding.py:24-45 with reverse = True) in fp32: row i holds position
+// max_len - 1 - i, sin on the even columns and cos on the odd ones
+std::vector<float> rel_pos_table(int max_len, int dim) {
+    std::vector<float> div(dim / 2), tab((size_t)max_len * dim);
+    const float step = (float)-(std::log(10000.0) / (double)dim);
+    for (int j = 0; j < dim / 2; ++j) div[j] = std::exp((float)(2 * j) * step);
+    for (int i = 0; i < max_len; ++i)
+        for (int j = 0; j < dim / 2; ++j) {
+            const float a = (float)(max_len - 1 - i) * div[j];
+            tab[(size_t)i * dim + 2 * j] = std::sin(a);
+            tab[(size_t)i * dim + 2 * j + 1] = std::cos(a);
+        }
+    return tab;
+}
+
+inline T4 seq(float* p, int B, int T, int C) {
+    T4 t;
+    t.p = p;
+    t.B = B;
+    t.H = 1;
+    t.W = T;
+    t.C = C;
+    return t;
+}
+
+struct FFTLayer {
+    float *ln1w, *ln1b, *ln2w, *ln2b;
+    PackedW in_proj, out_proj, ffn1, ffn2;
+};
+
+// FFTBlocks from the first mask on (tts_modules.py:320-326): EncSALayer x n, the last LayerNorm, each times the mask
+struct FFTBlocks {
+    std::vector<FFTLayer> layers;
+    float *lnw = nullptr, *lnb = nullptr;
+    int H = 0, heads = 0, kernel = 0;
+
+    void build(WeightStore& ws, const StateDict& sd, const std::string& name, int n_layers, int hidden, int n_heads, int k) {
+        H = hidden;
+        heads = n_heads;
+        kernel = k;
+        const float s = 1.f / std::sqrt((float)k);
+        for (int i = 0; i < n_layers; ++i) {
+            const std::string p = name + ".layers." + std::to_string(i) + ".op.";
+            FFTLayer l;
+            MAA_CHECK(get(sd, p + "layer_norm1.weight").numel() == H && get(sd, p + "layer_norm2.weight").numel() == H, "FFTBlocks LayerNorm shape " + p);
+            l.ln1w = ws.vec(sd, p + "layer_norm1.weight");
+            l.ln1b = ws.vec(sd, p + "layer_norm1.bias");
+            l.ln2w = ws.vec(sd, p + "layer_norm2.weight");
+            l.ln2b = ws.vec(sd, p + "layer_norm2.bias");
+            l.in_proj = ws.pack_conv(sd, p + "self_attn.in_proj_weight", "", 1, 1);
+            l.out_proj = ws.pack_conv(sd, p + "self_attn.out_proj.weight", "", 1, 1);
+            MAA_CHECK(l.in_proj.N == 3 * H && l.in_proj.K == H && l.out_proj.N == H && l.out_proj.K == H, "FFTBlocks attention shape " + p);
+            l.ffn1 = ws.pack_conv(sd, p + "ffn.ffn_1.weight", "", 1, k);
+            MAA_CHECK(l.ffn1.N == 4 * H && l.ffn1.K == k * H, "FFTBlocks ffn_1 shape " + p);
+            const HostTensor& b1 = get(sd, p + "ffn.ffn_1.bias");
+            MAA_CHECK(b1.numel() == 4 * H, "FFTBlocks ffn_1 bias shape " + p);
+            std::vector<float> hb(l.ffn1.Npad, 0.f);
+            for (int c = 0; c < 4 * H; ++c) hb[c] = b1.data[c] * s;          // gelu((conv + b) * s) = gelu(s * conv + s * b)
+            l.ffn1.bias = ws.upload(hb);
+            l.ffn2 = ws.pack_conv(sd, p + "ffn.ffn_2.weight", p + "ffn.ffn_2.bias", 1, 1);
+            MAA_CHECK(l.ffn2.N == H && l.ffn2.K == 4 * H, "FFTBlocks ffn_2 shape " + p);
+            layers.push_back(l);
+        }
+        MAA_CHECK(get(sd, name + ".layer_norm.weight").numel() == H, "FFTBlocks last LayerNorm shape " + name);
+        lnw = ws.vec(sd, name + ".layer_norm.weight");
+        lnb = ws.vec(sd, name + ".layer_norm.bias");
+    }
+
+    // x [B*T, H], already times nonpad, is overwritten; out [B*T, H].  nonpad / hidden [B*T]: 1 / 0 and 0 / 1 on a live / padding row
+    void forward(Ctx& ctx, float* x, int B, int T, const float* nonpad, const float* hidden, float* out) const {
+        const long long rows = (long long)B * T;
+        const int dh = H / heads;
+        float* a = ctx.ws.alloc_f((size_t)rows * H);
+        float* y = ctx.ws.alloc_f((size_t)rows * H);
+        float* wide = ctx.ws.alloc_f((size_t)rows * 4 * H);          // qkv [rows, 3H], then the FFN's [rows, 4H]
+        for (const FFTLayer& l : layers) {
+            launch_layernorm(ctx, x, rows, H, l.ln1w, l.ln1b, FS2_EPS, a);
+            linear_into(ctx, a, H, rows, H, l.in_proj, nullptr, 0, wide, 3 * H);
+            attention_into(ctx, wide, 3 * H, dh, wide + H, 3 * H, dh, wide + 2 * H, 3 * H, dh, B, heads, dh, T, T,
+                           1.f / std::sqrt((float)dh), a, H, 0, 0, hidden);
+            linear_into(ctx, a, H, rows, H, l.out_proj, x, H, y, H);
+            launch_pe_affine_mask(ctx, y, rows, H, nullptr, nullptr, nonpad, x);
+            launch_layernorm(ctx, x, rows, H, l.ln2w, l.ln2b, FS2_EPS, a);
+            T4 ta = seq(a, B, T, H), tw = seq(wide, B, T, 4 * H);
+            ConvOpt co;
+            co.KW = kernel;
+            co.pad = (kernel - 1) / 2;
+            co.pad_h = 0;
+            co.act = 3;
+            co.alpha = 1.f / std::sqrt((float)kernel);
+            conv_into(ctx, ta, nullptr, l.ffn1, co, tw);
+            linear_into(ctx, wide, 4 * H, rows, 4 * H, l.ffn2, x, H, y, H);
+            launch_pe_affine_mask(ctx, y, rows, H, nullptr, nullptr, nonpad, x);
+        }
+        launch_layernorm(ctx, x, rows, H, lnw, lnb, FS2_EPS, y);
+        launch_pe_affine_mask(ctx, y, rows, H, nullptr, nullptr, nonpad, out);
+    }
+};
+
+}  // namespace
+
+struct FastSpeech2MIDI::Impl {
+    maa_fs2_config cfg;
+    int precision = 0;
+    WeightStore ws;
+    explicit Impl(int prec) : precision(prec), ws(prec != 0) {}
+    int Cp = 0;                          // predictor width
+    FFTBlocks enc, dec;
+    float *embed = nullptr, *midi = nullptr, *dur_w = nullptr, *dur_b = nullptr, *slur = nullptr, *rel_pe = nullptr;
+    std::vector<PackedW> dp_conv;
+    std::vector<float*> dp_lnw, dp_lnb;
+    float *dp_w = nullptr, *dp_b = nullptr;
+    PackedW mel_out;
+    float alpha = 1.f;
+    const float* table = nullptr;        // the decoder's sinusoid table [table_rows, hidden_size] on the device
+    int table_rows = 0;
+    DevSlab table_big;
+    std::vector<float> table_host;
+
+    void build(const StateDict& sd) {
+        const int H = cfg.hidden_size;
+        const HostTensor& e = get(sd, "encoder.embed_tokens.weight");
+        MAA_CHECK(e.numel() == (long long)cfg.vocab_size * H, "FastSpeech2MIDI: encoder.embed_tokens.weight must be [vocab_size, hidden_size]");
+        MAA_CHECK(get(sd, "midi_embed.weight").numel() == (long long)FS2_MIDI_ROWS * H && get(sd, "is_slur_embed.weight").numel() == 2LL * H &&
+                      get(sd, "midi_dur_layer.weight").numel() == H && get(sd, "midi_dur_layer.bias").numel() == H,
+                  "FastSpeech2MIDI: midi_embed [300, H], midi_dur_layer [H, 1] + [H], is_slur_embed [2, H]");
+        embed = ws.vec(sd, "encoder.embed_tokens.weight");
+        midi = ws.vec(sd, "midi_embed.weight");
+        dur_w = ws.vec(sd, "midi_dur_layer.weight");
+        dur_b = ws.vec(sd, "midi_dur_layer.bias");
+        slur = ws.vec(sd, "is_slur_embed.weight");
+        rel_pe = ws.upload(rel_pos_table(FS2_REL_MAX_LEN, H));
+        enc.build(ws, sd, "encoder", cfg.enc_layers, H, cfg.num_heads, cfg.enc_ffn_kernel_size);
+        dec.build(ws, sd, "decoder", cfg.dec_layers, H, cfg.num_heads, cfg.dec_ffn_kernel_size);
+        for (int i = 0; i < cfg.dur_predictor_layers; ++i) {
+            const std::string p = "dur_predictor.conv." + std::to_string(i) + ".";
+            dp_conv.push_back(ws.pack_conv(sd, p + "1.weight", p + "1.bias", 1, cfg.dur_predictor_kernel));
+            MAA_CHECK(dp_conv.back().N == Cp && dp_conv.back().K == cfg.dur_predictor_kernel * (i ? Cp : H), "DurationPredictor conv shape " + p);
+            MAA_CHECK(get(sd, p + "3.weight").numel() == Cp, "DurationPredictor LayerNorm shape " + p);
+            dp_lnw.push_back(ws.vec(sd, p + "3.weight"));
+            dp_lnb.push_back(ws.vec(sd, p + "3.bias"));
+        }
+        MAA_CHECK(get(sd, "dur_predictor.linear.weight").numel() == Cp && get(sd, "dur_predictor.linear.bias").numel() == 1,
+                  "DurationPredictor linear must be [1, C_p]");
+        dp_w = ws.vec(sd, "dur_predictor.linear.weight");
+        dp_b = ws.vec(sd, "dur_predictor.linear.bias");
+        mel_out = ws.pack_conv(sd, "mel_out.weight", "mel_out.bias", 1, 1);
+        MAA_CHECK(mel_out.N == cfg.audio_num_mel_bins && mel_out.K == H, "FastSpeech2MIDI: mel_out must be [audio_num_mel_bins, hidden_size]");
+        alpha = get(sd, "decoder.pos_embed_alpha").data[0];
+        // (encoder_embed_tokens.weight is encoder.embed_tokens.weight again; decoder.embed_positions._float_tensor is bookkeeping)
+        table_rows = FS2_TABLE_INIT;
+        table = ws.upload(sinusoid_table(table_rows, H));
+    }
+
+    // max_pos = padding_idx + 1 + seq_len rows (common_layers.py:126-133): rebuilt and uploaded when T_mel outgrows the table
+    void grow_table(Ctx& ctx, int T) {
+        if (T + 1 <= table_rows) return;
+        table_host = sinusoid_table(T + 1, cfg.hidden_size);
+        float* d = static_cast<float*>(table_big.get(table_host.size() * sizeof(float), ctx.stream));
+        MAA_HIP(hipMemcpyAsync(d, table_host.data(), table_host.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
+        table = d;
+        table_rows = T + 1;
+    }
+
+    void encode(Ctx& ctx, const int* tok, const int* pitch_midi, const float* midi_dur, const int* is_slur, int B, int T,
+                float* encoder_out, float* xs, int* dur, int* totals) {
+        const int H = cfg.hidden_size;
+        const long long rows = (long long)B * T;
+        float* nonpad = ctx.ws.alloc_f((size_t)rows);
+        float* hidden = ctx.ws.alloc_f((size_t)rows);
+        float* x = ctx.ws.alloc_f((size_t)rows * H);
+        launch_fs2_embed(ctx, tok, pitch_midi, midi_dur, is_slur, embed, cfg.vocab_size, midi, dur_w, dur_b, slur, rel_pe,
+                         std::sqrt((float)H), B, T, H, x, nonpad, hidden);
+        enc.forward(ctx, x, B, T, nonpad, hidden, encoder_out);
+        // ---- DurationPredictor on encoder_out * src_nonpadding (its padding rows are 0 already)      (tts_modules.py:98-118)
+        const size_t wide = (size_t)rows * (H > Cp ? H : Cp);
+        float* a = ctx.ws.alloc_f(wide);
+        float* b = ctx.ws.alloc_f(wide);
+        const float* src = encoder_out;
+        const int n = (int)dp_conv.size();
+        for (int i = 0; i < n; ++i) {
+            T4 tx = seq(const_cast<float*>(src), B, T, i ? Cp : H), ty = seq(a, B, T, Cp);
+            ConvOpt co;
+            co.KW = cfg.dur_predictor_kernel;
+            co.pad = (cfg.dur_predictor_kernel - 1) / 2;
+            co.pad_h = 0;
+            co.act = 2;
+            conv_into(ctx, tx, nullptr, dp_conv[i], co, ty);
+            if (i + 1 < n) {
+                launch_layernorm(ctx, a, rows, Cp, dp_lnw[i], dp_lnb[i], FS2_EPS, b);
+                launch_pe_affine_mask(ctx, b, rows, Cp, nullptr, nullptr, nonpad, b);
+                src = b;
+            } else {
+                launch_fs2_dur_head(ctx, a, rows, Cp, dp_lnw[i], dp_lnb[i], FS2_EPS, dp_w, dp_b, nonpad, xs, dur);
+            }
+        }
+        launch_fs2_length(ctx, dur, B, T, totals, 0, nullptr);
+    }
+
+    void decode(Ctx& ctx, const float* encoder_out, const int* mel2ph, int B, int T, int T_mel, float* decoder_inp, float* mel) {
+        const int H = cfg.hidden_size, M = cfg.audio_num_mel_bins;
+        const long long rows = (long long)B * T_mel;
+        float* tgt = ctx.ws.alloc_f((size_t)rows);
+        launch_fs2_expand(ctx, encoder_out, mel2ph, B, T, T_mel, H, decoder_inp, tgt);
+        if (!mel) return;
+        // ---- FastspeechDecoder: mask from the data, positions counted on it      (tts_modules.py:313-320)
+        float* nonpad = ctx.ws.alloc_f((size_t)rows);
+        float* hidden = ctx.ws.alloc_f((size_t)rows);
+        float* x = ctx.ws.alloc_f((size_t)rows * H);
+        float* y = ctx.ws.alloc_f((size_t)rows * H);
+        launch_pe_frame_mask(ctx, decoder_inp, rows, H, nonpad);
+        launch_fs2_hidden(ctx, nonpad, rows, hidden);
+        launch_pe_pos_add(ctx, decoder_inp, B, T_mel, H, table, alpha, x);
+        launch_pe_affine_mask(ctx, x, rows, H, nullptr, nullptr, nonpad, x);
+        dec.forward(ctx, x, B, T_mel, nonpad, hidden, y);
+        linear_into(ctx, y, H, rows, H, mel_out, nullptr, 0, mel, M);
+        launch_pe_affine_mask(ctx, mel, rows, M, nullptr, nullptr, tgt, mel);
+    }
+};
+
+FastSpeech2MIDI::FastSpeech2MIDI(const maa_fs2_config& cfg, const StateDict& sd, int precision) : impl_(new Impl(precision)) {
+    impl_->cfg = cfg;
+    impl_->Cp = cfg.predictor_hidden > 0 ? cfg.predictor_hidden : cfg.hidden_size;
+    try {
+        impl_->build(sd);
+    } catch (...) {
+        delete impl_;
+        throw;
+    }
+}
+FastSpeech2MIDI::~FastSpeech2MIDI() { delete impl_; }
+const maa_fs2_config& FastSpeech2MIDI::config() const { return impl_->cfg; }
+
+void FastSpeech2MIDI::encode(Ctx& ctx, const int* tokens, const int* pitch_midi, const float* midi_dur, const int* is_slur, int B, int T,
+                             float* encoder_out, float* xs, int* dur, int* totals) {
+    Impl& m = *impl_;
+    MAA_CHECK(T <= FS2_REL_MAX_LEN, "FastSpeech2MIDI: more tokens than RelPositionalEncoding's max_len (5000)");
+    PrecisionGuard pg(ctx, m.precision);
+    run_sized(ctx, [&] { m.encode(ctx, tokens, pitch_midi, midi_dur, is_slur, B, T, encoder_out, xs, dur, totals); });
+}
+
+void FastSpeech2MIDI::length_regulate(Ctx& ctx, const int* dur, int B, int T, int T_mel, int* mel2ph) {
+    run_sized(ctx, [&] { launch_fs2_length(ctx, dur, B, T, nullptr, T_mel, mel2ph); });
+}
+
+void FastSpeech2MIDI::decode(Ctx& ctx, const float* encoder_out, const int* mel2ph, int B, int T, int T_mel, float* decoder_inp,
+                             float* mel_out) {
+    Impl& m = *impl_;
+    PrecisionGuard pg(ctx, m.precision);
+    if (mel_out) m.grow_table(ctx, T_mel);
+    run_sized(ctx, [&] { m.decode(ctx, encoder_out, mel2ph, B, T, T_mel, decoder_inp, mel_out); });
+}
+
+}  // namespace maa

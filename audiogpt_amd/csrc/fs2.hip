@@ -1,0 +1,244 @@
+// Row kernels of DiffSinger's FastSpeech2MIDI front end (score -> decoder_inp, mel2ph, coarse mel), channels-last [B*T, C],
+// wave64: one wave per row, four channels per lane per step; reductions are wave shuffles.  The contractions between them are
+// fs2.cpp's; the masked attention is flash_attn.hip (bf16 modes) or blocks.cpp's three launches (exact fp32).
+//
+// Replaces (NeuralSeq/): modules/diffsinger_midi/fs2.py:12-23,60-65 the four embeddings with
+// modules/commons/espnet_positional_embedding.py:102-113 RelPositionalEncoding and tts_modules.py:314,320 the first mask;
+// tts_modules.py:98-118 the duration predictor's last LayerNorm, Linear(C, 1), mask and out2dur; :204-214 LengthRegulator;
+// modules/fastspeech/fs2.py:117-122,132 expand + mask of the encoder states.
+// All of them are memory-bound on a few hundred to a few thousand rows.
+#include "maa_internal.h"
+
+namespace maa {
+namespace {
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+inline dim3 row_grid(long long rows) { return dim3((unsigned)((rows + 3) / 4)); }
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// x = ((scale * E[tok] + M[midi] + (dur * w + b) + S[slur]) * scale + pe[t]) * live,  live = tok != 0: the embedding scale is
+// applied twice, as the reference does (forward_embedding's embed_scale, then RelPositionalEncoding's xscale).
+// nonpad[row] = live, hidden[row] = 1 - live (the key mask of the attention).  midi_dur / is_slur may be null: their term is 0.
+__global__ __launch_bounds__(256) void fs2_embed_kernel(const int* __restrict__ tok, const int* __restrict__ midi,
+                                                        const float* __restrict__ midi_dur, const int* __restrict__ slur,
+                                                        const float* __restrict__ E, int vocab, const float* __restrict__ Mi,
+                                                        const float* __restrict__ dw, const float* __restrict__ db,
+                                                        const float* __restrict__ S, const float* __restrict__ pe, float scale,
+                                                        long long rows, int T, int H, float* __restrict__ x,
+                                                        float* __restrict__ nonpad, float* __restrict__ hidden) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int t = (int)(row % T);
+    const int tk = tok[row];
+    const float live = tk != 0 ? 1.f : 0.f;
+    const float* e = E + (long long)clampi(tk, 0, vocab - 1) * H;
+    const float* m = Mi + (long long)clampi(midi[row], 0, 299) * H;
+    const float* s = slur ? S + (long long)clampi(slur[row], 0, 1) * H : nullptr;
+    const float d = midi_dur ? midi_dur[row] : 0.f;
+    const float* p = pe + (long long)t * H;
+    for (int c = lane * 4; c < H; c += 256) {
+        const float4 ev = *reinterpret_cast<const float4*>(e + c);
+        const float4 mv = *reinterpret_cast<const float4*>(m + c);
+        const float4 pv = *reinterpret_cast<const float4*>(p + c);
+        float4 v = make_float4(scale * ev.x + mv.x, scale * ev.y + mv.y, scale * ev.z + mv.z, scale * ev.w + mv.w);
+        if (midi_dur) {
+            const float4 w = *reinterpret_cast<const float4*>(dw + c);
+            const float4 b = *reinterpret_cast<const float4*>(db + c);
+            v.x += d * w.x + b.x;
+            v.y += d * w.y + b.y;
+            v.z += d * w.z + b.z;
+            v.w += d * w.w + b.w;
+        }
+        if (s) {
+            const float4 sv = *reinterpret_cast<const float4*>(s + c);
+            v.x += sv.x;
+            v.y += sv.y;
+            v.z += sv.z;
+            v.w += sv.w;
+        }
+        v.x = (v.x * scale + pv.x) * live;
+        v.y = (v.y * scale + pv.y) * live;
+        v.z = (v.z * scale + pv.z) * live;
+        v.w = (v.w * scale + pv.w) * live;
+        *reinterpret_cast<float4*>(x + row * H + c) = v;
+    }
+    if (lane == 0) {
+        nonpad[row] = live;
+        hidden[row] = 1.f - live;
+    }
+}
+
+// hidden[i] = 1 where nonpad[i] == 0, else 0
+__global__ __launch_bounds__(256) void fs2_hidden_kernel(const float* __restrict__ nonpad, long long n, float* __restrict__ hidden) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) hidden[i] = nonpad[i] == 0.f ? 1.f : 0.f;
+}
+
+// The duration predictor's last layer after its convolution (whose epilogue did the ReLU): LayerNorm over the row (kept in
+// registers, C <= 1024), mask, Linear(C, 1), mask -> xs[row]; dur[row] = max(rint(exp(xs) - 1), 0) (torch.round = half to even).
+// A padding row is 0 in both.
+__global__ __launch_bounds__(256) void fs2_dur_head_kernel(const float* __restrict__ x, long long rows, int C,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                           const float* __restrict__ w, const float* __restrict__ bias,
+                                                           const float* __restrict__ nonpad, float* __restrict__ xs,
+                                                           int* __restrict__ dur) {
+    constexpr int NR = 4;
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* src = x + row * C;
+    float4 v[NR];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const int c = (lane + 64 * i) * 4;
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < C) v[i] = *reinterpret_cast<const float4*>(src + c);
+        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    }
+    const float mean = wave_sum(s) / (float)C;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const int c = (lane + 64 * i) * 4;
+        if (c < C) {
+            const float a = v[i].x - mean, b = v[i].y - mean, d = v[i].z - mean, e = v[i].w - mean;
+            q += (a * a + b * b) + (d * d + e * e);
+        }
+    }
+    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)C + eps);
+    float d0 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const int c = (lane + 64 * i) * 4;
+        if (c < C) {
+            const float4 g = *reinterpret_cast<const float4*>(gamma + c);
+            const float4 bt = *reinterpret_cast<const float4*>(beta + c);
+            const float4 w0 = *reinterpret_cast<const float4*>(w + c);
+            const float yx = (v[i].x - mean) * rstd * g.x + bt.x, yy = (v[i].y - mean) * rstd * g.y + bt.y;
+            const float yz = (v[i].z - mean) * rstd * g.z + bt.z, yw = (v[i].w - mean) * rstd * g.w + bt.w;
+            d0 += (yx * w0.x + yy * w0.y) + (yz * w0.z + yw * w0.w);
+        }
+    }
+    d0 = wave_sum(d0) + bias[0];
+    if (lane == 0) {
+        const float o = nonpad[row] != 0.f ? d0 : 0.f;
+        xs[row] = o;
+        dur[row] = (int)fmaxf(rintf(expf(o) - 1.f), 0.f);
+    }
+}
+
+// LengthRegulator, one block per sample.  The inclusive running sum of dur[b, :] goes to cum[b, :] (256 tokens per step: a scan
+// inside each wave, the waves' sums through LDS, the carry in a register); totals[b] = its last value, when asked for.
+// mel2ph, when asked for: frame p belongs to the first token whose running sum exceeds p (1-based), 0 from the total on.
+__global__ __launch_bounds__(256) void fs2_length_kernel(const int* __restrict__ dur, int T, int* cum,
+                                                         int* __restrict__ totals, int T_mel, int* __restrict__ mel2ph) {
+    __shared__ int wsum[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int* src = dur + (long long)blockIdx.x * T;
+    int* cs = cum + (long long)blockIdx.x * T;
+    int carry = 0;
+    for (int t0 = 0; t0 < T; t0 += 256) {
+        const int t = t0 + (int)threadIdx.x;
+        int v = t < T ? src[t] : 0;
+        v = v > 0 ? v : 0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int u = __shfl_up(v, o, 64);
+            if (lane >= o) v += u;
+        }
+        __syncthreads();
+        if (lane == 63) wsum[w] = v;
+        __syncthreads();
+        int before = carry;
+        for (int i = 0; i < w; ++i) before += wsum[i];
+        if (t < T) cs[t] = before + v;
+        carry += (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    }
+    if (totals && threadIdx.x == 0) totals[blockIdx.x] = carry;
+    if (!mel2ph) return;
+    __syncthreads();          // (block-wide: cum[b, :] written above is read below by other threads)
+    int* dst = mel2ph + (long long)blockIdx.x * T_mel;
+    for (int p = threadIdx.x; p < T_mel; p += 256) {
+        int lo = 0, hi = T;      // first t in [0, T) with cs[t] > p; T: none
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (cs[mid] > p) hi = mid;
+            else lo = mid + 1;
+        }
+        dst[p] = lo < T ? lo + 1 : 0;
+    }
+}
+
+// decoder_inp[b, p] = encoder_out[b, mel2ph[b, p] - 1] where mel2ph > 0, else 0; tgt[b, p] = (mel2ph > 0)
+__global__ __launch_bounds__(256) void fs2_expand_kernel(const float* __restrict__ enc, const int* __restrict__ mel2ph, long long rows,
+                                                         int T, int T_mel, int H, float* __restrict__ out, float* __restrict__ tgt) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const long long b = row / T_mel;
+    const int ph = clampi(mel2ph[row], 0, T);
+    const float* src = enc + (b * T + (ph > 0 ? ph - 1 : 0)) * H;
+    for (int c = lane * 4; c < H; c += 256) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ph > 0) v = *reinterpret_cast<const float4*>(src + c);
+        *reinterpret_cast<float4*>(out + row * H + c) = v;
+    }
+    if (lane == 0) tgt[row] = ph > 0 ? 1.f : 0.f;
+}
+
+}  // namespace
+
+void launch_fs2_embed(const Ctx& ctx, const int* tok, const int* midi, const float* midi_dur, const int* slur, const float* E, int vocab,
+                      const float* Mi, const float* dw, const float* db, const float* S, const float* pe, float scale, int B, int T, int H,
+                      float* x, float* nonpad, float* hidden) {
+    if (ctx.ws.dry) return;
+    MAA_CHECK(H % 4 == 0, "FastSpeech2MIDI: hidden_size must be a multiple of 4");
+    const long long rows = (long long)B * T;
+    ProfScope prof(ctx, "fs2_rows", 0.0, 20.0 * rows * (double)H);
+    hipLaunchKernelGGL(fs2_embed_kernel, row_grid(rows), dim3(256), 0, ctx.stream, tok, midi, midi_dur, slur, E, vocab, Mi, dw, db, S, pe,
+                       scale, rows, T, H, x, nonpad, hidden);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_hidden(const Ctx& ctx, const float* nonpad, long long n, float* hidden) {
+    if (ctx.ws.dry) return;
+    ProfScope prof(ctx, "fs2_rows", 0.0, 8.0 * n);
+    hipLaunchKernelGGL(fs2_hidden_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx.stream, nonpad, n, hidden);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_dur_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
+                         const float* w, const float* bias, const float* nonpad, float* xs, int* dur) {
+    if (ctx.ws.dry) return;
+    MAA_CHECK(C % 4 == 0 && C <= 1024, "FastSpeech2MIDI: predictor width must be a multiple of 4, at most 1024");
+    ProfScope prof(ctx, "fs2_rows", 0.0, 4.0 * rows * (double)C);
+    hipLaunchKernelGGL(fs2_dur_head_kernel, row_grid(rows), dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, w, bias, nonpad, xs, dur);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_length(Ctx& ctx, const int* dur, int B, int T, int* totals, int T_mel, int* mel2ph) {
+    int* cum = reinterpret_cast<int*>(ctx.ws.alloc_f((size_t)B * T));
+    if (ctx.ws.dry) return;
+    ProfScope prof(ctx, "fs2_rows", 0.0, 8.0 * B * ((double)T + T_mel));
+    hipLaunchKernelGGL(fs2_length_kernel, dim3((unsigned)B), dim3(256), 0, ctx.stream, dur, T, cum, totals, T_mel, mel2ph);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_expand(const Ctx& ctx, const float* enc, const int* mel2ph, int B, int T, int T_mel, int H, float* out, float* tgt) {
+    if (ctx.ws.dry) return;
+    MAA_CHECK(H % 4 == 0, "FastSpeech2MIDI: hidden_size must be a multiple of 4");
+    const long long rows = (long long)B * T_mel;
+    ProfScope prof(ctx, "fs2_rows", 0.0, 8.0 * rows * (double)H);
+    hipLaunchKernelGGL(fs2_expand_kernel, row_grid(rows), dim3(256), 0, ctx.stream, enc, mel2ph, rows, T, T_mel, H, out, tgt);
+    MAA_HIP(hipGetLastError());
+}
+
+}  // namespace maa

@@ -322,10 +322,14 @@ void launch_split32_unpack(const Ctx& ctx, const float* x, long long rows, int C
 // fused softmax(alpha q k^T) v for the bf16 precision modes; false = shape not covered, use the GEMM path
 bool launch_flash_attention(const Ctx& ctx, const float* q, int ldq, int hsq, const float* k, int ldk, int hsk,
                             const float* v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
-                            float* out, int ldo, int out_split = 0, int causal = 0);
+                            float* out, int ldo, int out_split = 0, int causal = 0, const float* key_mask = nullptr);
+// key_mask [B, Nk] (non-zero = hidden from every query of the sample): taken at dh = 128, the FastSpeech2 blocks' head width
 bool flash_attention_covers(const Ctx& ctx, int dh);    // head widths launch_flash_attention takes in this mode
 // in-place row softmax over `cols` columns of a [rows, ld] matrix; columns [cols, ld) are zeroed
 void launch_softmax(const Ctx& ctx, float* s, long long rows, int cols, int ld, int causal_nq = 0);
+// the same with a key mask [rows / rows_per_sample, cols]: a column whose mask entry is non-zero gets weight 0, a row with no
+// visible column is written as zeros
+void launch_softmax_masked(const Ctx& ctx, float* s, long long rows, int cols, int ld, const float* key_mask, long long rows_per_sample);
 
 // ------------------------------------------------------------------------------------------ elementwise
 void launch_timestep_embedding(const Ctx& ctx, const float* t, int B, int dim, float* out);   // [cos | sin]

@@ -105,6 +105,36 @@ private:
     Impl* impl_;
 };
 
+// What the extractor and the FastSpeech2 front end share (pitch.hip, pitch_extractor.cpp):
+// mask[row] = 0 where every channel of the row is +-0, else 1
+void launch_pe_frame_mask(const Ctx& ctx, const float* mel, long long rows, int M, float* mask);
+// out = (x * scale + shift) * mask[row]; scale == nullptr: out = x * mask[row] (out may be x)
+void launch_pe_affine_mask(const Ctx& ctx, const float* x, long long rows, int C, const float* scale, const float* shift,
+                           const float* mask, float* out);
+// out = x + alpha * table[make_positions(x[..., 0])], the positions counted on the device
+void launch_pe_pos_add(Ctx& ctx, const float* x, int B, int T, int C, const float* table, float alpha, float* out);
+// SinusoidalPositionalEmbedding.get_embedding(rows, dim, padding_idx = 0) in fp32
+std::vector<float> sinusoid_table(int rows, int dim);
+
+// DiffSinger's FastSpeech2MIDI front end (fs2.cpp, fs2.hip): score -> encoder_out / durations, then mel2ph -> decoder_inp / mel_out
+class FastSpeech2MIDI {
+public:
+    FastSpeech2MIDI(const maa_fs2_config& cfg, const StateDict& sd, int precision);
+    ~FastSpeech2MIDI();
+    // tokens / pitch_midi / is_slur (optional) int32 [B, T], midi_dur (optional) [B, T] -> encoder_out [B, T, H], xs [B, T],
+    // dur int32 [B, T], totals int32 [B]
+    void encode(Ctx& ctx, const int* tokens, const int* pitch_midi, const float* midi_dur, const int* is_slur, int B, int T,
+                float* encoder_out, float* xs, int* dur, int* totals);
+    void length_regulate(Ctx& ctx, const int* dur, int B, int T, int T_mel, int* mel2ph);
+    // encoder_out [B, T, H], mel2ph int32 [B, T_mel] -> decoder_inp [B, T_mel, H], mel_out (optional) [B, T_mel, mel bins]
+    void decode(Ctx& ctx, const float* encoder_out, const int* mel2ph, int B, int T, int T_mel, float* decoder_inp, float* mel_out);
+    const maa_fs2_config& config() const;
+
+private:
+    struct Impl;
+    Impl* impl_;
+};
+
 class Encoder {
 public:
     Encoder(const maa_encoder_config& cfg, const StateDict& sd, int precision);

@@ -436,6 +436,28 @@ __global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ s, lon
     }
 }
 
+// softmax_kernel<0> with a key mask of the row's sample: three passes over memory, a hidden column counts as -inf
+__global__ __launch_bounds__(256) void softmax_masked_kernel(float* __restrict__ s, long long rows, int cols, int ld,
+                                                             const float* __restrict__ key_mask, long long rows_per_sample) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float* p = s + row * ld;
+    const float* hid = key_mask + (row / rows_per_sample) * cols;
+    float m = -INFINITY;
+    for (int c = lane; c < cols; c += 64) m = fmaxf(m, hid[c] != 0.f ? -INFINITY : p[c]);
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int c = lane; c < cols; c += 64) {
+        const float e = hid[c] != 0.f || m == -INFINITY ? 0.f : expf(p[c] - m);
+        p[c] = e;
+        sum += e;
+    }
+    sum = wave_sum(sum);
+    const float inv = sum > 0.f ? 1.f / sum : 0.f;
+    for (int c = lane; c < ld; c += 64) p[c] = c < cols ? p[c] * inv : 0.f;
+}
+
 // fp32 rows -> split32 rows (same pitch): what a normalisation with out_split = 1 does to its result, on its own
 // (slope != 1: leaky-relu first -- the pre-activated input of the vocoders' first MRF convolution)
 __global__ __launch_bounds__(256) void split32_pack_kernel(const float* __restrict__ x, long long rows, int C, float slope,
@@ -553,6 +575,15 @@ void launch_softmax(const Ctx& ctx, float* s, long long rows, int cols, int ld, 
         hipLaunchKernelGGL(softmax_kernel<17>, grid, dim3(256), 0, ctx.stream, s, rows, cols, ld, causal_nq);
     else
         hipLaunchKernelGGL(softmax_kernel<0>, grid, dim3(256), 0, ctx.stream, s, rows, cols, ld, causal_nq);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_softmax_masked(const Ctx& ctx, float* s, long long rows, int cols, int ld, const float* key_mask, long long rows_per_sample) {
+    if (ctx.ws.dry) return;
+    MAA_CHECK(ld >= cols && key_mask && rows_per_sample > 0, "masked softmax arguments");
+    ProfScope prof(ctx, "softmax", 0.0, 8.0 * rows * (double)ld);
+    hipLaunchKernelGGL(softmax_masked_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx.stream, s, rows, cols, ld, key_mask,
+                       rows_per_sample);
     MAA_HIP(hipGetLastError());
 }
 

@@ -19,20 +19,11 @@
 
 namespace maa {
 
-void launch_pe_frame_mask(const Ctx& ctx, const float* mel, long long rows, int M, float* mask);
-void launch_pe_affine_mask(const Ctx& ctx, const float* x, long long rows, int C, const float* scale, const float* shift,
-                           const float* mask, float* out);
 void launch_pe_gn_relu_res(Ctx& ctx, const float* y, const float* res, int B, int T, int C, int groups, const float* gamma,
                            const float* beta, float eps, float* out);
-void launch_pe_pos_add(Ctx& ctx, const float* x, int B, int T, int C, const float* table, float alpha, float* out);
 void launch_pe_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
                     const float* w, const float* bias, const float* mask, int norm, float f0_mean, float f0_std, int use_uv,
                     float* pitch_pred, float* f0);
-
-namespace {
-
-constexpr int PE_PRENET_LAYERS = 3, PE_PREDICTOR_LAYERS = 5, PE_KERNEL = 5, PE_TABLE_INIT = 4096;
-constexpr float PE_EPS = 1e-5f;
 
 // SinusoidalPositionalEmbedding.get_embedding(rows, dim, padding_idx = 0) in fp32 (common_layers.py:104-121)
 std::vector<float> sinusoid_table(int rows, int dim) {
@@ -48,6 +39,11 @@ std::vector<float> sinusoid_table(int rows, int dim) {
         }
     return tab;
 }
+
+namespace {
+
+constexpr int PE_PRENET_LAYERS = 3, PE_PREDICTOR_LAYERS = 5, PE_KERNEL = 5, PE_TABLE_INIT = 4096;
+constexpr float PE_EPS = 1e-5f;
 
 inline T4 seq(float* p, int B, int T, int C) {
     T4 t;

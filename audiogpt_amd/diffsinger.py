@@ -1,10 +1,10 @@
 """DiffSinger's shallow-diffusion sampler with the reference's Python surface, backed by the HIP library.
 
 Inference subset of `GaussianDiffusion` (NeuralSeq/modules/diff/shallow_diffusion_tts.py:66-283) as the T2S tool drives
-it (audio-chatgpt.py:298-339 -> NeuralSeq/inference/svs/ds_e2e.py): the FastSpeech2 front end (`self.fs2`) that turns
-phonemes into the conditioning `decoder_inp` and the coarse mel is outside the accelerated path and stays with the
-caller; what runs on the device is the part that costs the time -- `denoise_fn` (DiffNet, 20 gated dilated residual
-layers) inside the sampling loop.  Both loops of forward(infer=True) are here: the PLMS loop (`pndm_speedup`, K_step /
+it (audio-chatgpt.py:298-339 -> NeuralSeq/inference/svs/ds_e2e.py): the part that costs the time is `denoise_fn` (DiffNet,
+20 gated dilated residual layers) inside the sampling loop; the FastSpeech2(MIDI) front end (`self.fs2`) that turns tokens and
+note features into the conditioning `decoder_inp`, `mel2ph` and the coarse mel runs on the device in front of it
+(`FastSpeech2MIDI`, once per utterance).  Both loops of forward(infer=True) are here: the PLMS loop (`pndm_speedup`, K_step /
 pndm_speedup evaluations per utterance, ds1000.yaml) and the ancestral chain every other shipped configuration takes
 (K_step p_sample steps: popcs_ds_beta6.yaml, lj_ds_beta6.yaml, ds100_adj_rel.yaml, ds60_rel.yaml, ds1000-10dil.yaml).
 
@@ -17,6 +17,9 @@ so the mel never leaves the device between the diffusion and the waveform.
 
     e2e = DiffSingerE2E(gd, hifigan.vocoder, pe=PitchExtractor(ctx=gd.ctx, state_dict=pe_ckpt_sd))
     wav = e2e.infer(fs2_mel, cond)                                # [1, B * T * hop], run_vocoder's shape
+
+    e2e = DiffSingerE2E(gd, hifigan.vocoder, pe=..., fs2=FastSpeech2MIDI(ctx=gd.ctx, state_dict=ckpt_fs2_sd))
+    wav = e2e.forward_model(txt_tokens, pitch_midi, midi_dur, is_slur)      # score -> waveform, no model on the host
 """
 import numpy as np
 import torch
@@ -289,13 +292,101 @@ class PitchExtractor(object):
         return self
 
 
-class DiffSingerE2E(object):
-    """The tail of DiffSingerE2EInfer.forward_model (inference/svs/ds_e2e.py:36-45) with BaseSVSInfer.run_vocoder
-    (base_svs_infer.py:61-70): mel_out -> f0 (pe, when set) -> waveform.  diffusion: a GaussianDiffusion; vocoder: a
-    backend.Vocoder (forward / forward_f0) on the same device; use_nsf: hparams['use_nsf']."""
+class FastSpeech2MIDI(object):
+    """modules/diffsinger_midi/fs2.py:46-118 with the reference's call surface: `fs2(txt_tokens, infer=True, pitch_midi=...,
+    midi_dur=..., is_slur=...)` -> the reference's dict, device tensors.  cfg: the hparams it reads (config.FASTSPEECH2_MIDI);
+    state_dict: the checkpoint's (a `model.fs2.` or `fs2.` prefix is stripped), seeded random weights when None.  ctx: an existing
+    Context, e.g. the diffusion's, so the stages share one stream.
 
-    def __init__(self, diffusion, vocoder, pe=None, use_nsf=True):
-        self.diffusion, self.vocoder, self.pe, self.use_nsf = diffusion, vocoder, pe, bool(use_nsf)
+    The network runs as two device calls, encode (tokens -> encoder_out, durations) and decode (mel2ph -> decoder_inp, mel_out);
+    T_mel = max_b sum(dur) sizes decode's outputs, so with predicted durations the B per-sample totals are read back between the
+    two: the single device-to-host read per utterance.  With a caller's mel2ph there is none.
+
+    The integer inputs are checked on the host, where preprocess_input leaves them (a tensor handed over on the device is copied
+    back for that): tokens in [0, vocab_size), pitch_midi in [0, 300), is_slur in {0, 1}, a live token in every sample, a given
+    mel2ph within [0, T_txt] with a frame per sample.  A sample whose predicted durations sum to 0 frames is refused: the
+    reference's decoder has no visible key there and returns NaN."""
+
+    def __init__(self, cfg=None, device="cuda:0", state_dict=None, ctx=None, precision=None, seed=17):
+        self.cfg = dict(cfg or C.FASTSPEECH2_MIDI)
+        backend.fs2_config(self.cfg)                   # refuses an unsupported configuration before a context is made
+        self.ctx = ctx or Context(device, precision=precision or default_precision())
+        self.device = self.ctx.device
+        sd = state_dict if state_dict is not None else WT.make_fs2_state_dict(self.cfg, seed=seed)
+        sd = WT.strip_prefix(sd, "model.fs2.") or WT.strip_prefix(sd, "fs2.") or sd
+        self.net = backend.FastSpeech2MIDI(self.ctx, self.cfg, sd)
+
+    def _check(self, txt_tokens, pitch_midi, is_slur, mel2ph):
+        what = "FastSpeech2MIDI"
+        tok = torch.as_tensor(txt_tokens).cpu()
+        if tok.dim() != 2 or tok.shape[0] < 1 or tok.shape[1] < 1:
+            raise ValueError("%s: txt_tokens %s is not [B, T_txt]" % (what, tuple(tok.shape)))
+        V = int(self.cfg["vocab_size"])
+        if int(tok.min()) < 0 or int(tok.max()) >= V:
+            raise ValueError("%s: txt_tokens outside [0, vocab_size = %d): the token table has no such row" % (what, V))
+        if not bool((tok > 0).any(dim=1).all()):
+            raise ValueError("%s: a sample with no live token (all padding, token 0): its attention has no visible key" % what)
+        if pitch_midi is None:
+            raise ValueError("%s: pitch_midi is required (fs2.py:60)" % what)
+        midi = torch.as_tensor(pitch_midi).cpu()
+        if int(midi.min()) < 0 or int(midi.max()) >= 300:
+            raise ValueError("%s: pitch_midi outside [0, 300): midi_embed has 300 rows" % what)
+        if is_slur is not None:
+            sl = torch.as_tensor(is_slur).cpu()
+            if int(sl.min()) < 0 or int(sl.max()) > 1:
+                raise ValueError("%s: is_slur outside {0, 1}: is_slur_embed has 2 rows" % what)
+        if mel2ph is not None:
+            m = torch.as_tensor(mel2ph).cpu()
+            if m.dim() != 2 or m.shape[0] != tok.shape[0] or m.shape[1] < 1:
+                raise ValueError("%s: mel2ph %s is not [B = %d, T_mel]" % (what, tuple(m.shape), tok.shape[0]))
+            if int(m.min()) < 0 or int(m.max()) > tok.shape[1]:
+                raise ValueError("%s: mel2ph outside [0, T_txt = %d]: a frame points at no token" % (what, tok.shape[1]))
+            if not bool((m > 0).any(dim=1).all()):
+                raise ValueError("%s: a sample whose mel2ph is all 0: no frame, its decoder has no visible key" % what)
+
+    @torch.no_grad()
+    def forward(self, txt_tokens, mel2ph=None, skip_decoder=False, infer=True, pitch_midi=None, midi_dur=None, is_slur=None):
+        """-> {'decoder_inp' [B, T_mel, H], 'mel2ph' [B, T_mel] long, 'dur', 'mel_out' [B, T_mel, 80] unless skip_decoder}, and
+        'dur_choice' [B, T_txt] long when mel2ph was predicted.  'dur' is the duration predictor's log-domain output: [B, T_txt, 1]
+        when mel2ph was predicted, [B, T_txt] when it was given, as the reference returns it."""
+        if not infer:
+            raise ValueError("FastSpeech2MIDI: only infer=True is built (no dropout, no losses)")
+        self._check(txt_tokens, pitch_midi, is_slur, mel2ph)
+        enc, xs, dur, totals = self.net.encode(txt_tokens, pitch_midi, midi_dur, is_slur)
+        ret = {}
+        if mel2ph is None:
+            tot = totals.cpu()                         # the one device-to-host read: T_mel sizes everything after it
+            if int(tot.min()) < 1:
+                raise ValueError("FastSpeech2MIDI: the predicted durations of sample %d sum to 0 frames: the reference's decoder "
+                                 "returns NaN there" % int(tot.argmin()))
+            m2p = self.net.length_regulate(dur, int(tot.max()))
+            ret["dur"], ret["dur_choice"] = xs[:, :, None], dur.long()
+        else:
+            m2p = torch.as_tensor(mel2ph).to(device=self.device, dtype=torch.int32)
+            ret["dur"] = xs
+        ret["mel2ph"] = m2p.long()
+        ret["decoder_inp"], mel_out = self.net.decode(enc, m2p, skip_decoder=skip_decoder)
+        if not skip_decoder:
+            ret["mel_out"] = mel_out
+        return ret
+
+    __call__ = forward
+
+    def eval(self):
+        return self
+
+    def to(self, *args, **kwargs):
+        return self
+
+
+class DiffSingerE2E(object):
+    """DiffSingerE2EInfer.forward_model (inference/svs/ds_e2e.py:22-45) with BaseSVSInfer.run_vocoder (base_svs_infer.py:61-70):
+    score -> (fs2, when set) decoder_inp, mel2ph, coarse mel -> the diffusion's mel_out -> f0 (pe, when set) -> waveform.
+    diffusion: a GaussianDiffusion; vocoder: a backend.Vocoder (forward / forward_f0) on the same device; use_nsf:
+    hparams['use_nsf']; fs2: a FastSpeech2MIDI on the same device, needed by forward_model only."""
+
+    def __init__(self, diffusion, vocoder, pe=None, use_nsf=True, fs2=None):
+        self.diffusion, self.vocoder, self.pe, self.use_nsf, self.fs2 = diffusion, vocoder, pe, bool(use_nsf), fs2
 
     @torch.no_grad()
     def run_vocoder(self, c, f0=None, **draws):
@@ -324,3 +415,13 @@ class DiffSingerE2E(object):
         if noise_sine is not None:
             draws["noise"] = noise_sine
         return self.mel_to_wav(mel_out, **draws)
+
+    @torch.no_grad()
+    def forward_model(self, txt_tokens, pitch_midi, midi_dur, is_slur, mel2ph=None, **draws):
+        """Score -> [1, B * T_mel * hop]: the front end, then infer with cond = its decoder_inp as [B, H, T_mel] (a device
+        transpose, no host round trip) and fs2_mels = its mel_out.  As shallow_diffusion_tts.py:273-276 the final mask uses the
+        ARGUMENT mel2ph: predicted durations (mel2ph None) leave the mel unmasked.  draws: as infer takes them."""
+        if self.fs2 is None:
+            raise ValueError("DiffSingerE2E.forward_model needs the front end: pass fs2=FastSpeech2MIDI(...)")
+        ret = self.fs2(txt_tokens, mel2ph=mel2ph, infer=True, pitch_midi=pitch_midi, midi_dur=midi_dur, is_slur=is_slur)
+        return self.infer(ret["mel_out"], ret["decoder_inp"].transpose(1, 2), mel2ph=mel2ph, **draws)

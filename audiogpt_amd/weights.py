@@ -380,6 +380,53 @@ def make_pe_state_dict(cfg, seed=13):
     return sd
 
 
+def make_fs2_state_dict(cfg, seed=17):
+    """FastSpeech2MIDI (NeuralSeq/modules/diffsinger_midi/fs2.py:46-53 over modules/fastspeech/fs2.py:22-55) in the reference key
+    layout and order: 116 keys at config.FASTSPEECH2_MIDI, the shared `encoder_embed_tokens.weight` / `encoder.embed_tokens.weight`
+    (one tensor) and the `decoder.embed_positions._float_tensor` bookkeeping entry included.  The LayerNorm affines are drawn away
+    from 1 / 0 (the LayerNorm of a zero padding row is its bias, which leaks into live rows through the FFN convolution) and
+    decoder.pos_embed_alpha away from 1, so a port that skipped either shows.  Row 0 of the token and MIDI tables is the padding
+    row and is zero, as nn.Embedding(padding_idx = 0) keeps it."""
+    g, sd = _Gen(seed), {}
+    H, V, M = cfg["hidden_size"], cfg["vocab_size"], cfg["audio_num_mel_bins"]
+    Cp = cfg["predictor_hidden"] if cfg["predictor_hidden"] > 0 else H
+    kd = cfg["dur_predictor_kernel"]
+
+    def table(rows, pad):
+        w = g.normal((rows, H), H ** -0.5)
+        if pad:
+            w[0] = 0.0
+        return w
+
+    def fft(name, n_layers, k):
+        for i in range(n_layers):
+            p = f"{name}.layers.{i}.op."
+            sd[p + "layer_norm1.weight"], sd[p + "layer_norm1.bias"] = g.gamma(H), g.beta(H)
+            sd[p + "self_attn.in_proj_weight"] = g.weight((3 * H, H), 1.4)
+            sd[p + "self_attn.out_proj.weight"] = g.weight((H, H))
+            sd[p + "layer_norm2.weight"], sd[p + "layer_norm2.bias"] = g.gamma(H), g.beta(H)
+            sd[p + "ffn.ffn_1.weight"], sd[p + "ffn.ffn_1.bias"] = g.weight((4 * H, H, k), 1.4), g.bias(4 * H)
+            sd[p + "ffn.ffn_2.weight"], sd[p + "ffn.ffn_2.bias"] = g.weight((H, 4 * H)), g.bias(H)
+        sd[f"{name}.layer_norm.weight"], sd[f"{name}.layer_norm.bias"] = g.gamma(H), g.beta(H)
+
+    sd["encoder_embed_tokens.weight"] = table(V, True)
+    sd["decoder.pos_embed_alpha"] = torch.tensor([0.8], dtype=torch.float32)
+    sd["decoder.embed_positions._float_tensor"] = torch.zeros(1, dtype=torch.float32)
+    fft("decoder", cfg["dec_layers"], cfg["dec_ffn_kernel_size"])
+    sd["mel_out.weight"], sd["mel_out.bias"] = g.weight((M, H)), g.bias(M)
+    for i in range(cfg["dur_predictor_layers"]):
+        p, cin = f"dur_predictor.conv.{i}.", (H if i == 0 else Cp)
+        sd[p + "1.weight"], sd[p + "1.bias"] = g.weight((Cp, cin, kd), 1.4), g.bias(Cp)
+        sd[p + "3.weight"], sd[p + "3.bias"] = g.gamma(Cp), g.beta(Cp)
+    sd["dur_predictor.linear.weight"], sd["dur_predictor.linear.bias"] = g.weight((1, Cp)), g.bias(1)
+    fft("encoder", cfg["enc_layers"], cfg["enc_ffn_kernel_size"])
+    sd["encoder.embed_tokens.weight"] = sd["encoder_embed_tokens.weight"]
+    sd["midi_embed.weight"] = table(300, True)
+    sd["midi_dur_layer.weight"], sd["midi_dur_layer.bias"] = g.weight((H, 1)), g.bias(H)
+    sd["is_slur_embed.weight"] = table(2, False)
+    return sd
+
+
 # ----------------------------------------------------------------------------- conditioning encoders
 def make_clap_text_state_dict(cfg, seed=11):
     """`caption_encoder.`-relative keys of the CLAP checkpoint FrozenCLAPEmbedder loads (encoders/modules.py:179-183):

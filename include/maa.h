@@ -409,6 +409,43 @@ int maa_pitch_extractor_destroy(maa_pitch_extractor* pe);
 int maa_pitch_extractor_forward(maa_ctx* ctx, maa_pitch_extractor* pe, const float* d_mel, int B, int T, float* d_pitch_pred,
                                 float* d_f0, float* d_mel_hidden);
 
+/* ---- DiffSinger FastSpeech2MIDI (the e2e singing configurations' front end: score -> decoder_inp, mel2ph, coarse mel) ----
+ * NeuralSeq/modules/diffsinger_midi/fs2.py:46-118 over modules/fastspeech/fs2.py:22-72,140-163,222-226 and
+ * tts_modules.py:59-143,179-214,276-384, as DiffSingerE2EInfer.forward_model calls it (inference/svs/ds_e2e.py).  The flags
+ * below the sizes name hparams whose other values are refused at creation, with the reason. */
+typedef struct maa_fs2_config {
+    int vocab_size, hidden_size, enc_layers, dec_layers, num_heads;       /* hidden_size / num_heads must be 128 */
+    int enc_ffn_kernel_size, dec_ffn_kernel_size;                         /* odd */
+    int dur_predictor_layers, dur_predictor_kernel, predictor_hidden;     /* predictor_hidden <= 0: hidden_size */
+    int audio_num_mel_bins;
+    int ffn_padding_same, ffn_act_gelu, dur_loss_mse, rel_pos, use_pos_embed, encoder_fft, decoder_fft;      /* must be 1 */
+    int use_pitch_embed, use_energy_embed, use_spk_id, use_spk_embed, use_bert;                              /* must be 0 */
+} maa_fs2_config;
+typedef struct maa_fs2 maa_fs2;
+/* tensors: the FastSpeech2MIDI state_dict ({encoder,decoder}.layers.{i}.op.{layer_norm1,layer_norm2}.*,
+ * .op.self_attn.{in_proj_weight,out_proj.weight}, .op.ffn.{ffn_1,ffn_2}.*, {encoder,decoder}.layer_norm.*, encoder.embed_tokens.weight,
+ * decoder.pos_embed_alpha, mel_out.*, dur_predictor.conv.{i}.{1,3}.*, dur_predictor.linear.*, midi_embed.weight, midi_dur_layer.*,
+ * is_slur_embed.weight); encoder_embed_tokens.weight (the same tensor) and decoder.embed_positions._float_tensor are accepted and
+ * ignored */
+int maa_fs2_create(maa_ctx* ctx, const maa_fs2_config* cfg, const maa_tensor* tensors, int n_tensors, maa_fs2** out);
+int maa_fs2_destroy(maa_fs2* fs2);
+/* The three calls below issue launches on the context's stream only: no device-to-host copy, no synchronisation.  Integer
+ * tensors are int32 on the device; their value ranges are the caller's to check (the kernels clamp an index, they do not report).
+ *
+ * encode: d_tokens [B, T] (0 = padding), d_pitch_midi [B, T] in [0, 300), d_midi_dur [B, T] or NULL, d_is_slur [B, T] in {0, 1}
+ * or NULL -> d_encoder_out [B, T, hidden_size] (0 on padding rows), d_xs [B, T] (the duration predictor's log-domain output,
+ * ret['dur']), d_dur [B, T] = clamp(round(exp(xs) - 1), min = 0) (ret['dur_choice']) and d_totals [B], the samples' frame counts:
+ * T_mel = max(d_totals) is what the caller reads back to size the outputs of the next two calls. */
+int maa_fs2_encode(maa_ctx* ctx, maa_fs2* fs2, const int* d_tokens, const int* d_pitch_midi, const float* d_midi_dur,
+                   const int* d_is_slur, int B, int T, float* d_encoder_out, float* d_xs, int* d_dur, int* d_totals);
+/* LengthRegulator: d_dur [B, T] (>= 0) -> d_mel2ph [B, T_mel], frame -> 1-based token, 0 past the sample's total. */
+int maa_fs2_length_regulate(maa_ctx* ctx, maa_fs2* fs2, const int* d_dur, int B, int T, int T_mel, int* d_mel2ph);
+/* decode: d_encoder_out [B, T, hidden_size], d_mel2ph [B, T_mel] in [0, T] -> d_decoder_inp [B, T_mel, hidden_size]
+ * (ret['decoder_inp']) and, unless NULL (skip_decoder), d_mel_out [B, T_mel, audio_num_mel_bins] (ret['mel_out']); both 0
+ * where mel2ph is 0. */
+int maa_fs2_decode(maa_ctx* ctx, maa_fs2* fs2, const float* d_encoder_out, const int* d_mel2ph, int B, int T, int T_mel,
+                   float* d_decoder_inp, float* d_mel_out);
+
 /* ---- conditioning encoders (the step before the sampler: text / image -> cross-attention context) ----------
  * kind 0: the CLAP text branch as FrozenCLAPEmbedder.encode runs it (ldm/modules/encoders/modules.py:204-211):
  *   transformers BertModel (bert-base-uncased, built by TextEncoder, CLAP/clap.py:41-45) on input_ids alone -- no
@@ -545,6 +582,12 @@ int maa_op_attention(maa_ctx* ctx, const float* d_q, const float* d_k, const flo
 int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const float* d_k, int ldk, int hsk,
                         const float* d_v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
                         float* d_y, int ldo, int out_split, int causal);
+/* The same layout with MultiheadAttention's key_padding_mask: d_key_mask [B, Nk] floats, non-zero = the key is hidden from every
+ * query of its sample (weight exactly 0).  A sample whose keys are all hidden is written as zeros.  The fused kernel takes
+ * dh = 128 in the bf16 modes; every other case runs the three-launch path.  causal must be 0 with a mask (an error otherwise). */
+int maa_op_attention_masked(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const float* d_k, int ldk, int hsk,
+                            const float* d_v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
+                            float* d_y, int ldo, int out_split, int causal, const float* d_key_mask);
 /* GroupNorm exactly as the models call it (tests of the normalisation kernels), on channels-last DEVICE buffers the caller has
  * laid out: rows of d_x1 [B,HW,*] have pitch ld1 >= C1 floats and hold channels 0 .. C1; the optional second source d_x2
  * [B,HW,*] (pitch ld2 >= C2; NULL with C2 = 0 for none) holds channels C1 .. C1+C2 -- a decoder ResBlock's (h | skip) without
