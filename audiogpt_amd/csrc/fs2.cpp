@@ -15,7 +15,10 @@
 //   * one FFTBlocks serves the encoder (mask = token 0) and the decoder (mask = an all-zero decoder_inp row, found on the device)
 // The three entry points issue launches on the context's stream only: no device-to-host copy, no synchronisation.  T_mel sizes
 // decode's outputs, so the caller reads the B totals between encode and decode -- the one read per utterance.
+// The "same" Conv1d with its epilogue activation, the decoder's sinusoid table and the predictor stack are seq_layers.h's,
+// shared with pitch_extractor.cpp; what stays here is the embeddings, FFTBlocks, the length regulator and the order of the whole.
 #include "models.h"
+#include "seq_layers.h"
 
 #include <cmath>
 #include <vector>
@@ -25,7 +28,6 @@ namespace maa {
 void launch_fs2_embed(const Ctx& ctx, const int* tok, const int* midi, const float* midi_dur, const int* slur, const float* E, int vocab,
                       const float* Mi, const float* dw, const float* db, const float* S, const float* pe, float scale, int B, int T, int H,
                       float* x, float* nonpad, float* hidden);
-void launch_fs2_hidden(const Ctx& ctx, const float* nonpad, long long n, float* hidden);
 void launch_fs2_dur_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
                          const float* w, const float* bias, const float* nonpad, float* xs, int* dur);
 void launch_fs2_length(Ctx& ctx, const int* dur, int B, int T, int* totals, int T_mel, int* mel2ph);
@@ -49,16 +51,6 @@ std::vector<float> rel_pos_table(int max_len, int dim) {
             tab[(size_t)i * dim + 2 * j + 1] = std::cos(a);
         }
     return tab;
-}
-
-inline T4 seq(float* p, int B, int T, int C) {
-    T4 t;
-    t.p = p;
-    t.B = B;
-    t.H = 1;
-    t.W = T;
-    t.C = C;
-    return t;
 }
 
 struct FFTLayer {
@@ -119,14 +111,7 @@ struct FFTBlocks {
             linear_into(ctx, a, H, rows, H, l.out_proj, x, H, y, H);
             launch_pe_affine_mask(ctx, y, rows, H, nullptr, nullptr, nonpad, x);
             launch_layernorm(ctx, x, rows, H, l.ln2w, l.ln2b, FS2_EPS, a);
-            T4 ta = seq(a, B, T, H), tw = seq(wide, B, T, 4 * H);
-            ConvOpt co;
-            co.KW = kernel;
-            co.pad = (kernel - 1) / 2;
-            co.pad_h = 0;
-            co.act = 3;
-            co.alpha = 1.f / std::sqrt((float)kernel);
-            conv_into(ctx, ta, nullptr, l.ffn1, co, tw);
+            conv1d_act(ctx, a, H, l.ffn1, kernel, B, T, 3, 1.f / std::sqrt((float)kernel), wide);
             linear_into(ctx, wide, 4 * H, rows, 4 * H, l.ffn2, x, H, y, H);
             launch_pe_affine_mask(ctx, y, rows, H, nullptr, nullptr, nonpad, x);
         }
@@ -145,15 +130,10 @@ struct FastSpeech2MIDI::Impl {
     int Cp = 0;                          // predictor width
     FFTBlocks enc, dec;
     float *embed = nullptr, *midi = nullptr, *dur_w = nullptr, *dur_b = nullptr, *slur = nullptr, *rel_pe = nullptr;
-    std::vector<PackedW> dp_conv;
-    std::vector<float*> dp_lnw, dp_lnb;
-    float *dp_w = nullptr, *dp_b = nullptr;
+    ConvPredictor dp;
     PackedW mel_out;
     float alpha = 1.f;
-    const float* table = nullptr;        // the decoder's sinusoid table [table_rows, hidden_size] on the device
-    int table_rows = 0;
-    DevSlab table_big;
-    std::vector<float> table_host;
+    SinusoidTable table;                 // the decoder's, [max(2000, T_mel + 1), hidden_size]
 
     void build(const StateDict& sd) {
         const int H = cfg.hidden_size;
@@ -170,34 +150,12 @@ struct FastSpeech2MIDI::Impl {
         rel_pe = ws.upload(rel_pos_table(FS2_REL_MAX_LEN, H));
         enc.build(ws, sd, "encoder", cfg.enc_layers, H, cfg.num_heads, cfg.enc_ffn_kernel_size);
         dec.build(ws, sd, "decoder", cfg.dec_layers, H, cfg.num_heads, cfg.dec_ffn_kernel_size);
-        for (int i = 0; i < cfg.dur_predictor_layers; ++i) {
-            const std::string p = "dur_predictor.conv." + std::to_string(i) + ".";
-            dp_conv.push_back(ws.pack_conv(sd, p + "1.weight", p + "1.bias", 1, cfg.dur_predictor_kernel));
-            MAA_CHECK(dp_conv.back().N == Cp && dp_conv.back().K == cfg.dur_predictor_kernel * (i ? Cp : H), "DurationPredictor conv shape " + p);
-            MAA_CHECK(get(sd, p + "3.weight").numel() == Cp, "DurationPredictor LayerNorm shape " + p);
-            dp_lnw.push_back(ws.vec(sd, p + "3.weight"));
-            dp_lnb.push_back(ws.vec(sd, p + "3.bias"));
-        }
-        MAA_CHECK(get(sd, "dur_predictor.linear.weight").numel() == Cp && get(sd, "dur_predictor.linear.bias").numel() == 1,
-                  "DurationPredictor linear must be [1, C_p]");
-        dp_w = ws.vec(sd, "dur_predictor.linear.weight");
-        dp_b = ws.vec(sd, "dur_predictor.linear.bias");
+        dp.build(ws, sd, "DurationPredictor", "dur_predictor.", cfg.dur_predictor_layers, cfg.dur_predictor_kernel, H, Cp, 1);
         mel_out = ws.pack_conv(sd, "mel_out.weight", "mel_out.bias", 1, 1);
         MAA_CHECK(mel_out.N == cfg.audio_num_mel_bins && mel_out.K == H, "FastSpeech2MIDI: mel_out must be [audio_num_mel_bins, hidden_size]");
         alpha = get(sd, "decoder.pos_embed_alpha").data[0];
         // (encoder_embed_tokens.weight is encoder.embed_tokens.weight again; decoder.embed_positions._float_tensor is bookkeeping)
-        table_rows = FS2_TABLE_INIT;
-        table = ws.upload(sinusoid_table(table_rows, H));
-    }
-
-    // max_pos = padding_idx + 1 + seq_len rows (common_layers.py:126-133): rebuilt and uploaded when T_mel outgrows the table
-    void grow_table(Ctx& ctx, int T) {
-        if (T + 1 <= table_rows) return;
-        table_host = sinusoid_table(T + 1, cfg.hidden_size);
-        float* d = static_cast<float*>(table_big.get(table_host.size() * sizeof(float), ctx.stream));
-        MAA_HIP(hipMemcpyAsync(d, table_host.data(), table_host.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
-        table = d;
-        table_rows = T + 1;
+        table.build(ws, FS2_TABLE_INIT, H);
     }
 
     void encode(Ctx& ctx, const int* tok, const int* pitch_midi, const float* midi_dur, const int* is_slur, int B, int T,
@@ -214,24 +172,8 @@ struct FastSpeech2MIDI::Impl {
         const size_t wide = (size_t)rows * (H > Cp ? H : Cp);
         float* a = ctx.ws.alloc_f(wide);
         float* b = ctx.ws.alloc_f(wide);
-        const float* src = encoder_out;
-        const int n = (int)dp_conv.size();
-        for (int i = 0; i < n; ++i) {
-            T4 tx = seq(const_cast<float*>(src), B, T, i ? Cp : H), ty = seq(a, B, T, Cp);
-            ConvOpt co;
-            co.KW = cfg.dur_predictor_kernel;
-            co.pad = (cfg.dur_predictor_kernel - 1) / 2;
-            co.pad_h = 0;
-            co.act = 2;
-            conv_into(ctx, tx, nullptr, dp_conv[i], co, ty);
-            if (i + 1 < n) {
-                launch_layernorm(ctx, a, rows, Cp, dp_lnw[i], dp_lnb[i], FS2_EPS, b);
-                launch_pe_affine_mask(ctx, b, rows, Cp, nullptr, nullptr, nonpad, b);
-                src = b;
-            } else {
-                launch_fs2_dur_head(ctx, a, rows, Cp, dp_lnw[i], dp_lnb[i], FS2_EPS, dp_w, dp_b, nonpad, xs, dur);
-            }
-        }
+        const float* y = dp.run(ctx, encoder_out, B, T, nonpad, a, b);
+        launch_fs2_dur_head(ctx, y, rows, Cp, dp.gamma(), dp.beta(), dp.EPS, dp.lin_w, dp.lin_b, nonpad, xs, dur);
         launch_fs2_length(ctx, dur, B, T, totals, 0, nullptr);
     }
 
@@ -246,9 +188,8 @@ struct FastSpeech2MIDI::Impl {
         float* hidden = ctx.ws.alloc_f((size_t)rows);
         float* x = ctx.ws.alloc_f((size_t)rows * H);
         float* y = ctx.ws.alloc_f((size_t)rows * H);
-        launch_pe_frame_mask(ctx, decoder_inp, rows, H, nonpad);
-        launch_fs2_hidden(ctx, nonpad, rows, hidden);
-        launch_pe_pos_add(ctx, decoder_inp, B, T_mel, H, table, alpha, x);
+        launch_pe_frame_mask(ctx, decoder_inp, rows, H, nonpad, hidden);
+        launch_pe_pos_add(ctx, decoder_inp, B, T_mel, H, table.ptr(), alpha, x);
         launch_pe_affine_mask(ctx, x, rows, H, nullptr, nullptr, nonpad, x);
         dec.forward(ctx, x, B, T_mel, nonpad, hidden, y);
         linear_into(ctx, y, H, rows, H, mel_out, nullptr, 0, mel, M);
@@ -285,7 +226,7 @@ void FastSpeech2MIDI::decode(Ctx& ctx, const float* encoder_out, const int* mel2
                              float* mel_out) {
     Impl& m = *impl_;
     PrecisionGuard pg(ctx, m.precision);
-    if (mel_out) m.grow_table(ctx, T_mel);
+    if (mel_out) m.table.grow(ctx, T_mel);
     run_sized(ctx, [&] { m.decode(ctx, encoder_out, mel2ph, B, T, T_mel, decoder_inp, mel_out); });
 }
 

@@ -7,18 +7,13 @@
 // tts_modules.py:98-118 the duration predictor's last LayerNorm, Linear(C, 1), mask and out2dur; :204-214 LengthRegulator;
 // modules/fastspeech/fs2.py:117-122,132 expand + mask of the encoder states.
 // All of them are memory-bound on a few hundred to a few thousand rows.
+// The launch grid and the duration head's LayerNorm + Linear stage are row_device.h's, shared with norm.hip's LayerNorm and
+// pitch.hip's head; the decoder's masks, masked products and positional add are pitch.hip's launches (models.h).
 #include "maa_internal.h"
+#include "row_device.h"
 
 namespace maa {
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-inline dim3 row_grid(long long rows) { return dim3((unsigned)((rows + 3) / 4)); }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
@@ -75,63 +70,27 @@ __global__ __launch_bounds__(256) void fs2_embed_kernel(const int* __restrict__ 
     }
 }
 
-// hidden[i] = 1 where nonpad[i] == 0, else 0
-__global__ __launch_bounds__(256) void fs2_hidden_kernel(const float* __restrict__ nonpad, long long n, float* __restrict__ hidden) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) hidden[i] = nonpad[i] == 0.f ? 1.f : 0.f;
-}
+// out2dur: max(rint(exp(xs) - 1), 0) (torch.round = half to even)
+__device__ __forceinline__ int fs2_out2dur(float xs) { return (int)fmaxf(rintf(expf(xs) - 1.f), 0.f); }
 
 // The duration predictor's last layer after its convolution (whose epilogue did the ReLU): LayerNorm over the row (kept in
-// registers, C <= 1024), mask, Linear(C, 1), mask -> xs[row]; dur[row] = max(rint(exp(xs) - 1), 0) (torch.round = half to even).
-// A padding row is 0 in both.
+// registers, C <= 256 * NR), mask, Linear(C, 1) (row_device.h), mask -> xs[row]; dur[row] = out2dur(xs).  A padding row is 0 in
+// both.
+template <int NR>
 __global__ __launch_bounds__(256) void fs2_dur_head_kernel(const float* __restrict__ x, long long rows, int C,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                            const float* __restrict__ w, const float* __restrict__ bias,
                                                            const float* __restrict__ nonpad, float* __restrict__ xs,
                                                            int* __restrict__ dur) {
-    constexpr int NR = 4;
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* src = x + row * C;
-    float4 v[NR];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < C) v[i] = *reinterpret_cast<const float4*>(src + c);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        if (c < C) {
-            const float a = v[i].x - mean, b = v[i].y - mean, d = v[i].z - mean, e = v[i].w - mean;
-            q += (a * a + b * b) + (d * d + e * e);
-        }
-    }
-    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)C + eps);
-    float d0 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        if (c < C) {
-            const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-            const float4 bt = *reinterpret_cast<const float4*>(beta + c);
-            const float4 w0 = *reinterpret_cast<const float4*>(w + c);
-            const float yx = (v[i].x - mean) * rstd * g.x + bt.x, yy = (v[i].y - mean) * rstd * g.y + bt.y;
-            const float yz = (v[i].z - mean) * rstd * g.z + bt.z, yw = (v[i].w - mean) * rstd * g.w + bt.w;
-            d0 += (yx * w0.x + yy * w0.y) + (yz * w0.z + yw * w0.w);
-        }
-    }
-    d0 = wave_sum(d0) + bias[0];
+    float d[1];
+    ln_head_dots<NR, 1>(x + row * C, C, lane, gamma, beta, eps, w, bias, d);
     if (lane == 0) {
-        const float o = nonpad[row] != 0.f ? d0 : 0.f;
+        const float o = nonpad[row] != 0.f ? d[0] : 0.f;
         xs[row] = o;
-        dur[row] = (int)fmaxf(rintf(expf(o) - 1.f), 0.f);
+        dur[row] = fs2_out2dur(o);
     }
 }
 
@@ -208,19 +167,20 @@ void launch_fs2_embed(const Ctx& ctx, const int* tok, const int* midi, const flo
     MAA_HIP(hipGetLastError());
 }
 
-void launch_fs2_hidden(const Ctx& ctx, const float* nonpad, long long n, float* hidden) {
-    if (ctx.ws.dry) return;
-    ProfScope prof(ctx, "fs2_rows", 0.0, 8.0 * n);
-    hipLaunchKernelGGL(fs2_hidden_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx.stream, nonpad, n, hidden);
-    MAA_HIP(hipGetLastError());
-}
-
 void launch_fs2_dur_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
                          const float* w, const float* bias, const float* nonpad, float* xs, int* dur) {
     if (ctx.ws.dry) return;
     MAA_CHECK(C % 4 == 0 && C <= 1024, "FastSpeech2MIDI: predictor width must be a multiple of 4, at most 1024");
     ProfScope prof(ctx, "fs2_rows", 0.0, 4.0 * rows * (double)C);
-    hipLaunchKernelGGL(fs2_dur_head_kernel, row_grid(rows), dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, w, bias, nonpad, xs, dur);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, row_grid(rows), dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, w, bias, nonpad, xs, dur);
+    };
+    if (C <= 256)
+        go(fs2_dur_head_kernel<1>);
+    else if (C <= 512)
+        go(fs2_dur_head_kernel<2>);
+    else
+        go(fs2_dur_head_kernel<4>);
     MAA_HIP(hipGetLastError());
 }
 

@@ -105,16 +105,16 @@ private:
     Impl* impl_;
 };
 
-// What the extractor and the FastSpeech2 front end share (pitch.hip, pitch_extractor.cpp):
-// mask[row] = 0 where every channel of the row is +-0, else 1
-void launch_pe_frame_mask(const Ctx& ctx, const float* mel, long long rows, int M, float* mask);
+// Row launches of pitch.hip that the extractor and the FastSpeech2 front end share.  Their shared host layers -- the "same"
+// Conv1d with an epilogue activation, the sinusoid table, the convolutional predictor stack -- are seq_layers.h's; the device
+// code under their LayerNorms and heads is row_device.h's.
+// mask[row] = 0 where every channel of the row is +-0, else 1; hidden (optional) [row] = 1 - mask[row], an attention key mask
+void launch_pe_frame_mask(const Ctx& ctx, const float* mel, long long rows, int M, float* mask, float* hidden = nullptr);
 // out = (x * scale + shift) * mask[row]; scale == nullptr: out = x * mask[row] (out may be x)
 void launch_pe_affine_mask(const Ctx& ctx, const float* x, long long rows, int C, const float* scale, const float* shift,
                            const float* mask, float* out);
 // out = x + alpha * table[make_positions(x[..., 0])], the positions counted on the device
 void launch_pe_pos_add(Ctx& ctx, const float* x, int B, int T, int C, const float* table, float alpha, float* out);
-// SinusoidalPositionalEmbedding.get_embedding(rows, dim, padding_idx = 0) in fp32
-std::vector<float> sinusoid_table(int rows, int dim);
 
 // DiffSinger's FastSpeech2MIDI front end (fs2.cpp, fs2.hip): score -> encoder_out / durations, then mel2ph -> decoder_inp / mel_out
 class FastSpeech2MIDI {

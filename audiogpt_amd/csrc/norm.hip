@@ -6,20 +6,13 @@
 // All three are HBM/L2-bound; reductions are wave64 shuffles plus one LDS hop across the 4 waves.
 #include "igemm_device.h"
 #include "maa_internal.h"
+#include "row_device.h"
 
 namespace maa {
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
+// the waves' sums added left to right over blockDim / 64 waves (not pitch.hip's (r0 + r1) + (r2 + r3): another rounding, so the
+// two stay apart)
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -336,7 +329,7 @@ GnFusedPlan gn_fused_plan(int C, int C1, int HW, int groups) {
     return pl;
 }
 
-// LayerNorm: one wave per row, four channels per lane per step, row cached in registers (C <= 256*NR)
+// LayerNorm: one wave per row, four channels per lane per step, row cached in registers (C <= 256*NR): row_device.h's LnRow
 template <int NR>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, long long rows, int C,
                                                         const float* __restrict__ gamma,
@@ -345,44 +338,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63;
     const long long row = (long long)xcd_contiguous((int)blockIdx.x, (int)gridDim.x) * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* src = x + row * C;
-    float4 v[NR];
-    float s = 0.f;
+    LnRow<NR> r;
+    r.load(x + row * C, C, lane, eps);
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
         const int c = (lane + 64 * i) * 4;
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < C) t = *reinterpret_cast<const float4*>(src + c);
-        v[i].x = t.x;
-        v[i].y = t.y;
-        v[i].z = t.z;
-        v[i].w = t.w;
-        s += (t.x + t.y) + (t.z + t.w);
-    }
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        if (c < C) {
-            const float a = v[i].x - mean, b = v[i].y - mean, d = v[i].z - mean, e = v[i].w - mean;
-            q += (a * a + b * b) + (d * d + e * e);
-        }
-    }
-    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)C + eps);
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        if (c < C) {
-            const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-            const float4 bt = *reinterpret_cast<const float4*>(beta + c);
-            float4 y;
-            y.x = (v[i].x - mean) * rstd * g.x + bt.x;
-            y.y = (v[i].y - mean) * rstd * g.y + bt.y;
-            y.z = (v[i].z - mean) * rstd * g.z + bt.z;
-            y.w = (v[i].w - mean) * rstd * g.w + bt.w;
-            store4(out, row, c, C, split, y);
-        }
+        if (c < C) store4(out, row, c, C, split, r.norm(i, c, gamma, beta));
     }
 }
 
@@ -550,7 +511,7 @@ void launch_layernorm(const Ctx& ctx, const float* x, long long rows, int C, con
     if (ctx.ws.dry) return;
     MAA_CHECK(C <= 2048 && C % 4 == 0, "layernorm width");
     ProfScope prof(ctx, "layernorm", 0.0, 8.0 * rows * (double)C);
-    dim3 grid((unsigned)((rows + 3) / 4));
+    const dim3 grid = row_grid(rows);
     if (C <= 256)
         hipLaunchKernelGGL(layernorm_kernel<1>, grid, dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, out, out_split);
     else if (C <= 512)
@@ -566,7 +527,7 @@ void launch_softmax(const Ctx& ctx, float* s, long long rows, int cols, int ld, 
     if (ctx.ws.dry) return;
     MAA_CHECK(ld >= cols, "softmax ld");
     ProfScope prof(ctx, "softmax", 0.0, 8.0 * rows * (double)ld);
-    dim3 grid((unsigned)((rows + 3) / 4));
+    const dim3 grid = row_grid(rows);
     if (ld <= 128)
         hipLaunchKernelGGL(softmax_kernel<2>, grid, dim3(256), 0, ctx.stream, s, rows, cols, ld, causal_nq);
     else if (ld <= 256)
@@ -582,7 +543,7 @@ void launch_softmax_masked(const Ctx& ctx, float* s, long long rows, int cols, i
     if (ctx.ws.dry) return;
     MAA_CHECK(ld >= cols && key_mask && rows_per_sample > 0, "masked softmax arguments");
     ProfScope prof(ctx, "softmax", 0.0, 8.0 * rows * (double)ld);
-    hipLaunchKernelGGL(softmax_masked_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx.stream, s, rows, cols, ld, key_mask,
+    hipLaunchKernelGGL(softmax_masked_kernel, row_grid(rows), dim3(256), 0, ctx.stream, s, rows, cols, ld, key_mask,
                        rows_per_sample);
     MAA_HIP(hipGetLastError());
 }

@@ -6,18 +6,16 @@
 // make_positions and modules/commons/common_layers.py:141-142 the table gather, tts_modules.py:253-254 the positional add;
 // tts_modules.py:240,259 the last LayerNorm and Linear(C, 2), utils/pitch_utils.py:63-76 denorm_f0.
 // All of them are memory-bound; a [1500, 256] activation is 1.5 MB and stays in L2 between launches.
+// The wave reductions, the launch grid and the head's LayerNorm + Linear stage are row_device.h's (with norm.hip's LayerNorm and
+// fs2.hip's duration head); the frame mask, the masked affine and the positional add also serve the FastSpeech2 front end.
 #include "maa_internal.h"
+#include "row_device.h"
 
 namespace maa {
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// 256 threads: sum over the block, the same value in every thread (fixed order: bit-reproducible)
+// 256 threads: sum over the block, the same value in every thread (fixed order: bit-reproducible).  The four waves' sums add as
+// (r0 + r1) + (r2 + r3), not left to right as norm.hip's block_sum does: another rounding, so the two stay apart
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -27,11 +25,9 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-inline dim3 row_grid(long long rows) { return dim3((unsigned)((rows + 3) / 4)); }
-
-// mask[row] = 0 where every bin of the frame is +-0, else 1      (pe.py:29-30, :143)
+// mask[row] = 0 where every bin of the frame is +-0, else 1      (pe.py:29-30, :143); hidden (optional) [row] = 1 - mask[row]
 __global__ __launch_bounds__(256) void pe_frame_mask_kernel(const float* __restrict__ mel, long long rows, int M,
-                                                            float* __restrict__ mask) {
+                                                            float* __restrict__ mask, float* __restrict__ hidden) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -42,7 +38,10 @@ __global__ __launch_bounds__(256) void pe_frame_mask_kernel(const float* __restr
         any |= (v.x | v.y | v.z | v.w) & 0x7fffffffu;
     }
     const unsigned long long nz = __ballot(any != 0u);
-    if (lane == 0) mask[row] = nz ? 1.f : 0.f;
+    if (lane == 0) {
+        mask[row] = nz ? 1.f : 0.f;
+        if (hidden) hidden[row] = nz ? 0.f : 1.f;
+    }
 }
 
 // out = (x * scale + shift) * mask[row]; scale == nullptr: out = x * mask[row]      (pe.py:35 / :40)
@@ -169,9 +168,16 @@ __global__ __launch_bounds__(256) void pe_pos_add_kernel(const float* __restrict
     }
 }
 
+// denorm_f0.  norm 0: 2 ** v; 1: v * f0_std + f0_mean.  use_uv: 0 where the logit is > 0; then 0 where the frame is padding.
+__device__ __forceinline__ float pe_denorm_f0(float v, float uv, float live, int norm, float f0_mean, float f0_std, int use_uv) {
+    float f = norm == 0 ? exp2f(v) : v * f0_std + f0_mean;
+    if (use_uv && uv > 0.f) f = 0.f;
+    if (live == 0.f) f = 0.f;
+    return f;
+}
+
 // The predictor's last layer after its convolution (whose epilogue did the ReLU): LayerNorm over the row (kept in registers,
-// C <= 256 * NR), Linear(C, 2), denorm_f0 -> pitch_pred[row] = {f0 value, voicing logit}, f0[row].
-// norm 0: 2 ** v; 1: v * f0_std + f0_mean.  use_uv: 0 where the logit is > 0; then 0 where the frame is padding.
+// C <= 256 * NR) and Linear(C, 2) (row_device.h), denorm_f0 -> pitch_pred[row] = {f0 value, voicing logit}, f0[row].
 template <int NR>
 __global__ __launch_bounds__(256) void pe_head_kernel(const float* __restrict__ x, long long rows, int C,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -181,60 +187,21 @@ __global__ __launch_bounds__(256) void pe_head_kernel(const float* __restrict__ 
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* src = x + row * C;
-    float4 v[NR];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < C) v[i] = *reinterpret_cast<const float4*>(src + c);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        if (c < C) {
-            const float a = v[i].x - mean, b = v[i].y - mean, d = v[i].z - mean, e = v[i].w - mean;
-            q += (a * a + b * b) + (d * d + e * e);
-        }
-    }
-    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)C + eps);
-    float d0 = 0.f, d1 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        if (c < C) {
-            const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-            const float4 bt = *reinterpret_cast<const float4*>(beta + c);
-            const float4 w0 = *reinterpret_cast<const float4*>(w + c);
-            const float4 w1 = *reinterpret_cast<const float4*>(w + C + c);
-            const float yx = (v[i].x - mean) * rstd * g.x + bt.x, yy = (v[i].y - mean) * rstd * g.y + bt.y;
-            const float yz = (v[i].z - mean) * rstd * g.z + bt.z, yw = (v[i].w - mean) * rstd * g.w + bt.w;
-            d0 += (yx * w0.x + yy * w0.y) + (yz * w0.z + yw * w0.w);
-            d1 += (yx * w1.x + yy * w1.y) + (yz * w1.z + yw * w1.w);
-        }
-    }
-    d0 = wave_sum(d0) + bias[0];
-    d1 = wave_sum(d1) + bias[1];
+    float d[2];
+    ln_head_dots<NR, 2>(x + row * C, C, lane, gamma, beta, eps, w, bias, d);
     if (lane == 0) {
-        float f = norm == 0 ? exp2f(d0) : d0 * f0_std + f0_mean;
-        if (use_uv && d1 > 0.f) f = 0.f;
-        if (mask[row] == 0.f) f = 0.f;
-        *reinterpret_cast<float2*>(pitch_pred + row * 2) = make_float2(d0, d1);
-        f0[row] = f;
+        *reinterpret_cast<float2*>(pitch_pred + row * 2) = make_float2(d[0], d[1]);
+        f0[row] = pe_denorm_f0(d[0], d[1], mask[row], norm, f0_mean, f0_std, use_uv);
     }
 }
 
 }  // namespace
 
-void launch_pe_frame_mask(const Ctx& ctx, const float* mel, long long rows, int M, float* mask) {
+void launch_pe_frame_mask(const Ctx& ctx, const float* mel, long long rows, int M, float* mask, float* hidden) {
     if (ctx.ws.dry) return;
     MAA_CHECK(M % 4 == 0, "pitch extractor: n_mel_bins must be a multiple of 4");
     ProfScope prof(ctx, "pe_rows", 0.0, 4.0 * rows * (double)M);
-    hipLaunchKernelGGL(pe_frame_mask_kernel, row_grid(rows), dim3(256), 0, ctx.stream, mel, rows, M, mask);
+    hipLaunchKernelGGL(pe_frame_mask_kernel, row_grid(rows), dim3(256), 0, ctx.stream, mel, rows, M, mask, hidden);
     MAA_HIP(hipGetLastError());
 }
 

@@ -12,7 +12,10 @@
 //   * the sinusoid table is built on the host with the reference's fp32 formula: init_size rows at creation, grown to T + 1
 // forward issues launches on the context's stream only: no device-to-host copy, no synchronisation (growing the workspace
 // or the table past 4096 rows, once per new largest shape, reallocates).
+// The "same" Conv1d + ReLU, the sinusoid table and the predictor stack are seq_layers.h's, shared with fs2.cpp; what stays here
+// is the Prenet with its BatchNorm folding, ConvStacks and the order of the whole.
 #include "models.h"
+#include "seq_layers.h"
 
 #include <cmath>
 #include <vector>
@@ -25,35 +28,10 @@ void launch_pe_head(const Ctx& ctx, const float* x, long long rows, int C, const
                     const float* w, const float* bias, const float* mask, int norm, float f0_mean, float f0_std, int use_uv,
                     float* pitch_pred, float* f0);
 
-// SinusoidalPositionalEmbedding.get_embedding(rows, dim, padding_idx = 0) in fp32 (common_layers.py:104-121)
-std::vector<float> sinusoid_table(int rows, int dim) {
-    const int half = dim / 2;
-    const float step = (float)-(std::log(10000.0) / (double)(half - 1));
-    std::vector<float> freq(half), tab((size_t)rows * dim, 0.f);
-    for (int j = 0; j < half; ++j) freq[j] = std::exp((float)j * step);
-    for (int p = 1; p < rows; ++p)              // (row 0 = padding_idx stays zero)
-        for (int j = 0; j < half; ++j) {
-            const float a = (float)p * freq[j];
-            tab[(size_t)p * dim + j] = std::sin(a);
-            tab[(size_t)p * dim + half + j] = std::cos(a);
-        }
-    return tab;
-}
-
 namespace {
 
 constexpr int PE_PRENET_LAYERS = 3, PE_PREDICTOR_LAYERS = 5, PE_KERNEL = 5, PE_TABLE_INIT = 4096;
 constexpr float PE_EPS = 1e-5f;
-
-inline T4 seq(float* p, int B, int T, int C) {
-    T4 t;
-    t.p = p;
-    t.B = B;
-    t.H = 1;
-    t.W = T;
-    t.C = C;
-    return t;
-}
 
 }  // namespace
 
@@ -63,15 +41,12 @@ struct PitchExtractor::Impl {
     WeightStore ws;
     explicit Impl(int prec) : precision(prec), ws(prec != 0) {}
     int Cp = 0;                         // predictor width
-    std::vector<PackedW> pre_conv, enc_conv, pp_conv;
-    std::vector<float*> bn_scale, bn_shift, gn_w, gn_b, ln_w, ln_b;
+    std::vector<PackedW> pre_conv, enc_conv;
+    std::vector<float*> bn_scale, bn_shift, gn_w, gn_b;
     PackedW pre_out, enc_in, enc_out;
-    float *lin_w = nullptr, *lin_b = nullptr;
+    ConvPredictor pp;
     float alpha = 1.f;
-    const float* table = nullptr;       // [table_rows, hidden_size] on the device
-    int table_rows = 0;
-    DevSlab table_big;                  // the table once T + 1 exceeds init_size
-    std::vector<float> table_host;      // source of the grown table's upload
+    SinusoidTable table;                // [max(4096, T + 1), hidden_size]
 
     void build(const StateDict& sd) {
         const int H = cfg.hidden_size;
@@ -103,42 +78,10 @@ struct PitchExtractor::Impl {
             enc_out = ws.pack_conv(sd, "mel_encoder.out_proj.weight", "mel_encoder.out_proj.bias", 1, 1);
             MAA_CHECK(enc_in.N == H && enc_out.N == H, "ConvStacks projection shape");
         }
-        for (int i = 0; i < PE_PREDICTOR_LAYERS; ++i) {
-            const std::string p = "pitch_predictor.conv." + std::to_string(i) + ".";
-            pp_conv.push_back(ws.pack_conv(sd, p + "1.weight", p + "1.bias", 1, cfg.predictor_kernel));
-            MAA_CHECK(pp_conv.back().N == Cp && pp_conv.back().K == cfg.predictor_kernel * (i ? Cp : H), "PitchPredictor conv shape " + p);
-            MAA_CHECK(get(sd, p + "3.weight").numel() == Cp, "PitchPredictor LayerNorm shape " + p);
-            ln_w.push_back(ws.vec(sd, p + "3.weight"));
-            ln_b.push_back(ws.vec(sd, p + "3.bias"));
-        }
-        const HostTensor& lw = get(sd, "pitch_predictor.linear.weight");
-        MAA_CHECK(lw.numel() == 2LL * Cp && get(sd, "pitch_predictor.linear.bias").numel() == 2, "PitchPredictor linear must be [2, C_p]");
-        lin_w = ws.vec(sd, "pitch_predictor.linear.weight");
-        lin_b = ws.vec(sd, "pitch_predictor.linear.bias");
+        pp.build(ws, sd, "PitchPredictor", "pitch_predictor.", PE_PREDICTOR_LAYERS, cfg.predictor_kernel, H, Cp, 2);
         alpha = get(sd, "pitch_predictor.pos_embed_alpha").data[0];
         // (mel_prenet.layers.i.2.num_batches_tracked and pitch_predictor.embed_positions._float_tensor are bookkeeping: not read)
-        table_rows = PE_TABLE_INIT;
-        table = ws.upload(sinusoid_table(table_rows, H));
-    }
-
-    // max_pos = padding_idx + 1 + seq_len rows (common_layers.py:126-133): rebuilt and uploaded when T outgrows the table
-    void grow_table(Ctx& ctx, int T) {
-        if (T + 1 <= table_rows) return;
-        table_host = sinusoid_table(T + 1, cfg.hidden_size);
-        float* d = static_cast<float*>(table_big.get(table_host.size() * sizeof(float), ctx.stream));
-        MAA_HIP(hipMemcpyAsync(d, table_host.data(), table_host.size() * sizeof(float), hipMemcpyHostToDevice, ctx.stream));
-        table = d;
-        table_rows = T + 1;
-    }
-
-    void conv(Ctx& ctx, float* x, int Cin, const PackedW& w, int k, int B, int T, float* y) {
-        T4 a = seq(x, B, T, Cin), o = seq(y, B, T, w.N);
-        ConvOpt co;
-        co.KW = k;
-        co.pad = (k - 1) / 2;
-        co.pad_h = 0;
-        co.act = 2;
-        conv_into(ctx, a, nullptr, w, co, o);
+        table.build(ws, PE_TABLE_INIT, H);
     }
 
     void forward(Ctx& ctx, const float* mel, int B, int T, float* pitch_pred, float* f0, float* hidden_out) {
@@ -153,7 +96,7 @@ struct PitchExtractor::Impl {
         const float* src = mel;
         for (int i = 0; i < PE_PRENET_LAYERS; ++i) {
             float* y = i % 2 ? b : a;
-            conv(ctx, const_cast<float*>(src), i ? H : M, pre_conv[i], PE_KERNEL, B, T, y);
+            conv1d_act(ctx, src, i ? H : M, pre_conv[i], PE_KERNEL, B, T, 2, 1.f, y);
             launch_pe_affine_mask(ctx, y, rows, H, bn_scale[i], bn_shift[i], mask, y);
             src = y;
         }
@@ -165,7 +108,7 @@ struct PitchExtractor::Impl {
             float *x = a, *y = b;
             linear_into(ctx, h, H, rows, H, enc_in, nullptr, 0, x, H);
             for (int i = 0; i < cfg.conv_layers; ++i) {
-                T4 tx = seq(x, B, T, H), ty = seq(y, B, T, H);
+                T4 tx = seq_t4(x, B, T, H), ty = seq_t4(y, B, T, H);
                 conv1d_same(ctx, tx, enc_conv[i], PE_KERNEL, 1, 0.f, nullptr, 1.f, 0, ty);
                 launch_pe_gn_relu_res(ctx, y, x, B, T, H, H / 16, gn_w[i], gn_b[i], PE_EPS, y);
                 float* t = x;
@@ -179,17 +122,10 @@ struct PitchExtractor::Impl {
             MAA_HIP(hipMemcpyAsync(hidden_out, h, (size_t)rows * H * sizeof(float), hipMemcpyDeviceToDevice, ctx.stream));
         // ---- PitchPredictor (tts_modules.py:247-260) and denorm_f0
         float* x = h == a ? b : a;
-        launch_pe_pos_add(ctx, h, B, T, H, table, alpha, x);
-        float* y = h;
-        for (int i = 0; i < PE_PREDICTOR_LAYERS; ++i) {
-            conv(ctx, x, i ? Cp : H, pp_conv[i], cfg.predictor_kernel, B, T, y);
-            if (i + 1 < PE_PREDICTOR_LAYERS) {
-                launch_layernorm(ctx, y, rows, Cp, ln_w[i], ln_b[i], PE_EPS, x);
-            } else {
-                launch_pe_head(ctx, y, rows, Cp, ln_w[i], ln_b[i], PE_EPS, lin_w, lin_b, mask, cfg.pitch_norm, cfg.f0_mean, cfg.f0_std,
-                               cfg.use_uv, pitch_pred, f0);
-            }
-        }
+        launch_pe_pos_add(ctx, h, B, T, H, table.ptr(), alpha, x);
+        const float* y = pp.run(ctx, x, B, T, nullptr, h, x);          // (a LayerNorm writes over x, which its convolution has read)
+        launch_pe_head(ctx, y, rows, Cp, pp.gamma(), pp.beta(), pp.EPS, pp.lin_w, pp.lin_b, mask, cfg.pitch_norm, cfg.f0_mean, cfg.f0_std,
+                       cfg.use_uv, pitch_pred, f0);
     }
 };
 
@@ -209,7 +145,7 @@ const maa_pitch_extractor_config& PitchExtractor::config() const { return impl_-
 void PitchExtractor::forward(Ctx& ctx, const float* mel, int B, int T, float* pitch_pred, float* f0, float* hidden_out) {
     Impl& m = *impl_;
     PrecisionGuard pg(ctx, m.precision);
-    m.grow_table(ctx, T);
+    m.table.grow(ctx, T);
     run_sized(ctx, [&] { m.forward(ctx, mel, B, T, pitch_pred, f0, hidden_out); });
 }
 

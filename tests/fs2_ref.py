@@ -20,7 +20,7 @@ from tests import pe_ref as P
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 # (file, array prefix) of every golden forward
-CASES = [("fs2_b2_t33", ""), ("fs2_short", "t1."), ("fs2_short", "t4."), ("fs2_given_mel2ph", "")]
+CASES = [("fs2_b2_t33", ""), ("fs2_short", "t1."), ("fs2_short", "t4."), ("fs2_given_mel2ph", ""), ("fs2_ph384_b2_t9", "")]
 FLOATS = ("encoder_out", "xs", "decoder_inp", "mel_out")
 EPS = 1e-5
 REL_MAX_LEN = 5000

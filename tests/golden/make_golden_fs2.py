@@ -1,6 +1,6 @@
 """Golden vectors of DiffSinger's FastSpeech2MIDI, from the REFERENCE's own class (run in the build container only).
 
-    python tests/golden/make_golden_fs2.py      # needs /root/reference; writes tests/golden/fs2_*.npz
+    python tests/golden/make_golden_fs2.py [name ...]     # needs /root/reference; writes tests/golden/fs2_*.npz (or the named ones)
 
 The real `modules.diffsinger_midi.fs2.FastSpeech2MIDI` is constructed on the CPU with the approach of make_golden_pe.py:
 `utils.hparams.hparams` is used as the plain dict it is and updated with the keys the class reads; empty stub modules stand in
@@ -8,7 +8,8 @@ for `librosa` and `pycwt`, which the imports pull in and the inference path neve
 stubs are installed: its availability probe raises on a stub without `__spec__`); the dictionary is an object with `__len__`
 and `pad()`.  Weights are `WT.make_fs2_state_dict(cfg, seed=17)` loaded with strict=True and are not stored, except
 `dur_predictor.linear.bias`, which the generator moves so that the median duration of the live tokens of the first case is
-3 - 5 frames (random weights put it near 0); the later cases reuse that bias.
+3 - 5 frames (random weights put it near 0); the later cases reuse that bias, except fs2_ph384_b2_t9 (predictor_hidden = 384,
+one encoder and one decoder layer: other weights), which moves its own the same way.
 
 Durations are a rounding, so the input seed is searched (deterministically, at most 64 attempts from the case's first seed on)
 until NO live token of the case lies within the bf16x3 gate of a rounding boundary:
@@ -200,7 +201,13 @@ def main():
     assert int((m2p[0] > 0).sum()) == 66 and int((m2p[1] > 0).sum()) == 40
     cases["fs2_given_mel2ph"], _ = case(fs2, hparams, "given_mel2ph", base, [("", 2, 33, pads33)], seed=53, linear_bias=bias,
                                         given={"": m2p})
+    # a predictor wider than one float4 per lane (the duration head's second register layout): small, its own duration bias
+    wide = dict(base, predictor_hidden=384, enc_layers=1, dec_layers=1)
+    cases["fs2_ph384_b2_t9"], _ = case(fs2, hparams, "ph384_b2_t9", wide, [("", 2, 9, {1: range(6, 9)})], seed=54)
+    only = sys.argv[1:]          # names of the files to (re)write; none: all of them
     for name, arrays in cases.items():
+        if only and name not in only:
+            continue
         path = os.path.join(HERE, name + ".npz")
         np.savez_compressed(path, **arrays)
         print(name, "%d bytes" % os.path.getsize(path))

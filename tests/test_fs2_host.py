@@ -65,6 +65,9 @@ def test_golden_cases_are_what_the_tests_need():
     assert m["mel2ph_in"].shape == (2, 70) and "dur_choice" not in m
     z = (torch.from_numpy(m["mel2ph_in"]) == 0).sum(-1)
     assert int(z[0]) != int(z[1]) and 6 not in m["mel2ph_in"][0].tolist()              # token 5 (1-based 6) has no frame
+    wcfg, _, w = R.load_case("fs2_ph384_b2_t9")
+    assert wcfg["predictor_hidden"] == 384 and wcfg["hidden_size"] == 256            # the duration head leaves one float4 per lane
+    assert w["txt_tokens"].shape == (2, 9) and (w["txt_tokens"][0] != 0).all() and (w["txt_tokens"][1] == 0).tolist() == [False] * 6 + [True] * 3
 
 
 def test_state_dict_keys_match_reference():
@@ -214,7 +217,8 @@ def test_new_kernels_do_not_spill(tmp_path):
                              r"\s+\.vgpr_spill_count:\s+(\d+)", open(out).read()):
             meta[m.group(1)] = (int(m.group(2)), int(m.group(3)), int(m.group(4)))
     names = " ".join(meta)
-    for k in ("fs2_embed_kernel", "fs2_hidden_kernel", "fs2_dur_head_kernel", "fs2_length_kernel", "fs2_expand_kernel",
+    for k in ("fs2_embed_kernel", "fs2_dur_head_kernelILi1E", "fs2_dur_head_kernelILi2E", "fs2_dur_head_kernelILi4E", "fs2_length_kernel",
+              "fs2_expand_kernel",
               "flash_attn_kernelILi128ELi3ELb1E", "flash_attn_kernelILi128ELi1ELb1E"):
         assert k in names, k
     for name, (private, vg, spill) in meta.items():
