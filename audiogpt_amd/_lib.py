@@ -95,6 +95,12 @@ class maa_fs2_config(C.Structure):
         "use_pitch_embed", "use_energy_embed", "use_spk_id", "use_spk_embed", "use_bert")]
 
 
+class maa_fs2_pitch_config(C.Structure):
+    _fields_ = [(k, C.c_int) for k in (
+        "hidden_size", "predictor_hidden", "predictor_layers", "predictor_kernel", "ffn_padding_same", "pitch_type_frame",
+        "pitch_ar", "use_uv", "pitch_norm")] + [("f0_mean", C.c_float), ("f0_std", C.c_float)]
+
+
 class maa_encoder_config(C.Structure):
     _fields_ = [("kind", C.c_int), ("layers", C.c_int), ("width", C.c_int), ("heads", C.c_int), ("mlp_dim", C.c_int),
                 ("d_proj", C.c_int), ("vocab", C.c_int), ("max_positions", C.c_int), ("patch", C.c_int),
@@ -147,6 +153,7 @@ EXPORTS = [
     "maa_plms_sample", "maa_ds_ddpm_sample", "maa_ds_ddpm_update",
     "maa_pitch_extractor_create", "maa_pitch_extractor_destroy", "maa_pitch_extractor_forward",
     "maa_fs2_create", "maa_fs2_destroy", "maa_fs2_encode", "maa_fs2_length_regulate", "maa_fs2_decode",
+    "maa_fs2_run_decoder", "maa_fs2_pitch_create", "maa_fs2_pitch_destroy", "maa_fs2_pitch_forward",
     "maa_encoder_create", "maa_encoder_destroy", "maa_encoder_text", "maa_encoder_image",
     "maa_encoder_text_cls", "maa_clap_audio_create", "maa_clap_audio_destroy", "maa_clap_audio_embed", "maa_clap_similarity",
     "maa_spectral_create", "maa_spectral_destroy", "maa_spectral_forward", "maa_resampler_create", "maa_resampler_destroy",
@@ -219,6 +226,10 @@ def load():
         "maa_fs2_encode": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
         "maa_fs2_length_regulate": [vp, vp, vp, ci, ci, ci, vp],
         "maa_fs2_decode": [vp, vp, vp, vp, ci, ci, ci, vp, vp],
+        "maa_fs2_run_decoder": [vp, vp, vp, vp, ci, ci, vp],
+        "maa_fs2_pitch_create": [vp, C.POINTER(maa_fs2_pitch_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+        "maa_fs2_pitch_destroy": [vp],
+        "maa_fs2_pitch_forward": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
         "maa_encoder_create": [vp, C.POINTER(maa_encoder_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
         "maa_encoder_destroy": [vp],
         "maa_encoder_text": [vp, vp, vp, ci, ci, vp],

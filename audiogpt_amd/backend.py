@@ -1166,7 +1166,10 @@ class PitchExtractor:
 def fs2_config(cfg):
     """maa_fs2_config of a FastSpeech2MIDI hparams dict (config.FASTSPEECH2_MIDI); refuses what the library does not build, with
     the reason, before any device is touched."""
-    for k in ("use_pitch_embed", "use_energy_embed", "use_spk_id", "use_spk_embed", "use_bert"):
+    if cfg.get("use_pitch_embed", False):
+        raise L.MaaError("FastSpeech2MIDI: use_pitch_embed is not supported by this handle: the pitch branch is FS2Pitch beside "
+                         "it, composed by diffsinger.FastSpeech2MIDICascade")
+    for k in ("use_energy_embed", "use_spk_id", "use_spk_embed", "use_bert"):
         if cfg.get(k, False):
             raise L.MaaError("FastSpeech2MIDI: %s is not supported: no shipped e2e singing configuration sets it and its branch "
                              "is not built" % k)
@@ -1263,9 +1266,118 @@ class FastSpeech2MIDI:
                                                 self._p(mel)))
         return dec_inp, mel
 
+    def run_decoder(self, decoder_inp, mel2ph):
+        """FastSpeech2.run_decoder: decoder_inp [B, T_mel, H] (an all-zero row is padding), mel2ph [B, T_mel] -> mel_out
+        [B, T_mel, mel bins]: decode's second half on a decoder_inp another stage finished (FS2Pitch)."""
+        x = _f32(decoder_inp, self.ctx.device)
+        m2p = self._i32(mel2ph)
+        if x.dim() != 3 or x.shape[2] != self.cfg["hidden_size"] or x.shape[0] < 1 or x.shape[1] < 1:
+            raise L.MaaError("FastSpeech2MIDI.run_decoder: decoder_inp %s is not [B, T_mel, %d]" % (tuple(x.shape), self.cfg["hidden_size"]))
+        B, T_mel, _ = x.shape
+        if tuple(m2p.shape) != (B, T_mel):
+            raise L.MaaError("FastSpeech2MIDI.run_decoder: mel2ph %s is not [%d, %d]" % (tuple(m2p.shape), B, T_mel))
+        mel = torch.empty(B, T_mel, self.cfg["audio_num_mel_bins"], device=self.ctx.device)
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_fs2_run_decoder(self.ctx.h, self.h, self._p(x), self._p(m2p), B, T_mel, self._p(mel)))
+        return mel
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.maa_fs2_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fs2_pitch_config(cfg):
+    """maa_fs2_pitch_config of a FastSpeech2MIDI hparams dict with use_pitch_embed (config.FASTSPEECH2_MIDI_CASCADE); refuses what
+    the library does not build, with the reason, before any device is touched."""
+    what = "FastSpeech2MIDI pitch branch"
+    ptype = cfg.get("pitch_type", "frame")
+    if ptype == "ph":
+        raise L.MaaError("%s: pitch_type 'ph' is not supported: only 'frame' is built (the phoneme-level predictor reads "
+                         "encoder_out and gathers the coarse pitch by mel2ph; no shipped singing configuration sets it)" % what)
+    if ptype == "cwt":
+        raise L.MaaError("%s: pitch_type 'cwt' is not supported: the reference's own modules/fastspeech/fs2.py:191-203 reads "
+                         "self.cwt_predictor / self.cwt_stats_layers, which that class never creates, so no oracle exists" % what)
+    if ptype != "frame":
+        raise L.MaaError("%s: pitch_type %r: the reference has 'frame', 'ph' and 'cwt'" % (what, ptype))
+    if cfg.get("pitch_ar", False):
+        raise L.MaaError("%s: pitch_ar is not supported: no shipped singing configuration sets it and the autoregressive "
+                         "predictor is not built" % what)
+    if cfg.get("use_energy_embed", False):
+        raise L.MaaError("%s: use_energy_embed is not supported: no shipped configuration sets it and its branch is not built" % what)
+    for k in ("use_spk_id", "use_spk_embed"):
+        if cfg.get(k, False):
+            raise L.MaaError("%s: %s is not supported: the speaker embedding added to pitch_inp and decoder_inp is not built" % (what, k))
+    pad = cfg.get("ffn_padding", "SAME")
+    if pad != "SAME":
+        raise L.MaaError("%s: ffn_padding %r is not supported: only 'SAME' (kernel // 2 zeros on both sides) is built, the causal "
+                         "'LEFT' padding (kernel - 1, 0) is not" % (what, pad))
+    norm = cfg.get("pitch_norm", "log")
+    if norm not in ("log", "standard"):
+        raise L.MaaError("%s: pitch_norm %r: the reference has 'log' and 'standard'" % (what, norm))
+    c = L.maa_fs2_pitch_config()
+    c.hidden_size, c.predictor_hidden = int(cfg["hidden_size"]), int(cfg.get("predictor_hidden", -1))
+    c.predictor_layers, c.predictor_kernel = int(cfg.get("predictor_layers", 5)), int(cfg.get("predictor_kernel", 5))
+    c.ffn_padding_same = c.pitch_type_frame = 1
+    c.pitch_ar = 0
+    c.use_uv = int(bool(cfg.get("use_uv", True)))
+    c.pitch_norm = 0 if norm == "log" else 1
+    c.f0_mean, c.f0_std = float(cfg.get("f0_mean", 0.0)), float(cfg.get("f0_std", 1.0))
+    return c
+
+
+class FS2Pitch:
+    """maa_fs2_pitch handle: FastSpeech2.add_pitch, pitch_type 'frame' (NeuralSeq/modules/fastspeech/fs2.py:174-220), with the mask
+    of :132: PitchPredictor, denorm_f0, f0_to_coarse and the pitch_embed row added to decoder_inp.  state_dict: the pitch_embed /
+    pitch_predictor keys (others are ignored)."""
+
+    def __init__(self, ctx, cfg, state_dict):
+        self.ctx, self.cfg = ctx, dict(cfg)
+        c = fs2_pitch_config(self.cfg)
+        arr, n, keep = L.tensor_list(state_dict)
+        h = C.c_void_p()
+        with ctx.lock:
+            L.check(ctx.lib.maa_fs2_pitch_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
+        self.h = h
+
+    def forward(self, origin, mel2ph, f0=None, uv=None, return_coarse=False):
+        """origin [B, T_mel, H] (FastSpeech2MIDI.decode's decoder_inp: 0 where mel2ph is 0), mel2ph [B, T_mel], f0 / uv [B, T_mel]
+        or None each (the caller's normalised f0 and unvoiced flags; neither is written) -> (decoder_inp [B, T_mel, H], pitch_pred
+        [B, T_mel, 2], f0_denorm [B, T_mel]) on the device; with return_coarse also coarse int32 [B, T_mel], the pitch_embed rows."""
+        dev = self.ctx.device
+        x = _f32(origin, dev)
+        m2p = torch.as_tensor(mel2ph).to(device=dev, dtype=torch.int32).contiguous()
+        if x.dim() != 3 or x.shape[2] != self.cfg["hidden_size"] or x.shape[0] < 1 or x.shape[1] < 1:
+            raise L.MaaError("FS2Pitch.forward: origin %s is not [B, T_mel, %d]" % (tuple(x.shape), self.cfg["hidden_size"]))
+        B, T_mel, H = x.shape
+        if tuple(m2p.shape) != (B, T_mel):
+            raise L.MaaError("FS2Pitch.forward: mel2ph %s is not [%d, %d]" % (tuple(m2p.shape), B, T_mel))
+        f0 = _f32(torch.as_tensor(f0), dev) if f0 is not None else None
+        uv = _f32(torch.as_tensor(uv), dev) if uv is not None else None
+        for name, t in (("f0", f0), ("uv", uv)):
+            if t is not None and tuple(t.shape) != (B, T_mel):
+                raise L.MaaError("FS2Pitch.forward: %s %s is not [%d, %d]" % (name, tuple(t.shape), B, T_mel))
+        dec_inp = torch.empty(B, T_mel, H, device=dev)
+        pitch_pred = torch.empty(B, T_mel, 2, device=dev)
+        f0_denorm = torch.empty(B, T_mel, device=dev)
+        coarse = torch.empty(B, T_mel, dtype=torch.int32, device=dev) if return_coarse else None
+        p = FastSpeech2MIDI._p
+        with self.ctx.lock:
+            L.check(self.ctx.lib.maa_fs2_pitch_forward(self.ctx.h, self.h, p(x), p(m2p), p(f0), p(uv), B, T_mel, p(dec_inp),
+                                                       p(pitch_pred), p(f0_denorm), p(coarse)))
+        return (dec_inp, pitch_pred, f0_denorm, coarse) if return_coarse else (dec_inp, pitch_pred, f0_denorm)
+
+    __call__ = forward
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.maa_fs2_pitch_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -128,6 +128,12 @@ FASTSPEECH2_MIDI = dict(vocab_size=64, hidden_size=256, enc_layers=4, dec_layers
                         audio_num_mel_bins=80, ffn_padding="SAME", ffn_act="gelu", dur_loss="mse", rel_pos=True, use_pos_embed=True,
                         encoder_type="fft", decoder_type="fft", use_pitch_embed=False, use_energy_embed=False, use_spk_id=False,
                         use_spk_embed=False, use_bert=False)
+# FastSpeech2MIDI of the cascade singing configuration (inference/svs/ds_cascade.py): egs_bases/svs/midi/cascade/opencs/ds60_rel.yaml
+# with its fs2 in aux_rel.yaml, over egs_bases/tts/fs2.yaml and egs_bases/singing/base.yaml: use_pitch_embed true, the frame-level
+# pitch predictor (5 layers, kernel 5) with a voicing logit, log2 f0 (f0_mean / f0_std are read with pitch_norm 'standard' only).
+# popcs_ds_beta6.yaml and lj_ds_beta6.yaml resolve to the same pitch hparams over the plain (non-MIDI) encoder, which is not built.
+FASTSPEECH2_MIDI_CASCADE = dict(FASTSPEECH2_MIDI, use_pitch_embed=True, pitch_type="frame", use_uv=True, pitch_norm="log",
+                                pitch_ar=False, predictor_layers=5, predictor_kernel=5, f0_mean=0.0, f0_std=1.0)
 
 # BigVGAN's args.yml (vocoder/logs/bigv16k53w) does not ship with the reference
 # (SURVEY.md section 0.3); these are the generator defaults it is exercised with here.

@@ -32,6 +32,9 @@ struct maa_pitch_extractor {
 struct maa_fs2 {
     std::unique_ptr<maa::FastSpeech2MIDI> m;
 };
+struct maa_fs2_pitch {
+    std::unique_ptr<maa::FS2Pitch> m;
+};
 struct maa_encoder {
     std::unique_ptr<maa::Encoder> m;
 };
@@ -538,7 +541,7 @@ int maa_fs2_create(maa_ctx* ctx, const maa_fs2_config* cfg, const maa_tensor* te
     return guarded([&] {
         MAA_CHECK(cfg && out, "bad fs2_create arguments: null pointer");
         // (a configuration that cannot run is refused before the device is touched)
-        MAA_CHECK(!cfg->use_pitch_embed, "FastSpeech2MIDI: hparams['use_pitch_embed'] is not built -- no shipped e2e singing configuration sets it");
+        MAA_CHECK(!cfg->use_pitch_embed, "FastSpeech2MIDI: hparams['use_pitch_embed'] is not built into this handle -- the pitch branch is maa_fs2_pitch, beside it");
         MAA_CHECK(!cfg->use_energy_embed, "FastSpeech2MIDI: hparams['use_energy_embed'] is not built -- no shipped e2e singing configuration sets it");
         MAA_CHECK(!cfg->use_spk_id && !cfg->use_spk_embed,
                   "FastSpeech2MIDI: hparams['use_spk_id'] / ['use_spk_embed'] are not built -- no shipped e2e singing configuration sets them");
@@ -599,6 +602,57 @@ int maa_fs2_decode(maa_ctx* ctx, maa_fs2* fs2, const float* d_encoder_out, const
         MAA_CHECK(B > 0 && T > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_decode arguments: B, T, T_mel");
         bind(ctx);
         fs2->m->decode(ctx->c, d_encoder_out, d_mel2ph, B, T, T_mel, d_decoder_inp, d_mel_out);
+    });
+}
+int maa_fs2_run_decoder(maa_ctx* ctx, maa_fs2* fs2, const float* d_decoder_inp, const int* d_mel2ph, int B, int T_mel, float* d_mel_out) {
+    return guarded([&] {
+        MAA_CHECK(ctx && fs2 && d_decoder_inp && d_mel2ph && d_mel_out, "bad fs2_run_decoder arguments: null pointer");
+        MAA_CHECK(B > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_run_decoder arguments: B, T_mel");
+        bind(ctx);
+        fs2->m->run_decoder(ctx->c, d_decoder_inp, d_mel2ph, B, T_mel, d_mel_out);
+    });
+}
+
+// ------------------------------------------------------------------------------------------ FastSpeech2MIDI pitch branch
+int maa_fs2_pitch_create(maa_ctx* ctx, const maa_fs2_pitch_config* cfg, const maa_tensor* tensors, int n_tensors, maa_fs2_pitch** out) {
+    return guarded([&] {
+        MAA_CHECK(cfg && out, "bad fs2_pitch_create arguments: null pointer");
+        // (a configuration that cannot run is refused before the device is touched)
+        MAA_CHECK(cfg->pitch_type_frame != 0,
+                  "FastSpeech2MIDI pitch: hparams['pitch_type'] must be 'frame' -- 'ph' is not built, and 'cwt' reads cwt_predictor / "
+                  "cwt_stats_layers, which the reference's FastSpeech2 never creates");
+        MAA_CHECK(!cfg->pitch_ar, "FastSpeech2MIDI pitch: hparams['pitch_ar'] is not built -- no shipped singing configuration sets it");
+        MAA_CHECK(cfg->ffn_padding_same != 0,
+                  "FastSpeech2MIDI pitch: hparams['ffn_padding'] must be 'SAME' -- the causal 'LEFT' padding (kernel - 1, 0) is not built");
+        MAA_CHECK(cfg->pitch_norm == 0 || cfg->pitch_norm == 1, "bad FastSpeech2MIDI pitch config: pitch_norm is 0 ('log') or 1 ('standard')");
+        MAA_CHECK(cfg->hidden_size >= 4 && cfg->hidden_size % 4 == 0 && cfg->hidden_size <= 1024 && cfg->predictor_hidden <= 1024 &&
+                      (cfg->predictor_hidden <= 0 || cfg->predictor_hidden % 4 == 0),
+                  "bad FastSpeech2MIDI pitch config: hidden_size and predictor_hidden (<= 0 for hidden_size) multiples of 4, at most 1024");
+        MAA_CHECK(cfg->predictor_layers >= 1 && cfg->predictor_kernel >= 1 && cfg->predictor_kernel % 2 == 1,
+                  "bad FastSpeech2MIDI pitch config: predictor_layers >= 1, predictor_kernel odd ('SAME' padding keeps the length only then)");
+        bind(ctx);
+        auto sd = to_state_dict(tensors, n_tensors);
+        auto* p = new maa_fs2_pitch;
+        try {
+            p->m.reset(new maa::FS2Pitch(*cfg, sd, ctx->c.dtype));
+        } catch (...) {
+            delete p;
+            throw;
+        }
+        *out = p;
+    });
+}
+int maa_fs2_pitch_destroy(maa_fs2_pitch* h) {
+    return guarded([&] { delete h; });
+}
+int maa_fs2_pitch_forward(maa_ctx* ctx, maa_fs2_pitch* h, const float* d_origin, const int* d_mel2ph, const float* d_f0, const float* d_uv,
+                          int B, int T_mel, float* d_decoder_inp, float* d_pitch_pred, float* d_f0_denorm, int* d_coarse) {
+    return guarded([&] {
+        MAA_CHECK(ctx && h && d_origin && d_mel2ph && d_decoder_inp && d_pitch_pred && d_f0_denorm, "bad fs2_pitch_forward arguments: null pointer");
+        MAA_CHECK(B > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_pitch_forward arguments: B, T_mel");
+        MAA_CHECK(d_decoder_inp != d_origin, "bad fs2_pitch_forward arguments: d_decoder_inp may not alias d_origin");
+        bind(ctx);
+        h->m->forward(ctx->c, d_origin, d_mel2ph, d_f0, d_uv, B, T_mel, d_decoder_inp, d_pitch_pred, d_f0_denorm, d_coarse);
     });
 }
 

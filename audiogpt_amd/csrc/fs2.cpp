@@ -13,8 +13,11 @@
 //   * a padding row is NOT zero where in_proj and ffn_1 read it: LayerNorm of a zero row is its bias, and through the k-wide
 //     convolution that reaches the live neighbours, as in the reference.  Rows are masked where the reference masks them, no earlier
 //   * one FFTBlocks serves the encoder (mask = token 0) and the decoder (mask = an all-zero decoder_inp row, found on the device)
-// The three entry points issue launches on the context's stream only: no device-to-host copy, no synchronisation.  T_mel sizes
+// The entry points issue launches on the context's stream only: no device-to-host copy, no synchronisation.  T_mel sizes
 // decode's outputs, so the caller reads the B totals between encode and decode -- the one read per utterance.
+// The cascade configurations (use_pitch_embed: inference/svs/ds_cascade.py, midi/cascade/opencs/ds60_rel.yaml) add FS2Pitch, a
+// second handle: decode without the decoder -> its PitchPredictor and pitch tail finish decoder_inp (fs2.py:125-132,187-220) ->
+// run_decoder, decode's second half on that decoder_inp.
 // The "same" Conv1d with its epilogue activation, the decoder's sinusoid table and the predictor stack are seq_layers.h's,
 // shared with pitch_extractor.cpp; what stays here is the embeddings, FFTBlocks, the length regulator and the order of the whole.
 #include "models.h"
@@ -32,10 +35,15 @@ void launch_fs2_dur_head(const Ctx& ctx, const float* x, long long rows, int C, 
                          const float* w, const float* bias, const float* nonpad, float* xs, int* dur);
 void launch_fs2_length(Ctx& ctx, const int* dur, int B, int T, int* totals, int T_mel, int* mel2ph);
 void launch_fs2_expand(const Ctx& ctx, const float* enc, const int* mel2ph, int B, int T, int T_mel, int H, float* out, float* tgt);
+void launch_fs2_tgt_mask(const Ctx& ctx, const int* mel2ph, long long rows, float* tgt);
+void launch_fs2_pitch_tail(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
+                           const float* w, const float* bias, const int* mel2ph, const float* f0_in, const float* uv_in, int norm,
+                           float f0_mean, float f0_std, int use_uv, const float* origin, const float* table, int H, float* pitch_pred,
+                           float* f0_denorm, int* coarse, float* decoder_inp);
 
 namespace {
 
-constexpr int FS2_REL_MAX_LEN = 5000, FS2_TABLE_INIT = 2000, FS2_MIDI_ROWS = 300;
+constexpr int FS2_REL_MAX_LEN = 5000, FS2_TABLE_INIT = 2000, FS2_MIDI_ROWS = 300, FS2_PITCH_ROWS = 300, FS2_PITCH_TABLE_INIT = 4096;
 constexpr float FS2_EPS = 1e-5f;
 
 // RelPositionalEncoding's table (espnet_positional_embedding.py:24-45 with reverse = True) in fp32: row i holds position
@@ -178,11 +186,25 @@ struct FastSpeech2MIDI::Impl {
     }
 
     void decode(Ctx& ctx, const float* encoder_out, const int* mel2ph, int B, int T, int T_mel, float* decoder_inp, float* mel) {
-        const int H = cfg.hidden_size, M = cfg.audio_num_mel_bins;
+        const int H = cfg.hidden_size;
         const long long rows = (long long)B * T_mel;
         float* tgt = ctx.ws.alloc_f((size_t)rows);
         launch_fs2_expand(ctx, encoder_out, mel2ph, B, T, T_mel, H, decoder_inp, tgt);
-        if (!mel) return;
+        if (mel) decoder(ctx, decoder_inp, tgt, B, T_mel, mel);
+    }
+
+    // FastSpeech2.run_decoder (fs2.py:222-226) on a decoder_inp some other stage finished (the pitch branch): tgt from mel2ph
+    void run_decoder(Ctx& ctx, const float* decoder_inp, const int* mel2ph, int B, int T_mel, float* mel) {
+        const long long rows = (long long)B * T_mel;
+        float* tgt = ctx.ws.alloc_f((size_t)rows);
+        launch_fs2_tgt_mask(ctx, mel2ph, rows, tgt);
+        decoder(ctx, decoder_inp, tgt, B, T_mel, mel);
+    }
+
+    // decoder_inp [B*T_mel, H], tgt [B*T_mel] = (mel2ph > 0) -> mel [B*T_mel, M]
+    void decoder(Ctx& ctx, const float* decoder_inp, const float* tgt, int B, int T_mel, float* mel) {
+        const int H = cfg.hidden_size, M = cfg.audio_num_mel_bins;
+        const long long rows = (long long)B * T_mel;
         // ---- FastspeechDecoder: mask from the data, positions counted on it      (tts_modules.py:313-320)
         float* nonpad = ctx.ws.alloc_f((size_t)rows);
         float* hidden = ctx.ws.alloc_f((size_t)rows);
@@ -228,6 +250,71 @@ void FastSpeech2MIDI::decode(Ctx& ctx, const float* encoder_out, const int* mel2
     PrecisionGuard pg(ctx, m.precision);
     if (mel_out) m.table.grow(ctx, T_mel);
     run_sized(ctx, [&] { m.decode(ctx, encoder_out, mel2ph, B, T, T_mel, decoder_inp, mel_out); });
+}
+
+void FastSpeech2MIDI::run_decoder(Ctx& ctx, const float* decoder_inp, const int* mel2ph, int B, int T_mel, float* mel_out) {
+    Impl& m = *impl_;
+    PrecisionGuard pg(ctx, m.precision);
+    m.table.grow(ctx, T_mel);
+    run_sized(ctx, [&] { m.run_decoder(ctx, decoder_inp, mel2ph, B, T_mel, mel_out); });
+}
+
+// ---- the pitch branch of the cascade configurations (use_pitch_embed, pitch_type 'frame'): fs2.py:56-64,125-128,174-220
+struct FS2Pitch::Impl {
+    maa_fs2_pitch_config cfg;
+    int precision = 0;
+    WeightStore ws;
+    explicit Impl(int prec) : precision(prec), ws(prec != 0) {}
+    int Cp = 0;                          // predictor width
+    float* embed = nullptr;              // pitch_embed.weight [300, H]
+    ConvPredictor pp;
+    float alpha = 1.f;
+    SinusoidTable table;                 // the predictor's, [max(4096, T_mel + 1), hidden_size]
+
+    void build(const StateDict& sd) {
+        const int H = cfg.hidden_size;
+        MAA_CHECK(get(sd, "pitch_embed.weight").numel() == (long long)FS2_PITCH_ROWS * H, "FastSpeech2MIDI pitch: pitch_embed.weight must be [300, hidden_size]");
+        embed = ws.vec(sd, "pitch_embed.weight");
+        pp.build(ws, sd, "FastSpeech2MIDI PitchPredictor", "pitch_predictor.", cfg.predictor_layers, cfg.predictor_kernel, H, Cp, 2);
+        alpha = get(sd, "pitch_predictor.pos_embed_alpha").data[0];
+        // (pitch_predictor.embed_positions._float_tensor is bookkeeping: not read)
+        table.build(ws, FS2_PITCH_TABLE_INIT, H);
+    }
+
+    void forward(Ctx& ctx, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B, int T_mel, float* decoder_inp,
+                 float* pitch_pred, float* f0_denorm, int* coarse) {
+        const int H = cfg.hidden_size;
+        const long long rows = (long long)B * T_mel;
+        const size_t wide = (size_t)rows * (H > Cp ? H : Cp);
+        float* a = ctx.ws.alloc_f(wide);
+        float* b = ctx.ws.alloc_f(wide);
+        // ---- PitchPredictor (tts_modules.py:247-260) on pitch_inp = origin (0 where mel2ph is 0 already); no mask between its layers
+        launch_pe_pos_add(ctx, origin, B, T_mel, H, table.ptr(), alpha, b);
+        const float* y = pp.run(ctx, b, B, T_mel, nullptr, a, b);          // (a LayerNorm writes over b, which its convolution has read)
+        launch_fs2_pitch_tail(ctx, y, rows, Cp, pp.gamma(), pp.beta(), pp.EPS, pp.lin_w, pp.lin_b, mel2ph, f0, uv, cfg.pitch_norm,
+                              cfg.f0_mean, cfg.f0_std, cfg.use_uv, origin, embed, H, pitch_pred, f0_denorm, coarse, decoder_inp);
+    }
+};
+
+FS2Pitch::FS2Pitch(const maa_fs2_pitch_config& cfg, const StateDict& sd, int precision) : impl_(new Impl(precision)) {
+    impl_->cfg = cfg;
+    impl_->Cp = cfg.predictor_hidden > 0 ? cfg.predictor_hidden : cfg.hidden_size;
+    try {
+        impl_->build(sd);
+    } catch (...) {
+        delete impl_;
+        throw;
+    }
+}
+FS2Pitch::~FS2Pitch() { delete impl_; }
+const maa_fs2_pitch_config& FS2Pitch::config() const { return impl_->cfg; }
+
+void FS2Pitch::forward(Ctx& ctx, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B, int T_mel,
+                       float* decoder_inp, float* pitch_pred, float* f0_denorm, int* coarse) {
+    Impl& m = *impl_;
+    PrecisionGuard pg(ctx, m.precision);
+    m.table.grow(ctx, T_mel);
+    run_sized(ctx, [&] { m.forward(ctx, origin, mel2ph, f0, uv, B, T_mel, decoder_inp, pitch_pred, f0_denorm, coarse); });
 }
 
 }  // namespace maa

@@ -5,12 +5,16 @@
 // Replaces (NeuralSeq/): modules/diffsinger_midi/fs2.py:12-23,60-65 the four embeddings with
 // modules/commons/espnet_positional_embedding.py:102-113 RelPositionalEncoding and tts_modules.py:314,320 the first mask;
 // tts_modules.py:98-118 the duration predictor's last LayerNorm, Linear(C, 1), mask and out2dur; :204-214 LengthRegulator;
-// modules/fastspeech/fs2.py:117-122,132 expand + mask of the encoder states.
+// modules/fastspeech/fs2.py:117-122,132 expand + mask of the encoder states; and, for the cascade configurations
+// (use_pitch_embed), fs2.py:187-220 the pitch tail: the predictor's last LayerNorm + Linear(C, 2), denorm_f0,
+// utils/pitch_utils.py:15-31 f0_to_coarse, the pitch_embed gather and the mask, one launch.
 // All of them are memory-bound on a few hundred to a few thousand rows.
 // The launch grid and the duration head's LayerNorm + Linear stage are row_device.h's, shared with norm.hip's LayerNorm and
 // pitch.hip's head; the decoder's masks, masked products and positional add are pitch.hip's launches (models.h).
 #include "maa_internal.h"
 #include "row_device.h"
+
+#include <cmath>
 
 namespace maa {
 namespace {
@@ -153,6 +157,66 @@ __global__ __launch_bounds__(256) void fs2_expand_kernel(const float* __restrict
     if (lane == 0) tgt[row] = ph > 0 ? 1.f : 0.f;
 }
 
+// tgt[i] = (mel2ph[i] > 0): run_decoder's last mask, where no expand has made it
+__global__ __launch_bounds__(256) void fs2_tgt_mask_kernel(const int* __restrict__ mel2ph, long long rows, float* __restrict__ tgt) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < rows) tgt[i] = mel2ph[i] > 0 ? 1.f : 0.f;
+}
+
+// f0_to_coarse (utils/pitch_utils.py:15-31) in fp32, in the reference's operation order: mel_min = 1127 ln(1 + 50 / 700) and
+// mel_span = 1127 ln(1 + 1100 / 700) - mel_min arrive rounded to fp32, as torch rounds the Python scalars.  Always in [1, 255]
+// (a NaN lands in bin 1), so the table read below stays inside its 300 rows.
+__device__ __forceinline__ int fs2_f0_to_coarse(float f0, float mel_min, float mel_span) {
+    float m = 1127.f * logf(1.f + f0 / 700.f);
+    if (m > 0.f) m = (m - mel_min) * 254.f / mel_span + 1.f;
+    if (!(m > 1.f)) m = 1.f;
+    if (m > 255.f) m = 255.f;
+    return (int)(m + 0.5f);
+}
+
+// add_pitch after the predictor's last convolution (modules/fastspeech/fs2.py:187-220, pitch_type 'frame') and the mask of :132.
+// Row r: LayerNorm (registers, C <= 256 * NR) and Linear(C, 2) -> {value, voicing logit}; f0 = f0_in[r] if given, else the value;
+// with use_uv the frame is unvoiced where uv_in[r] > 0 if given, else where the logit is > 0 (the two inputs are independently
+// nullable, :210-213); without use_uv no frame is, a caller's uv included (denorm_f0 reads it under hparams['use_uv'] only);
+// denorm_f0 -> f0_denorm[r] (0 where unvoiced or mel2ph[r] == 0); f0_to_coarse -> coarse[r] (optional); then all lanes:
+// decoder_inp[r, :] = (origin[r, :] + pitch_embed[coarse, :]) * (mel2ph[r] > 0).  Every lane holds the same dots, so nothing is
+// broadcast and no [B, T] tensor goes through memory between the head and the gather.
+// pitch_pred[r, 0] is 0 on a padding frame when f0 was predicted: the reference's `f0[pitch_padding] = 0` (:215-216) writes
+// through the view f0 = pitch_pred[:, :, 0].  A caller's f0 is only read.
+template <int NR>
+__global__ __launch_bounds__(256) void fs2_pitch_tail_kernel(const float* __restrict__ x, long long rows, int C,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                             const float* __restrict__ w, const float* __restrict__ bias,
+                                                             const int* __restrict__ mel2ph, const float* __restrict__ f0_in,
+                                                             const float* __restrict__ uv_in, int norm, float f0_mean, float f0_std,
+                                                             int use_uv, float mel_min, float mel_span,
+                                                             const float* __restrict__ origin, const float* __restrict__ table, int H,
+                                                             float* __restrict__ pitch_pred, float* __restrict__ f0_denorm,
+                                                             int* __restrict__ coarse, float* __restrict__ decoder_inp) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float d[2];
+    ln_head_dots<NR, 2>(x + row * C, C, lane, gamma, beta, eps, w, bias, d);
+    const float live = mel2ph[row] > 0 ? 1.f : 0.f;
+    const float f0 = f0_in ? f0_in[row] : d[0];
+    const float uv = uv_in ? uv_in[row] : d[1];
+    const float f = pe_denorm_f0(f0, uv, live, norm, f0_mean, f0_std, use_uv);
+    const int bin = fs2_f0_to_coarse(f, mel_min, mel_span);
+    if (lane == 0) {
+        *reinterpret_cast<float2*>(pitch_pred + row * 2) = make_float2(f0_in || live != 0.f ? d[0] : 0.f, d[1]);
+        f0_denorm[row] = f;
+        if (coarse) coarse[row] = bin;
+    }
+    const float* e = table + (long long)bin * H;
+    for (int c = lane * 4; c < H; c += 256) {
+        const float4 o = *reinterpret_cast<const float4*>(origin + row * H + c);
+        const float4 p = *reinterpret_cast<const float4*>(e + c);
+        *reinterpret_cast<float4*>(decoder_inp + row * H + c) =
+            make_float4((o.x + p.x) * live, (o.y + p.y) * live, (o.z + p.z) * live, (o.w + p.w) * live);
+    }
+}
+
 }  // namespace
 
 void launch_fs2_embed(const Ctx& ctx, const int* tok, const int* midi, const float* midi_dur, const int* slur, const float* E, int vocab,
@@ -198,6 +262,37 @@ void launch_fs2_expand(const Ctx& ctx, const float* enc, const int* mel2ph, int 
     const long long rows = (long long)B * T_mel;
     ProfScope prof(ctx, "fs2_rows", 0.0, 8.0 * rows * (double)H);
     hipLaunchKernelGGL(fs2_expand_kernel, row_grid(rows), dim3(256), 0, ctx.stream, enc, mel2ph, rows, T, T_mel, H, out, tgt);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_tgt_mask(const Ctx& ctx, const int* mel2ph, long long rows, float* tgt) {
+    if (ctx.ws.dry) return;
+    ProfScope prof(ctx, "fs2_rows", 0.0, 8.0 * rows);
+    hipLaunchKernelGGL(fs2_tgt_mask_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx.stream, mel2ph, rows, tgt);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_pitch_tail(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
+                           const float* w, const float* bias, const int* mel2ph, const float* f0_in, const float* uv_in, int norm,
+                           float f0_mean, float f0_std, int use_uv, const float* origin, const float* table, int H, float* pitch_pred,
+                           float* f0_denorm, int* coarse, float* decoder_inp) {
+    if (ctx.ws.dry) return;
+    MAA_CHECK(C % 4 == 0 && C <= 1024, "FastSpeech2MIDI pitch: predictor width must be a multiple of 4, at most 1024");
+    MAA_CHECK(H % 4 == 0, "FastSpeech2MIDI pitch: hidden_size must be a multiple of 4");
+    // f0_mel_min and f0_mel_max - f0_mel_min of pitch_utils.py:15-19 (f0_min 50, f0_max 1100), double there, fp32 in the tensor op
+    const double mel_lo = 1127.0 * std::log(1.0 + 50.0 / 700.0), mel_hi = 1127.0 * std::log(1.0 + 1100.0 / 700.0);
+    const float mel_min = (float)mel_lo, mel_span = (float)(mel_hi - mel_lo);
+    ProfScope prof(ctx, "fs2_rows", 0.0, 4.0 * rows * ((double)C + 3.0 * H));
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, row_grid(rows), dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, w, bias, mel2ph, f0_in, uv_in, norm,
+                           f0_mean, f0_std, use_uv, mel_min, mel_span, origin, table, H, pitch_pred, f0_denorm, coarse, decoder_inp);
+    };
+    if (C <= 256)
+        go(fs2_pitch_tail_kernel<1>);
+    else if (C <= 512)
+        go(fs2_pitch_tail_kernel<2>);
+    else
+        go(fs2_pitch_tail_kernel<4>);
     MAA_HIP(hipGetLastError());
 }
 

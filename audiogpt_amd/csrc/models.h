@@ -128,7 +128,25 @@ public:
     void length_regulate(Ctx& ctx, const int* dur, int B, int T, int T_mel, int* mel2ph);
     // encoder_out [B, T, H], mel2ph int32 [B, T_mel] -> decoder_inp [B, T_mel, H], mel_out (optional) [B, T_mel, mel bins]
     void decode(Ctx& ctx, const float* encoder_out, const int* mel2ph, int B, int T, int T_mel, float* decoder_inp, float* mel_out);
+    // decode's second half on a decoder_inp [B, T_mel, H] the caller supplies (run_decoder, fs2.py:222-226) -> mel_out
+    void run_decoder(Ctx& ctx, const float* decoder_inp, const int* mel2ph, int B, int T_mel, float* mel_out);
     const maa_fs2_config& config() const;
+
+private:
+    struct Impl;
+    Impl* impl_;
+};
+
+// The pitch branch the cascade singing configurations add to that front end (fs2.cpp, fs2.hip: use_pitch_embed, pitch_type frame)
+class FS2Pitch {
+public:
+    FS2Pitch(const maa_fs2_pitch_config& cfg, const StateDict& sd, int precision);
+    ~FS2Pitch();
+    // origin [B, T_mel, H] (decode's decoder_inp), mel2ph int32 [B, T_mel], f0 / uv (each optional) [B, T_mel] -> decoder_inp
+    // [B, T_mel, H], pitch_pred [B, T_mel, 2], f0_denorm [B, T_mel], coarse (optional) int32 [B, T_mel]
+    void forward(Ctx& ctx, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B, int T_mel,
+                 float* decoder_inp, float* pitch_pred, float* f0_denorm, int* coarse);
+    const maa_fs2_pitch_config& config() const;
 
 private:
     struct Impl;

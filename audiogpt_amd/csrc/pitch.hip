@@ -168,16 +168,8 @@ __global__ __launch_bounds__(256) void pe_pos_add_kernel(const float* __restrict
     }
 }
 
-// denorm_f0.  norm 0: 2 ** v; 1: v * f0_std + f0_mean.  use_uv: 0 where the logit is > 0; then 0 where the frame is padding.
-__device__ __forceinline__ float pe_denorm_f0(float v, float uv, float live, int norm, float f0_mean, float f0_std, int use_uv) {
-    float f = norm == 0 ? exp2f(v) : v * f0_std + f0_mean;
-    if (use_uv && uv > 0.f) f = 0.f;
-    if (live == 0.f) f = 0.f;
-    return f;
-}
-
 // The predictor's last layer after its convolution (whose epilogue did the ReLU): LayerNorm over the row (kept in registers,
-// C <= 256 * NR) and Linear(C, 2) (row_device.h), denorm_f0 -> pitch_pred[row] = {f0 value, voicing logit}, f0[row].
+// C <= 256 * NR) and Linear(C, 2), denorm_f0 (all row_device.h) -> pitch_pred[row] = {f0 value, voicing logit}, f0[row].
 template <int NR>
 __global__ __launch_bounds__(256) void pe_head_kernel(const float* __restrict__ x, long long rows, int C,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float eps,

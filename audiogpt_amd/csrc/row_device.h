@@ -1,5 +1,5 @@
 // Device helpers of the one-wave-per-row kernels (norm.hip, pitch.hip, fs2.hip), wave64: the wave reductions, the row
-// LayerNorm held in registers, and the "last LayerNorm + narrow Linear" stage of the two predictor heads.  Device code only.
+// LayerNorm held in registers, the "last LayerNorm + narrow Linear" stage of the predictor heads and denorm_f0.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,6 +87,16 @@ __device__ __forceinline__ void ln_head_dots(const float* __restrict__ src, int 
     }
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) d[o] = wave_sum(d[o]) + bias[o];
+}
+
+// denorm_f0 (utils/pitch_utils.py:63-76).  norm 0: 2 ** v; 1: v * f0_std + f0_mean.  use_uv: 0 where uv (a voicing logit, or a
+// caller's flag) is > 0; then 0 where the frame is padding.  Shared by the extractor's head (pitch.hip) and the cascade front
+// end's pitch tail (fs2.hip).
+__device__ __forceinline__ float pe_denorm_f0(float v, float uv, float live, int norm, float f0_mean, float f0_std, int use_uv) {
+    float f = norm == 0 ? exp2f(v) : v * f0_std + f0_mean;
+    if (use_uv && uv > 0.f) f = 0.f;
+    if (live == 0.f) f = 0.f;
+    return f;
 }
 
 }  // namespace maa

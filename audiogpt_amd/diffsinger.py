@@ -20,6 +20,13 @@ so the mel never leaves the device between the diffusion and the waveform.
 
     e2e = DiffSingerE2E(gd, hifigan.vocoder, pe=..., fs2=FastSpeech2MIDI(ctx=gd.ctx, state_dict=ckpt_fs2_sd))
     wav = e2e.forward_model(txt_tokens, pitch_midi, midi_dur, is_slur)      # score -> waveform, no model on the host
+
+The cascade configuration (NeuralSeq/inference/svs/ds_cascade.py, ds60_rel.yaml: use_pitch_embed, no PitchExtractor) predicts the
+pitch in the front end and sings it: `FastSpeech2MIDICascade` adds the pitch branch to the front end, `DiffSingerCascade` hands its
+f0 to the vocoder.
+
+    cas = DiffSingerCascade(gd, hifigan.vocoder, FastSpeech2MIDICascade(ctx=gd.ctx, state_dict=ckpt_fs2_sd))
+    wav = cas.forward_model(txt_tokens, pitch_midi, midi_dur, is_slur)      # f0=, uv=, mel2ph=: a caller's, else predicted
 """
 import numpy as np
 import torch
@@ -379,6 +386,56 @@ class FastSpeech2MIDI(object):
         return self
 
 
+class FastSpeech2MIDICascade(FastSpeech2MIDI):
+    """FastSpeech2MIDI with use_pitch_embed, as the cascade singing configuration runs it (inference/svs/ds_cascade.py over
+    midi/cascade/opencs/ds60_rel.yaml; modules/fastspeech/fs2.py:125-132,174-220, pitch_type 'frame'): after the expand, a
+    PitchPredictor reads the frames, denorm_f0 and f0_to_coarse pick a row of pitch_embed, and that row is added to decoder_inp
+    before the decoder.  cfg: config.FASTSPEECH2_MIDI_CASCADE; state_dict: the reference's full FastSpeech2MIDI state dict (a
+    `model.fs2.` or `fs2.` prefix is stripped), seeded random weights when None.
+
+    Two handles on one context: a backend.FastSpeech2MIDI built from the cfg with use_pitch_embed cleared, and a backend.FS2Pitch.
+    Device calls, in order: encode -> (the totals read, with predicted durations: still the single device-to-host read) ->
+    length_regulate -> decode without the decoder -> the pitch branch -> run_decoder.
+
+    f0 [B, T_mel] is the NORMALISED pitch the reference takes (log2 Hz with pitch_norm 'log'), uv [B, T_mel] its unvoiced flags
+    (> 0: unvoiced); each may be None and is then predicted.  The reference zeroes the caller's f0 in place on padding frames
+    (fs2.py:215-216); here the caller's tensors are only read."""
+
+    def __init__(self, cfg=None, device="cuda:0", state_dict=None, ctx=None, precision=None, seed=17):
+        self.cfg = dict(cfg or C.FASTSPEECH2_MIDI_CASCADE)
+        if not self.cfg.get("use_pitch_embed"):
+            raise backend.L.MaaError("FastSpeech2MIDICascade: use_pitch_embed is false in this configuration: that is FastSpeech2MIDI")
+        inner = dict(self.cfg, use_pitch_embed=False)
+        backend.fs2_pitch_config(self.cfg)             # both refuse an unsupported configuration before a context is made
+        backend.fs2_config(inner)
+        self.ctx = ctx or Context(device, precision=precision or default_precision())
+        self.device = self.ctx.device
+        sd = state_dict if state_dict is not None else WT.make_fs2_state_dict(self.cfg, seed=seed)
+        sd = WT.strip_prefix(sd, "model.fs2.") or WT.strip_prefix(sd, "fs2.") or sd
+        is_pitch = lambda k: k.startswith(("pitch_embed.", "pitch_predictor."))      # noqa: E731
+        self.net = backend.FastSpeech2MIDI(self.ctx, inner, {k: v for k, v in sd.items() if not is_pitch(k)})
+        self.pitch = backend.FS2Pitch(self.ctx, self.cfg, {k: v for k, v in sd.items() if is_pitch(k)})
+
+    @torch.no_grad()
+    def forward(self, txt_tokens, mel2ph=None, f0=None, uv=None, skip_decoder=False, infer=True, pitch_midi=None, midi_dur=None,
+                is_slur=None):
+        """-> FastSpeech2MIDI.forward's dict with decoder_inp carrying the pitch embedding, plus 'pitch_pred' [B, T_mel, 2] (value
+        and voicing logit; the value is 0 on padding frames when f0 was predicted, as in the reference) and 'f0_denorm' [B, T_mel]
+        (Hz; 0 on unvoiced and padding frames) -- what ds_cascade.py hands the NSF vocoder."""
+        ret = super().forward(txt_tokens, mel2ph=mel2ph, skip_decoder=True, infer=infer, pitch_midi=pitch_midi, midi_dur=midi_dur,
+                              is_slur=is_slur)
+        B, T_mel = ret["mel2ph"].shape
+        for name, t in (("f0", f0), ("uv", uv)):
+            if t is not None and tuple(torch.as_tensor(t).shape) != (B, T_mel):
+                raise ValueError("FastSpeech2MIDICascade: %s %s is not [B = %d, T_mel = %d]" % (name, tuple(torch.as_tensor(t).shape), B, T_mel))
+        ret["decoder_inp"], ret["pitch_pred"], ret["f0_denorm"] = self.pitch.forward(ret["decoder_inp"], ret["mel2ph"], f0=f0, uv=uv)
+        if not skip_decoder:
+            ret["mel_out"] = self.net.run_decoder(ret["decoder_inp"], ret["mel2ph"])
+        return ret
+
+    __call__ = forward
+
+
 class DiffSingerE2E(object):
     """DiffSingerE2EInfer.forward_model (inference/svs/ds_e2e.py:22-45) with BaseSVSInfer.run_vocoder (base_svs_infer.py:61-70):
     score -> (fs2, when set) decoder_inp, mel2ph, coarse mel -> the diffusion's mel_out -> f0 (pe, when set) -> waveform.
@@ -409,12 +466,16 @@ class DiffSingerE2E(object):
         """diffusion.infer(fs2_mels, cond, mel2ph=mel2ph, **kw) followed by mel_to_wav.  rand_ini / noise_sine: SineGen's two draws
         (`noise` is q_sample's draw of diffusion.infer)."""
         mel_out = self.diffusion.infer(fs2_mels, cond, mel2ph=mel2ph, **kw)
+        return self.mel_to_wav(mel_out, **self._sine_draws(rand_ini, noise_sine))
+
+    @staticmethod
+    def _sine_draws(rand_ini, noise_sine):
         draws = {}
         if rand_ini is not None:
             draws["rand_ini"] = rand_ini
         if noise_sine is not None:
             draws["noise"] = noise_sine
-        return self.mel_to_wav(mel_out, **draws)
+        return draws
 
     @torch.no_grad()
     def forward_model(self, txt_tokens, pitch_midi, midi_dur, is_slur, mel2ph=None, **draws):
@@ -425,3 +486,23 @@ class DiffSingerE2E(object):
             raise ValueError("DiffSingerE2E.forward_model needs the front end: pass fs2=FastSpeech2MIDI(...)")
         ret = self.fs2(txt_tokens, mel2ph=mel2ph, infer=True, pitch_midi=pitch_midi, midi_dur=midi_dur, is_slur=is_slur)
         return self.infer(ret["mel_out"], ret["decoder_inp"].transpose(1, 2), mel2ph=mel2ph, **draws)
+
+
+class DiffSingerCascade(DiffSingerE2E):
+    """DiffSingerCascadeInfer.forward_model (inference/svs/ds_cascade.py:22-34): the front end predicts the pitch itself
+    (pe_enable false, no PitchExtractor), and its f0_denorm goes straight to the NSF vocoder with the diffusion's mel.
+    diffusion / vocoder / use_nsf: as DiffSingerE2E, whose run_vocoder this shares; fs2: a FastSpeech2MIDICascade on the same
+    device.  Nothing leaves the device between score and waveform except the durations' totals."""
+
+    def __init__(self, diffusion, vocoder, fs2, use_nsf=True):
+        super().__init__(diffusion, vocoder, pe=None, use_nsf=use_nsf, fs2=fs2)
+
+    @torch.no_grad()
+    def forward_model(self, txt_tokens, pitch_midi, midi_dur, is_slur, mel2ph=None, f0=None, uv=None, rand_ini=None, noise_sine=None,
+                      **draws):
+        """Score -> [1, B * T_mel * hop].  mel2ph / f0 / uv: a caller's, else predicted (FastSpeech2MIDICascade); the final mask
+        of the diffusion uses the ARGUMENT mel2ph, as DiffSingerE2E.forward_model.  rand_ini / noise_sine: SineGen's two draws;
+        draws: as GaussianDiffusion.infer takes them."""
+        ret = self.fs2(txt_tokens, mel2ph=mel2ph, f0=f0, uv=uv, infer=True, pitch_midi=pitch_midi, midi_dur=midi_dur, is_slur=is_slur)
+        mel_out = self.diffusion.infer(ret["mel_out"], ret["decoder_inp"].transpose(1, 2), mel2ph=mel2ph, **draws)
+        return self.run_vocoder(mel_out, f0=ret["f0_denorm"], **self._sine_draws(rand_ini, noise_sine))

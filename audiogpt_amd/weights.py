@@ -386,7 +386,9 @@ def make_fs2_state_dict(cfg, seed=17):
     (one tensor) and the `decoder.embed_positions._float_tensor` bookkeeping entry included.  The LayerNorm affines are drawn away
     from 1 / 0 (the LayerNorm of a zero padding row is its bias, which leaks into live rows through the FFN convolution) and
     decoder.pos_embed_alpha away from 1, so a port that skipped either shows.  Row 0 of the token and MIDI tables is the padding
-    row and is zero, as nn.Embedding(padding_idx = 0) keeps it."""
+    row and is zero, as nn.Embedding(padding_idx = 0) keeps it.  With cfg['use_pitch_embed'] (config.FASTSPEECH2_MIDI_CASCADE) the
+    25 keys of the pitch branch are added (pitch_embed, pitch_predictor: 141 keys); every other tensor is the same with and without
+    it, for every seed."""
     g, sd = _Gen(seed), {}
     H, V, M = cfg["hidden_size"], cfg["vocab_size"], cfg["audio_num_mel_bins"]
     Cp = cfg["predictor_hidden"] if cfg["predictor_hidden"] > 0 else H
@@ -424,7 +426,26 @@ def make_fs2_state_dict(cfg, seed=17):
     sd["midi_embed.weight"] = table(300, True)
     sd["midi_dur_layer.weight"], sd["midi_dur_layer.bias"] = g.weight((H, 1)), g.bias(H)
     sd["is_slur_embed.weight"] = table(2, False)
-    return sd
+    if not cfg.get("use_pitch_embed"):
+        return sd
+    # The pitch branch (fs2.py:56-64): drawn AFTER everything above, so the tensors above are the same with and without it, then
+    # put where the reference's state_dict() has them, between dur_predictor and encoder.  pitch_embed's row 0 is its padding row.
+    kp, pitch = cfg.get("predictor_kernel", 5), {}
+    pitch["pitch_embed.weight"] = table(300, True)
+    pitch["pitch_predictor.pos_embed_alpha"] = torch.tensor([0.7], dtype=torch.float32)
+    for i in range(cfg.get("predictor_layers", 5)):
+        p, cin = f"pitch_predictor.conv.{i}.", (H if i == 0 else Cp)
+        pitch[p + "1.weight"], pitch[p + "1.bias"] = g.weight((Cp, cin, kp), 1.4), g.bias(Cp)
+        pitch[p + "3.weight"], pitch[p + "3.bias"] = g.gamma(Cp), g.beta(Cp)
+    n_out = 2 if cfg.get("pitch_type", "frame") == "frame" else 1
+    pitch["pitch_predictor.linear.weight"], pitch["pitch_predictor.linear.bias"] = g.weight((n_out, Cp)), g.bias(n_out)
+    pitch["pitch_predictor.embed_positions._float_tensor"] = torch.zeros(1, dtype=torch.float32)
+    out = {}
+    for k, v in sd.items():
+        out[k] = v
+        if k == "dur_predictor.linear.bias":
+            out.update(pitch)
+    return out
 
 
 # ----------------------------------------------------------------------------- conditioning encoders

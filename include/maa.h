@@ -445,6 +445,43 @@ int maa_fs2_length_regulate(maa_ctx* ctx, maa_fs2* fs2, const int* d_dur, int B,
  * where mel2ph is 0. */
 int maa_fs2_decode(maa_ctx* ctx, maa_fs2* fs2, const float* d_encoder_out, const int* d_mel2ph, int B, int T, int T_mel,
                    float* d_decoder_inp, float* d_mel_out);
+/* replaces: FastSpeech2.run_decoder (fs2.py:222-226), the second half of decode on a decoder_inp the caller supplies (the pitch
+ * branch below finishes one): d_decoder_inp [B, T_mel, hidden_size] (an all-zero row is padding), d_mel2ph [B, T_mel] ->
+ * d_mel_out [B, T_mel, audio_num_mel_bins], 0 where mel2ph is 0.  Launches on the context's stream only. */
+int maa_fs2_run_decoder(maa_ctx* ctx, maa_fs2* fs2, const float* d_decoder_inp, const int* d_mel2ph, int B, int T_mel,
+                        float* d_mel_out);
+
+/* ---- FastSpeech2MIDI pitch branch (the cascade singing configurations: use_pitch_embed over midi/cascade/opencs/aux_rel.yaml) ----
+ * FastSpeech2.add_pitch, pitch_type 'frame' (modules/fastspeech/fs2.py:56-64,125-132,187-220): PitchPredictor on the expanded
+ * encoder states, denorm_f0, f0_to_coarse (utils/pitch_utils.py:15-31), the pitch_embed row added to decoder_inp.  A second
+ * handle beside maa_fs2, which keeps refusing use_pitch_embed: encode -> length_regulate -> decode (d_mel_out NULL) ->
+ * maa_fs2_pitch_forward -> maa_fs2_run_decoder. */
+typedef struct maa_fs2_pitch_config {
+    int hidden_size, predictor_hidden, predictor_layers, predictor_kernel;      /* predictor_hidden <= 0: hidden_size; kernel odd */
+    int ffn_padding_same, pitch_type_frame;      /* must be 1: 'LEFT' padding, pitch_type 'ph' and 'cwt' are refused */
+    int pitch_ar;                                /* must be 0 */
+    int use_uv;                                  /* frames with a voicing logit (or a caller's uv) > 0 get f0 = 0 */
+    int pitch_norm;                              /* 0 'log' (f0 = 2 ** x), 1 'standard' (f0 = x * f0_std + f0_mean) */
+    float f0_mean, f0_std;
+} maa_fs2_pitch_config;
+typedef struct maa_fs2_pitch maa_fs2_pitch;
+/* tensors: pitch_embed.weight [300, hidden_size], pitch_predictor.conv.{i}.{1,3}.*, pitch_predictor.linear.* ([2, C_p], [2]),
+ * pitch_predictor.pos_embed_alpha; pitch_predictor.embed_positions._float_tensor is accepted and ignored, as is every other key
+ * of the FastSpeech2MIDI state_dict */
+int maa_fs2_pitch_create(maa_ctx* ctx, const maa_fs2_pitch_config* cfg, const maa_tensor* tensors, int n_tensors, maa_fs2_pitch** out);
+int maa_fs2_pitch_destroy(maa_fs2_pitch* h);
+/* d_origin [B, T_mel, hidden_size]: maa_fs2_decode's d_decoder_inp (decoder_inp_origin; its rows are 0 where mel2ph is 0, which is
+ * pitch_inp = origin * (mel2ph > 0) already), d_mel2ph [B, T_mel], d_f0 / d_uv [B, T_mel] or NULL each (the caller's normalised
+ * f0 and its unvoiced flags; what is NULL is predicted, and neither is written; without use_uv no frame is unvoiced and d_uv is
+ * not read, as denorm_f0 reads uv under hparams['use_uv'] only) -> d_decoder_inp [B, T_mel, hidden_size] =
+ * (origin + pitch_embed[coarse]) * (mel2ph > 0) (ret['decoder_inp'], may not alias d_origin), d_pitch_pred [B, T_mel, 2]
+ * (ret['pitch_pred']: value and voicing logit; the value is 0 on padding frames when f0 was predicted, as the reference's in-place
+ * f0[pitch_padding] = 0 leaves it), d_f0_denorm [B, T_mel] (ret['f0_denorm'], 0 on unvoiced and padding frames) and, unless
+ * NULL, d_coarse int32 [B, T_mel], the table rows taken, in [1, 255].  Launches on the context's stream only: no device-to-host
+ * copy, no synchronisation. */
+int maa_fs2_pitch_forward(maa_ctx* ctx, maa_fs2_pitch* h, const float* d_origin, const int* d_mel2ph, const float* d_f0,
+                          const float* d_uv, int B, int T_mel, float* d_decoder_inp, float* d_pitch_pred, float* d_f0_denorm,
+                          int* d_coarse);
 
 /* ---- conditioning encoders (the step before the sampler: text / image -> cross-attention context) ----------
  * kind 0: the CLAP text branch as FrozenCLAPEmbedder.encode runs it (ldm/modules/encoders/modules.py:204-211):
