@@ -142,26 +142,98 @@ class maa_igemm_ex_args(C.Structure):
                 ("d_c", C.c_void_p), ("ldc", C.c_int), ("d_c2", C.c_void_p), ("ldc2", C.c_int), ("c2_slope", C.c_float)]
 
 
-EXPORTS = [
-    "maa_last_error", "maa_version", "maa_ctx_create", "maa_ctx_destroy", "maa_ctx_synchronize",
-    "maa_ctx_set_stream", "maa_ctx_set_precision", "maa_ctx_set_cfg_split", "maa_ctx_set_concurrency", "maa_ctx_reload_tuning", "maa_ctx_workspace_bytes", "maa_prof_begin", "maa_prof_end", "maa_unet_create", "maa_unet_destroy",
-    "maa_unet_set_context", "maa_unet_forward", "maa_ddim_update", "maa_ddim_sample", "maa_ddim_stochastic_encode", "maa_ddim_decode",
-    "maa_ldm_plms_sample", "maa_ddpm_sample", "maa_ddpm_update",
-    "maa_vae_create",
-    "maa_vae_destroy", "maa_vae_decode", "maa_vae_decode_spec", "maa_vae_encode_moments", "maa_vocoder_create", "maa_vocoder_destroy",
-    "maa_vocoder_forward", "maa_vocoder_forward_f0", "maa_diffnet_create", "maa_diffnet_destroy", "maa_diffnet_forward",
-    "maa_plms_sample", "maa_ds_ddpm_sample", "maa_ds_ddpm_update",
-    "maa_pitch_extractor_create", "maa_pitch_extractor_destroy", "maa_pitch_extractor_forward",
-    "maa_fs2_create", "maa_fs2_destroy", "maa_fs2_encode", "maa_fs2_length_regulate", "maa_fs2_decode",
-    "maa_fs2_run_decoder", "maa_fs2_pitch_create", "maa_fs2_pitch_destroy", "maa_fs2_pitch_forward",
-    "maa_encoder_create", "maa_encoder_destroy", "maa_encoder_text", "maa_encoder_image",
-    "maa_encoder_text_cls", "maa_clap_audio_create", "maa_clap_audio_destroy", "maa_clap_audio_embed", "maa_clap_similarity",
-    "maa_spectral_create", "maa_spectral_destroy", "maa_spectral_forward", "maa_resampler_create", "maa_resampler_destroy",
-    "maa_resampler_forward", "maa_op_linear", "maa_op_conv", "maa_op_groupnorm", "maa_op_layernorm",
-    "maa_op_attention", "maa_op_attention_ex", "maa_op_conv_transpose1d", "maa_op_snake_aa", "maa_op_bench_conv", "maa_calib",
-    "maa_op_mrf_pair", "maa_op_groupnorm_ex", "maa_op_layernorm_ex", "maa_op_split32", "maa_op_igemm_ex",
-    "maa_unet_forward_split", "maa_op_unfold", "maa_op_fold", "maa_op_attention_masked",
-]
+# The one list of the library's entries: name -> argument types (every entry returns an int status).  load() applies it and
+# EXPORTS is derived from it; a new entry of include/maa.h is added here and nowhere else.
+vp, ci, cf, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)
+SIGNATURES = {
+    "maa_ctx_create": [ci, vp, C.POINTER(vp)],
+    "maa_ctx_destroy": [vp],
+    "maa_ctx_synchronize": [vp],
+    "maa_ctx_set_stream": [vp, vp],
+    "maa_ctx_workspace_bytes": [vp, C.POINTER(C.c_size_t)],
+    "maa_ctx_set_precision": [vp, ci],
+    "maa_ctx_set_cfg_split": [vp, ci],
+    "maa_ctx_set_concurrency": [vp, ci],
+    "maa_ctx_reload_tuning": [vp],
+    "maa_prof_begin": [vp, ci],
+    "maa_prof_end": [vp, C.POINTER(maa_prof_row), ci, C.POINTER(ci)],
+    "maa_unet_create": [vp, C.POINTER(maa_unet_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_unet_destroy": [vp],
+    "maa_unet_set_context": [vp, vp, vp, ci, ci],
+    "maa_unet_forward": [vp, vp, vp, vp, ci, ci, ci, vp],
+    "maa_ddim_update": [vp, vp, vp, vp, cf, vp, C.c_int64, vp, vp],
+    "maa_ddim_sample": [vp, vp, C.POINTER(maa_ddim_args), vp],
+    "maa_ddim_stochastic_encode": [vp, vp, ci, cf, vp, vp, fp, fp, ci, vp, ci, ci, ci, ci, vp],
+    "maa_ddim_decode": [vp, vp, C.POINTER(maa_ddim_args), ci, vp],
+    "maa_ldm_plms_sample": [vp, vp, C.POINTER(maa_ddim_args), vp],
+    "maa_ddpm_sample": [vp, vp, C.POINTER(maa_ddpm_args), vp],
+    "maa_ddpm_update": [vp, vp, vp, vp, fp, fp, fp, fp, fp, ci, vp, cf, ci, ci, ci, ci, ci, vp, vp],
+    "maa_vae_create": [vp, C.POINTER(maa_vae_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_vae_destroy": [vp],
+    "maa_vae_decode": [vp, vp, vp, ci, ci, ci, cf, vp],
+    "maa_vae_decode_spec": [vp, vp, vp, ci, ci, ci, cf, vp],
+    "maa_vae_encode_moments": [vp, vp, vp, ci, ci, ci, vp],
+    "maa_vocoder_create": [vp, C.POINTER(maa_vocoder_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_vocoder_destroy": [vp],
+    "maa_vocoder_forward": [vp, vp, vp, ci, ci, vp],
+    "maa_vocoder_forward_f0": [vp, vp, vp, vp, vp, vp, ci, ci, vp],
+    "maa_diffnet_create": [vp, C.POINTER(maa_diffnet_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_diffnet_destroy": [vp],
+    "maa_diffnet_forward": [vp, vp, vp, vp, vp, ci, ci, vp],
+    "maa_plms_sample": [vp, vp, C.POINTER(maa_plms_args), vp],
+    "maa_ds_ddpm_sample": [vp, vp, C.POINTER(maa_ds_ddpm_args), vp],
+    "maa_ds_ddpm_update": [vp, vp, vp, vp, fp, fp, fp, fp, fp, ci, ci, ci, ci, ci, vp],
+    "maa_pitch_extractor_create": [vp, C.POINTER(maa_pitch_extractor_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_pitch_extractor_destroy": [vp],
+    "maa_pitch_extractor_forward": [vp, vp, vp, ci, ci, vp, vp, vp],
+    "maa_fs2_create": [vp, C.POINTER(maa_fs2_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_fs2_destroy": [vp],
+    "maa_fs2_encode": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
+    "maa_fs2_length_regulate": [vp, vp, vp, ci, ci, ci, vp],
+    "maa_fs2_decode": [vp, vp, vp, vp, ci, ci, ci, vp, vp],
+    "maa_fs2_run_decoder": [vp, vp, vp, vp, ci, ci, vp],
+    "maa_fs2_pitch_create": [vp, C.POINTER(maa_fs2_pitch_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_fs2_pitch_destroy": [vp],
+    "maa_fs2_pitch_forward": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
+    "maa_encoder_create": [vp, C.POINTER(maa_encoder_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_encoder_destroy": [vp],
+    "maa_encoder_text": [vp, vp, vp, ci, ci, vp],
+    "maa_encoder_image": [vp, vp, vp, ci, vp],
+    "maa_encoder_text_cls": [vp, vp, vp, ci, ci, vp],
+    "maa_clap_audio_create": [vp, C.POINTER(maa_clap_audio_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_clap_audio_destroy": [vp],
+    "maa_clap_audio_embed": [vp, vp, vp, ci, ci, vp, vp],
+    "maa_clap_similarity": [vp, vp, vp, ci, ci, ci, cf, vp],
+    "maa_spectral_create": [vp, C.POINTER(maa_spectral_config), fp, fp, C.POINTER(vp)],
+    "maa_spectral_destroy": [vp],
+    "maa_spectral_forward": [vp, vp, vp, ci, ci, vp],
+    "maa_resampler_create": [vp, ci, ci, ci, ci, fp, C.POINTER(vp)],
+    "maa_resampler_destroy": [vp],
+    "maa_resampler_forward": [vp, vp, vp, ci, ci, vp],
+    "maa_op_linear": [vp, vp, ci, ci, fp, fp, ci, ci, vp, vp, ci],
+    "maa_op_conv": [vp, vp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, vp, vp, ci],
+    "maa_op_groupnorm": [vp, vp, ci, ci, ci, fp, fp, cf, ci, vp],
+    "maa_op_layernorm": [vp, vp, ci, ci, fp, fp, cf, vp],
+    "maa_op_attention": [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp],
+    "maa_op_attention_ex": [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, ci],
+    "maa_op_attention_masked": [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, ci, vp],
+    "maa_op_conv_transpose1d": [vp, vp, ci, ci, ci, fp, fp, ci, ci, ci, cf, vp],
+    "maa_op_snake_aa": [vp, vp, ci, ci, ci, fp, fp, ci, vp],
+    "maa_op_bench_conv": [vp, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)],
+    "maa_calib": [vp, ci, C.POINTER(C.c_double)],
+    "maa_op_mrf_pair": [vp, vp, ci, ci, ci, fp, fp, ci, ci, cf, fp, fp, ci, ci, cf, cf, ci, vp],
+    "maa_op_groupnorm_ex": [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, fp, fp, cf, ci, vp, ci, vp],
+    "maa_op_igemm_ex": [vp, C.POINTER(maa_igemm_ex_args)],
+    "maa_op_layernorm_ex": [vp, vp, ci, ci, fp, fp, cf, vp, ci],
+    "maa_op_split32": [vp, vp, ci, ci, cf, ci, vp],
+    "maa_unet_forward_split": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, fp, vp],
+    "maa_op_unfold": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp],
+    "maa_op_fold": [vp, vp, fp, ci, ci, ci, ci, ci, ci, ci, ci, vp],
+}
+del vp, ci, cf, fp
+
+# every symbol include/maa.h declares: the two that return a string, then the table's
+EXPORTS = ["maa_last_error", "maa_version"] + list(SIGNATURES)
 
 _lib = None
 
@@ -177,98 +249,12 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:
         raise MaaError("cannot load %s: %s" % (LIB_PATH, e))
-    vp, ci, cf, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)
     lib.maa_last_error.restype = C.c_char_p
     lib.maa_version.restype = C.c_char_p
-    sig = {
-        "maa_ctx_create": [ci, vp, C.POINTER(vp)],
-        "maa_ctx_destroy": [vp],
-        "maa_ctx_synchronize": [vp],
-        "maa_ctx_set_stream": [vp, vp],
-        "maa_ctx_workspace_bytes": [vp, C.POINTER(C.c_size_t)],
-        "maa_ctx_set_precision": [vp, ci],
-        "maa_ctx_set_cfg_split": [vp, ci],
-        "maa_ctx_set_concurrency": [vp, ci],
-        "maa_ctx_reload_tuning": [vp],
-        "maa_prof_begin": [vp, ci],
-        "maa_prof_end": [vp, C.POINTER(maa_prof_row), ci, C.POINTER(ci)],
-        "maa_unet_create": [vp, C.POINTER(maa_unet_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
-        "maa_unet_destroy": [vp],
-        "maa_unet_set_context": [vp, vp, vp, ci, ci],
-        "maa_unet_forward": [vp, vp, vp, vp, ci, ci, ci, vp],
-        "maa_ddim_update": [vp, vp, vp, vp, cf, vp, C.c_int64, vp, vp],
-        "maa_ddim_sample": [vp, vp, C.POINTER(maa_ddim_args), vp],
-        "maa_ddim_stochastic_encode": [vp, vp, ci, cf, vp, vp, fp, fp, ci, vp, ci, ci, ci, ci, vp],
-        "maa_ddim_decode": [vp, vp, C.POINTER(maa_ddim_args), ci, vp],
-        "maa_ldm_plms_sample": [vp, vp, C.POINTER(maa_ddim_args), vp],
-        "maa_ddpm_sample": [vp, vp, C.POINTER(maa_ddpm_args), vp],
-        "maa_ddpm_update": [vp, vp, vp, vp, fp, fp, fp, fp, fp, ci, vp, cf, ci, ci, ci, ci, ci, vp, vp],
-        "maa_vae_create": [vp, C.POINTER(maa_vae_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
-        "maa_vae_destroy": [vp],
-        "maa_vae_decode": [vp, vp, vp, ci, ci, ci, cf, vp],
-        "maa_vae_decode_spec": [vp, vp, vp, ci, ci, ci, cf, vp],
-        "maa_vae_encode_moments": [vp, vp, vp, ci, ci, ci, vp],
-        "maa_vocoder_create": [vp, C.POINTER(maa_vocoder_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
-        "maa_vocoder_destroy": [vp],
-        "maa_vocoder_forward": [vp, vp, vp, ci, ci, vp],
-        "maa_vocoder_forward_f0": [vp, vp, vp, vp, vp, vp, ci, ci, vp],
-        "maa_diffnet_create": [vp, C.POINTER(maa_diffnet_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
-        "maa_diffnet_destroy": [vp],
-        "maa_diffnet_forward": [vp, vp, vp, vp, vp, ci, ci, vp],
-        "maa_plms_sample": [vp, vp, C.POINTER(maa_plms_args), vp],
-        "maa_ds_ddpm_sample": [vp, vp, C.POINTER(maa_ds_ddpm_args), vp],
-        "maa_ds_ddpm_update": [vp, vp, vp, vp, fp, fp, fp, fp, fp, ci, ci, ci, ci, ci, vp],
-        "maa_pitch_extractor_create": [vp, C.POINTER(maa_pitch_extractor_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
-        "maa_pitch_extractor_destroy": [vp],
-        "maa_pitch_extractor_forward": [vp, vp, vp, ci, ci, vp, vp, vp],
-        "maa_fs2_create": [vp, C.POINTER(maa_fs2_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
-        "maa_fs2_destroy": [vp],
-        "maa_fs2_encode": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
-        "maa_fs2_length_regulate": [vp, vp, vp, ci, ci, ci, vp],
-        "maa_fs2_decode": [vp, vp, vp, vp, ci, ci, ci, vp, vp],
-        "maa_fs2_run_decoder": [vp, vp, vp, vp, ci, ci, vp],
-        "maa_fs2_pitch_create": [vp, C.POINTER(maa_fs2_pitch_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
-        "maa_fs2_pitch_destroy": [vp],
-        "maa_fs2_pitch_forward": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
-        "maa_encoder_create": [vp, C.POINTER(maa_encoder_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
-        "maa_encoder_destroy": [vp],
-        "maa_encoder_text": [vp, vp, vp, ci, ci, vp],
-        "maa_encoder_image": [vp, vp, vp, ci, vp],
-        "maa_encoder_text_cls": [vp, vp, vp, ci, ci, vp],
-        "maa_clap_audio_create": [vp, C.POINTER(maa_clap_audio_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
-        "maa_clap_audio_destroy": [vp],
-        "maa_clap_audio_embed": [vp, vp, vp, ci, ci, vp, vp],
-        "maa_clap_similarity": [vp, vp, vp, ci, ci, ci, cf, vp],
-        "maa_spectral_create": [vp, C.POINTER(maa_spectral_config), fp, fp, C.POINTER(vp)],
-        "maa_spectral_destroy": [vp],
-        "maa_spectral_forward": [vp, vp, vp, ci, ci, vp],
-        "maa_resampler_create": [vp, ci, ci, ci, ci, fp, C.POINTER(vp)],
-        "maa_resampler_destroy": [vp],
-        "maa_resampler_forward": [vp, vp, vp, ci, ci, vp],
-        "maa_op_linear": [vp, vp, ci, ci, fp, fp, ci, ci, vp, vp, ci],
-        "maa_op_conv": [vp, vp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, vp, vp, ci],
-        "maa_op_groupnorm": [vp, vp, ci, ci, ci, fp, fp, cf, ci, vp],
-        "maa_op_layernorm": [vp, vp, ci, ci, fp, fp, cf, vp],
-        "maa_op_attention": [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp],
-        "maa_op_attention_ex": [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, ci],
-        "maa_op_attention_masked": [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, ci, vp],
-        "maa_op_conv_transpose1d": [vp, vp, ci, ci, ci, fp, fp, ci, ci, ci, cf, vp],
-        "maa_op_snake_aa": [vp, vp, ci, ci, ci, fp, fp, ci, vp],
-        "maa_op_bench_conv": [vp, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)],
-        "maa_calib": [vp, ci, C.POINTER(C.c_double)],
-        "maa_op_mrf_pair": [vp, vp, ci, ci, ci, fp, fp, ci, ci, cf, fp, fp, ci, ci, cf, cf, ci, vp],
-        "maa_op_groupnorm_ex": [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, fp, fp, cf, ci, vp, ci, vp],
-        "maa_op_igemm_ex": [vp, C.POINTER(maa_igemm_ex_args)],
-        "maa_op_layernorm_ex": [vp, vp, ci, ci, fp, fp, cf, vp, ci],
-        "maa_op_split32": [vp, vp, ci, ci, cf, ci, vp],
-        "maa_unet_forward_split": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, fp, vp],
-        "maa_op_unfold": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp],
-        "maa_op_fold": [vp, vp, fp, ci, ci, ci, ci, ci, ci, ci, ci, vp],
-    }
-    for name, argtypes in sig.items():
+    for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
-        fn.restype = ci
+        fn.restype = C.c_int
     _lib = lib
     return lib
 

@@ -37,11 +37,48 @@ def _f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
-class Context:
+class _Handle:
+    """What every object over a library handle repeats: `h` made by a create entry on a context, calls that pass (context, handle)
+    first under the context's lock, output tensors on the context's device, and close / __del__ through the destroy entry the
+    class names.  A new model handle sets `_destroy`, calls `_create` in its __init__ and `_call` in its methods."""
+
+    _destroy = None          # the name of the maa_*_destroy entry
+
+    def _create(self, ctx, entry, *args, state_dict=None):
+        """self.h = what the create entry `entry` makes on `ctx` from `args` (then, with a state_dict, its tensor list)."""
+        self.ctx, self.lib, self.device = ctx, ctx.lib, ctx.device
+        if state_dict is not None:
+            arr, n, keep = L.tensor_list(state_dict)      # `keep`: the host copies `arr` points into live until the call is over
+            args += (arr, n)
+        h = C.c_void_p()
+        ctx._call(entry, *args, C.byref(h))
+        self.h = h
+
+    def _call(self, entry, *args):
+        """entry(context, this handle, *args) under the context's lock; raises MaaError on a non-zero status."""
+        self.ctx._call(entry, self.h, *args)
+
+    def _empty(self, *shape, dtype=torch.float32):
+        return torch.empty(*shape, dtype=dtype, device=self.device)
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.lib, self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
     """One (device, stream) execution context.  Calls are serialised with a lock, like the reference's
     non re-entrant sampler (ddim.py:27-56)."""
 
     PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}
+    _destroy = "maa_ctx_destroy"
 
     def __init__(self, device="cuda:0", stream=None, precision="f32"):
         self.lib = L.load()
@@ -63,45 +100,49 @@ class Context:
         self.set_precision(precision)
         _contexts.add(self)
 
+    def _call(self, entry, *args):
+        """entry(this context, *args) under the lock; raises MaaError on a non-zero status."""
+        with self.lock:
+            L.check(getattr(self.lib, entry)(self.h, *args))
+
     def reload_tuning(self):
         if getattr(self, "h", None):
-            with self.lock:
-                L.check(self.lib.maa_ctx_reload_tuning(self.h))
+            self._call("maa_ctx_reload_tuning")
 
     def set_precision(self, precision):
         """Arithmetic of the contractions for models created from now on (and for the op_* calls)."""
-        L.check(self.lib.maa_ctx_set_precision(self.h, self.PRECISIONS[precision]))
+        self._call("maa_ctx_set_precision", self.PRECISIONS[precision])
         self.precision = precision
 
     def set_cfg_split(self, mode):
         """Classifier-free guidance inside `ddim_sample`: True -> the two halves of the UNet batch as two lanes (two branches of
         the captured step graph), False -> one stream, None -> the default policy: two lanes unless the context has been told that three or more are in
         flight on the device (`set_concurrency`; one batch owning the GPU gains 4 %, with three in flight the extra lanes lose up to 24 %).  The results are the same bit for bit."""
-        L.check(self.lib.maa_ctx_set_cfg_split(self.h, -1 if mode is None else int(bool(mode))))
+        self._call("maa_ctx_set_cfg_split", -1 if mode is None else int(bool(mode)))
 
     def set_concurrency(self, n):
         """The serving arrangement as a hint: how many contexts' launches the caller keeps in flight on this device (None: not told,
         treated as 1).  >= 3: one stream per guided DDIM step and tiles by least total workgroup time; 1 or 2: this
         context (nearly) owns the GPU (two CFG lanes, tiles by least launch time).  Bit-identical either way (include/maa.h)."""
-        L.check(self.lib.maa_ctx_set_concurrency(self.h, -1 if n is None else int(n)))
+        self._call("maa_ctx_set_concurrency", -1 if n is None else int(n))
 
     def synchronize(self):
-        L.check(self.lib.maa_ctx_synchronize(self.h))
+        self._call("maa_ctx_synchronize")
 
     def workspace_bytes(self):
         n = C.c_size_t()
-        L.check(self.lib.maa_ctx_workspace_bytes(self.h, C.byref(n)))
+        self._call("maa_ctx_workspace_bytes", C.byref(n))
         return n.value
 
     def prof_begin(self, detail=False):
         """Start per-kernel hipEvent timing of every launch on this context (eager launches only)."""
-        L.check(self.lib.maa_prof_begin(self.h, int(detail)))
+        self._call("maa_prof_begin", int(detail))
 
     def prof_end(self):
         """Stop timing; returns {kernel: dict(launches, ms, flops, bytes)}."""
         rows = (L.maa_prof_row * 512)()
         n = C.c_int()
-        L.check(self.lib.maa_prof_end(self.h, rows, 512, C.byref(n)))
+        self._call("maa_prof_end", rows, 512, C.byref(n))
         return {rows[i].name.decode(): dict(launches=int(rows[i].launches), ms=rows[i].ms, flops=rows[i].flops,
                                             bytes=rows[i].bytes) for i in range(n.value)}
 
@@ -111,20 +152,9 @@ class Context:
         out = {}
         for kind, key in ((0, "mfma_bf16_tflops"), (1, "copy_gbs"), (2, "l2_read_gbs"), (3, "infinity_cache_read_gbs")):
             v = C.c_double()
-            L.check(self.lib.maa_calib(self.h, kind, C.byref(v)))
+            self._call("maa_calib", kind, C.byref(v))
             out[key] = v.value
         return out
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.maa_ctx_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- single operators (parity tests / kernel profiling) -------------------------------------
     def op_linear(self, a, w, b=None, geglu=False, res=None, split_out=False):
@@ -135,11 +165,11 @@ class Context:
         N = w.shape[0]
         wt, wp = L.host_f32(w)
         bt, bp = L.host_f32(b) if b is not None else (None, None)
-        y = torch.empty(M, N // 2 if geglu else N, device=self.device)
+        y = self._empty(M, N // 2 if geglu else N)
         r = _f32(res, self.device) if res is not None else None
         assert r is None or tuple(r.shape) == tuple(y.shape)
-        L.check(self.lib.maa_op_linear(self.h, L.dptr(a), M, K, wp, bp, N, int(geglu), L.dptr(y),
-                                       L.dptr(r) if r is not None else None, int(split_out)))
+        self._call("maa_op_linear", L.dptr(a), M, K, wp, bp, N, int(geglu), L.dptr(y), L.dptr(r) if r is not None else None,
+                   int(split_out))
         return y
 
     def op_conv(self, x, w, b=None, stride=1, pad=0, dil=1, up=False, leaky=0.0, out_hw=None, rowadd=None, res=None,
@@ -159,14 +189,13 @@ class Context:
             Ho, Wo = out_hw
         wt, wp = L.host_f32(w)
         bt, bp = L.host_f32(b) if b is not None else (None, None)
-        y = torch.empty((B, Ho, Wo, Cout) if split_out else (B, Cout, Ho, Wo), device=self.device)
+        y = self._empty((B, Ho, Wo, Cout) if split_out else (B, Cout, Ho, Wo))
         ra = _f32(rowadd, self.device) if rowadd is not None else None
         r = _f32(res, self.device) if res is not None else None
         assert ra is None or tuple(ra.shape) == (B, Cout)
         assert r is None or tuple(r.shape) == (B, Cout, Ho, Wo)
-        L.check(self.lib.maa_op_conv(self.h, L.dptr(x), B, Cin, H, W, wp, bp, Cout, KH, KW, stride, pad, dil,
-                                     int(up), float(leaky), L.dptr(y), Ho, Wo, L.dptr(ra) if ra is not None else None,
-                                     L.dptr(r) if r is not None else None, int(split_out)))
+        self._call("maa_op_conv", L.dptr(x), B, Cin, H, W, wp, bp, Cout, KH, KW, stride, pad, dil, int(up), float(leaky), L.dptr(y),
+                   Ho, Wo, L.dptr(ra) if ra is not None else None, L.dptr(r) if r is not None else None, int(split_out))
         return y
 
     def op_groupnorm(self, x, gamma, beta, eps, silu=False):
@@ -176,7 +205,7 @@ class Context:
         gt, gp = L.host_f32(gamma)
         bt, bp = L.host_f32(beta)
         y = torch.empty_like(x)
-        L.check(self.lib.maa_op_groupnorm(self.h, L.dptr(x), B, Cc, HW, gp, bp, float(eps), int(silu), L.dptr(y)))
+        self._call("maa_op_groupnorm", L.dptr(x), B, Cc, HW, gp, bp, float(eps), int(silu), L.dptr(y))
         return y
 
     def op_layernorm(self, x, gamma, beta, eps=1e-5):
@@ -185,7 +214,7 @@ class Context:
         gt, gp = L.host_f32(gamma)
         bt, bp = L.host_f32(beta)
         y = torch.empty_like(x)
-        L.check(self.lib.maa_op_layernorm(self.h, L.dptr(x), rows, Cc, gp, bp, float(eps), L.dptr(y)))
+        self._call("maa_op_layernorm", L.dptr(x), rows, Cc, gp, bp, float(eps), L.dptr(y))
         return y
 
     def op_attention(self, q, k, v, heads, alpha):
@@ -193,8 +222,7 @@ class Context:
         B, Nq, Cc = q.shape
         Nk = k.shape[1]
         y = torch.empty_like(q)
-        L.check(self.lib.maa_op_attention(self.h, L.dptr(q), L.dptr(k), L.dptr(v), B, heads, Cc // heads, Nq, Nk,
-                                          float(alpha), L.dptr(y)))
+        self._call("maa_op_attention", L.dptr(q), L.dptr(k), L.dptr(v), B, heads, Cc // heads, Nq, Nk, float(alpha), L.dptr(y))
         return y
 
     def op_attention_ex(self, q, ldq, hsq, k, ldk, hsk, v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, out, ldo,
@@ -204,11 +232,9 @@ class Context:
         Writes into `out`; nothing is allocated, copied or checked beyond what the C entry point checks."""
         for t in (q, k, v, out):
             assert t.is_cuda and t.dtype == torch.float32, (t.device, t.dtype)
-        L.check(self.lib.maa_op_attention_ex(self.h, C.c_void_p(q.data_ptr()), int(ldq), int(hsq),
-                                             C.c_void_p(k.data_ptr()), int(ldk), int(hsk),
-                                             C.c_void_p(v.data_ptr()), int(ldv), int(hsv), int(B), int(heads), int(dh),
-                                             int(Nq), int(Nk), float(alpha), C.c_void_p(out.data_ptr()), int(ldo),
-                                             int(out_split), int(causal)))
+        self._call("maa_op_attention_ex", C.c_void_p(q.data_ptr()), int(ldq), int(hsq), C.c_void_p(k.data_ptr()), int(ldk),
+                   int(hsk), C.c_void_p(v.data_ptr()), int(ldv), int(hsv), int(B), int(heads), int(dh), int(Nq), int(Nk),
+                   float(alpha), C.c_void_p(out.data_ptr()), int(ldo), int(out_split), int(causal))
         return out
 
     def op_attention_masked(self, q, ldq, hsq, k, ldk, hsk, v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, out, ldo, key_mask,
@@ -218,11 +244,9 @@ class Context:
         for t in (q, k, v, out, key_mask):
             assert t.is_cuda and t.dtype == torch.float32, (t.device, t.dtype)
         assert key_mask.is_contiguous() and tuple(key_mask.shape) == (B, Nk), tuple(key_mask.shape)
-        L.check(self.lib.maa_op_attention_masked(self.h, C.c_void_p(q.data_ptr()), int(ldq), int(hsq),
-                                                 C.c_void_p(k.data_ptr()), int(ldk), int(hsk),
-                                                 C.c_void_p(v.data_ptr()), int(ldv), int(hsv), int(B), int(heads), int(dh),
-                                                 int(Nq), int(Nk), float(alpha), C.c_void_p(out.data_ptr()), int(ldo),
-                                                 int(out_split), int(causal), C.c_void_p(key_mask.data_ptr())))
+        self._call("maa_op_attention_masked", C.c_void_p(q.data_ptr()), int(ldq), int(hsq), C.c_void_p(k.data_ptr()), int(ldk),
+                   int(hsk), C.c_void_p(v.data_ptr()), int(ldv), int(hsv), int(B), int(heads), int(dh), int(Nq), int(Nk),
+                   float(alpha), C.c_void_p(out.data_ptr()), int(ldo), int(out_split), int(causal), C.c_void_p(key_mask.data_ptr()))
         return out
 
     def op_groupnorm_ex(self, x1, ld1, C1, x2, ld2, C2, B, HW, groups, gamma, beta, eps, silu, out, out_split=0, raw=None):
@@ -235,8 +259,8 @@ class Context:
         bt, bp = L.host_f32(beta)
         assert gt.numel() == C1 + C2 and bt.numel() == C1 + C2
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        L.check(self.lib.maa_op_groupnorm_ex(self.h, ptr(x1), int(ld1), int(C1), ptr(x2), int(ld2), int(C2), int(B), int(HW),
-                                             int(groups), gp, bp, float(eps), int(silu), ptr(out), int(out_split), ptr(raw)))
+        self._call("maa_op_groupnorm_ex", ptr(x1), int(ld1), int(C1), ptr(x2), int(ld2), int(C2), int(B), int(HW), int(groups), gp,
+                   bp, float(eps), int(silu), ptr(out), int(out_split), ptr(raw))
         return out
 
     def op_igemm_ex(self, x1, ld1, C1, x2, ld2, C2, B, H, W, Ho, Wo, w, bias, c, ldc, stride=1, pad_w=0, pad_h=-1, dil=1, up=0,
@@ -261,7 +285,7 @@ class Context:
             ld_rowadd=int(ld_rowadd), d_res=ptr(res), ldr=int(ldr), act=int(act), act_slope=float(act_slope),
             out_scale=float(out_scale), accumulate=int(accumulate), geglu=int(geglu), c_split=int(c_split), d_c=ptr(c), ldc=int(ldc),
             d_c2=ptr(c2), ldc2=int(ldc2), c2_slope=float(c2_slope))
-        L.check(self.lib.maa_op_igemm_ex(self.h, C.byref(a)))
+        self._call("maa_op_igemm_ex", C.byref(a))
         return c
 
     def op_layernorm_ex(self, x, gamma, beta, eps=1e-5, out_split=0):
@@ -271,7 +295,7 @@ class Context:
         gt, gp = L.host_f32(gamma)
         bt, bp = L.host_f32(beta)
         y = torch.empty_like(x)
-        L.check(self.lib.maa_op_layernorm_ex(self.h, L.dptr(x), rows, Cc, gp, bp, float(eps), L.dptr(y), int(out_split)))
+        self._call("maa_op_layernorm_ex", L.dptr(x), rows, Cc, gp, bp, float(eps), L.dptr(y), int(out_split))
         return y
 
     def op_split32(self, x, slope=1.0, unpack=False):
@@ -280,7 +304,7 @@ class Context:
         x = _f32(x, self.device)
         rows, Cc = x.shape
         y = torch.empty_like(x)
-        L.check(self.lib.maa_op_split32(self.h, L.dptr(x), rows, Cc, float(slope), int(unpack), L.dptr(y)))
+        self._call("maa_op_split32", L.dptr(x), rows, Cc, float(slope), int(unpack), L.dptr(y))
         return y
 
     def op_unfold(self, x, ks, stride):
@@ -289,8 +313,8 @@ class Context:
         B, Cc, H, W = x.shape
         (kh, kw), (sh, sw) = ks, stride
         n = ((H - kh) // sh + 1) * ((W - kw) // sw + 1) if min(kh, kw, sh, sw) > 0 else 0
-        y = torch.empty(B * max(n, 0), Cc, kh, kw, device=self.device)
-        L.check(self.lib.maa_op_unfold(self.h, L.dptr(x), B, Cc, H, W, kh, kw, sh, sw, L.dptr(y)))
+        y = self._empty(B * max(n, 0), Cc, kh, kw)
+        self._call("maa_op_unfold", L.dptr(x), B, Cc, H, W, kh, kw, sh, sw, L.dptr(y))
         return y
 
     def op_fold(self, crops, weight, size, ks, stride):
@@ -301,8 +325,8 @@ class Context:
         n = wt.shape[1]
         assert wt.shape[0] == kh * kw and crops.shape[0] % n == 0 and tuple(crops.shape[2:]) == (kh, kw)
         B, Cc = crops.shape[0] // n, crops.shape[1]
-        y = torch.empty(B, Cc, H, W, device=self.device)
-        L.check(self.lib.maa_op_fold(self.h, L.dptr(crops), wp, B, Cc, H, W, kh, kw, sh, sw, L.dptr(y)))
+        y = self._empty(B, Cc, H, W)
+        self._call("maa_op_fold", L.dptr(crops), wp, B, Cc, H, W, kh, kw, sh, sw, L.dptr(y))
         return y
 
     def op_conv_transpose1d(self, x, w, b, stride, leaky=0.0):
@@ -311,9 +335,8 @@ class Context:
         _, Cout, k = w.shape
         wt, wp = L.host_f32(w)
         bt, bp = L.host_f32(b)
-        y = torch.empty(B, Cout, Ln * stride, device=self.device)
-        L.check(self.lib.maa_op_conv_transpose1d(self.h, L.dptr(x), B, Cin, Ln, wp, bp, Cout, k, stride, float(leaky),
-                                                 L.dptr(y)))
+        y = self._empty(B, Cout, Ln * stride)
+        self._call("maa_op_conv_transpose1d", L.dptr(x), B, Cin, Ln, wp, bp, Cout, k, stride, float(leaky), L.dptr(y))
         return y
 
     def op_mrf_pair(self, x, w1, b1, d1, slope1, w2=None, b2=None, d2=1, slope2=0.0, out_scale=1.0, out=None):
@@ -327,15 +350,14 @@ class Context:
         b2t, b2p = L.host_f32(b2) if b2 is not None else (None, None)
         y = _f32(out, self.device).clone() if out is not None else torch.empty_like(x)
         assert y.shape == x.shape
-        L.check(self.lib.maa_op_mrf_pair(self.h, L.dptr(x), B, Cc, Ln, w1p, b1p, w1.shape[2], int(d1), float(slope1), w2p, b2p,
-                                         w2.shape[2] if w2 is not None else 1, int(d2), float(slope2), float(out_scale),
-                                         int(out is not None), L.dptr(y)))
+        self._call("maa_op_mrf_pair", L.dptr(x), B, Cc, Ln, w1p, b1p, w1.shape[2], int(d1), float(slope1), w2p, b2p,
+                   w2.shape[2] if w2 is not None else 1, int(d2), float(slope2), float(out_scale), int(out is not None), L.dptr(y))
         return y
 
     def op_bench_conv(self, B, H, W, Cin, Cout, taps=9, pre_split=True, iters=20):
         """Kernel-only time (ms per launch) of one conv in this context's precision mode, synthetic data."""
         ms = C.c_float()
-        L.check(self.lib.maa_op_bench_conv(self.h, B, H, W, Cin, Cout, taps, int(pre_split), iters, C.byref(ms)))
+        self._call("maa_op_bench_conv", B, H, W, Cin, Cout, taps, int(pre_split), iters, C.byref(ms))
         return ms.value
 
     def op_snake_aa(self, x, alpha, beta, logscale):
@@ -344,7 +366,7 @@ class Context:
         at, ap = L.host_f32(alpha)
         bt, bp = L.host_f32(beta)
         y = torch.empty_like(x)
-        L.check(self.lib.maa_op_snake_aa(self.h, L.dptr(x), B, Cc, Ln, ap, bp, int(logscale), L.dptr(y)))
+        self._call("maa_op_snake_aa", L.dptr(x), B, Cc, Ln, ap, bp, int(logscale), L.dptr(y))
         return y
 
 
@@ -354,11 +376,13 @@ def _fill(arr, values):
     return len(values)
 
 
-class UNet:
+class UNet(_Handle):
     """maa_unet handle: replaces instantiate_from_config(unet_config) + load_state_dict."""
 
+    _destroy = "maa_unet_destroy"
+
     def __init__(self, ctx, cfg, state_dict):
-        self.ctx, self.cfg = ctx, cfg
+        self.cfg = cfg
         c = L.maa_unet_config()
         c.in_channels, c.out_channels, c.model_channels = cfg["in_channels"], cfg["out_channels"], cfg["model_channels"]
         c.num_res_blocks = cfg["num_res_blocks"]
@@ -370,11 +394,7 @@ class UNet:
         c.context_dim = cfg["context_dim"] or 0
         c.legacy, c.resblock_updown = int(cfg["legacy"]), int(cfg["resblock_updown"])
         c.add_context_to_emb = int(cfg.get("add_context_to_emb", False))
-        arr, n, keep = L.tensor_list(state_dict)
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_unet_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
-        self.h = h
+        self._create(ctx, "maa_unet_create", C.byref(c), state_dict=state_dict)
         self._context = None
         self._context_len = None
 
@@ -402,11 +422,9 @@ class UNet:
             if self._context_len != context.shape[1]:
                 self.set_context(context)          # (fixes the token count the C entry reads the context with)
             cp = L.dptr(context)
-        out = torch.empty(B, self.cfg["out_channels"], H, W, device=self.ctx.device)
+        out = self._empty(B, self.cfg["out_channels"], H, W)
         wp = C.cast(sp.weight.data_ptr(), C.POINTER(C.c_float))
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_unet_forward_split(self.ctx.h, self.h, L.dptr(x), L.dptr(tf), cp, B, H, W, sp.kh, sp.kw,
-                                                        sp.sh, sp.sw, wp, L.dptr(out)))
+        self._call("maa_unet_forward_split", L.dptr(x), L.dptr(tf), cp, B, H, W, sp.kh, sp.kw, sp.sh, sp.sw, wp, L.dptr(out))
         self._context = None          # the library's context is now the tiled one: a plain forward sets its own again
         return out
 
@@ -415,8 +433,7 @@ class UNet:
         context = _f32(context, self.ctx.device)
         self._context = context                 # keep alive: the I2A variant re-reads it every forward
         B, Ln, _ = context.shape
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_unet_set_context(self.ctx.h, self.h, L.dptr(context), B, Ln))
+        self._call("maa_unet_set_context", L.dptr(context), B, Ln)
         self._context_len = Ln
 
     def forward(self, x, t, context=None):
@@ -426,9 +443,8 @@ class UNet:
         x = _f32(x, self.ctx.device)
         tf = t.to(device=self.ctx.device, dtype=torch.float32).contiguous()
         B, _, H, W = x.shape
-        out = torch.empty(B, self.cfg["out_channels"], H, W, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_unet_forward(self.ctx.h, self.h, L.dptr(x), L.dptr(tf), B, H, W, L.dptr(out)))
+        out = self._empty(B, self.cfg["out_channels"], H, W)
+        self._call("maa_unet_forward", L.dptr(x), L.dptr(tf), B, H, W, L.dptr(out))
         return out
 
     __call__ = forward
@@ -496,7 +512,7 @@ class UNet:
         mask / x0 / noise_q [S, B, C, H, W] / sqrt_ac, sqrt_1mac [S]: the mask blend of ddim.py:147-150;
         sigmas [S] / noise_p [S, B, C, H, W] / temperature: the eta > 0 noise term of ddim.py:210-225.  Noise tensors
         are in loop order (first step first)."""
-        return self._sample("ddim_sample", self.ctx.lib.maa_ddim_sample, x_T, timesteps, alphas, alphas_prev, cond, uncond, scale,
+        return self._sample("ddim_sample", "maa_ddim_sample", x_T, timesteps, alphas, alphas_prev, cond, uncond, scale,
                             concat, use_graph, mask, x0, noise_q, sqrt_ac, sqrt_1mac, sigmas, noise_p, temperature, log_every_t,
                             split)
 
@@ -507,7 +523,7 @@ class UNet:
         Arguments and return value as ddim_sample's with eta 0 (PLMS has no noise term): the same tables, conditioning,
         mask / x0 / noise_q [S, B, C, H, W] / sqrt_ac, sqrt_1mac [S] blend before each step's first evaluation, and the logs
         of the final x_prev / pred_x0 of the logged steps; split as ddim_sample's."""
-        return self._sample("plms_sample", self.ctx.lib.maa_ldm_plms_sample, x_T, timesteps, alphas, alphas_prev, cond, uncond,
+        return self._sample("plms_sample", "maa_ldm_plms_sample", x_T, timesteps, alphas, alphas_prev, cond, uncond,
                             scale, concat, use_graph, mask, x0, noise_q, sqrt_ac, sqrt_1mac, None, None, 1.0, log_every_t, split)
 
     def _step_noise(self, what, v, name, dim, shape, keep):
@@ -528,7 +544,7 @@ class UNet:
         if key not in cache:
             if len(cache) >= 4:
                 cache.clear()
-            cache[key] = (torch.empty(*key, device=self.ctx.device), torch.empty(*key, device=self.ctx.device))
+            cache[key] = (self._empty(*key), self._empty(*key))
         return cache[key]
 
     def _copy_logs(self, logs):
@@ -589,7 +605,7 @@ class UNet:
             a.log_every_t, a.n_log = int(log_every_t), n_log
             a.d_log_x, a.d_log_x0 = logs[0].data_ptr(), logs[1].data_ptr()
         with self.ctx.lock:
-            L.check(entry(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
+            self._call(entry, C.byref(a), L.dptr(x))
             if logs is not None:
                 return (x,) + self._copy_logs(logs)
         return x
@@ -623,8 +639,7 @@ class UNet:
             a.h_sigmas = sg.ctypes.data_as(C.POINTER(C.c_float))
             a.d_noise_p = z.data_ptr() if t_start > 0 else None
         a.temperature = float(temperature)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_ddim_decode(self.ctx.h, self.h, C.byref(a), t_start, L.dptr(x)))
+        self._call("maa_ddim_decode", C.byref(a), t_start, L.dptr(x))
         return x
 
     def ddim_update(self, x, eps_uncond, eps_cond, scale, a_t, a_prev, sigma_t, sqrt_one_minus_at):
@@ -636,9 +651,8 @@ class UNet:
         ec = None if eps_cond is None else _f32(eps_cond, dev)
         coef = torch.tensor([a_t, a_prev, sigma_t, sqrt_one_minus_at], dtype=torch.float32).to(dev)
         x_prev, pred = torch.empty_like(x), torch.empty_like(x)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_ddim_update(self.ctx.h, L.dptr(x), L.dptr(eu), L.dptr(ec) if ec is not None else None,
-                                                 float(scale), L.dptr(coef), x.numel(), L.dptr(x_prev), L.dptr(pred)))
+        self.ctx._call("maa_ddim_update", L.dptr(x), L.dptr(eu), L.dptr(ec) if ec is not None else None, float(scale), L.dptr(coef),
+                       x.numel(), L.dptr(x_prev), L.dptr(pred))
         return x_prev, pred
 
     # the model's schedule buffers the ancestral chain reads, under the reference's names (ddpm.py:139-155)
@@ -737,7 +751,7 @@ class UNet:
             a.loop.log_every_t, a.loop.n_log = every, n_log
             a.loop.d_log_x, a.loop.d_log_x0 = logs[0].data_ptr(), logs[1].data_ptr()
         with self.ctx.lock:
-            L.check(self.ctx.lib.maa_ddpm_sample(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
+            self._call("maa_ddpm_sample", C.byref(a), L.dptr(x))
             if logs is not None:
                 return (x,) + self._copy_logs(logs)
         return x
@@ -767,22 +781,10 @@ class UNet:
         td = torch.from_numpy(th.astype(np.int32)).to(dev)
         x_prev, x_recon = torch.empty_like(x), torch.empty_like(x)
         fp = C.POINTER(C.c_float)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_ddpm_update(self.ctx.h, L.dptr(x), L.dptr(eps), C.c_void_p(td.data_ptr()),
-                                                 *[tb.ctypes.data_as(fp) for tb in tabs], n_tab, L.dptr(noise), float(temperature),
-                                                 int(bool(clip_denoised)), B, Cc, H, W, L.dptr(x_prev), L.dptr(x_recon)))
+        self.ctx._call("maa_ddpm_update", L.dptr(x), L.dptr(eps), C.c_void_p(td.data_ptr()),
+                       *[tb.ctypes.data_as(fp) for tb in tabs], n_tab, L.dptr(noise), float(temperature), int(bool(clip_denoised)),
+                       B, Cc, H, W, L.dptr(x_prev), L.dptr(x_recon))
         return x_prev, x_recon
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_unet_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def ddim_stochastic_encode(ctx, x0, t, sqrt_a, sqrt_1ma, noise, moments=False, scale_factor=1.0, noise_post=None):
@@ -824,40 +826,34 @@ def ddim_stochastic_encode(ctx, x0, t, sqrt_a, sqrt_1ma, noise, moments=False, s
     if th.min() < 0 or th.max() >= n_tab:
         raise L.MaaError("stochastic_encode: t must lie in [0, %d), got %s" % (n_tab, th.tolist()))
     td = torch.from_numpy(th.astype(np.int32)).to(dev)
-    out = torch.empty(shape, device=dev)
+    out = ctx._empty(shape)
     fp = C.POINTER(C.c_float)
-    with ctx.lock:
-        L.check(ctx.lib.maa_ddim_stochastic_encode(ctx.h, L.dptr(src), int(bool(moments)), float(scale_factor),
-                                                   L.dptr(npost) if npost is not None else None, C.c_void_p(td.data_ptr()),
-                                                   ta.ctypes.data_as(fp), tb.ctypes.data_as(fp), n_tab, L.dptr(noise),
-                                                   B, Cc, H, W, L.dptr(out)))
+    ctx._call("maa_ddim_stochastic_encode", L.dptr(src), int(bool(moments)), float(scale_factor),
+              L.dptr(npost) if npost is not None else None, C.c_void_p(td.data_ptr()), ta.ctypes.data_as(fp), tb.ctypes.data_as(fp),
+              n_tab, L.dptr(noise), B, Cc, H, W, L.dptr(out))
     return out
 
 
-class VAE:
+class VAE(_Handle):
+    _destroy = "maa_vae_destroy"
+
     def __init__(self, ctx, dd, state_dict):
-        self.ctx, self.dd = ctx, dd
+        self.dd = dd
         c = L.maa_vae_config()
         c.ch, c.out_ch, c.in_channels, c.z_channels = dd["ch"], dd["out_ch"], dd["in_channels"], dd["z_channels"]
         c.embed_dim, c.resolution, c.num_res_blocks = dd["embed_dim"], dd["resolution"], dd["num_res_blocks"]
         c.double_z = int(dd["double_z"])
         c.n_ch_mult = _fill(c.ch_mult, dd["ch_mult"])
         c.n_attn_resolutions = _fill(c.attn_resolutions, dd["attn_resolutions"])
-        arr, n, keep = L.tensor_list(state_dict)
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_vae_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
-        self.h = h
+        self._create(ctx, "maa_vae_create", C.byref(c), state_dict=state_dict)
 
     def decode(self, z, scale_factor=1.0):
         """decode_first_stage (ddpm_audio.py:352-359): z [B,4,h,w] -> mel [B,1,8h,8w]."""
         z = _f32(z, self.ctx.device)
         B, _, h, w = z.shape
         f = 2 ** (len(self.dd["ch_mult"]) - 1)
-        mel = torch.empty(B, self.dd["out_ch"], h * f, w * f, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_vae_decode(self.ctx.h, self.h, L.dptr(z), B, h, w, 1.0 / float(scale_factor),
-                                                L.dptr(mel)))
+        mel = self._empty(B, self.dd["out_ch"], h * f, w * f)
+        self._call("maa_vae_decode", L.dptr(z), B, h, w, 1.0 / float(scale_factor), L.dptr(mel))
         return mel
 
     def decode_spec(self, z, scale_factor=1.0):
@@ -865,10 +861,8 @@ class VAE:
         z = _f32(z, self.ctx.device)
         B, _, h, w = z.shape
         f = 2 ** (len(self.dd["ch_mult"]) - 1)
-        spec = torch.empty(B, h * f, w * f, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_vae_decode_spec(self.ctx.h, self.h, L.dptr(z), B, h, w, 1.0 / float(scale_factor),
-                                                     L.dptr(spec)))
+        spec = self._empty(B, h * f, w * f)
+        self._call("maa_vae_decode_spec", L.dptr(z), B, h, w, 1.0 / float(scale_factor), L.dptr(spec))
         return spec
 
     def encode_moments(self, mel):
@@ -876,26 +870,16 @@ class VAE:
         mel = _f32(mel, self.ctx.device)
         B, _, H, W = mel.shape
         f = 2 ** (len(self.dd["ch_mult"]) - 1)
-        out = torch.empty(B, 2 * self.dd["embed_dim"], H // f, W // f, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_vae_encode_moments(self.ctx.h, self.h, L.dptr(mel), B, H, W, L.dptr(out)))
+        out = self._empty(B, 2 * self.dd["embed_dim"], H // f, W // f)
+        self._call("maa_vae_encode_moments", L.dptr(mel), B, H, W, L.dptr(out))
         return out
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_vae_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class Vocoder(_Handle):
+    _destroy = "maa_vocoder_destroy"
 
-
-class Vocoder:
     def __init__(self, ctx, cfg, state_dict):
-        self.ctx, self.cfg = ctx, cfg
+        self.cfg = cfg
         c = L.maa_vocoder_config()
         c.kind = 1 if cfg["kind"] == "bigvgan" else 0
         c.num_mels, c.upsample_initial_channel = cfg["num_mels"], cfg["upsample_initial_channel"]
@@ -915,20 +899,15 @@ class Vocoder:
         c.resblock = int(cfg.get("resblock", "1"))                        # hifigan.py:119: '1' -> ResBlock1, else ResBlock2
         if c.resblock != 1:
             c.resblock = 2
-        arr, n, keep = L.tensor_list(state_dict)
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_vocoder_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
-        self.h = h
+        self._create(ctx, "maa_vocoder_create", C.byref(c), state_dict=state_dict)
         self.hop = int(np.prod(cfg["upsample_rates"]))
 
     def forward(self, mel):
         """mel [B, num_mels, T] -> wav [B, 1, T*hop] (HifiGanGenerator.forward, hifigan.py:144-169)."""
         mel = _f32(mel, self.ctx.device)
         B, _, T = mel.shape
-        wav = torch.empty(B, 1, T * self.hop, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_vocoder_forward(self.ctx.h, self.h, L.dptr(mel), B, T, L.dptr(wav)))
+        wav = self._empty(B, 1, T * self.hop)
+        self._call("maa_vocoder_forward", L.dptr(mel), B, T, L.dptr(wav))
         return wav
 
     def forward_f0(self, mel, f0, rand_ini=None, noise=None):
@@ -950,42 +929,27 @@ class Vocoder:
         rand_ini, noise = _f32(rand_ini, dev), _f32(noise, dev)
         if tuple(rand_ini.shape) != (B, H1) or tuple(noise.shape) != (B, Ln, H1):
             raise L.MaaError("forward_f0: rand_ini must be [%d, %d] and noise [%d, %d, %d]" % (B, H1, B, Ln, H1))
-        wav = torch.empty(B, 1, Ln, device=dev)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_vocoder_forward_f0(self.ctx.h, self.h, L.dptr(mel), L.dptr(f0), L.dptr(rand_ini),
-                                                        L.dptr(noise), B, T, L.dptr(wav)))
+        wav = self._empty(B, 1, Ln)
+        self._call("maa_vocoder_forward_f0", L.dptr(mel), L.dptr(f0), L.dptr(rand_ini), L.dptr(noise), B, T, L.dptr(wav))
         return wav
 
     def __call__(self, mel, f0=None, **kw):
         return self.forward(mel) if f0 is None else self.forward_f0(mel, f0, **kw)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_vocoder_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DiffNet:
+class DiffNet(_Handle):
     """maa_diffnet handle: DiffSinger's denoiser (NeuralSeq/modules/diff/net.py:84-130) and the PLMS loop over it
     (NeuralSeq/modules/diff/shallow_diffusion_tts.py:166-201, 262-269)."""
 
+    _destroy = "maa_diffnet_destroy"
+
     def __init__(self, ctx, cfg, state_dict):
-        self.ctx, self.cfg = ctx, cfg
+        self.cfg = cfg
         c = L.maa_diffnet_config()
         c.in_dims, c.hidden_size = cfg["in_dims"], cfg["hidden_size"]
         c.residual_layers, c.residual_channels = cfg["residual_layers"], cfg["residual_channels"]
         c.dilation_cycle_length = cfg["dilation_cycle_length"]
-        arr, n, keep = L.tensor_list(state_dict)
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_diffnet_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
-        self.h = h
+        self._create(ctx, "maa_diffnet_create", C.byref(c), state_dict=state_dict)
 
     def forward(self, spec, diffusion_step, cond):
         """spec [B, 1, M, T], diffusion_step [B] or [B, 1] (integer steps), cond [B, H, T] -> eps [B, 1, M, T]."""
@@ -997,8 +961,7 @@ class DiffNet:
             raise L.MaaError("DiffNet.forward: spec %s / step %s / cond %s do not fit in_dims %d, hidden_size %d"
                              % (tuple(spec.shape), tuple(t.shape), tuple(cond.shape), self.cfg["in_dims"], self.cfg["hidden_size"]))
         out = torch.empty_like(spec)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_diffnet_forward(self.ctx.h, self.h, L.dptr(spec), L.dptr(t), L.dptr(cond), B, T, L.dptr(out)))
+        self._call("maa_diffnet_forward", L.dptr(spec), L.dptr(t), L.dptr(cond), B, T, L.dptr(out))
         return out
 
     __call__ = forward
@@ -1019,8 +982,7 @@ class DiffNet:
         a.d_cond = cond.data_ptr()
         a.h_alphas_cumprod = ac.ctypes.data_as(C.POINTER(C.c_float))
         a.use_graph = int(use_graph)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_plms_sample(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
+        self._call("maa_plms_sample", C.byref(a), L.dptr(x))
         return x
 
     @staticmethod
@@ -1065,8 +1027,7 @@ class DiffNet:
         a.clip_denoised, a.use_graph = int(bool(clip_denoised)), int(bool(use_graph))
         a.d_cond, a.d_noise = cond.data_ptr(), noise.data_ptr()
         a.h_sqrt_recip_ac, a.h_sqrt_recipm1_ac, a.h_coef1, a.h_coef2, a.h_sigma = ptrs
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_ds_ddpm_sample(self.ctx.h, self.h, C.byref(a), L.dptr(x)))
+        self._call("maa_ds_ddpm_sample", C.byref(a), L.dptr(x))
         return x
 
     def ddpm_update(self, x, eps, t, tables, noise, clip_denoised=True):
@@ -1082,21 +1043,9 @@ class DiffNet:
                              % (what, tuple(x.shape), tuple(eps.shape), tuple(noise.shape), tuple(t.shape)))
         B, _, M, T = x.shape
         tabs, ptrs = self._ddpm_tables(what, tables)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_ds_ddpm_update(self.ctx.h, L.dptr(eps), L.dptr(t), L.dptr(noise), *ptrs, int(tabs[0].shape[0]),
-                                                    B, M, T, int(bool(clip_denoised)), L.dptr(x)))
+        self.ctx._call("maa_ds_ddpm_update", L.dptr(eps), L.dptr(t), L.dptr(noise), *ptrs, int(tabs[0].shape[0]), B, M, T,
+                       int(bool(clip_denoised)), L.dptr(x))
         return x
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_diffnet_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def pe_config(cfg):
@@ -1122,17 +1071,14 @@ def pe_config(cfg):
     return c
 
 
-class PitchExtractor:
+class PitchExtractor(_Handle):
     """maa_pitch_extractor handle: DiffSinger's PitchExtractor (NeuralSeq/modules/fastspeech/pe.py:119-149), mel -> f0."""
 
+    _destroy = "maa_pitch_extractor_destroy"
+
     def __init__(self, ctx, cfg, state_dict):
-        self.ctx, self.cfg = ctx, dict(cfg)
-        c = pe_config(self.cfg)
-        arr, n, keep = L.tensor_list(state_dict)
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_pitch_extractor_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
-        self.h = h
+        self.cfg = dict(cfg)
+        self._create(ctx, "maa_pitch_extractor_create", C.byref(pe_config(self.cfg)), state_dict=state_dict)
 
     def forward(self, mel, return_hidden=False):
         """mel [B, T, n_mel_bins] (an all-zero frame is padding) -> (pitch_pred [B, T, 2], f0 [B, T]) on the device; with
@@ -1141,26 +1087,14 @@ class PitchExtractor:
         if mel.dim() != 3 or mel.shape[2] != self.cfg["n_mel_bins"] or mel.shape[0] < 1 or mel.shape[1] < 1:
             raise L.MaaError("PitchExtractor.forward: mel %s is not [B, T, %d]" % (tuple(mel.shape), self.cfg["n_mel_bins"]))
         B, T, _ = mel.shape
-        pitch_pred = torch.empty(B, T, 2, device=self.ctx.device)
-        f0 = torch.empty(B, T, device=self.ctx.device)
-        hidden = torch.empty(B, T, self.cfg["hidden_size"], device=self.ctx.device) if return_hidden else None
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_pitch_extractor_forward(self.ctx.h, self.h, L.dptr(mel), B, T, L.dptr(pitch_pred), L.dptr(f0),
-                                                             L.dptr(hidden) if return_hidden else None))
+        pitch_pred = self._empty(B, T, 2)
+        f0 = self._empty(B, T)
+        hidden = self._empty(B, T, self.cfg["hidden_size"]) if return_hidden else None
+        self._call("maa_pitch_extractor_forward", L.dptr(mel), B, T, L.dptr(pitch_pred), L.dptr(f0),
+                   L.dptr(hidden) if return_hidden else None)
         return (pitch_pred, f0, hidden) if return_hidden else (pitch_pred, f0)
 
     __call__ = forward
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_pitch_extractor_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def fs2_config(cfg):
@@ -1202,18 +1136,15 @@ def fs2_config(cfg):
     return c
 
 
-class FastSpeech2MIDI:
+class FastSpeech2MIDI(_Handle):
     """maa_fs2 handle: DiffSinger's FastSpeech2MIDI front end (NeuralSeq/modules/diffsinger_midi/fs2.py:46-118).  Integer tensors
     cross the boundary as int32; nothing here reads the device."""
 
+    _destroy = "maa_fs2_destroy"
+
     def __init__(self, ctx, cfg, state_dict):
-        self.ctx, self.cfg = ctx, dict(cfg)
-        c = fs2_config(self.cfg)
-        arr, n, keep = L.tensor_list(state_dict)
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_fs2_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
-        self.h = h
+        self.cfg = dict(cfg)
+        self._create(ctx, "maa_fs2_create", C.byref(fs2_config(self.cfg)), state_dict=state_dict)
 
     def _i32(self, t):
         return torch.as_tensor(t).to(device=self.ctx.device, dtype=torch.int32).contiguous()
@@ -1232,22 +1163,20 @@ class FastSpeech2MIDI:
             if t is not None and tuple(t.shape) != (B, T):
                 raise L.MaaError("FastSpeech2MIDI.encode: %s %s is not txt_tokens' [%d, %d]" % (name, tuple(t.shape), B, T))
         dev = self.ctx.device
-        enc = torch.empty(B, T, self.cfg["hidden_size"], device=dev)
-        xs = torch.empty(B, T, device=dev)
-        dur = torch.empty(B, T, dtype=torch.int32, device=dev)
-        totals = torch.empty(B, dtype=torch.int32, device=dev)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_fs2_encode(self.ctx.h, self.h, self._p(tok), self._p(midi), self._p(dur_f), self._p(slur), B, T,
-                                                self._p(enc), self._p(xs), self._p(dur), self._p(totals)))
+        enc = self._empty(B, T, self.cfg["hidden_size"])
+        xs = self._empty(B, T)
+        dur = self._empty(B, T, dtype=torch.int32)
+        totals = self._empty(B, dtype=torch.int32)
+        self._call("maa_fs2_encode", self._p(tok), self._p(midi), self._p(dur_f), self._p(slur), B, T, self._p(enc), self._p(xs),
+                   self._p(dur), self._p(totals))
         return enc, xs, dur, totals
 
     def length_regulate(self, dur, T_mel):
         """dur int32 [B, T] -> mel2ph int32 [B, T_mel]."""
         dur = self._i32(dur)
         B, T = dur.shape
-        mel2ph = torch.empty(B, int(T_mel), dtype=torch.int32, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_fs2_length_regulate(self.ctx.h, self.h, self._p(dur), B, T, int(T_mel), self._p(mel2ph)))
+        mel2ph = self._empty(B, int(T_mel), dtype=torch.int32)
+        self._call("maa_fs2_length_regulate", self._p(dur), B, T, int(T_mel), self._p(mel2ph))
         return mel2ph
 
     def decode(self, encoder_out, mel2ph, skip_decoder=False):
@@ -1259,11 +1188,9 @@ class FastSpeech2MIDI:
             raise L.MaaError("FastSpeech2MIDI.decode: mel2ph %s is not [%d, T_mel]" % (tuple(m2p.shape), B))
         T_mel = int(m2p.shape[1])
         dev = self.ctx.device
-        dec_inp = torch.empty(B, T_mel, self.cfg["hidden_size"], device=dev)
-        mel = None if skip_decoder else torch.empty(B, T_mel, self.cfg["audio_num_mel_bins"], device=dev)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_fs2_decode(self.ctx.h, self.h, self._p(enc), self._p(m2p), B, T, T_mel, self._p(dec_inp),
-                                                self._p(mel)))
+        dec_inp = self._empty(B, T_mel, self.cfg["hidden_size"])
+        mel = None if skip_decoder else self._empty(B, T_mel, self.cfg["audio_num_mel_bins"])
+        self._call("maa_fs2_decode", self._p(enc), self._p(m2p), B, T, T_mel, self._p(dec_inp), self._p(mel))
         return dec_inp, mel
 
     def run_decoder(self, decoder_inp, mel2ph):
@@ -1276,21 +1203,9 @@ class FastSpeech2MIDI:
         B, T_mel, _ = x.shape
         if tuple(m2p.shape) != (B, T_mel):
             raise L.MaaError("FastSpeech2MIDI.run_decoder: mel2ph %s is not [%d, %d]" % (tuple(m2p.shape), B, T_mel))
-        mel = torch.empty(B, T_mel, self.cfg["audio_num_mel_bins"], device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_fs2_run_decoder(self.ctx.h, self.h, self._p(x), self._p(m2p), B, T_mel, self._p(mel)))
+        mel = self._empty(B, T_mel, self.cfg["audio_num_mel_bins"])
+        self._call("maa_fs2_run_decoder", self._p(x), self._p(m2p), B, T_mel, self._p(mel))
         return mel
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_fs2_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def fs2_pitch_config(cfg):
@@ -1332,19 +1247,16 @@ def fs2_pitch_config(cfg):
     return c
 
 
-class FS2Pitch:
+class FS2Pitch(_Handle):
     """maa_fs2_pitch handle: FastSpeech2.add_pitch, pitch_type 'frame' (NeuralSeq/modules/fastspeech/fs2.py:174-220), with the mask
     of :132: PitchPredictor, denorm_f0, f0_to_coarse and the pitch_embed row added to decoder_inp.  state_dict: the pitch_embed /
     pitch_predictor keys (others are ignored)."""
 
+    _destroy = "maa_fs2_pitch_destroy"
+
     def __init__(self, ctx, cfg, state_dict):
-        self.ctx, self.cfg = ctx, dict(cfg)
-        c = fs2_pitch_config(self.cfg)
-        arr, n, keep = L.tensor_list(state_dict)
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_fs2_pitch_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
-        self.h = h
+        self.cfg = dict(cfg)
+        self._create(ctx, "maa_fs2_pitch_create", C.byref(fs2_pitch_config(self.cfg)), state_dict=state_dict)
 
     def forward(self, origin, mel2ph, f0=None, uv=None, return_coarse=False):
         """origin [B, T_mel, H] (FastSpeech2MIDI.decode's decoder_inp: 0 where mel2ph is 0), mel2ph [B, T_mel], f0 / uv [B, T_mel]
@@ -1363,31 +1275,19 @@ class FS2Pitch:
         for name, t in (("f0", f0), ("uv", uv)):
             if t is not None and tuple(t.shape) != (B, T_mel):
                 raise L.MaaError("FS2Pitch.forward: %s %s is not [%d, %d]" % (name, tuple(t.shape), B, T_mel))
-        dec_inp = torch.empty(B, T_mel, H, device=dev)
-        pitch_pred = torch.empty(B, T_mel, 2, device=dev)
-        f0_denorm = torch.empty(B, T_mel, device=dev)
-        coarse = torch.empty(B, T_mel, dtype=torch.int32, device=dev) if return_coarse else None
+        dec_inp = self._empty(B, T_mel, H)
+        pitch_pred = self._empty(B, T_mel, 2)
+        f0_denorm = self._empty(B, T_mel)
+        coarse = self._empty(B, T_mel, dtype=torch.int32) if return_coarse else None
         p = FastSpeech2MIDI._p
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_fs2_pitch_forward(self.ctx.h, self.h, p(x), p(m2p), p(f0), p(uv), B, T_mel, p(dec_inp),
-                                                       p(pitch_pred), p(f0_denorm), p(coarse)))
+        self._call("maa_fs2_pitch_forward", p(x), p(m2p), p(f0), p(uv), B, T_mel, p(dec_inp), p(pitch_pred), p(f0_denorm),
+                   p(coarse))
         return (dec_inp, pitch_pred, f0_denorm, coarse) if return_coarse else (dec_inp, pitch_pred, f0_denorm)
 
     __call__ = forward
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_fs2_pitch_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Encoder:
+class Encoder(_Handle):
     """maa_encoder handle: a conditioning tower on the device.
 
     kind "text":  BertModel(input_ids) + CLAP Projection per token, FrozenCLAPEmbedder.encode
@@ -1395,19 +1295,17 @@ class Encoder:
     kind "image": open_clip VisionTransformer + L2 normalisation, FrozenGlobalNormOpenCLIPEmbedder.forward_img
                   (ldm/modules/encoders/modules.py:340-343)"""
 
+    _destroy = "maa_encoder_destroy"
+
     def __init__(self, ctx, cfg, state_dict):
-        self.ctx, self.cfg = ctx, cfg
+        self.cfg = cfg
         c = L.maa_encoder_config()
         c.kind = {"text": 0, "image": 1, "clip_text": 2}[cfg["kind"]]
         c.layers, c.width, c.heads, c.mlp_dim, c.d_proj = cfg["layers"], cfg["width"], cfg["heads"], cfg["mlp_dim"], cfg["d_proj"]
         c.vocab, c.max_positions = cfg.get("vocab", 0), cfg.get("max_positions", 0)
         c.patch, c.image = cfg.get("patch", 0), cfg.get("image", 0)
         c.ln_eps = cfg["ln_eps"]
-        arr, n, keep = L.tensor_list(state_dict)
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_encoder_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
-        self.h = h
+        self._create(ctx, "maa_encoder_create", C.byref(c), state_dict=state_dict)
 
     def encode_tokens(self, input_ids):
         """input_ids [B, L] (any integer dtype) -> [B, L, d_proj] (kind "text") / unit-length [B, d_proj] ("clip_text")."""
@@ -1419,9 +1317,8 @@ class Encoder:
         ids = ids.to(device=self.ctx.device, dtype=torch.int32).contiguous()
         B, Ln = ids.shape
         shape = (B, Ln, self.cfg["d_proj"]) if self.cfg["kind"] == "text" else (B, self.cfg["d_proj"])
-        out = torch.empty(*shape, dtype=torch.float32, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_encoder_text(self.ctx.h, self.h, C.c_void_p(ids.data_ptr()), B, Ln, L.dptr(out)))
+        out = self._empty(*shape, dtype=torch.float32)
+        self._call("maa_encoder_text", C.c_void_p(ids.data_ptr()), B, Ln, L.dptr(out))
         return out
 
     def encode_cls(self, input_ids):
@@ -1433,10 +1330,8 @@ class Encoder:
         if ids.dim() != 2 or ids.shape[1] > self.cfg["max_positions"]:
             raise L.MaaError("encode_cls: input_ids %s must be [B, L <= %d]" % (tuple(ids.shape), self.cfg["max_positions"]))
         ids = ids.to(device=self.ctx.device, dtype=torch.int32).contiguous()
-        out = torch.empty(ids.shape[0], self.cfg["d_proj"], dtype=torch.float32, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_encoder_text_cls(self.ctx.h, self.h, C.c_void_p(ids.data_ptr()), ids.shape[0],
-                                                      ids.shape[1], L.dptr(out)))
+        out = self._empty(ids.shape[0], self.cfg["d_proj"], dtype=torch.float32)
+        self._call("maa_encoder_text_cls", C.c_void_p(ids.data_ptr()), ids.shape[0], ids.shape[1], L.dptr(out))
         return out
 
     def encode_image(self, image):
@@ -1447,37 +1342,24 @@ class Encoder:
         S = self.cfg["image"]
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, S, S):
             raise L.MaaError("encode_image: image %s must be [B, 3, %d, %d]" % (tuple(x.shape), S, S))
-        out = torch.empty(x.shape[0], self.cfg["d_proj"], dtype=torch.float32, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_encoder_image(self.ctx.h, self.h, L.dptr(x), x.shape[0], L.dptr(out)))
+        out = self._empty(x.shape[0], self.cfg["d_proj"], dtype=torch.float32)
+        self._call("maa_encoder_image", L.dptr(x), x.shape[0], L.dptr(out))
         return out
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_encoder_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ClapAudio:
+class ClapAudio(_Handle):
     """maa_clap_audio handle: Cnn14 from the log-mel on + Projection, unit-length rows (the audio side of the CLAP
     best-of-n scorer: wav_evaluation/models/audio.py:150-176, clap.py:8-39, CLAPWrapper.py:184-189)."""
 
+    _destroy = "maa_clap_audio_destroy"
+
     def __init__(self, ctx, cfg, state_dict):
-        self.ctx, self.cfg = ctx, cfg
+        self.cfg = cfg
         c = L.maa_clap_audio_config()
         c.mel_bins, c.out_emb, c.d_proj, c.bn_eps = cfg["mel_bins"], cfg["out_emb"], cfg["d_proj"], cfg.get("bn_eps", 1e-5)
         c.n_blocks = _fill(c.channels, cfg["channels"])
-        arr, n, keep = L.tensor_list({k: v for k, v in state_dict.items() if not k.endswith("num_batches_tracked")})
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_clap_audio_create(ctx.h, C.byref(c), arr, n, C.byref(h)))
-        self.h = h
+        self._create(ctx, "maa_clap_audio_create", C.byref(c),
+                     state_dict={k: v for k, v in state_dict.items() if not k.endswith("num_batches_tracked")})
 
     def embed(self, logmel, return_embedding=False):
         """logmel [B, 1, T, mel_bins] -> z [B, d_proj] (unit length) [, relu(fc1) embedding [B, out_emb]]."""
@@ -1485,23 +1367,10 @@ class ClapAudio:
         if x.dim() != 4 or x.shape[1] != 1 or x.shape[3] != self.cfg["mel_bins"]:
             raise L.MaaError("ClapAudio.embed: logmel %s must be [B, 1, T, %d]" % (tuple(x.shape), self.cfg["mel_bins"]))
         B, _, T, _ = x.shape
-        z = torch.empty(B, self.cfg["d_proj"], dtype=torch.float32, device=self.ctx.device)
-        emb = torch.empty(B, self.cfg["out_emb"], dtype=torch.float32, device=self.ctx.device) if return_embedding else None
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_clap_audio_embed(self.ctx.h, self.h, L.dptr(x), B, T,
-                                                      L.dptr(emb) if emb is not None else None, L.dptr(z)))
+        z = self._empty(B, self.cfg["d_proj"], dtype=torch.float32)
+        emb = self._empty(B, self.cfg["out_emb"], dtype=torch.float32) if return_embedding else None
+        self._call("maa_clap_audio_embed", L.dptr(x), B, T, L.dptr(emb) if emb is not None else None, L.dptr(z))
         return (z, emb) if return_embedding else z
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_clap_audio_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def clap_similarity(ctx, audio_embeddings, text_embeddings, scale=1.0):
@@ -1509,21 +1378,21 @@ def clap_similarity(ctx, audio_embeddings, text_embeddings, scale=1.0):
     a, t = _f32(audio_embeddings, ctx.device), _f32(text_embeddings, ctx.device)
     if a.dim() != 2 or t.dim() != 2 or a.shape[1] != t.shape[1]:
         raise L.MaaError("clap_similarity: embeddings %s / %s must be [N, D] with one D" % (tuple(a.shape), tuple(t.shape)))
-    out = torch.empty(a.shape[0], t.shape[0], dtype=torch.float32, device=ctx.device)
-    with ctx.lock:
-        L.check(ctx.lib.maa_clap_similarity(ctx.h, L.dptr(a), L.dptr(t), a.shape[0], t.shape[0], a.shape[1], float(scale),
-                                            L.dptr(out)))
+    out = ctx._empty(a.shape[0], t.shape[0], dtype=torch.float32)
+    ctx._call("maa_clap_similarity", L.dptr(a), L.dptr(t), a.shape[0], t.shape[0], a.shape[1], float(scale), L.dptr(out))
     return out
 
 
-class Spectral:
+class Spectral(_Handle):
     """maa_spectral handle: waveform [B, n] -> log-mel (framed DFT GEMM -> |.|^p -> mel GEMM -> log), exact fp32.
     cfg: n_fft, hop, n_mels, pad_mode ("constant" | "reflect"), power (1 | 2), log_kind ("db" | "transforms_16000"),
     amin, ref, out_layout ("btm" = [B, frames, n_mels] | "bmt" = [B, n_mels, frames]); basis [2 n_freq, n_fft], melw
     [n_mels, n_freq] are host matrices (audiogpt_amd/mel.py builds them)."""
 
+    _destroy = "maa_spectral_destroy"
+
     def __init__(self, ctx, cfg, basis, melw):
-        self.ctx, self.cfg = ctx, dict(cfg)
+        self.cfg = dict(cfg)
         c = L.maa_spectral_config()
         c.n_fft, c.hop, c.n_freq, c.n_mels = cfg["n_fft"], cfg["hop"], cfg["n_fft"] // 2 + 1, cfg["n_mels"]
         c.pad_mode = {"constant": 0, "reflect": 1}[cfg["pad_mode"]]
@@ -1535,10 +1404,7 @@ class Spectral:
         mt, mp = L.host_f32(torch.as_tensor(melw))
         if tuple(bt.shape) != (2 * c.n_freq, c.n_fft) or tuple(mt.shape) != (c.n_mels, c.n_freq):
             raise L.MaaError("Spectral: basis %s / melw %s do not match the configuration" % (tuple(bt.shape), tuple(mt.shape)))
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_spectral_create(ctx.h, C.byref(c), bp, mp, C.byref(h)))
-        self.h = h
+        self._create(ctx, "maa_spectral_create", C.byref(c), bp, mp)
 
     def frames(self, n):
         return 1 + n // self.cfg["hop"]
@@ -1549,60 +1415,33 @@ class Spectral:
             x = x[None]
         B, n = x.shape
         T, M = self.frames(n), self.cfg["n_mels"]
-        out = torch.empty((B, T, M) if self.cfg["out_layout"] == "btm" else (B, M, T), dtype=torch.float32,
-                          device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_spectral_forward(self.ctx.h, self.h, L.dptr(x), B, n, L.dptr(out)))
+        out = self._empty((B, T, M) if self.cfg["out_layout"] == "btm" else (B, M, T))
+        self._call("maa_spectral_forward", L.dptr(x), B, n, L.dptr(out))
         return out
 
     __call__ = forward
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_spectral_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Resampler:
+class Resampler(_Handle):
     """maa_resampler handle: torchaudio.transforms.Resample(orig, new) with its default sinc / Hann kernel bank
     (kernels [new/g, 2 width + orig/g], built on the host by audiogpt_amd/clap.sinc_resample_kernel), exact fp32."""
 
+    _destroy = "maa_resampler_destroy"
+
     def __init__(self, ctx, orig, new, width, kernels):
-        self.ctx = ctx
         kt, kp = L.host_f32(torch.as_tensor(kernels))
         self.orig, self.new, self.width = int(orig), int(new), int(width)
         if kt.dim() != 2 or kt.shape[0] != self.new or kt.shape[1] != 2 * width + self.orig:
             raise L.MaaError("Resampler: kernel bank %s must be [new, 2 width + orig]" % (tuple(kt.shape),))
-        h = C.c_void_p()
-        with ctx.lock:
-            L.check(ctx.lib.maa_resampler_create(ctx.h, self.orig, self.new, int(width), kt.shape[1], kp, C.byref(h)))
-        self.h = h
+        self._create(ctx, "maa_resampler_create", self.orig, self.new, int(width), kt.shape[1], kp)
 
     def forward(self, wav):
         x = _f32(wav, self.ctx.device)
         if x.dim() == 1:
             x = x[None]
         B, n = x.shape
-        out = torch.empty(B, -(-self.new * n // self.orig), dtype=torch.float32, device=self.ctx.device)
-        with self.ctx.lock:
-            L.check(self.ctx.lib.maa_resampler_forward(self.ctx.h, self.h, L.dptr(x), B, n, L.dptr(out)))
+        out = self._empty(B, -(-self.new * n // self.orig), dtype=torch.float32)
+        self._call("maa_resampler_forward", L.dptr(x), B, n, L.dptr(out))
         return out
 
     __call__ = forward
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.maa_resampler_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,5 +1,9 @@
 // extern "C" surface of libaudiogpt_mi355x (include/maa.h): argument checking, handle ownership and the
 // exception -> status translation.  No C++ type or exception crosses this file's boundary.
+//
+// Every entry runs in one order: the argument and configuration checks that touch no device, then bind(ctx), then the work.  A
+// malformed call so fails the same way with or without a device, and the checks can be tested without one.  Only a check that
+// needs the context's or a model's state comes after bind.  A model handle is made by create_handle and freed by destroy_handle.
 #include "models.h"
 
 #include <cstdint>
@@ -14,39 +18,23 @@ struct maa_ctx {
     maa::Ctx c;
     bool owns_stream = false;
 };
-struct maa_unet {
-    std::unique_ptr<maa::UNet> m;
+// the opaque handles of maa.h: each owns one model executor
+template <class M>
+struct Handle {
+    using Model = M;
+    std::unique_ptr<M> m;
 };
-struct maa_vae {
-    std::unique_ptr<maa::VAE> m;
-};
-struct maa_vocoder {
-    std::unique_ptr<maa::Vocoder> m;
-};
-struct maa_diffnet {
-    std::unique_ptr<maa::DiffNet> m;
-};
-struct maa_pitch_extractor {
-    std::unique_ptr<maa::PitchExtractor> m;
-};
-struct maa_fs2 {
-    std::unique_ptr<maa::FastSpeech2MIDI> m;
-};
-struct maa_fs2_pitch {
-    std::unique_ptr<maa::FS2Pitch> m;
-};
-struct maa_encoder {
-    std::unique_ptr<maa::Encoder> m;
-};
-struct maa_clap_audio {
-    std::unique_ptr<maa::ClapAudio> m;
-};
-struct maa_spectral {
-    std::unique_ptr<maa::Spectral> m;
-};
-struct maa_resampler {
-    std::unique_ptr<maa::Resampler> m;
-};
+struct maa_unet : Handle<maa::UNet> {};
+struct maa_vae : Handle<maa::VAE> {};
+struct maa_vocoder : Handle<maa::Vocoder> {};
+struct maa_diffnet : Handle<maa::DiffNet> {};
+struct maa_pitch_extractor : Handle<maa::PitchExtractor> {};
+struct maa_fs2 : Handle<maa::FastSpeech2MIDI> {};
+struct maa_fs2_pitch : Handle<maa::FS2Pitch> {};
+struct maa_encoder : Handle<maa::Encoder> {};
+struct maa_clap_audio : Handle<maa::ClapAudio> {};
+struct maa_spectral : Handle<maa::Spectral> {};
+struct maa_resampler : Handle<maa::Resampler> {};
 
 namespace {
 
@@ -85,6 +73,19 @@ maa::StateDict to_state_dict(const maa_tensor* tensors, int n) {
 void bind(maa_ctx* ctx) {
     MAA_CHECK(ctx != nullptr, "null context");
     MAA_HIP(hipSetDevice(ctx->c.device));
+}
+
+// The handle lifecycle of every model: the executor is constructed into a handle that a unique_ptr owns, and the caller's
+// *out receives it only when nothing threw, so a constructor that throws leaves nothing behind.
+template <class H, class... Args>
+void create_handle(H** out, Args&&... args) {
+    auto h = std::make_unique<H>();
+    h->m = std::make_unique<typename H::Model>(std::forward<Args>(args)...);
+    *out = h.release();
+}
+template <class H>
+int destroy_handle(H* h) {
+    return guarded([&] { delete h; });
 }
 
 // single-tensor state dict helpers for the operator entry points
@@ -171,8 +172,8 @@ int maa_ctx_synchronize(maa_ctx* ctx) {
 }
 int maa_ctx_set_stream(maa_ctx* ctx, void* hip_stream) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(hip_stream != nullptr, "set_stream needs a non-default stream");
+        bind(ctx);
         if (ctx->owns_stream) (void)hipStreamDestroy(ctx->c.stream);
         ctx->owns_stream = false;
         ctx->c.stream = static_cast<hipStream_t>(hip_stream);
@@ -180,7 +181,8 @@ int maa_ctx_set_stream(maa_ctx* ctx, void* hip_stream) {
 }
 int maa_ctx_workspace_bytes(maa_ctx* ctx, size_t* out) {
     return guarded([&] {
-        MAA_CHECK(ctx && out, "null argument");
+        MAA_CHECK(out != nullptr, "null argument");
+        bind(ctx);
         // the second CFG lane (ddim.cpp) owns a workspace of its own, about half a batch's UNet arena, which is kept once it exists
         *out = ctx->c.ws.capacity() + (ctx->c.side ? ctx->c.side->ws.capacity() : 0);
     });
@@ -188,24 +190,24 @@ int maa_ctx_workspace_bytes(maa_ctx* ctx, size_t* out) {
 
 int maa_ctx_set_concurrency(maa_ctx* ctx, int n) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(n >= -1 && n != 0, "concurrency: -1 (guess from the live contexts) or the number of contexts kept in flight (>= 1)");
+        bind(ctx);
         if (ctx->c.kept_full() != (n >= 3)) ctx->c.drop_step_graphs();      // captured under the other arrangement's launches
         ctx->c.concurrency = n;
     });
 }
 int maa_ctx_set_cfg_split(maa_ctx* ctx, int mode) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(mode >= -1 && mode <= 1, "cfg_split: -1 (default policy), 0 (one stream) or 1 (two lanes)");
+        bind(ctx);
         ctx->c.cfg_split = mode;
     });
 }
 
 int maa_ctx_set_precision(maa_ctx* ctx, int mode) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(mode >= 0 && mode <= 2, "precision mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
+        bind(ctx);
         ctx->c.dtype = mode;
     });
 }
@@ -225,8 +227,9 @@ int maa_prof_begin(maa_ctx* ctx, int detail) {
 }
 int maa_prof_end(maa_ctx* ctx, maa_prof_row* rows, int max_rows, int* n_rows) {
     return guarded([&] {
+        MAA_CHECK(rows && n_rows && max_rows > 0, "prof_end without prof_begin / null output");
         bind(ctx);
-        MAA_CHECK(ctx->c.prof && rows && n_rows && max_rows > 0, "prof_end without prof_begin / null output");
+        MAA_CHECK(ctx->c.prof, "prof_end without prof_begin / null output");
         auto agg = ctx->c.prof->collect(ctx->c.stream);
         delete ctx->c.prof;
         ctx->c.prof = nullptr;
@@ -266,36 +269,31 @@ int maa_prof_end(maa_ctx* ctx, maa_prof_row* rows, int max_rows, int* n_rows) {
 int maa_unet_create(maa_ctx* ctx, const maa_unet_config* cfg, const maa_tensor* tensors, int n_tensors,
                     maa_unet** out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(cfg && out, "null argument");
         MAA_CHECK(cfg->n_channel_mult > 0 && cfg->n_channel_mult <= 8 && cfg->model_channels % 32 == 0,
                   "unsupported UNet config");
         auto sd = to_state_dict(tensors, n_tensors);
-        auto* u = new maa_unet;
-        u->m.reset(new maa::UNet(*cfg, sd, ctx->c.dtype));
-        *out = u;
+        bind(ctx);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
     });
 }
-int maa_unet_destroy(maa_unet* u) {
-    return guarded([&] { delete u; });
-}
+int maa_unet_destroy(maa_unet* u) { return destroy_handle(u); }
 int maa_unet_set_context(maa_ctx* ctx, maa_unet* u, const float* d_context, int B, int L) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(u && d_context && B > 0 && L > 0, "bad set_context arguments");
+        bind(ctx);
         u->m->set_context(ctx->c, d_context, B, L);
     });
 }
 int maa_unet_forward(maa_ctx* ctx, maa_unet* u, const float* d_x, const float* d_t, int B, int H, int W,
                      float* d_out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(u && d_x && d_t && d_out && B > 0 && H > 0 && W > 0, "bad forward arguments");
+        bind(ctx);
         u->m->forward(ctx->c, d_x, d_t, u->m->context_ptr, B, H, W, d_out);
     });
 }
 
-// (the arguments are checked before the context is bound: a malformed call fails the same way with or without a device)
 int maa_unet_forward_split(maa_ctx* ctx, maa_unet* u, const float* d_x, const float* d_t, const float* d_context, int B, int H, int W,
                            int kh, int kw, int sh, int sw, const float* h_weight, float* d_out) {
     return guarded([&] {
@@ -310,19 +308,18 @@ int maa_unet_forward_split(maa_ctx* ctx, maa_unet* u, const float* d_x, const fl
 int maa_ddim_update(maa_ctx* ctx, const float* d_x, const float* d_eps_uncond, const float* d_eps_cond, float scale,
                     const float* d_coef, int64_t n, float* d_x_prev, float* d_pred_x0) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_x && d_eps_uncond && d_coef && d_x_prev && n > 0, "bad ddim_update arguments");
+        bind(ctx);
         maa::launch_ddim_update(ctx->c, d_x, d_eps_uncond, d_eps_cond, scale, d_coef, n, d_x_prev, d_pred_x0);
     });
 }
 int maa_ddim_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, float* d_x) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(u && args && d_x && args->h_timesteps && args->h_alphas && args->h_alphas_prev, "bad ddim_sample arguments");
+        bind(ctx);
         maa::ddim_sample(ctx->c, *u->m, *args, d_x);
     });
 }
-// (the arguments are checked before the context is bound: a malformed call fails the same way with or without a device)
 int maa_ddim_stochastic_encode(maa_ctx* ctx, const float* d_x0_or_moments, int from_moments, float scale_factor,
                                const float* d_noise_post, const int32_t* d_t, const float* h_sqrt_a, const float* h_sqrt_1ma, int n_tab,
                                const float* d_noise, int B, int C, int H, int W, float* d_out) {
@@ -348,7 +345,6 @@ int maa_ldm_plms_sample(maa_ctx* ctx, maa_unet* u, const maa_ddim_args* args, fl
         maa::ldm_plms_sample(ctx->c, *u->m, *args, d_x);
     });
 }
-// (as above: every argument error is reported before the context is bound and anything is launched)
 int maa_ddpm_sample(maa_ctx* ctx, maa_unet* u, const maa_ddpm_args* args, float* d_x) {
     return guarded([&] {
         maa::check_ddpm_sample_args(u, args, d_x);
@@ -372,35 +368,31 @@ int maa_ddpm_update(maa_ctx* ctx, const float* d_x, const float* d_eps, const in
 // ------------------------------------------------------------------------------------------ VAE
 int maa_vae_create(maa_ctx* ctx, const maa_vae_config* cfg, const maa_tensor* tensors, int n_tensors, maa_vae** out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(cfg && out && cfg->n_ch_mult > 0 && cfg->n_ch_mult <= 8, "bad VAE config");
         auto sd = to_state_dict(tensors, n_tensors);
-        auto* v = new maa_vae;
-        v->m.reset(new maa::VAE(*cfg, sd, ctx->c.dtype));
-        *out = v;
+        bind(ctx);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
     });
 }
-int maa_vae_destroy(maa_vae* v) {
-    return guarded([&] { delete v; });
-}
+int maa_vae_destroy(maa_vae* v) { return destroy_handle(v); }
 int maa_vae_decode(maa_ctx* ctx, maa_vae* v, const float* d_z, int B, int h, int w, float inv_scale, float* d_mel) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(v && d_z && d_mel && B > 0 && h > 0 && w > 0, "bad vae_decode arguments");
+        bind(ctx);
         v->m->decode(ctx->c, d_z, B, h, w, inv_scale, d_mel);
     });
 }
 int maa_vae_decode_spec(maa_ctx* ctx, maa_vae* v, const float* d_z, int B, int h, int w, float inv_scale, float* d_spec) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(v && d_z && d_spec && B > 0 && h > 0 && w > 0, "bad vae_decode_spec arguments");
+        bind(ctx);
         v->m->decode_spec(ctx->c, d_z, B, h, w, inv_scale, d_spec);
     });
 }
 int maa_vae_encode_moments(maa_ctx* ctx, maa_vae* v, const float* d_mel, int B, int H, int W, float* d_moments) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(v && d_mel && d_moments && B > 0 && H > 0 && W > 0, "bad vae_encode arguments");
+        bind(ctx);
         v->m->encode_moments(ctx->c, d_mel, B, H, W, d_moments);
     });
 }
@@ -412,30 +404,26 @@ int maa_vocoder_create(maa_ctx* ctx, const maa_vocoder_config* cfg, const maa_te
         MAA_CHECK(cfg && out && cfg->n_upsamples > 0 && cfg->n_upsamples <= 8 && cfg->n_kernels > 0 &&
                       cfg->n_kernels <= 8 && cfg->n_dilations > 0 && cfg->n_dilations <= 8,
                   "bad vocoder config");
-        // (the generator's build refuses these too; here a config it cannot run is refused before the device is touched)
+        // (the generator's build refuses these too)
         for (int i = 0; i < cfg->n_upsamples; ++i) maa::check_convtr_polyphase(cfg->upsample_kernel_sizes[i], cfg->upsample_rates[i]);
-        bind(ctx);
         auto sd = to_state_dict(tensors, n_tensors);
-        auto* v = new maa_vocoder;
-        v->m.reset(new maa::Vocoder(*cfg, sd, ctx->c.dtype));
-        *out = v;
+        bind(ctx);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
     });
 }
-int maa_vocoder_destroy(maa_vocoder* v) {
-    return guarded([&] { delete v; });
-}
+int maa_vocoder_destroy(maa_vocoder* v) { return destroy_handle(v); }
 int maa_vocoder_forward(maa_ctx* ctx, maa_vocoder* v, const float* d_mel, int B, int T, float* d_wav) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(v && d_mel && d_wav && B > 0 && T > 0, "bad vocoder_forward arguments");
+        bind(ctx);
         v->m->forward(ctx->c, d_mel, B, T, d_wav);
     });
 }
 int maa_vocoder_forward_f0(maa_ctx* ctx, maa_vocoder* v, const float* d_mel, const float* d_f0, const float* d_rand_ini,
                            const float* d_noise, int B, int T, float* d_wav) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(v && d_mel && d_f0 && d_rand_ini && d_noise && d_wav && B > 0 && T > 0, "bad vocoder_forward_f0 arguments");
+        bind(ctx);
         v->m->forward_f0(ctx->c, d_mel, d_f0, d_rand_ini, d_noise, B, T, d_wav);
     });
 }
@@ -445,38 +433,34 @@ int maa_vocoder_forward_f0(maa_ctx* ctx, maa_vocoder* v, const float* d_mel, con
 int maa_diffnet_create(maa_ctx* ctx, const maa_diffnet_config* cfg, const maa_tensor* tensors, int n_tensors,
                        maa_diffnet** out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(cfg && out && cfg->in_dims > 0 && cfg->hidden_size > 0 && cfg->residual_layers > 0 &&
                       cfg->residual_channels > 0 && cfg->residual_channels % 2 == 0 && cfg->dilation_cycle_length > 0,
                   "bad DiffNet config");
         auto sd = to_state_dict(tensors, n_tensors);
-        auto* d = new maa_diffnet;
-        d->m.reset(new maa::DiffNet(*cfg, sd, ctx->c.dtype));
-        *out = d;
+        bind(ctx);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
     });
 }
-int maa_diffnet_destroy(maa_diffnet* d) {
-    return guarded([&] { delete d; });
-}
+int maa_diffnet_destroy(maa_diffnet* d) { return destroy_handle(d); }
 int maa_diffnet_forward(maa_ctx* ctx, maa_diffnet* d, const float* d_spec, const float* d_t, const float* d_cond, int B,
                         int T, float* d_eps) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d && d_spec && d_t && d_cond && d_eps && B > 0 && T > 0, "bad diffnet_forward arguments");
+        bind(ctx);
         d->m->forward(ctx->c, d_spec, d_t, d_cond, B, T, d_eps);
     });
 }
 int maa_plms_sample(maa_ctx* ctx, maa_diffnet* d, const maa_plms_args* args, float* d_x) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d && args && d_x, "bad plms_sample arguments");
+        bind(ctx);
         d->m->plms_sample(ctx->c, *args, d_x);
     });
 }
 int maa_ds_ddpm_sample(maa_ctx* ctx, maa_diffnet* d, const maa_ds_ddpm_args* args, float* d_x) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d && args && d_x, "bad ds_ddpm_sample arguments: null pointer");
+        bind(ctx);
         d->m->ddpm_sample(ctx->c, *args, d_x);
     });
 }
@@ -484,11 +468,11 @@ int maa_ds_ddpm_update(maa_ctx* ctx, const float* d_eps, const float* d_t, const
                        const float* h_sqrt_recipm1_ac, const float* h_coef1, const float* h_coef2, const float* h_sigma,
                        int timesteps, int B, int M, int T, int clip_denoised, float* d_x) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_eps && d_t && d_noise && d_x, "bad ds_ddpm_update arguments: null pointer");
         MAA_CHECK(h_sqrt_recip_ac && h_sqrt_recipm1_ac && h_coef1 && h_coef2 && h_sigma,
                   "bad ds_ddpm_update arguments: the posterior tables are missing");
         MAA_CHECK(d_x != d_eps && d_x != d_noise, "bad ds_ddpm_update arguments: d_x is updated in place and may not alias the inputs");
+        bind(ctx);
         maa::ds_ddpm_update(ctx->c, d_eps, d_t, d_noise, h_sqrt_recip_ac, h_sqrt_recipm1_ac, h_coef1, h_coef2, h_sigma, timesteps,
                             B, M, T, clip_denoised != 0, d_x);
     });
@@ -499,7 +483,6 @@ int maa_pitch_extractor_create(maa_ctx* ctx, const maa_pitch_extractor_config* c
                                maa_pitch_extractor** out) {
     return guarded([&] {
         MAA_CHECK(cfg && out, "bad pitch_extractor_create arguments: null pointer");
-        // (a configuration that cannot run is refused before the device is touched)
         MAA_CHECK(cfg->ffn_padding_same != 0,
                   "PitchExtractor: hparams['ffn_padding'] must be 'SAME' -- the causal 'LEFT' padding (kernel - 1, 0) is not built");
         MAA_CHECK(cfg->n_mel_bins > 0 && cfg->n_mel_bins % 4 == 0 && cfg->hidden_size >= 16 && cfg->hidden_size % 16 == 0 &&
@@ -511,27 +494,18 @@ int maa_pitch_extractor_create(maa_ctx* ctx, const maa_pitch_extractor_config* c
         MAA_CHECK(cfg->predictor_kernel >= 1 && cfg->predictor_kernel % 2 == 1,
                   "bad PitchExtractor config: predictor_kernel must be odd ('SAME' padding keeps the length only then)");
         MAA_CHECK(cfg->pitch_norm == 0 || cfg->pitch_norm == 1, "bad PitchExtractor config: pitch_norm is 0 ('log') or 1 ('standard')");
-        bind(ctx);
         auto sd = to_state_dict(tensors, n_tensors);
-        auto* p = new maa_pitch_extractor;
-        try {
-            p->m.reset(new maa::PitchExtractor(*cfg, sd, ctx->c.dtype));
-        } catch (...) {
-            delete p;
-            throw;
-        }
-        *out = p;
+        bind(ctx);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
     });
 }
-int maa_pitch_extractor_destroy(maa_pitch_extractor* pe) {
-    return guarded([&] { delete pe; });
-}
+int maa_pitch_extractor_destroy(maa_pitch_extractor* pe) { return destroy_handle(pe); }
 int maa_pitch_extractor_forward(maa_ctx* ctx, maa_pitch_extractor* pe, const float* d_mel, int B, int T, float* d_pitch_pred,
                                 float* d_f0, float* d_mel_hidden) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(pe && d_mel && d_pitch_pred && d_f0, "bad pitch_extractor_forward arguments: null pointer");
         MAA_CHECK(B > 0 && T > 0 && (long long)B * T < (1LL << 31) / 1024, "bad pitch_extractor_forward arguments: B, T");
+        bind(ctx);
         pe->m->forward(ctx->c, d_mel, B, T, d_pitch_pred, d_f0, d_mel_hidden);
     });
 }
@@ -540,7 +514,6 @@ int maa_pitch_extractor_forward(maa_ctx* ctx, maa_pitch_extractor* pe, const flo
 int maa_fs2_create(maa_ctx* ctx, const maa_fs2_config* cfg, const maa_tensor* tensors, int n_tensors, maa_fs2** out) {
     return guarded([&] {
         MAA_CHECK(cfg && out, "bad fs2_create arguments: null pointer");
-        // (a configuration that cannot run is refused before the device is touched)
         MAA_CHECK(!cfg->use_pitch_embed, "FastSpeech2MIDI: hparams['use_pitch_embed'] is not built into this handle -- the pitch branch is maa_fs2_pitch, beside it");
         MAA_CHECK(!cfg->use_energy_embed, "FastSpeech2MIDI: hparams['use_energy_embed'] is not built -- no shipped e2e singing configuration sets it");
         MAA_CHECK(!cfg->use_spk_id && !cfg->use_spk_embed,
@@ -563,25 +536,16 @@ int maa_fs2_create(maa_ctx* ctx, const maa_fs2_config* cfg, const maa_tensor* te
                   "bad FastSpeech2MIDI config: the FFN and predictor kernels must be odd ('SAME' padding keeps the length only then)");
         MAA_CHECK(cfg->dur_predictor_layers >= 1 && cfg->predictor_hidden <= 1024 && (cfg->predictor_hidden <= 0 || cfg->predictor_hidden % 4 == 0),
                   "bad FastSpeech2MIDI config: dur_predictor_layers >= 1, predictor_hidden a multiple of 4 (or <= 0 for hidden_size), at most 1024");
-        bind(ctx);
         auto sd = to_state_dict(tensors, n_tensors);
-        auto* p = new maa_fs2;
-        try {
-            p->m.reset(new maa::FastSpeech2MIDI(*cfg, sd, ctx->c.dtype));
-        } catch (...) {
-            delete p;
-            throw;
-        }
-        *out = p;
+        bind(ctx);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
     });
 }
-int maa_fs2_destroy(maa_fs2* fs2) {
-    return guarded([&] { delete fs2; });
-}
+int maa_fs2_destroy(maa_fs2* fs2) { return destroy_handle(fs2); }
 int maa_fs2_encode(maa_ctx* ctx, maa_fs2* fs2, const int* d_tokens, const int* d_pitch_midi, const float* d_midi_dur,
                    const int* d_is_slur, int B, int T, float* d_encoder_out, float* d_xs, int* d_dur, int* d_totals) {
     return guarded([&] {
-        MAA_CHECK(ctx && fs2 && d_tokens && d_pitch_midi && d_encoder_out && d_xs && d_dur && d_totals, "bad fs2_encode arguments: null pointer");
+        MAA_CHECK(fs2 && d_tokens&& d_pitch_midi && d_encoder_out && d_xs && d_dur && d_totals, "bad fs2_encode arguments: null pointer");
         MAA_CHECK(B > 0 && T > 0 && (long long)B * T < (1LL << 31) / 4096, "bad fs2_encode arguments: B, T");
         bind(ctx);
         fs2->m->encode(ctx->c, d_tokens, d_pitch_midi, d_midi_dur, d_is_slur, B, T, d_encoder_out, d_xs, d_dur, d_totals);
@@ -589,7 +553,7 @@ int maa_fs2_encode(maa_ctx* ctx, maa_fs2* fs2, const int* d_tokens, const int* d
 }
 int maa_fs2_length_regulate(maa_ctx* ctx, maa_fs2* fs2, const int* d_dur, int B, int T, int T_mel, int* d_mel2ph) {
     return guarded([&] {
-        MAA_CHECK(ctx && fs2 && d_dur && d_mel2ph, "bad fs2_length_regulate arguments: null pointer");
+        MAA_CHECK(fs2 && d_dur&& d_mel2ph, "bad fs2_length_regulate arguments: null pointer");
         MAA_CHECK(B > 0 && T > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_length_regulate arguments: B, T, T_mel");
         bind(ctx);
         fs2->m->length_regulate(ctx->c, d_dur, B, T, T_mel, d_mel2ph);
@@ -598,7 +562,7 @@ int maa_fs2_length_regulate(maa_ctx* ctx, maa_fs2* fs2, const int* d_dur, int B,
 int maa_fs2_decode(maa_ctx* ctx, maa_fs2* fs2, const float* d_encoder_out, const int* d_mel2ph, int B, int T, int T_mel,
                    float* d_decoder_inp, float* d_mel_out) {
     return guarded([&] {
-        MAA_CHECK(ctx && fs2 && d_encoder_out && d_mel2ph && d_decoder_inp, "bad fs2_decode arguments: null pointer");
+        MAA_CHECK(fs2 && d_encoder_out&& d_mel2ph && d_decoder_inp, "bad fs2_decode arguments: null pointer");
         MAA_CHECK(B > 0 && T > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_decode arguments: B, T, T_mel");
         bind(ctx);
         fs2->m->decode(ctx->c, d_encoder_out, d_mel2ph, B, T, T_mel, d_decoder_inp, d_mel_out);
@@ -606,7 +570,7 @@ int maa_fs2_decode(maa_ctx* ctx, maa_fs2* fs2, const float* d_encoder_out, const
 }
 int maa_fs2_run_decoder(maa_ctx* ctx, maa_fs2* fs2, const float* d_decoder_inp, const int* d_mel2ph, int B, int T_mel, float* d_mel_out) {
     return guarded([&] {
-        MAA_CHECK(ctx && fs2 && d_decoder_inp && d_mel2ph && d_mel_out, "bad fs2_run_decoder arguments: null pointer");
+        MAA_CHECK(fs2 && d_decoder_inp&& d_mel2ph && d_mel_out, "bad fs2_run_decoder arguments: null pointer");
         MAA_CHECK(B > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_run_decoder arguments: B, T_mel");
         bind(ctx);
         fs2->m->run_decoder(ctx->c, d_decoder_inp, d_mel2ph, B, T_mel, d_mel_out);
@@ -617,7 +581,6 @@ int maa_fs2_run_decoder(maa_ctx* ctx, maa_fs2* fs2, const float* d_decoder_inp, 
 int maa_fs2_pitch_create(maa_ctx* ctx, const maa_fs2_pitch_config* cfg, const maa_tensor* tensors, int n_tensors, maa_fs2_pitch** out) {
     return guarded([&] {
         MAA_CHECK(cfg && out, "bad fs2_pitch_create arguments: null pointer");
-        // (a configuration that cannot run is refused before the device is touched)
         MAA_CHECK(cfg->pitch_type_frame != 0,
                   "FastSpeech2MIDI pitch: hparams['pitch_type'] must be 'frame' -- 'ph' is not built, and 'cwt' reads cwt_predictor / "
                   "cwt_stats_layers, which the reference's FastSpeech2 never creates");
@@ -630,25 +593,16 @@ int maa_fs2_pitch_create(maa_ctx* ctx, const maa_fs2_pitch_config* cfg, const ma
                   "bad FastSpeech2MIDI pitch config: hidden_size and predictor_hidden (<= 0 for hidden_size) multiples of 4, at most 1024");
         MAA_CHECK(cfg->predictor_layers >= 1 && cfg->predictor_kernel >= 1 && cfg->predictor_kernel % 2 == 1,
                   "bad FastSpeech2MIDI pitch config: predictor_layers >= 1, predictor_kernel odd ('SAME' padding keeps the length only then)");
-        bind(ctx);
         auto sd = to_state_dict(tensors, n_tensors);
-        auto* p = new maa_fs2_pitch;
-        try {
-            p->m.reset(new maa::FS2Pitch(*cfg, sd, ctx->c.dtype));
-        } catch (...) {
-            delete p;
-            throw;
-        }
-        *out = p;
+        bind(ctx);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
     });
 }
-int maa_fs2_pitch_destroy(maa_fs2_pitch* h) {
-    return guarded([&] { delete h; });
-}
+int maa_fs2_pitch_destroy(maa_fs2_pitch* h) { return destroy_handle(h); }
 int maa_fs2_pitch_forward(maa_ctx* ctx, maa_fs2_pitch* h, const float* d_origin, const int* d_mel2ph, const float* d_f0, const float* d_uv,
                           int B, int T_mel, float* d_decoder_inp, float* d_pitch_pred, float* d_f0_denorm, int* d_coarse) {
     return guarded([&] {
-        MAA_CHECK(ctx && h && d_origin && d_mel2ph && d_decoder_inp && d_pitch_pred && d_f0_denorm, "bad fs2_pitch_forward arguments: null pointer");
+        MAA_CHECK(h && d_origin&& d_mel2ph && d_decoder_inp && d_pitch_pred && d_f0_denorm, "bad fs2_pitch_forward arguments: null pointer");
         MAA_CHECK(B > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_pitch_forward arguments: B, T_mel");
         MAA_CHECK(d_decoder_inp != d_origin, "bad fs2_pitch_forward arguments: d_decoder_inp may not alias d_origin");
         bind(ctx);
@@ -660,7 +614,6 @@ int maa_fs2_pitch_forward(maa_ctx* ctx, maa_fs2_pitch* h, const float* d_origin,
 int maa_encoder_create(maa_ctx* ctx, const maa_encoder_config* cfg, const maa_tensor* tensors, int n_tensors,
                        maa_encoder** out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(cfg && out && cfg->kind >= 0 && cfg->kind <= 2 && cfg->layers > 0 && cfg->width > 0 && cfg->heads > 0 &&
                       cfg->width % cfg->heads == 0 && cfg->width % 4 == 0 && cfg->mlp_dim > 0 && cfg->d_proj > 0 &&
                       cfg->d_proj % 4 == 0 && cfg->ln_eps > 0.f,
@@ -670,33 +623,30 @@ int maa_encoder_create(maa_ctx* ctx, const maa_encoder_config* cfg, const maa_te
         else
             MAA_CHECK(cfg->patch > 0 && cfg->image > 0 && cfg->image % cfg->patch == 0, "bad image encoder config");
         auto sd = to_state_dict(tensors, n_tensors);
-        auto* e = new maa_encoder;
-        e->m.reset(new maa::Encoder(*cfg, sd, ctx->c.dtype));
-        *out = e;
+        bind(ctx);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
     });
 }
-int maa_encoder_destroy(maa_encoder* e) {
-    return guarded([&] { delete e; });
-}
+int maa_encoder_destroy(maa_encoder* e) { return destroy_handle(e); }
 int maa_encoder_text(maa_ctx* ctx, maa_encoder* e, const int* d_ids, int B, int L, float* d_out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(e && d_ids && d_out && B > 0 && L > 0, "bad encoder_text arguments");
+        bind(ctx);
         e->m->text(ctx->c, d_ids, B, L, d_out);
     });
 }
 int maa_encoder_image(maa_ctx* ctx, maa_encoder* e, const float* d_img, int B, float* d_out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(e && d_img && d_out && B > 0, "bad encoder_image arguments");
+        bind(ctx);
         e->m->image(ctx->c, d_img, B, d_out);
     });
 }
 
 int maa_encoder_text_cls(maa_ctx* ctx, maa_encoder* e, const int* d_ids, int B, int L, float* d_out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(e && d_ids && d_out && B > 0 && L > 0, "bad encoder_text_cls arguments");
+        bind(ctx);
         e->m->text_cls(ctx->c, d_ids, B, L, d_out);
     });
 }
@@ -704,33 +654,29 @@ int maa_encoder_text_cls(maa_ctx* ctx, maa_encoder* e, const int* d_ids, int B, 
 int maa_clap_audio_create(maa_ctx* ctx, const maa_clap_audio_config* cfg, const maa_tensor* tensors, int n_tensors,
                           maa_clap_audio** out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(cfg && out && cfg->mel_bins > 0 && cfg->n_blocks > 0 && cfg->n_blocks <= 8 && cfg->out_emb > 0 &&
                       cfg->d_proj > 0 && cfg->d_proj % 4 == 0 && cfg->bn_eps > 0.f,
                   "bad clap_audio config");
         for (int i = 0; i < cfg->n_blocks; ++i) MAA_CHECK(cfg->channels[i] > 0, "bad clap_audio channel list");
         auto sd = to_state_dict(tensors, n_tensors);
-        auto* a = new maa_clap_audio;
-        a->m.reset(new maa::ClapAudio(*cfg, sd, ctx->c.dtype));
-        *out = a;
+        bind(ctx);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
     });
 }
-int maa_clap_audio_destroy(maa_clap_audio* a) {
-    return guarded([&] { delete a; });
-}
+int maa_clap_audio_destroy(maa_clap_audio* a) { return destroy_handle(a); }
 int maa_clap_audio_embed(maa_ctx* ctx, maa_clap_audio* a, const float* d_logmel, int B, int T, float* d_embedding,
                          float* d_z) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(a && d_logmel && d_z && B > 0 && T > 0, "bad clap_audio_embed arguments");
+        bind(ctx);
         a->m->embed(ctx->c, d_logmel, B, T, d_embedding, d_z);
     });
 }
 int maa_clap_similarity(maa_ctx* ctx, const float* d_audio, const float* d_text, int Na, int Nt, int D, float scale,
                         float* d_out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_audio && d_text && d_out && Na > 0 && Nt > 0 && D > 0, "bad clap_similarity arguments");
+        bind(ctx);
         maa::launch_similarity(ctx->c, d_audio, d_text, Na, Nt, D, scale, d_out);
     });
 }
@@ -738,24 +684,20 @@ int maa_clap_similarity(maa_ctx* ctx, const float* d_audio, const float* d_text,
 int maa_spectral_create(maa_ctx* ctx, const maa_spectral_config* cfg, const float* h_basis, const float* h_melw,
                         maa_spectral** out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(cfg && h_basis && h_melw && out, "bad spectral arguments");
         MAA_CHECK(cfg->n_fft > 0 && cfg->n_fft % 4 == 0 && cfg->hop > 0 && cfg->hop % 4 == 0 && cfg->n_freq == cfg->n_fft / 2 + 1 &&
                       cfg->n_mels > 0 && (cfg->pad_mode == 0 || cfg->pad_mode == 1) && (cfg->power == 1 || cfg->power == 2) &&
                       (cfg->log_kind == 0 || cfg->log_kind == 1) && cfg->amin > 0.f && (cfg->out_layout == 0 || cfg->out_layout == 1),
                   "bad spectral config (n_fft and hop must be multiples of 4)");
-        auto* s = new maa_spectral;
-        s->m.reset(new maa::Spectral(*cfg, h_basis, h_melw));
-        *out = s;
+        bind(ctx);
+        create_handle(out, *cfg, h_basis, h_melw);
     });
 }
-int maa_spectral_destroy(maa_spectral* s) {
-    return guarded([&] { delete s; });
-}
+int maa_spectral_destroy(maa_spectral* s) { return destroy_handle(s); }
 int maa_spectral_forward(maa_ctx* ctx, maa_spectral* s, const float* d_wav, int B, int n, float* d_out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(s && d_wav && d_out && B > 0 && n > 0, "bad spectral_forward arguments");
+        bind(ctx);
         MAA_CHECK(s->m->config().pad_mode == 0 || n > s->m->config().n_fft / 2, "signal too short for reflect padding");
         s->m->forward(ctx->c, d_wav, B, n, d_out);
     });
@@ -763,20 +705,16 @@ int maa_spectral_forward(maa_ctx* ctx, maa_spectral* s, const float* d_wav, int 
 
 int maa_resampler_create(maa_ctx* ctx, int orig, int neu, int width, int klen, const float* h_kernels, maa_resampler** out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(out && h_kernels && orig > 0 && neu > 0 && width > 0 && klen > 0, "bad resampler arguments");
-        auto* r = new maa_resampler;
-        r->m.reset(new maa::Resampler(orig, neu, width, klen, h_kernels));
-        *out = r;
+        bind(ctx);
+        create_handle(out, orig, neu, width, klen, h_kernels);
     });
 }
-int maa_resampler_destroy(maa_resampler* r) {
-    return guarded([&] { delete r; });
-}
+int maa_resampler_destroy(maa_resampler* r) { return destroy_handle(r); }
 int maa_resampler_forward(maa_ctx* ctx, maa_resampler* r, const float* d_wav, int B, int n, float* d_out) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(r && d_wav && d_out && B > 0 && n > 0, "bad resampler_forward arguments");
+        bind(ctx);
         r->m->forward(ctx->c, d_wav, B, n, d_out);
     });
 }
@@ -790,16 +728,16 @@ static bool op_presplit(const maa::Ctx& c, int channels, bool other_prologue) {
 int maa_op_linear(maa_ctx* ctx, const float* d_a, int M, int K, const float* h_w, const float* h_bias, int N,
                   int geglu, float* d_y, const float* d_res, int c_split) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_a && h_w && d_y && M > 0 && K > 0 && N > 0, "bad op_linear arguments");
         MAA_CHECK(!c_split || N % 32 == 0, "op_linear: split32 output needs a multiple of 32 columns");
         MAA_CHECK(!geglu || (!d_res && !c_split), "op_linear: GEGLU takes neither a residual nor split32 output here");
+        MAA_CHECK(!geglu || h_bias, "geglu needs a bias");
+        bind(ctx);
         OneShot s;
         s.add("w", h_w, {N, K});
         if (h_bias) s.add("b", h_bias, {N});
         maa::WeightStore ws(ctx->c.dtype != 0);
         maa::Ctx& c = ctx->c;
-        MAA_CHECK(!geglu || h_bias, "geglu needs a bias");
         maa::PackedW pw = geglu ? ws.pack_geglu(s.sd, "w", "b") : ws.pack_conv(s.sd, "w", h_bias ? "b" : "", 1, 1);
         const bool pre = op_presplit(c, K, false);
         maa::run_sized(c, [&] {
@@ -819,11 +757,11 @@ int maa_op_conv(maa_ctx* ctx, const float* d_x, int B, int Cin, int H, int W, co
                 int Cout, int KH, int KW, int stride, int pad, int dil, int upsample2, float leaky_slope, float* d_y,
                 int Ho, int Wo, const float* d_rowadd, const float* d_res, int c_split) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_x && h_w && d_y, "bad op_conv arguments");
         const bool extras = d_rowadd || d_res || c_split;
         MAA_CHECK(!extras || !upsample2, "op_conv: row add, residual and split32 output are not combined with the upsample");
         MAA_CHECK(!c_split || Cout % 32 == 0, "op_conv: split32 output needs a multiple of 32 channels");
+        bind(ctx);
         OneShot s;
         s.add("w", h_w, {Cout, Cin, KH, KW});
         if (h_bias) s.add("b", h_bias, {Cout});
@@ -880,7 +818,6 @@ int maa_op_conv(maa_ctx* ctx, const float* d_x, int B, int Cin, int H, int W, co
 
 int maa_op_igemm_ex(maa_ctx* ctx, const maa_igemm_ex_args* a) {
     return guarded([&] {
-        // (what does not need the device comes first: the argument checks can be tested without one)
         MAA_CHECK(a && a->d_x1 && a->h_w && a->d_c, "bad op_igemm_ex arguments: null pointer");
         MAA_CHECK(a->B > 0 && a->H > 0 && a->W > 0 && a->Ho > 0 && a->Wo > 0 && a->C1 > 0 && a->C2 >= 0 && a->Cout > 0 && a->KH > 0 &&
                       a->KW > 0 && a->stride > 0 && a->dil > 0 && a->pad_w >= 0 && a->pad_h >= -1,
@@ -965,8 +902,8 @@ int maa_op_igemm_ex(maa_ctx* ctx, const maa_igemm_ex_args* a) {
 
 int maa_calib(maa_ctx* ctx, int kind, double* out_value) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(out_value && kind >= 0 && kind <= 3, "bad calib arguments");
+        bind(ctx);
         *out_value = maa::calib_run(ctx->c, kind);
     });
 }
@@ -974,8 +911,8 @@ int maa_calib(maa_ctx* ctx, int kind, double* out_value) {
 int maa_op_groupnorm(maa_ctx* ctx, const float* d_x, int B, int C, int HW, const float* h_gamma, const float* h_beta,
                      float eps, int silu, float* d_y) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_x && h_gamma && h_beta && d_y, "bad op_groupnorm arguments");
+        bind(ctx);
         maa::WeightStore ws(ctx->c.dtype != 0);
         maa::Ctx& c = ctx->c;
         float* g = ws.upload(std::vector<float>(h_gamma, h_gamma + C));
@@ -993,8 +930,8 @@ int maa_op_groupnorm(maa_ctx* ctx, const float* d_x, int B, int C, int HW, const
 int maa_op_layernorm(maa_ctx* ctx, const float* d_x, int rows, int C, const float* h_gamma, const float* h_beta,
                      float eps, float* d_y) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_x && h_gamma && h_beta && d_y, "bad op_layernorm arguments");
+        bind(ctx);
         maa::WeightStore ws(ctx->c.dtype != 0);
         maa::Ctx& c = ctx->c;
         float* g = ws.upload(std::vector<float>(h_gamma, h_gamma + C));
@@ -1007,8 +944,8 @@ int maa_op_layernorm(maa_ctx* ctx, const float* d_x, int rows, int C, const floa
 int maa_op_attention(maa_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, int B, int heads, int dh,
                      int Nq, int Nk, float alpha, float* d_y) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_q && d_k && d_v && d_y, "bad op_attention arguments");
+        bind(ctx);
         maa::Ctx& c = ctx->c;
         const int C = heads * dh;
         maa::run_sized(c, [&] {
@@ -1022,11 +959,11 @@ int maa_op_attention_ex(maa_ctx* ctx, const float* d_q, int ldq, int hsq, const 
                         const float* d_v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
                         float* d_y, int ldo, int out_split, int causal) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_q && d_k && d_v && d_y, "bad op_attention_ex arguments");
         MAA_CHECK(B > 0 && heads > 0 && dh > 0 && Nq > 0 && Nk > 0, "bad op_attention_ex sizes");
         MAA_CHECK(ldq >= dh && ldk >= dh && ldv >= dh && hsq >= 0 && hsk >= 0 && hsv >= 0 && ldo >= heads * dh,
                   "bad op_attention_ex strides");
+        bind(ctx);
         maa::Ctx& c = ctx->c;
         maa::run_sized(c, [&] {
             maa::attention_into(c, d_q, ldq, hsq, d_k, ldk, hsk, d_v, ldv, hsv, B, heads, dh, Nq, Nk, alpha, d_y, ldo,
@@ -1040,7 +977,7 @@ int maa_op_attention_masked(maa_ctx* ctx, const float* d_q, int ldq, int hsq, co
                             const float* d_v, int ldv, int hsv, int B, int heads, int dh, int Nq, int Nk, float alpha,
                             float* d_y, int ldo, int out_split, int causal, const float* d_key_mask) {
     return guarded([&] {
-        MAA_CHECK(ctx && d_q && d_k && d_v && d_y && d_key_mask, "bad op_attention_masked arguments");
+        MAA_CHECK(d_q && d_k && d_v && d_y && d_key_mask, "bad op_attention_masked arguments");
         MAA_CHECK(B > 0 && heads > 0 && dh > 0 && Nq > 0 && Nk > 0, "bad op_attention_masked sizes");
         MAA_CHECK(ldq >= dh && ldk >= dh && ldv >= dh && hsq >= 0 && hsk >= 0 && hsv >= 0 && ldo >= heads * dh,
                   "bad op_attention_masked strides");
@@ -1058,7 +995,6 @@ int maa_op_groupnorm_ex(maa_ctx* ctx, const float* d_x1, int ld1, int C1, const 
                         int groups, const float* h_gamma, const float* h_beta, float eps, int silu, float* d_y, int out_split,
                         float* d_raw) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_x1 && h_gamma && h_beta && d_y, "bad op_groupnorm_ex arguments");
         MAA_CHECK(B > 0 && HW > 0 && groups > 0 && C1 > 0 && C2 >= 0 && eps > 0.f, "bad op_groupnorm_ex sizes");
         MAA_CHECK((C2 == 0) == (d_x2 == nullptr), "op_groupnorm_ex: a second source needs both d_x2 and C2");
@@ -1069,6 +1005,7 @@ int maa_op_groupnorm_ex(maa_ctx* ctx, const float* d_x1, int ld1, int C1, const 
         MAA_CHECK((!out_split && !d_raw) || C % 32 == 0, "op_groupnorm_ex: split32 rows are whole 32-channel lines");
         MAA_CHECK((reinterpret_cast<uintptr_t>(d_x1) | reinterpret_cast<uintptr_t>(d_x2) | reinterpret_cast<uintptr_t>(d_y) |
                    reinterpret_cast<uintptr_t>(d_raw)) % 16 == 0, "op_groupnorm_ex: buffers must be 16-byte aligned");
+        bind(ctx);
         maa::WeightStore ws(ctx->c.dtype != 0);
         maa::Ctx& c = ctx->c;
         float* g = ws.upload(std::vector<float>(h_gamma, h_gamma + C));
@@ -1083,10 +1020,10 @@ int maa_op_groupnorm_ex(maa_ctx* ctx, const float* d_x1, int ld1, int C1, const 
 int maa_op_layernorm_ex(maa_ctx* ctx, const float* d_x, int rows, int C, const float* h_gamma, const float* h_beta, float eps,
                         float* d_y, int out_split) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_x && h_gamma && h_beta && d_y, "bad op_layernorm_ex arguments");
         MAA_CHECK(rows > 0 && C > 0 && C % 4 == 0 && C <= 2048 && eps > 0.f, "bad op_layernorm_ex sizes");
         MAA_CHECK(!out_split || C % 32 == 0, "op_layernorm_ex: split32 rows are whole 32-channel lines");
+        bind(ctx);
         maa::WeightStore ws(ctx->c.dtype != 0);
         maa::Ctx& c = ctx->c;
         float* g = ws.upload(std::vector<float>(h_gamma, h_gamma + C));
@@ -1098,9 +1035,9 @@ int maa_op_layernorm_ex(maa_ctx* ctx, const float* d_x, int rows, int C, const f
 
 int maa_op_split32(maa_ctx* ctx, const float* d_x, int rows, int C, float slope, int unpack, float* d_y) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_x && d_y && d_x != d_y, "bad op_split32 arguments");
         MAA_CHECK(rows > 0 && C > 0 && C % 32 == 0, "op_split32: split32 rows are whole 32-channel lines");
+        bind(ctx);
         maa::Ctx& c = ctx->c;
         if (unpack)
             maa::launch_split32_unpack(c, d_x, rows, C, d_y);
@@ -1195,8 +1132,8 @@ int maa_op_conv_transpose1d(maa_ctx* ctx, const float* d_x, int B, int Cin, int 
 int maa_op_bench_conv(maa_ctx* ctx, int B, int H, int W, int Cin, int Cout, int taps, int pre_split, int iters,
                       float* ms_per_launch) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(ms_per_launch && iters > 0 && (taps == 1 || taps == 9), "bad op_bench_conv arguments");
+        bind(ctx);
         maa::Ctx& c = ctx->c;
         const int k = taps == 9 ? 3 : 1;
         std::vector<float> hw((size_t)Cout * Cin * taps), hb(Cout, 0.1f);
@@ -1277,8 +1214,8 @@ int maa_op_bench_conv(maa_ctx* ctx, int B, int H, int W, int Cin, int Cout, int 
 int maa_op_snake_aa(maa_ctx* ctx, const float* d_x, int B, int C, int L, const float* h_alpha, const float* h_beta,
                     int logscale, float* d_y) {
     return guarded([&] {
-        bind(ctx);
         MAA_CHECK(d_x && h_alpha && h_beta && d_y, "bad op_snake_aa arguments");
+        bind(ctx);
         maa::WeightStore ws(ctx->c.dtype != 0);
         maa::Ctx& c = ctx->c;
         std::vector<float> ha(C), hib(C);

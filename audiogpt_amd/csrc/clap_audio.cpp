@@ -155,14 +155,9 @@ struct ClapAudio::Impl {
 
 ClapAudio::ClapAudio(const maa_clap_audio_config& cfg, const StateDict& sd, int precision) : impl_(new Impl(precision)) {
     impl_->cfg = cfg;
-    try {
-        impl_->build(sd);
-    } catch (...) {
-        delete impl_;
-        throw;
-    }
+    impl_->build(sd);
 }
-ClapAudio::~ClapAudio() { delete impl_; }
+ClapAudio::~ClapAudio() = default;
 const maa_clap_audio_config& ClapAudio::config() const { return impl_->cfg; }
 void ClapAudio::embed(Ctx& ctx, const float* d_logmel, int B, int T, float* d_embedding, float* d_z) {
     PrecisionGuard guard(ctx, impl_->precision);
@@ -179,29 +174,24 @@ struct Spectral::Impl {
 
 Spectral::Spectral(const maa_spectral_config& cfg, const float* h_basis, const float* h_melw) : impl_(new Impl) {
     impl_->cfg = cfg;
-    try {
-        const int nf = cfg.n_freq;
-        impl_->ldm = (nf + 3) / 4 * 4;
-        StateDict tmp;
-        HostTensor hb;
-        hb.data = h_basis;
-        hb.shape = {2LL * nf, cfg.n_fft};
-        tmp["basis"] = hb;
-        impl_->basis = impl_->ws.pack_conv(tmp, "basis", "", 1, 1);
-        std::vector<float> mw((size_t)cfg.n_mels * impl_->ldm, 0.f);
-        for (int m = 0; m < cfg.n_mels; ++m)
-            std::memcpy(mw.data() + (size_t)m * impl_->ldm, h_melw + (size_t)m * nf, sizeof(float) * nf);
-        HostTensor hm;
-        hm.data = mw.data();
-        hm.shape = {cfg.n_mels, impl_->ldm};
-        tmp["melw"] = hm;
-        impl_->melw = impl_->ws.pack_conv(tmp, "melw", "", 1, 1);
-    } catch (...) {
-        delete impl_;
-        throw;
-    }
+    const int nf = cfg.n_freq;
+    impl_->ldm = (nf + 3) / 4 * 4;
+    StateDict tmp;
+    HostTensor hb;
+    hb.data = h_basis;
+    hb.shape = {2LL * nf, cfg.n_fft};
+    tmp["basis"] = hb;
+    impl_->basis = impl_->ws.pack_conv(tmp, "basis", "", 1, 1);
+    std::vector<float> mw((size_t)cfg.n_mels * impl_->ldm, 0.f);
+    for (int m = 0; m < cfg.n_mels; ++m)
+        std::memcpy(mw.data() + (size_t)m * impl_->ldm, h_melw + (size_t)m * nf, sizeof(float) * nf);
+    HostTensor hm;
+    hm.data = mw.data();
+    hm.shape = {cfg.n_mels, impl_->ldm};
+    tmp["melw"] = hm;
+    impl_->melw = impl_->ws.pack_conv(tmp, "melw", "", 1, 1);
 }
-Spectral::~Spectral() { delete impl_; }
+Spectral::~Spectral() = default;
 const maa_spectral_config& Spectral::config() const { return impl_->cfg; }
 
 void Spectral::forward(Ctx& ctx, const float* d_wav, int B, int n, float* d_out) {
@@ -241,22 +231,17 @@ Resampler::Resampler(int orig, int neu, int width, int klen, const float* h_kern
     impl_->width = width;
     impl_->klen = klen;
     impl_->kpad = (klen + 3) / 4 * 4;
-    try {
-        MAA_CHECK(klen == 2 * width + orig, "resampler kernel length must be 2 width + orig_freq");
-        std::vector<float> kw((size_t)neu * impl_->kpad, 0.f);
-        for (int p = 0; p < neu; ++p) std::memcpy(kw.data() + (size_t)p * impl_->kpad, h_kernels + (size_t)p * klen, sizeof(float) * klen);
-        StateDict tmp;
-        HostTensor h;
-        h.data = kw.data();
-        h.shape = {neu, impl_->kpad};
-        tmp["k"] = h;
-        impl_->bank = impl_->ws.pack_conv(tmp, "k", "", 1, 1);
-    } catch (...) {
-        delete impl_;
-        throw;
-    }
+    MAA_CHECK(klen == 2 * width + orig, "resampler kernel length must be 2 width + orig_freq");
+    std::vector<float> kw((size_t)neu * impl_->kpad, 0.f);
+    for (int p = 0; p < neu; ++p) std::memcpy(kw.data() + (size_t)p * impl_->kpad, h_kernels + (size_t)p * klen, sizeof(float) * klen);
+    StateDict tmp;
+    HostTensor h;
+    h.data = kw.data();
+    h.shape = {neu, impl_->kpad};
+    tmp["k"] = h;
+    impl_->bank = impl_->ws.pack_conv(tmp, "k", "", 1, 1);
 }
-Resampler::~Resampler() { delete impl_; }
+Resampler::~Resampler() = default;
 long long Resampler::out_length(long long n) const {
     return ((long long)impl_->neu * n + impl_->orig - 1) / impl_->orig;           // ceil(new * length / orig)
 }

@@ -195,7 +195,7 @@ DiffNet::DiffNet(const maa_diffnet_config& cfg, const StateDict& sd, int precisi
     impl_->cfg = cfg;
     impl_->build(sd);
 }
-DiffNet::~DiffNet() { delete impl_; }
+DiffNet::~DiffNet() = default;
 const maa_diffnet_config& DiffNet::config() const { return impl_->cfg; }
 
 void DiffNet::forward(Ctx& ctx, const float* spec, const float* t, const float* cond, int B, int T, float* out) {

@@ -271,19 +271,14 @@ struct Encoder::Impl {
 
 Encoder::Encoder(const maa_encoder_config& cfg, const StateDict& sd, int precision) : impl_(new Impl(precision)) {
     impl_->cfg = cfg;
-    try {
-        if (cfg.kind == 0)
-            impl_->build_text(sd);
-        else if (cfg.kind == 1)
-            impl_->build_image(sd);
-        else
-            impl_->build_clip_text(sd);
-    } catch (...) {
-        delete impl_;
-        throw;
-    }
+    if (cfg.kind == 0)
+        impl_->build_text(sd);
+    else if (cfg.kind == 1)
+        impl_->build_image(sd);
+    else
+        impl_->build_clip_text(sd);
 }
-Encoder::~Encoder() { delete impl_; }
+Encoder::~Encoder() = default;
 const maa_encoder_config& Encoder::config() const { return impl_->cfg; }
 
 void Encoder::text(Ctx& ctx, const int* d_ids, int B, int L, float* d_out) {

@@ -222,14 +222,9 @@ struct FastSpeech2MIDI::Impl {
 FastSpeech2MIDI::FastSpeech2MIDI(const maa_fs2_config& cfg, const StateDict& sd, int precision) : impl_(new Impl(precision)) {
     impl_->cfg = cfg;
     impl_->Cp = cfg.predictor_hidden > 0 ? cfg.predictor_hidden : cfg.hidden_size;
-    try {
-        impl_->build(sd);
-    } catch (...) {
-        delete impl_;
-        throw;
-    }
+    impl_->build(sd);
 }
-FastSpeech2MIDI::~FastSpeech2MIDI() { delete impl_; }
+FastSpeech2MIDI::~FastSpeech2MIDI() = default;
 const maa_fs2_config& FastSpeech2MIDI::config() const { return impl_->cfg; }
 
 void FastSpeech2MIDI::encode(Ctx& ctx, const int* tokens, const int* pitch_midi, const float* midi_dur, const int* is_slur, int B, int T,
@@ -299,14 +294,9 @@ struct FS2Pitch::Impl {
 FS2Pitch::FS2Pitch(const maa_fs2_pitch_config& cfg, const StateDict& sd, int precision) : impl_(new Impl(precision)) {
     impl_->cfg = cfg;
     impl_->Cp = cfg.predictor_hidden > 0 ? cfg.predictor_hidden : cfg.hidden_size;
-    try {
-        impl_->build(sd);
-    } catch (...) {
-        delete impl_;
-        throw;
-    }
+    impl_->build(sd);
 }
-FS2Pitch::~FS2Pitch() { delete impl_; }
+FS2Pitch::~FS2Pitch() = default;
 const maa_fs2_pitch_config& FS2Pitch::config() const { return impl_->cfg; }
 
 void FS2Pitch::forward(Ctx& ctx, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B, int T_mel,

@@ -1,7 +1,10 @@
-// Model executors behind the C ABI handles.
+// Model executors behind the C ABI handles.  Each owns its Impl through a unique_ptr: a constructor that throws (a state dict
+// without a key) frees what it had built, and the destructors, declared here, are defined where Impl is complete.
 #pragma once
 #include "../../include/maa.h"
 #include "blocks.h"
+
+#include <memory>
 
 namespace maa {
 
@@ -43,7 +46,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 class VAE {
@@ -58,7 +61,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 class Vocoder {
@@ -73,7 +76,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 class DiffNet {
@@ -88,7 +91,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 // DiffSinger's PitchExtractor (pitch_extractor.cpp, pitch.hip): the generated mel -> f0 for the NSF vocoder
@@ -102,7 +105,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 // Row launches of pitch.hip that the extractor and the FastSpeech2 front end share.  Their shared host layers -- the "same"
@@ -134,7 +137,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 // The pitch branch the cascade singing configurations add to that front end (fs2.cpp, fs2.hip: use_pitch_embed, pitch_type frame)
@@ -150,7 +153,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 class Encoder {
@@ -164,7 +167,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 // CLAP audio branch of the best-of-n scorer: Cnn14 from the log-mel on + Projection, unit-length rows (clap_audio.cpp)
@@ -177,7 +180,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 // framed DFT -> |.|^p -> mel filter bank -> log: the 16 kHz front end of the inpainting tool and the 44.1 kHz one of the
@@ -191,7 +194,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 // torchaudio-style polyphase sinc resampler as one strided FIR-bank contraction (clap_audio.cpp); always exact fp32
@@ -204,7 +207,7 @@ public:
 
 private:
     struct Impl;
-    Impl* impl_;
+    std::unique_ptr<Impl> impl_;
 };
 
 // ---- shared by the samplers' host code (ddim.cpp, diffnet.cpp)

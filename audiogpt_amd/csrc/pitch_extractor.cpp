@@ -132,14 +132,9 @@ struct PitchExtractor::Impl {
 PitchExtractor::PitchExtractor(const maa_pitch_extractor_config& cfg, const StateDict& sd, int precision) : impl_(new Impl(precision)) {
     impl_->cfg = cfg;
     impl_->Cp = cfg.predictor_hidden > 0 ? cfg.predictor_hidden : cfg.hidden_size;
-    try {
-        impl_->build(sd);
-    } catch (...) {
-        delete impl_;
-        throw;
-    }
+    impl_->build(sd);
 }
-PitchExtractor::~PitchExtractor() { delete impl_; }
+PitchExtractor::~PitchExtractor() = default;
 const maa_pitch_extractor_config& PitchExtractor::config() const { return impl_->cfg; }
 
 void PitchExtractor::forward(Ctx& ctx, const float* mel, int B, int T, float* pitch_pred, float* f0, float* hidden_out) {

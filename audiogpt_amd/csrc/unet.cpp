@@ -655,7 +655,7 @@ UNet::UNet(const maa_unet_config& cfg, const StateDict& sd, int precision) : imp
     impl_->cfg = cfg;
     impl_->build(sd);
 }
-UNet::~UNet() { delete impl_; }
+UNet::~UNet() = default;
 const maa_unet_config& UNet::config() const { return impl_->cfg; }
 size_t UNet::weight_bytes() const { return impl_->ws.bytes(); }
 

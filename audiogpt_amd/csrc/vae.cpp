@@ -297,7 +297,7 @@ VAE::VAE(const maa_vae_config& cfg, const StateDict& sd, int precision) : impl_(
     impl_->cfg = cfg;
     impl_->build(sd);
 }
-VAE::~VAE() { delete impl_; }
+VAE::~VAE() = default;
 const maa_vae_config& VAE::config() const { return impl_->cfg; }
 
 void VAE::decode(Ctx& ctx, const float* z, int B, int h, int w, float inv_scale, float* mel) {

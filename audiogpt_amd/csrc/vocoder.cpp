@@ -410,7 +410,7 @@ Vocoder::Vocoder(const maa_vocoder_config& cfg, const StateDict& sd, int precisi
     impl_->cfg = cfg;
     impl_->build(sd);
 }
-Vocoder::~Vocoder() { delete impl_; }
+Vocoder::~Vocoder() = default;
 int Vocoder::hop() const { return impl_->hop; }
 
 void Vocoder::forward(Ctx& ctx, const float* mel, int B, int T, float* wav) {

@@ -74,3 +74,35 @@ def test_gaussian_diffusion_infer_matches_oracle():
         xr = D.plms_sample(lambda x_, t_, c_: D.diffnet_forward(sd, cfg, x_, t_, c_), ac, x, cond, cfg["K_step"], cfg["pndm_speedup"])
     ref = D.denorm_spec(xr, smin, smax)
     check("f32_GaussianDiffusion.infer_vs_oracle", mel, ref, 5e-4)
+
+
+def test_create_without_a_key_fails_cleanly_and_leaves_the_context_usable():
+    """maa_diffnet_create on a state dict without the key the constructor reads last (every other weight is on the device by
+    then) is an error return that names the key; a create and a forward on the same context afterwards give the bits of a
+    create and a forward on a fresh context."""
+    import re
+
+    from audiogpt_amd._lib import MaaError
+    from audiogpt_amd.backend import Context, DiffNet
+    cfg = C.DIFFSINGER_DS1000
+    sd = WT.make_diffnet_state_dict(cfg, seed=7)
+    last = list(sd)[-1]
+    assert last == "output_projection.bias"
+    gen = torch.Generator().manual_seed(11)
+    B, T = 2, 37
+    x, cond, t = torch.randn(B, 1, cfg["in_dims"], T, generator=gen), torch.randn(B, cfg["hidden_size"], T, generator=gen), torch.tensor([17, 940])
+
+    def forward_on(ctx):
+        net = DiffNet(ctx, cfg, sd)
+        y = net(x, t, cond).cpu()
+        net.close()
+        return y
+
+    fresh = Context("cuda:0", precision="f32")
+    ref = forward_on(fresh)
+    fresh.close()
+    ctx = Context("cuda:0", precision="f32")
+    with pytest.raises(MaaError, match=re.escape(last)):
+        DiffNet(ctx, cfg, {k: v for k, v in sd.items() if k != last})
+    assert torch.equal(forward_on(ctx), ref)
+    ctx.close()

@@ -36,6 +36,25 @@ def test_binding_matches_header(lib_path):
     assert b"gfx950" in lib.maa_version()
 
 
+def _declared_argument_counts():
+    """{entry: number of parameters} of every status-returning entry include/maa.h declares."""
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "maa.h")).read(), flags=re.S)
+    return {m.group(1): len(m.group(2).split(",")) for m in re.finditer(r"\bint\s+(maa_[a-z0-9_]+)\s*\(([^)]*)\)", src)}
+
+
+def test_every_bound_signature_has_the_headers_argument_count(lib_path):
+    """The binding's one table (_lib.SIGNATURES) against the header, entry by entry: the same names, and as many argument types
+    as the declaration has parameters."""
+    from audiogpt_amd import _lib
+    lib = _lib.load()
+    declared = _declared_argument_counts()
+    assert sorted(declared) == sorted(_lib.SIGNATURES) and len(declared) >= 80
+    assert sorted(_lib.EXPORTS) == sorted(list(_lib.SIGNATURES) + ["maa_last_error", "maa_version"])
+    for name, n in declared.items():
+        assert len(_lib.SIGNATURES[name]) == n, name
+        assert len(getattr(lib, name).argtypes) == n and getattr(lib, name).restype is ctypes.c_int, name
+
+
 def test_error_path_without_gpu(lib_path):
     """No GPU in the build container: creating a context must fail cleanly with a message, not crash."""
     import torch
