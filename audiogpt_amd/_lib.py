@@ -142,6 +142,18 @@ class maa_igemm_ex_args(C.Structure):
                 ("d_c", C.c_void_p), ("ldc", C.c_int), ("d_c2", C.c_void_p), ("ldc2", C.c_int), ("c2_slope", C.c_float)]
 
 
+class maa_seq_rows_args(C.Structure):
+    _fields_ = [("kind", C.c_int), ("rows", C.c_int), ("B", C.c_int), ("T", C.c_int), ("C", C.c_int),
+                ("d_x", C.c_void_p), ("d_res", C.c_void_p), ("d_mask", C.c_void_p),
+                ("h_scale", C.POINTER(C.c_float)), ("h_shift", C.POINTER(C.c_float)), ("h_gamma", C.POINTER(C.c_float)),
+                ("h_beta", C.POINTER(C.c_float)), ("h_w", C.POINTER(C.c_float)), ("h_bias", C.POINTER(C.c_float)),
+                ("groups", C.c_int), ("eps", C.c_float), ("table_rows", C.c_int), ("alpha", C.c_float),
+                ("n_out", C.c_int), ("pitch_norm", C.c_int), ("f0_mean", C.c_float), ("f0_std", C.c_float), ("use_uv", C.c_int),
+                ("d_out", C.c_void_p), ("d_out2", C.c_void_p), ("d_pos", C.c_void_p), ("d_dur", C.c_void_p)]
+
+
+SEQ_KINDS = {"frame_mask": 0, "affine_mask": 1, "gn_relu_res": 2, "pos_add": 3, "head": 4}      # MAA_SEQ_* of include/maa.h
+
 # The one list of the library's entries: name -> argument types (every entry returns an int status).  load() applies it and
 # EXPORTS is derived from it; a new entry of include/maa.h is added here and nowhere else.
 vp, ci, cf, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)
@@ -225,6 +237,7 @@ SIGNATURES = {
     "maa_op_groupnorm_ex": [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, fp, fp, cf, ci, vp, ci, vp],
     "maa_op_igemm_ex": [vp, C.POINTER(maa_igemm_ex_args)],
     "maa_op_layernorm_ex": [vp, vp, ci, ci, fp, fp, cf, vp, ci],
+    "maa_op_seq_rows": [vp, C.POINTER(maa_seq_rows_args)],
     "maa_op_split32": [vp, vp, ci, ci, cf, ci, vp],
     "maa_unet_forward_split": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, fp, vp],
     "maa_op_unfold": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp],

@@ -288,6 +288,29 @@ class Context(_Handle):
         self._call("maa_op_igemm_ex", C.byref(a))
         return c
 
+    def op_seq_rows(self, kind, x, out, C_, rows=0, B=0, T=0, res=None, mask=None, scale=None, shift=None, gamma=None, beta=None,
+                    w=None, bias=None, groups=0, eps=1e-5, table_rows=0, alpha=1.0, n_out=0, pitch_norm=0, f0_mean=0.0, f0_std=1.0,
+                    use_uv=0, out2=None, pos=None, dur=None):
+        """maa_op_seq_rows: one row operator of the sequence models through the library's internal launch (`kind`: a key of
+        _lib.SEQ_KINDS; include/maa.h lists what each reads and writes).  x / res / mask / out / out2 are fp32 device tensors and
+        pos / dur int32 ones, possibly views into larger buffers (out may be x where the header allows it); scale / shift / gamma /
+        beta / w / bias come from the host.  Writes into the outputs; nothing is allocated, copied or checked beyond what the C
+        entry point checks."""
+        for t in (x, res, mask, out, out2):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32), (t.device, t.dtype)
+        for t in (pos, dur):
+            assert t is None or (t.is_cuda and t.dtype == torch.int32), (t.device, t.dtype)
+        keep = [L.host_f32(t) if t is not None else (None, None) for t in (scale, shift, gamma, beta, w, bias)]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        a = L.maa_seq_rows_args(
+            kind=L.SEQ_KINDS[kind], rows=int(rows), B=int(B), T=int(T), C=int(C_), d_x=ptr(x), d_res=ptr(res), d_mask=ptr(mask),
+            h_scale=keep[0][1], h_shift=keep[1][1], h_gamma=keep[2][1], h_beta=keep[3][1], h_w=keep[4][1], h_bias=keep[5][1],
+            groups=int(groups), eps=float(eps), table_rows=int(table_rows), alpha=float(alpha), n_out=int(n_out),
+            pitch_norm=int(pitch_norm), f0_mean=float(f0_mean), f0_std=float(f0_std), use_uv=int(use_uv), d_out=ptr(out),
+            d_out2=ptr(out2), d_pos=ptr(pos), d_dur=ptr(dur))
+        self._call("maa_op_seq_rows", C.byref(a))
+        return out
+
     def op_layernorm_ex(self, x, gamma, beta, eps=1e-5, out_split=0):
         """LayerNorm over the last dim of x [rows, C]; out_split = 1: the result as split32 rows in an fp32-typed tensor."""
         x = _f32(x, self.device)

@@ -5,6 +5,7 @@
 // malformed call so fails the same way with or without a device, and the checks can be tested without one.  Only a check that
 // needs the context's or a model's state comes after bind.  A model handle is made by create_handle and freed by destroy_handle.
 #include "models.h"
+#include "seq_layers.h"
 
 #include <cstdint>
 #include <cstring>
@@ -1029,6 +1030,72 @@ int maa_op_layernorm_ex(maa_ctx* ctx, const float* d_x, int rows, int C, const f
         float* g = ws.upload(std::vector<float>(h_gamma, h_gamma + C));
         float* b = ws.upload(std::vector<float>(h_beta, h_beta + C));
         maa::launch_layernorm(c, d_x, rows, C, g, b, eps, d_y, out_split ? 1 : 0);
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
+int maa_op_seq_rows(maa_ctx* ctx, const maa_seq_rows_args* a) {
+    return guarded([&] {
+        MAA_CHECK(a != nullptr, "bad op_seq_rows arguments: null pointer");
+        const int k = a->kind;
+        MAA_CHECK(k >= MAA_SEQ_FRAME_MASK && k <= MAA_SEQ_HEAD, "op_seq_rows: unknown kind");
+        const bool per_sample = k == MAA_SEQ_GN_RELU_RES || k == MAA_SEQ_POS_ADD;      // rows = B * T
+        bool ptrs = a->d_x && a->d_out;
+        if (k == MAA_SEQ_AFFINE_MASK) ptrs = ptrs && a->d_mask;
+        if (k == MAA_SEQ_GN_RELU_RES) ptrs = ptrs && a->d_res && a->h_gamma && a->h_beta;
+        if (k == MAA_SEQ_HEAD)
+            ptrs = ptrs && a->d_mask && a->h_gamma && a->h_beta && a->h_w && a->h_bias && (a->n_out == 1 ? a->d_dur != nullptr : a->d_out2 != nullptr);
+        MAA_CHECK(ptrs, "bad op_seq_rows arguments: null pointer");
+        if (per_sample)
+            MAA_CHECK(a->B >= 1 && a->T >= 1 && (long long)a->B * a->T < (1ll << 31), "op_seq_rows: rows < 1 (B and T must be at least 1)");
+        else
+            MAA_CHECK(a->rows >= 1, "op_seq_rows: rows < 1");
+        MAA_CHECK(a->C >= 4 && a->C % 4 == 0, "op_seq_rows: C % 4 != 0 (channel counts are positive multiples of 4)");
+        if (k == MAA_SEQ_AFFINE_MASK)
+            MAA_CHECK((a->h_scale == nullptr) == (a->h_shift == nullptr), "op_seq_rows: scale and shift come both or neither");
+        if (k == MAA_SEQ_GN_RELU_RES)
+            MAA_CHECK(a->groups > 0 && a->C % a->groups == 0 && (a->C / a->groups) % 4 == 0 && a->C / a->groups <= 256 && a->eps > 0.f,
+                      "op_seq_rows: groups must divide C into whole float4s, at most 256 channels per group");
+        if (k == MAA_SEQ_POS_ADD) MAA_CHECK(a->table_rows >= 2, "op_seq_rows: table_rows < 2");
+        if (k == MAA_SEQ_HEAD) {
+            MAA_CHECK(a->C <= 1024, "op_seq_rows: head C > 1024");
+            MAA_CHECK((a->n_out == 1 || a->n_out == 2) && a->eps > 0.f && (a->pitch_norm == 0 || a->pitch_norm == 1),
+                      "op_seq_rows: the head has n_out 1 or 2, pitch_norm 0 or 1");
+        }
+        bind(ctx);
+        maa::Ctx& c = ctx->c;
+        maa::WeightStore ws(c.dtype != 0);
+        const int C = a->C;
+        auto up = [&](const float* h, size_t n) { return h ? ws.upload(std::vector<float>(h, h + n)) : nullptr; };
+        switch (k) {
+        case MAA_SEQ_FRAME_MASK:
+            maa::launch_pe_frame_mask(c, a->d_x, a->rows, C, a->d_out, a->d_out2);
+            break;
+        case MAA_SEQ_AFFINE_MASK:
+            maa::launch_pe_affine_mask(c, a->d_x, a->rows, C, up(a->h_scale, C), up(a->h_shift, C), a->d_mask, a->d_out);
+            break;
+        case MAA_SEQ_GN_RELU_RES: {
+            const float *g = up(a->h_gamma, C), *b = up(a->h_beta, C);
+            maa::run_sized(c, [&] { maa::launch_pe_gn_relu_res(c, a->d_x, a->d_res, a->B, a->T, C, a->groups, g, b, a->eps, a->d_out); });
+            break;
+        }
+        case MAA_SEQ_POS_ADD: {
+            maa::SinusoidTable table;
+            table.build(ws, a->table_rows, C);
+            table.grow(c, a->T);
+            maa::run_sized(c, [&] { maa::launch_pe_pos_add(c, a->d_x, a->B, a->T, C, table.ptr(), a->alpha, a->d_out, a->d_pos); });
+            MAA_HIP(hipStreamSynchronize(c.stream));      // (the grown table is freed with `table`)
+            break;
+        }
+        default: {
+            const float *g = up(a->h_gamma, C), *b = up(a->h_beta, C), *w = up(a->h_w, (size_t)a->n_out * C), *bi = up(a->h_bias, a->n_out);
+            if (a->n_out == 2)
+                maa::launch_pe_head(c, a->d_x, a->rows, C, g, b, a->eps, w, bi, a->d_mask, a->pitch_norm, a->f0_mean, a->f0_std, a->use_uv,
+                                    a->d_out, a->d_out2);
+            else
+                maa::launch_fs2_dur_head(c, a->d_x, a->rows, C, g, b, a->eps, w, bi, a->d_mask, a->d_out, a->d_dur);
+        }
+        }
         MAA_HIP(hipStreamSynchronize(c.stream));
     });
 }

@@ -31,8 +31,6 @@ namespace maa {
 void launch_fs2_embed(const Ctx& ctx, const int* tok, const int* midi, const float* midi_dur, const int* slur, const float* E, int vocab,
                       const float* Mi, const float* dw, const float* db, const float* S, const float* pe, float scale, int B, int T, int H,
                       float* x, float* nonpad, float* hidden);
-void launch_fs2_dur_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
-                         const float* w, const float* bias, const float* nonpad, float* xs, int* dur);
 void launch_fs2_length(Ctx& ctx, const int* dur, int B, int T, int* totals, int T_mel, int* mel2ph);
 void launch_fs2_expand(const Ctx& ctx, const float* enc, const int* mel2ph, int B, int T, int T_mel, int H, float* out, float* tgt);
 void launch_fs2_tgt_mask(const Ctx& ctx, const int* mel2ph, long long rows, float* tgt);

@@ -116,8 +116,19 @@ void launch_pe_frame_mask(const Ctx& ctx, const float* mel, long long rows, int 
 // out = (x * scale + shift) * mask[row]; scale == nullptr: out = x * mask[row] (out may be x)
 void launch_pe_affine_mask(const Ctx& ctx, const float* x, long long rows, int C, const float* scale, const float* shift,
                            const float* mask, float* out);
-// out = x + alpha * table[make_positions(x[..., 0])], the positions counted on the device
-void launch_pe_pos_add(Ctx& ctx, const float* x, int B, int T, int C, const float* table, float alpha, float* out);
+// out = x + alpha * table[make_positions(x[..., 0])], the positions counted on the device; pos_out (optional) int [B, T] receives
+// them in place of the workspace buffer
+void launch_pe_pos_add(Ctx& ctx, const float* x, int B, int T, int C, const float* table, float alpha, float* out,
+                       int* pos_out = nullptr);
+// out = res + relu(GroupNorm(y)), the statistics over all T frames of a sample (out may be y)
+void launch_pe_gn_relu_res(Ctx& ctx, const float* y, const float* res, int B, int T, int C, int groups, const float* gamma,
+                           const float* beta, float eps, float* out);
+// The predictors' last LayerNorm + narrow Linear: Linear(C, 2) and denorm_f0 (pitch.hip), Linear(C, 1), mask and out2dur (fs2.hip)
+void launch_pe_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
+                    const float* w, const float* bias, const float* mask, int norm, float f0_mean, float f0_std, int use_uv,
+                    float* pitch_pred, float* f0);
+void launch_fs2_dur_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
+                         const float* w, const float* bias, const float* nonpad, float* xs, int* dur);
 
 // DiffSinger's FastSpeech2MIDI front end (fs2.cpp, fs2.hip): score -> encoder_out / durations, then mel2ph -> decoder_inp / mel_out
 class FastSpeech2MIDI {

@@ -219,9 +219,9 @@ void launch_pe_gn_relu_res(Ctx& ctx, const float* y, const float* res, int B, in
     MAA_HIP(hipGetLastError());
 }
 
-void launch_pe_pos_add(Ctx& ctx, const float* x, int B, int T, int C, const float* table, float alpha, float* out) {
+void launch_pe_pos_add(Ctx& ctx, const float* x, int B, int T, int C, const float* table, float alpha, float* out, int* pos_out) {
     const long long rows = (long long)B * T;
-    int* pos = reinterpret_cast<int*>(ctx.ws.alloc_f((size_t)rows));
+    int* pos = pos_out ? pos_out : reinterpret_cast<int*>(ctx.ws.alloc_f((size_t)rows));
     if (ctx.ws.dry) return;
     MAA_CHECK(C % 4 == 0, "pitch extractor: channel counts must be multiples of 4");
     ProfScope prof(ctx, "pe_rows", 0.0, 12.0 * rows * (double)C);

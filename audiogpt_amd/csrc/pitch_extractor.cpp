@@ -22,12 +22,6 @@
 
 namespace maa {
 
-void launch_pe_gn_relu_res(Ctx& ctx, const float* y, const float* res, int B, int T, int C, int groups, const float* gamma,
-                           const float* beta, float eps, float* out);
-void launch_pe_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
-                    const float* w, const float* bias, const float* mask, int norm, float f0_mean, float f0_std, int use_uv,
-                    float* pitch_pred, float* f0);
-
 namespace {
 
 constexpr int PE_PRENET_LAYERS = 3, PE_PREDICTOR_LAYERS = 5, PE_KERNEL = 5, PE_TABLE_INIT = 4096;

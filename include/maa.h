@@ -681,6 +681,57 @@ int maa_op_igemm_ex(maa_ctx* ctx, const maa_igemm_ex_args* args);
 /* maa_op_layernorm with the kernels' out_split argument (1: d_y [rows,C] as split32 rows, C % 32 == 0) */
 int maa_op_layernorm_ex(maa_ctx* ctx, const float* d_x, int rows, int C, const float* h_gamma, const float* h_beta, float eps,
                         float* d_y, int out_split);
+/* One row operator of DiffSinger's sequence models exactly as the models launch it (tests of the one-wave-per-row kernels of
+ * pitch.hip / fs2.hip and of the growing sinusoid table): the entry forwards to the library's internal launch and adds no
+ * arithmetic.  d_* are DEVICE buffers the caller has laid out, channels-last rows [rows, C]; h_* are HOST arrays, uploaded
+ * as the models upload their weights.  C % 4 == 0 everywhere.  kind:
+ *   MAA_SEQ_FRAME_MASK   d_x [rows, C] -> d_out [rows] = 0 where every channel of the row is +-0, else 1; d_out2 (or NULL)
+ *                        [rows] = 1 - d_out.
+ *   MAA_SEQ_AFFINE_MASK  d_out = (d_x * h_scale + h_shift) * d_mask[row], h_scale / h_shift [C] both or neither (neither:
+ *                        d_x * d_mask[row]); d_out may be d_x.
+ *   MAA_SEQ_GN_RELU_RES  d_out = d_res + relu(GroupNorm(d_x)), d_x / d_res [B * T, C], `groups` groups with the statistics over
+ *                        all T frames of a sample, h_gamma / h_beta [C], eps; C / groups a multiple of 4, at most 256; d_out may
+ *                        be d_x.
+ *   MAA_SEQ_POS_ADD      d_out = d_x + alpha * table[make_positions(d_x[..., 0])], d_x [B, T, C]; the sinusoid table is built
+ *                        with table_rows >= 2 rows and grown to T + 1 rows when T + 1 > table_rows, as the models' tables are;
+ *                        d_pos (or NULL) int [B, T] receives the positions.
+ *   MAA_SEQ_HEAD         a predictor's last LayerNorm (h_gamma / h_beta [C], eps) + Linear(C, n_out) (h_w [n_out, C], h_bias
+ *                        [n_out]) on d_x [rows, C], C <= 1024, d_mask [rows].  n_out = 2, the pitch head: d_out [rows, 2] =
+ *                        {value, voicing logit}, d_out2 [rows] = denorm_f0 under pitch_norm (0 'log', 1 'standard'), f0_mean,
+ *                        f0_std, use_uv, 0 where d_mask is 0.  n_out = 1, the duration head: d_out [rows] = the masked
+ *                        prediction xs, d_dur int [rows] = max(rint(exp(xs) - 1), 0).
+ * Checked here, before the context is touched: null pointers, rows (B, T) >= 1, C a positive multiple of 4, the head's
+ * C <= 1024 and n_out, the GroupNorm channel rule, table_rows >= 2. */
+#define MAA_SEQ_FRAME_MASK 0
+#define MAA_SEQ_AFFINE_MASK 1
+#define MAA_SEQ_GN_RELU_RES 2
+#define MAA_SEQ_POS_ADD 3
+#define MAA_SEQ_HEAD 4
+typedef struct {
+    int kind;
+    int rows, B, T, C;
+    const float* d_x;
+    const float* d_res;
+    const float* d_mask;
+    const float* h_scale;
+    const float* h_shift;
+    const float* h_gamma;
+    const float* h_beta;
+    const float* h_w;
+    const float* h_bias;
+    int groups;
+    float eps;
+    int table_rows;
+    float alpha;
+    int n_out, pitch_norm;
+    float f0_mean, f0_std;
+    int use_uv;
+    float* d_out;
+    float* d_out2;
+    int* d_pos;
+    int* d_dur;
+} maa_seq_rows_args;
+int maa_op_seq_rows(maa_ctx* ctx, const maa_seq_rows_args* args);
 /* The split32 row codec on its own, d_x / d_y [rows,C] on the device, C % 32 == 0: unpack = 0 writes the split32 rows of
  * leaky_relu(x, slope) (slope 1: of x), unpack = 1 reads split32 rows and writes hi + lo as fp32 (slope is ignored). */
 int maa_op_split32(maa_ctx* ctx, const float* d_x, int rows, int C, float slope, int unpack, float* d_y);

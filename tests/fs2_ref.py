@@ -93,9 +93,9 @@ def length_regulate(dur):
     return (torch.arange(1, dur.shape[1] + 1)[None, :, None] * mask.long()).sum(1)
 
 
-def forward(sd, cfg, txt_tokens, pitch_midi, midi_dur=None, is_slur=None, mel2ph=None, dtype=torch.float32):
-    """-> dict(encoder_out [B, T, H], xs [B, T], dur_choice [B, T] long, mel2ph [B, T_mel] long, decoder_inp, mel_out) in `dtype`;
-    dur_choice and mel2ph come from the prediction when mel2ph is None."""
+def encode(sd, cfg, txt_tokens, pitch_midi, midi_dur=None, is_slur=None, dtype=torch.float32):
+    """The encoder half of forward with the duration predictor -> (encoder_out [B, T, H], xs [B, T], dur_choice [B, T] long) in
+    `dtype`."""
     dt = dtype
     w = lambda key: sd[key].to(dt)      # noqa: E731
     H, heads = cfg["hidden_size"], cfg["num_heads"]
@@ -120,19 +120,49 @@ def forward(sd, cfg, txt_tokens, pitch_midi, midi_dur=None, is_slur=None, mel2ph
         y = y * keep[:, None, :]
     xs = F.linear(y.transpose(1, 2), w("dur_predictor.linear.weight"), w("dur_predictor.linear.bias"))[..., 0] * keep
     dur = torch.clamp(torch.round(xs.exp() - 1.0), min=0).long()
+    return enc, xs, dur
+
+
+def forward(sd, cfg, txt_tokens, pitch_midi, midi_dur=None, is_slur=None, mel2ph=None, dtype=torch.float32):
+    """-> dict(encoder_out [B, T, H], xs [B, T], dur_choice [B, T] long, mel2ph [B, T_mel] long, decoder_inp, mel_out) in `dtype`;
+    dur_choice and mel2ph come from the prediction when mel2ph is None."""
+    dt = dtype
+    enc, xs, dur = encode(sd, cfg, txt_tokens, pitch_midi, midi_dur, is_slur, dt)
     if mel2ph is None:
-        mel2ph = length_regulate(dur * (~pad).long())
-    mel2ph = mel2ph.long()
-    # ---- expand, decoder
+        mel2ph = length_regulate(dur * (~txt_tokens.eq(0)).long())
+    out = decode(sd, cfg, enc, mel2ph, dt)
+    return dict(encoder_out=enc, xs=xs, dur_choice=dur, mel2ph=out["mel2ph"], decoder_inp=out["decoder_inp"], mel_out=out["mel_out"])
+
+
+def expand(encoder_out, mel2ph):
+    """FastSpeech2.forward's expand and mask (fs2.py:117-122,132): encoder_out [B, T, H], mel2ph [B, T_mel] long -> decoder_inp."""
+    H = encoder_out.shape[-1]
+    tgt = (mel2ph > 0).to(encoder_out.dtype)[:, :, None]
+    return torch.gather(F.pad(encoder_out, [0, 0, 1, 0]), 1, mel2ph[..., None].repeat(1, 1, H)) * tgt
+
+
+def run_decoder(sd, cfg, decoder_inp, mel2ph, dtype=torch.float32):
+    """FastSpeech2.run_decoder (fs2.py:222-226): decoder_inp [B, T_mel, H] (an all-zero row is padding), mel2ph [B, T_mel] ->
+    mel_out [B, T_mel, mel bins] in `dtype`."""
+    dt = dtype
+    w = lambda key: sd[key].to(dt)      # noqa: E731
+    H = cfg["hidden_size"]
+    dec_inp = decoder_inp.to(dt)
     tgt = (mel2ph > 0).to(dt)[:, :, None]
-    dec_inp = torch.gather(F.pad(enc, [0, 0, 1, 0]), 1, mel2ph[..., None].repeat(1, 1, H)) * tgt
     dpad = dec_inp.abs().sum(-1).eq(0)
     Tm = dec_inp.shape[1]
     tab = P.sinusoid_table(max(2000, Tm + 1), H).to(dt)
     x = dec_inp + w("decoder.pos_embed_alpha") * tab[P.make_positions(dec_inp[..., 0])]
-    x = fft_blocks(sd, "decoder", x, dpad, heads, cfg["dec_layers"], cfg["dec_ffn_kernel_size"], dt)
-    mel = F.linear(x, w("mel_out.weight"), w("mel_out.bias")) * tgt
-    return dict(encoder_out=enc, xs=xs, dur_choice=dur, mel2ph=mel2ph, decoder_inp=dec_inp, mel_out=mel)
+    x = fft_blocks(sd, "decoder", x, dpad, cfg["num_heads"], cfg["dec_layers"], cfg["dec_ffn_kernel_size"], dt)
+    return F.linear(x, w("mel_out.weight"), w("mel_out.bias")) * tgt
+
+
+def decode(sd, cfg, encoder_out, mel2ph, dtype=torch.float32):
+    """The decoder half of forward: encoder_out [B, T, H], mel2ph [B, T_mel] -> dict(mel2ph long, decoder_inp, mel_out) in
+    `dtype`."""
+    mel2ph = mel2ph.long()
+    dec_inp = expand(encoder_out.to(dtype), mel2ph)
+    return dict(mel2ph=mel2ph, decoder_inp=dec_inp, mel_out=run_decoder(sd, cfg, dec_inp, mel2ph, dtype))
 
 
 # ---- the masked-attention operator test (tests/test_gpu_fs2.py): float64 reference and seeded inputs, heads = 2, dh = 128

@@ -67,6 +67,8 @@ def _configs():
                                     h_sqrt_recip_ac=_fp, h_sqrt_recipm1_ac=_fp, h_coef1=_fp, h_coef2=_fp, h_sigma=_fp),
         L.maa_igemm_ex_args: _struct(L.maa_igemm_ex_args, d_x1=_base, ld1=32, C1=32, B=1, H=1, W=1, Ho=1, Wo=1, h_w=_fp, Cout=32, KH=1,
                                      KW=1, stride=1, dil=1, pad_h=-1, alpha=1.0, out_scale=1.0, d_c=_base, ldc=32),
+        L.maa_seq_rows_args: _struct(L.maa_seq_rows_args, kind=L.SEQ_KINDS["head"], rows=1, C=32, d_x=_base, d_mask=_base, h_gamma=_fp,
+                                     h_beta=_fp, h_w=_fp, h_bias=_fp, eps=1e-5, n_out=2, d_out=_base, d_out2=_base),
         L.maa_prof_row: C.cast(_base, C.POINTER(L.maa_prof_row)),
         L.maa_tensor: None,          # an empty tensor list, with n_tensors = 0
     }

@@ -96,6 +96,69 @@ def test_normalisation_test_entries_are_bound_and_reject_null(lib_path):
     assert len(lib.maa_last_error()) > 0
 
 
+def test_sequence_row_test_entry_is_bound_and_refuses_by_name(lib_path):
+    """maa_op_seq_rows (tests/test_gpu_seq_ops.py) is declared, exported, bound with the header's argument count and a structure
+    that has the header's fields in the header's order, and every refusal -- null pointers, C % 4, the head's width, the GroupNorm
+    channel rule, rows < 1, table_rows < 2 -- comes back with its message before the context is touched."""
+    from audiogpt_amd import _lib
+    lib = _lib.load()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "maa.h")).read(), flags=re.S)
+    name = "maa_op_seq_rows"
+    assert name in _lib.EXPORTS and name in _declared_symbols()
+    decl = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
+    assert len(getattr(lib, name).argtypes) == len(decl.split(",")) == 2, name
+    body = re.search(r"typedef struct \{([^}]*)\} maa_seq_rows_args;", src).group(1)
+    fields = []
+    for stmt in body.split(";"):
+        stmt = stmt.strip()
+        if stmt:
+            fields += [f.strip().lstrip("*").strip() for f in re.sub(r"^(const\s+)?(float|int)\s*\*?", "", stmt).split(",")]
+    assert fields == [f[0] for f in _lib.maa_seq_rows_args._fields_]
+    for kind, value in _lib.SEQ_KINDS.items():
+        assert re.search(r"#define MAA_SEQ_%s %d\b" % (kind.upper(), value), src), kind
+    assert lib.maa_op_seq_rows(None, None) < 0 and b"null pointer" in lib.maa_last_error()
+    import numpy as np
+    buf = np.zeros(64, np.float32)
+    fp = buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    dp = buf.ctypes.data
+    base = {
+        "frame_mask": dict(rows=1, C=8, d_x=dp, d_out=dp),
+        "affine_mask": dict(rows=1, C=8, d_x=dp, d_mask=dp, d_out=dp),
+        "gn_relu_res": dict(B=1, T=1, C=8, d_x=dp, d_res=dp, h_gamma=fp, h_beta=fp, groups=2, eps=1e-5, d_out=dp),
+        "pos_add": dict(B=1, T=1, C=8, d_x=dp, table_rows=2, alpha=1.0, d_out=dp),
+        "head": dict(rows=1, C=8, d_x=dp, d_mask=dp, h_gamma=fp, h_beta=fp, h_w=fp, h_bias=fp, eps=1e-5, n_out=2, d_out=dp, d_out2=dp),
+    }
+
+    def refused(kind, message, **kw):
+        d = dict(base[kind], kind=_lib.SEQ_KINDS[kind])
+        d.update(kw)
+        st = lib.maa_op_seq_rows(None, ctypes.byref(_lib.maa_seq_rows_args(**d)))
+        assert st < 0 and message in lib.maa_last_error(), (kind, kw, lib.maa_last_error())
+
+    for kind in base:
+        refused(kind, b"null context")                                  # past every argument check
+        for p in [k for k, v in base[kind].items() if k.startswith(("d_", "h_"))]:
+            refused(kind, b"null pointer", **{p: None})
+        refused(kind, b"C % 4 != 0", C=6)
+        refused(kind, b"C % 4 != 0", C=0)
+        if "rows" in base[kind]:
+            refused(kind, b"rows < 1", rows=0)
+        else:
+            refused(kind, b"rows < 1", B=0)
+            refused(kind, b"rows < 1", T=0)
+    refused("head", b"null context", n_out=1, d_out2=None, d_dur=dp)
+    refused("head", b"null pointer", n_out=1)                            # the duration head writes d_dur
+    refused("head", b"head C > 1024", C=1028)
+    refused("head", b"n_out", n_out=3)
+    refused("affine_mask", b"both or neither", h_scale=fp)
+    refused("affine_mask", b"null context", h_scale=fp, h_shift=fp)
+    for bad in (dict(groups=0), dict(groups=3), dict(groups=8), dict(C=1024, groups=2)):      # 0, not a divisor, 1 per group, 512
+        refused("gn_relu_res", b"groups", **bad)
+    refused("pos_add", b"table_rows < 2", table_rows=1)
+    refused("pos_add", b"null context", d_pos=dp)
+    assert lib.maa_op_seq_rows(None, ctypes.byref(_lib.maa_seq_rows_args(kind=5))) < 0 and b"unknown kind" in lib.maa_last_error()
+
+
 def test_contraction_test_entry_is_bound_and_rejects_null(lib_path):
     """maa_op_igemm_ex (tests/test_gpu_igemm_ops.py) is declared, exported, bound with the header's argument count and a structure
     that has the header's fields in the header's order, and fails with a message on null arguments, on a pitch below its width and
