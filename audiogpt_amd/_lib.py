@@ -154,6 +154,22 @@ class maa_seq_rows_args(C.Structure):
 
 SEQ_KINDS = {"frame_mask": 0, "affine_mask": 1, "gn_relu_res": 2, "pos_add": 3, "head": 4}      # MAA_SEQ_* of include/maa.h
 
+
+class maa_sampler_step_args(C.Structure):
+    _fields_ = [("kind", C.c_int), ("B", C.c_int), ("nB", C.c_int), ("S", C.c_int),
+                ("n", C.c_int64), ("per", C.c_int64), ("per_in", C.c_int64),
+                ("scale", C.c_float), ("temperature", C.c_float),
+                ("start", C.c_int), ("clip", C.c_int), ("mode", C.c_int), ("interval", C.c_int), ("timesteps", C.c_int),
+                ("n_steps", C.c_int), ("emb_w", C.c_int), ("n_t", C.c_int)] + [(k, C.c_void_p) for k in (
+        "d_x", "d_concat", "d_xin", "d_eps_u", "d_eps_c", "d_e_prev", "d_coef", "d_tab_t", "d_tab", "d_step", "d_st", "d_cur_t",
+        "d_emb_tab", "d_cur_emb", "d_mask", "d_x0", "d_noise_q", "d_noise_p", "d_ring", "d_e_keep", "d_x_out", "d_log_x",
+        "d_log_x0")]
+
+
+# MAA_STEP_* of include/maa.h
+STEP_KINDS = {"ddim_prepare": 0, "ddim": 1, "plms": 2, "plms_euler_mid": 3, "plms_euler_final": 4, "ddpm": 5, "ds_plms": 6,
+              "ds_advance": 7, "ds_ddpm": 8}
+
 # The one list of the library's entries: name -> argument types (every entry returns an int status).  load() applies it and
 # EXPORTS is derived from it; a new entry of include/maa.h is added here and nowhere else.
 vp, ci, cf, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)
@@ -238,6 +254,7 @@ SIGNATURES = {
     "maa_op_igemm_ex": [vp, C.POINTER(maa_igemm_ex_args)],
     "maa_op_layernorm_ex": [vp, vp, ci, ci, fp, fp, cf, vp, ci],
     "maa_op_seq_rows": [vp, C.POINTER(maa_seq_rows_args)],
+    "maa_op_sampler_step": [vp, C.POINTER(maa_sampler_step_args)],
     "maa_op_split32": [vp, vp, ci, ci, cf, ci, vp],
     "maa_unet_forward_split": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, fp, vp],
     "maa_op_unfold": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp],

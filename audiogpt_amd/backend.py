@@ -311,6 +311,21 @@ class Context(_Handle):
         self._call("maa_op_seq_rows", C.byref(a))
         return out
 
+    def op_sampler_step(self, kind, **fields):
+        """maa_op_sampler_step: one step kernel of the sampling loops through the library's internal launch (`kind`: a key of
+        _lib.STEP_KINDS; include/maa.h lists what each reads and writes).  `fields` are the members of maa_sampler_step_args by
+        name: integers and floats as they are, d_* as device tensors (fp32, or int32 for d_step / d_st), possibly views into larger
+        buffers, or raw addresses.  Nothing is allocated, copied or checked beyond what the C entry point checks."""
+        a = L.maa_sampler_step_args(kind=L.STEP_KINDS[kind])
+        known = {f[0] for f in L.maa_sampler_step_args._fields_}
+        for name, v in fields.items():
+            assert name in known, name
+            if torch.is_tensor(v):
+                assert v.is_cuda and v.dtype == (torch.int32 if name in ("d_step", "d_st") else torch.float32), (name, v.device, v.dtype)
+                v = v.data_ptr()
+            setattr(a, name, v)
+        self._call("maa_op_sampler_step", C.byref(a))
+
     def op_layernorm_ex(self, x, gamma, beta, eps=1e-5, out_split=0):
         """LayerNorm over the last dim of x [rows, C]; out_split = 1: the result as split32 rows in an fp32-typed tensor."""
         x = _f32(x, self.device)

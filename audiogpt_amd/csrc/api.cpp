@@ -1100,6 +1100,106 @@ int maa_op_seq_rows(maa_ctx* ctx, const maa_seq_rows_args* a) {
     });
 }
 
+int maa_op_sampler_step(maa_ctx* ctx, const maa_sampler_step_args* a) {
+    return guarded([&] {
+        MAA_CHECK(a != nullptr, "bad op_sampler_step arguments: null pointer");
+        const int k = a->kind;
+        MAA_CHECK(k >= MAA_STEP_DDIM_PREPARE && k <= MAA_STEP_DS_DDPM, "op_sampler_step: unknown kind");
+        const bool ds = k >= MAA_STEP_DS_PLMS;
+        const bool rows = k == MAA_STEP_DDIM_PREPARE || k == MAA_STEP_DDIM || k == MAA_STEP_PLMS || k == MAA_STEP_PLMS_EULER_MID ||
+                          k == MAA_STEP_DDPM;                                   // reads or writes d_xin [nB, per_in]
+        const bool stepped = !ds && k != MAA_STEP_DDIM_PREPARE;                 // reads the coefficient slot
+        bool ptrs = true;
+        if (rows) ptrs = ptrs && a->d_xin;
+        if (stepped) ptrs = ptrs && a->d_eps_u && a->d_coef && a->d_x;
+        if (stepped && k != MAA_STEP_PLMS_EULER_MID) ptrs = ptrs && a->d_step;
+        if (k == MAA_STEP_DDIM_PREPARE)
+            ptrs = ptrs && a->d_x && a->d_tab_t && a->d_tab && a->d_step && a->d_cur_t && a->d_coef &&
+                   (!a->d_emb_tab || a->d_cur_emb);
+        if (k == MAA_STEP_PLMS) ptrs = ptrs && a->d_ring;
+        if (k == MAA_STEP_PLMS_EULER_MID) ptrs = ptrs && a->d_e_keep && a->d_tab_t && a->d_cur_t && (!a->d_emb_tab || a->d_cur_emb);
+        if (k == MAA_STEP_PLMS_EULER_FINAL) ptrs = ptrs && a->d_e_keep;
+        if (k == MAA_STEP_DDPM) ptrs = ptrs && a->d_tab && a->d_noise_p;
+        if (k == MAA_STEP_DS_PLMS) ptrs = ptrs && a->d_x && a->d_eps_u && a->d_ring && a->d_tab && a->d_st;
+        if (k == MAA_STEP_DS_ADVANCE) ptrs = ptrs && a->d_st && a->d_cur_t;
+        if (k == MAA_STEP_DS_DDPM) ptrs = ptrs && a->d_x && a->d_eps_u && a->d_noise_p && a->d_tab && a->d_st;
+        MAA_CHECK(ptrs, "bad op_sampler_step arguments: null pointer");
+        if (k != MAA_STEP_PLMS_EULER_FINAL && k != MAA_STEP_DS_PLMS && k != MAA_STEP_DS_DDPM)
+            MAA_CHECK(a->B >= 1, "op_sampler_step: B < 1");
+        if (rows) {
+            MAA_CHECK(a->per >= 1 && a->per_in >= a->per, "op_sampler_step: per < 1 (one sample is per >= 1 floats, per_in >= per apart)");
+            MAA_CHECK(a->n == (int64_t)a->B * a->per, "op_sampler_step: n % per != 0 (n is B samples of per floats)");
+        } else if (k != MAA_STEP_DS_ADVANCE) {
+            MAA_CHECK(a->n >= 1, "op_sampler_step: n < 1");
+        }
+        if (k == MAA_STEP_DDIM_PREPARE)
+            MAA_CHECK(a->per_in == a->per || a->d_concat, "bad op_sampler_step arguments: null pointer (concat channels need d_concat)");
+        if (k == MAA_STEP_DDIM_PREPARE || k == MAA_STEP_PLMS_EULER_MID) {
+            MAA_CHECK(a->nB == a->B || a->nB == 2 * a->B, "op_sampler_step: nB is B or 2 B");
+            MAA_CHECK(a->nB <= 256, "op_sampler_step: nB > 256");
+            MAA_CHECK(a->emb_w >= 0 && a->n_t >= 0, "op_sampler_step: emb_w or n_t negative");
+        }
+        if (k == MAA_STEP_DDIM_PREPARE || k == MAA_STEP_DDIM || k == MAA_STEP_PLMS) MAA_CHECK(a->S >= 1, "op_sampler_step: S < 1");
+        if (k == MAA_STEP_DDIM_PREPARE || k == MAA_STEP_DDPM)
+            MAA_CHECK(!a->d_mask || (a->d_x0 && a->d_noise_q), "op_sampler_step: mask given without x0 and its noise");
+        if (stepped && k != MAA_STEP_PLMS_EULER_MID)
+            MAA_CHECK((a->d_log_x == nullptr) == (a->d_log_x0 == nullptr), "op_sampler_step: the two logs come both or neither");
+        if (k == MAA_STEP_DS_PLMS) {
+            MAA_CHECK(a->mode >= 0 && a->mode <= 2, "op_sampler_step: mode outside 0..2");
+            MAA_CHECK(a->mode != 2 || a->d_e_prev, "op_sampler_step: mode 2 needs e_prev");
+            MAA_CHECK(a->mode != 1 || a->d_x_out, "op_sampler_step: mode 1 needs x_out");
+        }
+        if (k == MAA_STEP_DS_PLMS || k == MAA_STEP_DS_ADVANCE) MAA_CHECK(a->interval >= 1, "op_sampler_step: interval < 1");
+        if (k == MAA_STEP_DS_ADVANCE) MAA_CHECK(a->B <= 256, "op_sampler_step: B > 256 (the step-advance kernel is one workgroup)");
+        if (k == MAA_STEP_DS_DDPM) {
+            MAA_CHECK(a->timesteps >= 1 && a->n_steps >= 1, "op_sampler_step: timesteps or n_steps < 1");
+            MAA_CHECK(a->n % 4 == 0 && (reinterpret_cast<uintptr_t>(a->d_x) | reinterpret_cast<uintptr_t>(a->d_eps_u) |
+                                        reinterpret_cast<uintptr_t>(a->d_noise_p)) % 16 == 0,
+                      "op_sampler_step: the ds ancestral step takes whole aligned float4s");
+        }
+        bind(ctx);
+        maa::Ctx& c = ctx->c;
+        switch (k) {
+        case MAA_STEP_DDIM_PREPARE:
+            maa::launch_ddim_prepare(c, a->d_x, a->d_concat, a->B, a->nB, a->per, a->per_in - a->per, a->d_tab_t, a->d_tab, a->d_step,
+                                     a->d_xin, a->d_cur_t, a->d_coef, a->d_mask, a->d_x0, a->d_noise_q, a->S, a->d_emb_tab, a->emb_w,
+                                     a->d_cur_emb, a->n_t);
+            break;
+        case MAA_STEP_DDIM:
+            maa::launch_ddim_step(c, a->d_xin, a->per, a->per_in, a->d_eps_u, a->d_eps_c, a->scale, a->d_coef, a->n, a->d_x, a->d_noise_p,
+                                  a->temperature, a->S, a->d_log_x, a->d_log_x0, a->d_step);
+            break;
+        case MAA_STEP_PLMS:
+            maa::launch_ldm_plms_step(c, a->d_xin, a->per, a->per_in, a->d_eps_u, a->d_eps_c, a->scale, a->d_coef, a->n, a->d_x, a->d_ring,
+                                      a->S, a->d_log_x, a->d_log_x0, a->d_step);
+            break;
+        case MAA_STEP_PLMS_EULER_MID:
+            maa::launch_ldm_plms_euler_mid(c, a->d_xin, a->per, a->per_in, a->B, a->nB, a->d_eps_u, a->d_eps_c, a->scale, a->d_coef, a->d_x,
+                                           a->d_e_keep, a->d_tab_t, a->d_cur_t, a->d_emb_tab, a->emb_w, a->d_cur_emb, a->n_t);
+            break;
+        case MAA_STEP_PLMS_EULER_FINAL:
+            maa::launch_ldm_plms_euler_final(c, a->d_eps_u, a->d_eps_c, a->scale, a->d_coef, a->n, a->d_x, a->d_e_keep, a->d_log_x,
+                                             a->d_log_x0, a->d_step);
+            break;
+        case MAA_STEP_DDPM:
+            maa::launch_ddpm_step(c, a->d_xin, a->per, a->per_in, a->d_eps_u, a->d_eps_c, a->scale, a->d_coef, a->d_tab, a->n, a->d_x,
+                                  a->d_noise_p, a->start, a->clip != 0, a->d_mask, a->d_x0, a->d_noise_q, a->d_log_x, a->d_log_x0,
+                                  a->d_step);
+            break;
+        case MAA_STEP_DS_PLMS:
+            maa::launch_ds_plms(c, a->d_x, a->d_eps_u, a->d_e_prev, a->d_ring, a->n, a->d_tab, a->interval, a->d_st, a->mode, a->d_x_out);
+            break;
+        case MAA_STEP_DS_ADVANCE:
+            maa::launch_ds_plms_advance(c, a->d_st, a->interval, a->d_cur_t, a->B);
+            break;
+        default:
+            maa::launch_ds_ddpm_step(c, a->d_x, a->d_eps_u, a->d_noise_p, a->n, a->d_tab, a->timesteps, a->d_st, a->start, a->n_steps,
+                                     a->clip != 0 ? 1 : 0);
+        }
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
 int maa_op_split32(maa_ctx* ctx, const float* d_x, int rows, int C, float slope, int unpack, float* d_y) {
     return guarded([&] {
         MAA_CHECK(d_x && d_y && d_x != d_y, "bad op_split32 arguments");

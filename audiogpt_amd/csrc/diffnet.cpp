@@ -21,22 +21,6 @@
 
 namespace maa {
 
-void launch_ds_pos_emb(const Ctx& ctx, const float* t, int B, int dim, float* out);
-void launch_ds_mish(const Ctx& ctx, const float* x, long long n, float* out);
-void launch_ds_add_step(const Ctx& ctx, const float* x, const float* step, int ld_step, long long rows, int T, int C,
-                        float* out);
-void launch_ds_gate(const Ctx& ctx, const float* y, long long rows, int C, float* z);
-void launch_ds_residual(const Ctx& ctx, const float* y2, long long rows, int T, int C, float* x, float* skip, int first,
-                        const float* next_step, int ld_step, float* xin);
-void launch_ds_plms(const Ctx& ctx, float* x, const float* e, const float* e_prev, float* hist, long long n,
-                    const float* ac, int interval, int* st, int mode, float* x_out);
-void launch_ds_plms_advance(const Ctx& ctx, int* st, int interval, float* t_slot, int B);
-void launch_ds_fill(const Ctx& ctx, float* p, int n, float v);
-void launch_ds_ddpm_step(const Ctx& ctx, float* x, const float* e, const float* noise, long long n, const float* tab,
-                         int timesteps, const int* st, int start, int n_steps, int clip);
-void launch_ds_ddpm_update(const Ctx& ctx, float* x, const float* e, const float* noise, int B, long long per, const float* t,
-                           const float* tab, int timesteps, int clip, int* bad);
-
 struct DiffNet::Impl {
     maa_diffnet_config cfg;
     int precision = 0;

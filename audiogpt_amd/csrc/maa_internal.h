@@ -401,6 +401,24 @@ void launch_ddpm_update(const Ctx& ctx, const float* x, const float* eps, const 
 void launch_ddim_stochastic_encode(const Ctx& ctx, const float* x0, const float* moments, float scale_factor, const float* n_post,
                                    const int* t, const float* tab, int n_tab, const float* noise, int B, long long per, float* out,
                                    int* bad);
+// DiffSinger's DiffNet elementwise kernels and the step kernels of its two sampling loops (diffsinger.hip; the kernels carry the
+// formulas).  ds_plms: st = {t, history count, ring head}, hist [3][n], mode 0 multistep / 1 predictor into x_out / 2 corrector;
+// ds_plms_advance: one workgroup, B <= 256; ds_ddpm_step / ds_ddpm_update: n (per) % 4 == 0, x / e / noise 16-byte aligned.
+void launch_ds_pos_emb(const Ctx& ctx, const float* t, int B, int dim, float* out);
+void launch_ds_mish(const Ctx& ctx, const float* x, long long n, float* out);
+void launch_ds_add_step(const Ctx& ctx, const float* x, const float* step, int ld_step, long long rows, int T, int C,
+                        float* out);
+void launch_ds_gate(const Ctx& ctx, const float* y, long long rows, int C, float* z);
+void launch_ds_residual(const Ctx& ctx, const float* y2, long long rows, int T, int C, float* x, float* skip, int first,
+                        const float* next_step, int ld_step, float* xin);
+void launch_ds_plms(const Ctx& ctx, float* x, const float* e, const float* e_prev, float* hist, long long n,
+                    const float* ac, int interval, int* st, int mode, float* x_out);
+void launch_ds_plms_advance(const Ctx& ctx, int* st, int interval, float* t_slot, int B);
+void launch_ds_fill(const Ctx& ctx, float* p, int n, float v);
+void launch_ds_ddpm_step(const Ctx& ctx, float* x, const float* e, const float* noise, long long n, const float* tab,
+                         int timesteps, const int* st, int start, int n_steps, int clip);
+void launch_ds_ddpm_update(const Ctx& ctx, float* x, const float* e, const float* noise, int B, long long per, const float* t,
+                           const float* tab, int timesteps, int clip, int* bad);
 // BigVGAN Activation1d on [B, L, C]: up2 FIR -> snake -> down2 FIR (replicate padding)
 void launch_snake_aa(const Ctx& ctx, const float* x, int B, int L, int C, const float* inv_beta, const float* alpha,
                      float* out);

@@ -732,6 +732,75 @@ typedef struct {
     int* d_dur;
 } maa_seq_rows_args;
 int maa_op_seq_rows(maa_ctx* ctx, const maa_seq_rows_args* args);
+/* One step kernel of the sampling loops exactly as the loops launch it (tests of the ddim_* / ldm_plms_* / ddpm_step kernels of
+ * misc.hip and the ds_* step kernels of diffsinger.hip): `kind` selects one internal launch, the entry forwards every argument
+ * of it, synchronises the stream once and does nothing else.  EVERY buffer is the caller's DEVICE pointer and is passed through
+ * unchanged -- the coefficient slot, the device step index, the tables, the ring, the loop state: no hidden state, no workspace.
+ * n = B * per elements of the latent, one sample per `per`; the step's model input d_xin holds nB rows of per_in >= per floats
+ * (nB = 2 B: the classifier-free-guidance duplicate, [uncond ; cond]; per_in > per: concat channels behind the latent).  kind:
+ *   MAA_STEP_DDIM_PREPARE      idx = *d_step: d_xin [nB, per_in] = cat(d_x [B, per], d_concat [B, per_in - per]) per row (the
+ *                              latent first blended with d_mask / d_x0 / draw S - 1 - idx of d_noise_q [S, n] when d_mask),
+ *                              d_cur_t [n_t] (n_t <= 0: nB) = d_tab_t[idx], d_coef [8] = row idx of d_tab [S, 8], d_cur_emb
+ *                              [emb_w] = row idx of d_emb_tab (or NULL).
+ *   MAA_STEP_DDIM              the DDIM update: e = d_eps_u (+ scale (d_eps_c - d_eps_u)), x from the first B rows of d_xin,
+ *                              d_coef [8] = {a_t, a_prev, sigma, sqrt(1 - a_t), -, -, log slot, idx}, d_x [n] = x_prev, noise
+ *                              sigma z temperature with z = draw S - 1 - idx of d_noise_p (or NULL), slab `log slot` of d_log_x
+ *                              / d_log_x0 (slot -1: none), *d_step = idx - 1.
+ *   MAA_STEP_PLMS              PLMSSampler's steps i = S - 1 - idx >= 1 over d_ring [3, n]; otherwise as MAA_STEP_DDIM, no noise.
+ *   MAA_STEP_PLMS_EULER_MID    its step 0 after the first evaluation: e -> d_e_keep, x -> d_x (the saved latent), x_mid -> the
+ *                              latent channels of all nB rows of d_xin, d_cur_t / d_cur_emb to d_tab_t[max(idx - 1, 0)].
+ *   MAA_STEP_PLMS_EULER_FINAL  its step 0 after the second evaluation: d_x in place from (d_e_keep + e) / 2, logs, *d_step.
+ *   MAA_STEP_DDPM              one ancestral step, t = d_coef[7], row t of d_tab [T, 9] = {sqrt_recip_ac, sqrt_recipm1_ac, coef1,
+ *                              coef2, sd, temperature, sqrt_ac, sqrt_1mac, log slot}, draw start - t of d_noise_p and (blend
+ *                              after the step, when d_mask) d_noise_q; `clip` clamps x_recon; *d_step = t - 1.
+ *   MAA_STEP_DS_PLMS           DiffSinger's PLMS step on d_x [n] with e = d_eps_u, d_tab = alphas_cumprod, d_st = {t, history
+ *                              count, ring head}, d_ring [3, n]; mode 0: a multistep step, 1: the predictor into d_x_out (d_x and
+ *                              the ring untouched), 2: the corrector with d_e_prev.
+ *   MAA_STEP_DS_ADVANCE        d_st = {t - interval, count + 1, (head + 1) % 3}, d_cur_t [B] = max(t - interval, 0); B <= 256.
+ *   MAA_STEP_DS_DDPM           DiffSinger's ancestral step on d_x [n] in place, t = d_st[0], row t of d_tab [timesteps, 5], draw
+ *                              start - t of d_noise_p [n_steps, n]; n % 4 == 0 and d_x / d_eps_u / d_noise_p 16-byte aligned.
+ * Checked here, before the context is touched: null pointers per kind, B, per, n, nB, S, mode, mask without x0 and its noise.
+ * The index a kernel reads from a device slot cannot be checked here: the caller keeps it inside its table. */
+#define MAA_STEP_DDIM_PREPARE 0
+#define MAA_STEP_DDIM 1
+#define MAA_STEP_PLMS 2
+#define MAA_STEP_PLMS_EULER_MID 3
+#define MAA_STEP_PLMS_EULER_FINAL 4
+#define MAA_STEP_DDPM 5
+#define MAA_STEP_DS_PLMS 6
+#define MAA_STEP_DS_ADVANCE 7
+#define MAA_STEP_DS_DDPM 8
+typedef struct {
+    int kind;
+    int B, nB, S;
+    int64_t n, per, per_in;
+    float scale, temperature;
+    int start, clip, mode, interval, timesteps, n_steps, emb_w, n_t;
+    float* d_x;
+    const float* d_concat;
+    float* d_xin;
+    const float* d_eps_u;
+    const float* d_eps_c;
+    const float* d_e_prev;
+    float* d_coef;
+    const float* d_tab_t;
+    const float* d_tab;
+    int* d_step;
+    int* d_st;
+    float* d_cur_t;
+    const float* d_emb_tab;
+    float* d_cur_emb;
+    const float* d_mask;
+    const float* d_x0;
+    const float* d_noise_q;
+    const float* d_noise_p;
+    float* d_ring;
+    float* d_e_keep;
+    float* d_x_out;
+    float* d_log_x;
+    float* d_log_x0;
+} maa_sampler_step_args;
+int maa_op_sampler_step(maa_ctx* ctx, const maa_sampler_step_args* args);
 /* The split32 row codec on its own, d_x / d_y [rows,C] on the device, C % 32 == 0: unpack = 0 writes the split32 rows of
  * leaky_relu(x, slope) (slope 1: of x), unpack = 1 reads split32 rows and writes hi + lo as fp32 (slope is ignored). */
 int maa_op_split32(maa_ctx* ctx, const float* d_x, int rows, int C, float slope, int unpack, float* d_y);

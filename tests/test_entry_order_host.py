@@ -69,6 +69,9 @@ def _configs():
                                      KW=1, stride=1, dil=1, pad_h=-1, alpha=1.0, out_scale=1.0, d_c=_base, ldc=32),
         L.maa_seq_rows_args: _struct(L.maa_seq_rows_args, kind=L.SEQ_KINDS["head"], rows=1, C=32, d_x=_base, d_mask=_base, h_gamma=_fp,
                                      h_beta=_fp, h_w=_fp, h_bias=_fp, eps=1e-5, n_out=2, d_out=_base, d_out2=_base),
+        L.maa_sampler_step_args: _struct(L.maa_sampler_step_args, kind=L.STEP_KINDS["ddim"], B=1, nB=1, S=2, n=8, per=8, per_in=8,
+                                         scale=1.0, temperature=1.0, d_x=_base, d_xin=_base + 256, d_eps_u=_base + 512,
+                                         d_coef=_base + 768, d_step=_base + 1024),
         L.maa_prof_row: C.cast(_base, C.POINTER(L.maa_prof_row)),
         L.maa_tensor: None,          # an empty tensor list, with n_tensors = 0
     }

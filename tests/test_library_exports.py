@@ -159,6 +159,106 @@ def test_sequence_row_test_entry_is_bound_and_refuses_by_name(lib_path):
     assert lib.maa_op_seq_rows(None, ctypes.byref(_lib.maa_seq_rows_args(kind=5))) < 0 and b"unknown kind" in lib.maa_last_error()
 
 
+def test_sampler_step_test_entry_is_bound_and_refuses_by_name(lib_path):
+    """maa_op_sampler_step (tests/test_gpu_sampler_ops.py) is declared, exported, bound with the header's argument count and a
+    structure that has the header's fields in the header's order and the size the header's types give, and every host-side refusal
+    comes back with its own message before the context is touched."""
+    from audiogpt_amd import _lib
+    lib = _lib.load()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "maa.h")).read(), flags=re.S)
+    name = "maa_op_sampler_step"
+    assert name in _lib.EXPORTS and name in _declared_symbols()
+    decl = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
+    assert len(getattr(lib, name).argtypes) == len(decl.split(",")) == 2, name
+    body = re.search(r"typedef struct \{([^}]*)\} maa_sampler_step_args;", src).group(1)
+    ctype = {"int": ctypes.c_int, "float": ctypes.c_float, "int64_t": ctypes.c_int64}
+    fields = []
+    for stmt in body.split(";"):
+        stmt = stmt.strip()
+        if stmt:
+            m = re.match(r"^(?:const\s+)?(float|int64_t|int)\s*(\*?)\s*(.*)$", stmt)
+            fields += [(f.strip(), ctypes.c_void_p if m.group(2) else ctype[m.group(1)]) for f in m.group(3).split(",")]
+    assert fields == list(_lib.maa_sampler_step_args._fields_)
+
+    class Mirror(ctypes.Structure):          # the header's fields under the C layout rules
+        _fields_ = fields
+    assert ctypes.sizeof(Mirror) == ctypes.sizeof(_lib.maa_sampler_step_args) == 16 + 3 * 8 + 2 * 4 + 8 * 4 + 23 * 8
+    for kind, value in _lib.STEP_KINDS.items():
+        assert re.search(r"#define MAA_STEP_%s %d\b" % (kind.upper(), value), src), kind
+    assert len(set(_lib.STEP_KINDS.values())) == 9
+    assert lib.maa_op_sampler_step(None, None) < 0 and b"null pointer" in lib.maa_last_error()
+    import numpy as np
+    buf = np.zeros(256, np.float32)
+    dp = buf.ctypes.data + (-buf.ctypes.data) % 16          # stands in for device memory; never read
+    ldm = dict(B=2, nB=4, S=4, n=16, per=8, per_in=8, scale=3.0, temperature=1.0)
+    base = {
+        "ddim_prepare": dict(ldm, d_x=dp, d_tab_t=dp, d_tab=dp, d_step=dp, d_xin=dp, d_cur_t=dp, d_coef=dp),
+        "ddim": dict(ldm, d_xin=dp, d_eps_u=dp, d_coef=dp, d_x=dp, d_step=dp),
+        "plms": dict(ldm, d_xin=dp, d_eps_u=dp, d_coef=dp, d_x=dp, d_step=dp, d_ring=dp),
+        "plms_euler_mid": dict(ldm, d_xin=dp, d_eps_u=dp, d_coef=dp, d_x=dp, d_e_keep=dp, d_tab_t=dp, d_cur_t=dp),
+        "plms_euler_final": dict(ldm, d_eps_u=dp, d_coef=dp, d_x=dp, d_e_keep=dp, d_step=dp),
+        "ddpm": dict(ldm, d_xin=dp, d_eps_u=dp, d_coef=dp, d_tab=dp, d_x=dp, d_noise_p=dp, d_step=dp),
+        "ds_plms": dict(n=16, interval=10, mode=0, d_x=dp, d_eps_u=dp, d_ring=dp, d_tab=dp, d_st=dp),
+        "ds_advance": dict(B=2, interval=10, d_st=dp, d_cur_t=dp),
+        "ds_ddpm": dict(n=16, timesteps=5, n_steps=5, start=4, d_x=dp, d_eps_u=dp, d_noise_p=dp, d_tab=dp, d_st=dp),
+    }
+    assert sorted(base) == sorted(_lib.STEP_KINDS)
+
+    def refused(kind, message, **kw):
+        d = dict(base[kind], kind=_lib.STEP_KINDS[kind])
+        d.update(kw)
+        st = lib.maa_op_sampler_step(None, ctypes.byref(_lib.maa_sampler_step_args(**d)))
+        assert st < 0 and message in lib.maa_last_error(), (kind, kw, lib.maa_last_error())
+
+    rows = ("ddim_prepare", "ddim", "plms", "plms_euler_mid", "ddpm")
+    for kind in base:
+        refused(kind, b"null context")                                  # past every argument check
+        for p in [k for k in base[kind] if k.startswith("d_")]:
+            refused(kind, b"null pointer", **{p: None})
+        if kind in rows:
+            refused(kind, b"B < 1", B=0)
+            refused(kind, b"per < 1", per=0)
+            refused(kind, b"per < 1", per_in=4)
+            refused(kind, b"n % per != 0", n=17)
+            refused(kind, b"n % per != 0", n=24)
+        elif kind != "ds_advance":
+            refused(kind, b"n < 1", n=0)
+    for kind in ("ddim_prepare", "plms_euler_mid"):
+        refused(kind, b"nB is B or 2 B", nB=3)
+        refused(kind, b"null context", nB=2)
+        refused(kind, b"nB > 256", B=129, nB=258, n=129 * 8)
+        refused(kind, b"null pointer", d_emb_tab=dp)                      # an embedding table needs its slot
+        refused(kind, b"null context", d_emb_tab=dp, d_cur_emb=dp, emb_w=4)
+    refused("ddim_prepare", b"null pointer", per_in=12)                   # concat channels need d_concat
+    refused("ddim_prepare", b"null context", per_in=12, d_concat=dp)
+    for kind in ("ddim_prepare", "ddim", "plms"):
+        refused(kind, b"S < 1", S=0)
+    for kind in ("ddim_prepare", "ddpm"):
+        refused(kind, b"mask given without x0", d_mask=dp)
+        refused(kind, b"mask given without x0", d_mask=dp, d_x0=dp)
+        refused(kind, b"null context", d_mask=dp, d_x0=dp, d_noise_q=dp)
+    for kind in ("ddim", "plms", "plms_euler_final", "ddpm"):
+        refused(kind, b"both or neither", d_log_x=dp)
+        refused(kind, b"null context", d_log_x=dp, d_log_x0=dp)
+    refused("ds_plms", b"mode outside 0..2", mode=3)
+    refused("ds_plms", b"mode outside 0..2", mode=-1)
+    refused("ds_plms", b"mode 2 needs e_prev", mode=2)
+    refused("ds_plms", b"mode 1 needs x_out", mode=1)
+    refused("ds_plms", b"null context", mode=2, d_e_prev=dp)
+    refused("ds_plms", b"null context", mode=1, d_x_out=dp)
+    refused("ds_plms", b"interval < 1", interval=0)
+    refused("ds_advance", b"interval < 1", interval=0)
+    refused("ds_advance", b"B < 1", B=0)
+    refused("ds_advance", b"B > 256", B=257)
+    refused("ds_advance", b"null context", B=256)
+    refused("ds_ddpm", b"timesteps or n_steps < 1", timesteps=0)
+    refused("ds_ddpm", b"whole aligned float4s", n=18)
+    refused("ds_ddpm", b"whole aligned float4s", d_x=dp + 4)
+    for kind in (-1, 9):
+        assert lib.maa_op_sampler_step(None, ctypes.byref(_lib.maa_sampler_step_args(kind=kind))) < 0
+        assert b"unknown kind" in lib.maa_last_error()
+
+
 def test_contraction_test_entry_is_bound_and_rejects_null(lib_path):
     """maa_op_igemm_ex (tests/test_gpu_igemm_ops.py) is declared, exported, bound with the header's argument count and a structure
     that has the header's fields in the header's order, and fails with a message on null arguments, on a pitch below its width and
