@@ -92,7 +92,8 @@ class maa_fs2_config(C.Structure):
         "vocab_size", "hidden_size", "enc_layers", "dec_layers", "num_heads", "enc_ffn_kernel_size", "dec_ffn_kernel_size",
         "dur_predictor_layers", "dur_predictor_kernel", "predictor_hidden", "audio_num_mel_bins",
         "ffn_padding_same", "ffn_act_gelu", "dur_loss_mse", "rel_pos", "use_pos_embed", "encoder_fft", "decoder_fft",
-        "use_pitch_embed", "use_energy_embed", "use_spk_id", "use_spk_embed", "use_bert")]
+        "use_pitch_embed", "use_energy_embed", "use_spk_id", "use_spk_embed", "use_bert",
+        "plain", "num_spk", "use_split_spk_id", "predictor_layers", "predictor_kernel")]
 
 
 class maa_fs2_pitch_config(C.Structure):
@@ -217,12 +218,17 @@ SIGNATURES = {
     "maa_fs2_create": [vp, C.POINTER(maa_fs2_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
     "maa_fs2_destroy": [vp],
     "maa_fs2_encode": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
+    "maa_fs2_encode_plain": [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
+    "maa_fs2_speaker": [vp, vp, vp, vp, ci, vp],
+    "maa_fs2_add_speaker": [vp, vp, vp, vp, vp, ci, ci, vp],
+    "maa_fs2_finish": [vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp],
     "maa_fs2_length_regulate": [vp, vp, vp, ci, ci, ci, vp],
     "maa_fs2_decode": [vp, vp, vp, vp, ci, ci, ci, vp, vp],
     "maa_fs2_run_decoder": [vp, vp, vp, vp, ci, ci, vp],
     "maa_fs2_pitch_create": [vp, C.POINTER(maa_fs2_pitch_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
     "maa_fs2_pitch_destroy": [vp],
     "maa_fs2_pitch_forward": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
+    "maa_fs2_pitch_forward_from": [vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
     "maa_encoder_create": [vp, C.POINTER(maa_encoder_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
     "maa_encoder_destroy": [vp],
     "maa_encoder_text": [vp, vp, vp, ci, ci, vp],

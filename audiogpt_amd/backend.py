@@ -1246,6 +1246,141 @@ class FastSpeech2MIDI(_Handle):
         return mel
 
 
+def fs2_plain_config(cfg):
+    """maa_fs2_config (plain = 1) of a plain FastSpeech2 hparams dict (config.FASTSPEECH2) with use_pitch_embed cleared -- the
+    pitch branch is FS2Pitch beside the handle; refuses what the library does not build, with the reason, before any device is
+    touched."""
+    what = "FastSpeech2"
+    if cfg.get("use_pitch_embed", False):
+        raise L.MaaError("%s: use_pitch_embed is not supported by this handle: the pitch branch is FS2Pitch beside it, composed by "
+                         "diffsinger.FastSpeech2" % what)
+    if cfg.get("use_bert", False):
+        raise L.MaaError("%s: use_bert is not supported: BERTRelTransformerEncoder and its word-level features are not built" % what)
+    if not cfg.get("use_pos_embed", True):
+        raise L.MaaError("%s: use_pos_embed must be true: an encoder without positions is not built" % what)
+    if cfg.get("use_spk_id", False) and cfg.get("use_spk_embed", False):
+        raise L.MaaError("%s: use_spk_id and use_spk_embed are alternatives (the reference takes use_spk_id when both are set): "
+                         "set one" % what)
+    if cfg.get("use_split_spk_id", False) and not cfg.get("use_spk_id", False):
+        raise L.MaaError("%s: use_split_spk_id without use_spk_id: the reference builds no table for it" % what)
+    if cfg.get("use_spk_id", False) and int(cfg.get("num_spk", 0)) < 1:
+        raise L.MaaError("%s: use_spk_id needs num_spk >= 1 (the tables have num_spk + 1 rows)" % what)
+    pad = cfg.get("ffn_padding", "SAME")
+    if pad != "SAME":
+        raise L.MaaError("%s: ffn_padding %r is not supported: only 'SAME' (kernel // 2 zeros on both sides) is built, "
+                         "the causal 'LEFT' padding (kernel - 1, 0) is not" % (what, pad))
+    if cfg.get("ffn_act", "gelu") != "gelu":
+        raise L.MaaError("%s: ffn_act %r is not supported: only 'gelu' is built into the FFN's epilogue" % (what, cfg.get("ffn_act")))
+    if cfg.get("dur_loss", "mse") != "mse":
+        raise L.MaaError("%s: dur_loss %r is not supported: only 'mse' (round(exp(x) - 1)) is built" % (what, cfg.get("dur_loss")))
+    for k in ("encoder_type", "decoder_type"):
+        if cfg.get(k, "fft") != "fft":
+            raise L.MaaError("%s: %s %r is not supported: only 'fft' (FFTBlocks) is built" % (what, k, cfg.get(k)))
+    H, nh = int(cfg["hidden_size"]), int(cfg["num_heads"])
+    if nh < 1 or H != 128 * nh:
+        raise L.MaaError("%s: hidden_size %d / num_heads %d is not 128, the only head width the masked attention is "
+                         "built and tested for" % (what, H, nh))
+    c = L.maa_fs2_config()
+    for k in ("vocab_size", "hidden_size", "enc_layers", "dec_layers", "num_heads", "enc_ffn_kernel_size", "dec_ffn_kernel_size",
+              "audio_num_mel_bins"):
+        setattr(c, k, int(cfg[k]))
+    c.dur_predictor_layers, c.dur_predictor_kernel = int(cfg.get("dur_predictor_layers", 5)), int(cfg.get("dur_predictor_kernel", 3))
+    c.predictor_hidden = int(cfg.get("predictor_hidden", -1))
+    c.predictor_layers, c.predictor_kernel = int(cfg.get("predictor_layers", 5)), int(cfg.get("predictor_kernel", 5))
+    c.ffn_padding_same = c.ffn_act_gelu = c.dur_loss_mse = c.use_pos_embed = c.encoder_fft = c.decoder_fft = c.plain = 1
+    c.rel_pos = int(bool(cfg.get("rel_pos", False)))
+    c.use_energy_embed = int(bool(cfg.get("use_energy_embed", False)))
+    c.use_spk_id, c.use_spk_embed = int(bool(cfg.get("use_spk_id", False))), int(bool(cfg.get("use_spk_embed", False)))
+    c.use_split_spk_id = int(bool(cfg.get("use_split_spk_id", False)))
+    c.num_spk = int(cfg.get("num_spk", 0)) if c.use_spk_id else 0
+    return c
+
+
+class FastSpeech2Plain(FastSpeech2MIDI):
+    """maa_fs2 handle created with plain = 1: the reference's plain FastSpeech2 (NeuralSeq/modules/fastspeech/fs2.py) without its
+    pitch branch.  length_regulate, decode and run_decoder are FastSpeech2MIDI's; nothing here reads the device."""
+
+    def __init__(self, ctx, cfg, state_dict):
+        self.cfg = dict(cfg)
+        self._create(ctx, "maa_fs2_create", C.byref(fs2_plain_config(self.cfg)), state_dict=state_dict)
+
+    def encode(self, txt_tokens, spk_dur=None):
+        """[B, T] tokens, spk_dur [B, H] or None -> (encoder_out [B, T, H], xs [B, T], dur int32 [B, T], totals int32 [B])."""
+        tok = self._i32(txt_tokens)
+        B, T = tok.shape
+        H = self.cfg["hidden_size"]
+        spk_dur = _f32(spk_dur, self.ctx.device) if spk_dur is not None else None
+        if spk_dur is not None and tuple(spk_dur.shape) != (B, H):
+            raise L.MaaError("FastSpeech2Plain.encode: spk_dur %s is not [%d, %d]" % (tuple(spk_dur.shape), B, H))
+        enc = self._empty(B, T, H)
+        xs = self._empty(B, T)
+        dur = self._empty(B, T, dtype=torch.int32)
+        totals = self._empty(B, dtype=torch.int32)
+        self._call("maa_fs2_encode_plain", self._p(tok), self._p(spk_dur), B, T, self._p(enc), self._p(xs), self._p(dur),
+                   self._p(totals))
+        return enc, xs, dur, totals
+
+    def speaker(self, ids=None, vec=None):
+        """ids int [3, B] (speaker, dur, f0 ids) for a use_spk_id handle, vec [B, 256] for a use_spk_embed one -> [3, B, H]:
+        spk_embed, spk_embed_dur, spk_embed_f0."""
+        if ids is None and vec is None:
+            raise L.MaaError("FastSpeech2Plain.speaker: neither ids nor vec")
+        ids = self._i32(ids) if ids is not None else None
+        vec = _f32(vec, self.ctx.device) if vec is not None else None
+        if ids is not None and (ids.dim() != 2 or ids.shape[0] != 3 or ids.shape[1] < 1):
+            raise L.MaaError("FastSpeech2Plain.speaker: ids %s is not [3, B]" % (tuple(ids.shape),))
+        if vec is not None and (vec.dim() != 2 or vec.shape[1] != 256 or vec.shape[0] < 1):
+            raise L.MaaError("FastSpeech2Plain.speaker: vec %s is not [B, 256]" % (tuple(vec.shape),))
+        B = int(ids.shape[1] if ids is not None else vec.shape[0])
+        if ids is not None and vec is not None and vec.shape[0] != B:
+            raise L.MaaError("FastSpeech2Plain.speaker: ids and vec disagree on B")
+        out = self._empty(3, B, self.cfg["hidden_size"])
+        self._call("maa_fs2_speaker", self._p(ids), self._p(vec), B, self._p(out))
+        return out
+
+    def _frames(self, what, x, mel2ph):
+        x = _f32(x, self.ctx.device)
+        m2p = self._i32(mel2ph)
+        if x.dim() != 3 or x.shape[2] != self.cfg["hidden_size"] or x.shape[0] < 1 or x.shape[1] < 1:
+            raise L.MaaError("FastSpeech2Plain.%s: %s is not [B, T_mel, %d]" % (what, tuple(x.shape), self.cfg["hidden_size"]))
+        if tuple(m2p.shape) != tuple(x.shape[:2]):
+            raise L.MaaError("FastSpeech2Plain.%s: mel2ph %s is not %s" % (what, tuple(m2p.shape), tuple(x.shape[:2])))
+        return x, m2p
+
+    def _spk(self, what, spk, B):
+        if spk is None:
+            return None
+        spk = _f32(spk, self.ctx.device)
+        if tuple(spk.shape) != (B, self.cfg["hidden_size"]):
+            raise L.MaaError("FastSpeech2Plain.%s: the speaker vector %s is not [%d, %d]" % (what, tuple(spk.shape), B, self.cfg["hidden_size"]))
+        return spk
+
+    def add_speaker(self, x, spk, mel2ph):
+        """(x [B, T_mel, H] + spk [B, H]) * (mel2ph > 0): the pitch and energy predictors' input."""
+        x, m2p = self._frames("add_speaker", x, mel2ph)
+        B, T_mel, H = x.shape
+        out = self._empty(B, T_mel, H)
+        self._call("maa_fs2_add_speaker", self._p(x), self._p(self._spk("add_speaker", spk, B)), self._p(m2p), B, T_mel, self._p(out))
+        return out
+
+    def finish(self, pred_inp, acc, mel2ph, energy=None, spk=None, return_bin=False):
+        """The energy branch (when the handle has one) on pred_inp, then decoder_inp = (acc + energy_embed[bin] + spk[b]) *
+        (mel2ph > 0) -> (decoder_inp [B, T_mel, H], energy_pred [B, T_mel] or None[, energy_bin int32 [B, T_mel] or None])."""
+        acc, m2p = self._frames("finish", acc, mel2ph)
+        B, T_mel, H = acc.shape
+        has = bool(self.cfg.get("use_energy_embed", False))
+        pred_inp = self._frames("finish", pred_inp, m2p)[0] if has else None
+        energy = _f32(energy, self.ctx.device) if energy is not None and has else None
+        if energy is not None and tuple(energy.shape) != (B, T_mel):
+            raise L.MaaError("FastSpeech2Plain.finish: energy %s is not [%d, %d]" % (tuple(energy.shape), B, T_mel))
+        dec_inp = self._empty(B, T_mel, H)
+        energy_pred = self._empty(B, T_mel) if has else None
+        energy_bin = self._empty(B, T_mel, dtype=torch.int32) if has and return_bin else None
+        self._call("maa_fs2_finish", self._p(pred_inp), self._p(acc), self._p(m2p), self._p(energy), self._p(self._spk("finish", spk, B)),
+                   B, T_mel, self._p(dec_inp), self._p(energy_pred), self._p(energy_bin))
+        return (dec_inp, energy_pred, energy_bin) if return_bin else (dec_inp, energy_pred)
+
+
 def fs2_pitch_config(cfg):
     """maa_fs2_pitch_config of a FastSpeech2MIDI hparams dict with use_pitch_embed (config.FASTSPEECH2_MIDI_CASCADE); refuses what
     the library does not build, with the reason, before any device is touched."""
@@ -1296,10 +1431,11 @@ class FS2Pitch(_Handle):
         self.cfg = dict(cfg)
         self._create(ctx, "maa_fs2_pitch_create", C.byref(fs2_pitch_config(self.cfg)), state_dict=state_dict)
 
-    def forward(self, origin, mel2ph, f0=None, uv=None, return_coarse=False):
+    def forward(self, origin, mel2ph, f0=None, uv=None, return_coarse=False, pred_inp=None):
         """origin [B, T_mel, H] (FastSpeech2MIDI.decode's decoder_inp: 0 where mel2ph is 0), mel2ph [B, T_mel], f0 / uv [B, T_mel]
         or None each (the caller's normalised f0 and unvoiced flags; neither is written) -> (decoder_inp [B, T_mel, H], pitch_pred
-        [B, T_mel, 2], f0_denorm [B, T_mel]) on the device; with return_coarse also coarse int32 [B, T_mel], the pitch_embed rows."""
+        [B, T_mel, 2], f0_denorm [B, T_mel]) on the device; with return_coarse also coarse int32 [B, T_mel], the pitch_embed rows.
+        pred_inp [B, T_mel, H]: the predictor's input where it is not origin (a model with speakers: (origin + spk_f0) * tgt)."""
         dev = self.ctx.device
         x = _f32(origin, dev)
         m2p = torch.as_tensor(mel2ph).to(device=dev, dtype=torch.int32).contiguous()
@@ -1318,8 +1454,15 @@ class FS2Pitch(_Handle):
         f0_denorm = self._empty(B, T_mel)
         coarse = self._empty(B, T_mel, dtype=torch.int32) if return_coarse else None
         p = FastSpeech2MIDI._p
-        self._call("maa_fs2_pitch_forward", p(x), p(m2p), p(f0), p(uv), B, T_mel, p(dec_inp), p(pitch_pred), p(f0_denorm),
-                   p(coarse))
+        if pred_inp is not None:
+            pi = _f32(pred_inp, dev)
+            if tuple(pi.shape) != (B, T_mel, H):
+                raise L.MaaError("FS2Pitch.forward: pred_inp %s is not origin's [%d, %d, %d]" % (tuple(pi.shape), B, T_mel, H))
+            self._call("maa_fs2_pitch_forward_from", p(pi), p(x), p(m2p), p(f0), p(uv), B, T_mel, p(dec_inp), p(pitch_pred),
+                       p(f0_denorm), p(coarse))
+        else:
+            self._call("maa_fs2_pitch_forward", p(x), p(m2p), p(f0), p(uv), B, T_mel, p(dec_inp), p(pitch_pred), p(f0_denorm),
+                       p(coarse))
         return (dec_inp, pitch_pred, f0_denorm, coarse) if return_coarse else (dec_inp, pitch_pred, f0_denorm)
 
     __call__ = forward

@@ -135,6 +135,20 @@ FASTSPEECH2_MIDI = dict(vocab_size=64, hidden_size=256, enc_layers=4, dec_layers
 FASTSPEECH2_MIDI_CASCADE = dict(FASTSPEECH2_MIDI, use_pitch_embed=True, pitch_type="frame", use_uv=True, pitch_norm="log",
                                 pitch_ar=False, predictor_layers=5, predictor_kernel=5, f0_mean=0.0, f0_std=1.0)
 
+# The plain FastSpeech2 (modules/fastspeech/fs2.py) of the TTS configurations: egs_bases/tts/fs2.yaml over egs_bases/tts/base.yaml
+# (4 + 4 layers, 2 heads, 9-tap FFNs, dur_predictor 2 layers / kernel 3, predictor 2 layers / kernel 5, the frame-level pitch branch
+# with a voicing logit, pitch_norm standard; no rel_pos: sinusoid positions by token count; use_energy_embed false).  vocab_size is
+# a placeholder as above; f0_mean / f0_std are the data set's statistics, written into hparams by its binarizer -- placeholders.
+# It is also the `fs2` of both *_ds_beta6 chains (DIFFSPEECH_LJ_BETA6, DIFFSINGER_POPCS_BETA6).
+FASTSPEECH2 = dict(vocab_size=64, hidden_size=256, enc_layers=4, dec_layers=4, num_heads=2, enc_ffn_kernel_size=9,
+                   dec_ffn_kernel_size=9, dur_predictor_layers=2, dur_predictor_kernel=3, predictor_hidden=-1, predictor_layers=2,
+                   predictor_kernel=5, audio_num_mel_bins=80, ffn_padding="SAME", ffn_act="gelu", dur_loss="mse", rel_pos=False,
+                   use_pos_embed=True, encoder_type="fft", decoder_type="fft", use_pitch_embed=True, pitch_type="frame", use_uv=True,
+                   pitch_norm="standard", pitch_ar=False, f0_mean=220.0, f0_std=60.0, use_energy_embed=False, use_spk_id=False,
+                   use_split_spk_id=False, use_spk_embed=False, num_spk=1, use_bert=False)
+# egs/datasets/audio/libritts/fs2.yaml (use_spk_id true, num_spk 2320; vctk/fs2.yaml: 400)
+FASTSPEECH2_LIBRITTS = dict(FASTSPEECH2, use_spk_id=True, num_spk=2320)
+
 # BigVGAN's args.yml (vocoder/logs/bigv16k53w) does not ship with the reference
 # (SURVEY.md section 0.3); these are the generator defaults it is exercised with here.
 BIGVGAN_16K = dict(

@@ -516,11 +516,23 @@ int maa_fs2_create(maa_ctx* ctx, const maa_fs2_config* cfg, const maa_tensor* te
     return guarded([&] {
         MAA_CHECK(cfg && out, "bad fs2_create arguments: null pointer");
         MAA_CHECK(!cfg->use_pitch_embed, "FastSpeech2MIDI: hparams['use_pitch_embed'] is not built into this handle -- the pitch branch is maa_fs2_pitch, beside it");
-        MAA_CHECK(!cfg->use_energy_embed, "FastSpeech2MIDI: hparams['use_energy_embed'] is not built -- no shipped e2e singing configuration sets it");
-        MAA_CHECK(!cfg->use_spk_id && !cfg->use_spk_embed,
-                  "FastSpeech2MIDI: hparams['use_spk_id'] / ['use_spk_embed'] are not built -- no shipped e2e singing configuration sets them");
+        if (cfg->plain) {      // the plain FastSpeech2: energy, speakers and the token-counted sinusoid positions live in this handle
+            MAA_CHECK(cfg->use_pos_embed != 0, "FastSpeech2: hparams['use_pos_embed'] must be true -- an encoder without positions is not built");
+            MAA_CHECK(!(cfg->use_spk_id && cfg->use_spk_embed),
+                      "FastSpeech2: hparams['use_spk_id'] and ['use_spk_embed'] are alternatives (fs2.py:41-47) -- set one");
+            MAA_CHECK(!cfg->use_spk_id || (cfg->num_spk >= 1 && cfg->num_spk < (1 << 24)),
+                      "bad FastSpeech2 config: use_spk_id needs num_spk >= 1 (the table has num_spk + 1 rows)");
+            MAA_CHECK(!cfg->use_split_spk_id || cfg->use_spk_id, "bad FastSpeech2 config: use_split_spk_id without use_spk_id");
+            MAA_CHECK(!cfg->use_energy_embed || (cfg->predictor_layers >= 1 && cfg->predictor_kernel >= 1 && cfg->predictor_kernel % 2 == 1),
+                      "bad FastSpeech2 config: use_energy_embed needs predictor_layers >= 1 and an odd predictor_kernel ('SAME' padding "
+                      "keeps the length only then)");
+        } else {
+            MAA_CHECK(!cfg->use_energy_embed, "FastSpeech2MIDI: hparams['use_energy_embed'] is not built -- no shipped e2e singing configuration sets it");
+            MAA_CHECK(!cfg->use_spk_id && !cfg->use_spk_embed,
+                      "FastSpeech2MIDI: hparams['use_spk_id'] / ['use_spk_embed'] are not built -- no shipped e2e singing configuration sets them");
+        }
         MAA_CHECK(!cfg->use_bert, "FastSpeech2MIDI: hparams['use_bert'] is not built -- no shipped e2e singing configuration sets it");
-        MAA_CHECK(cfg->rel_pos != 0 && cfg->use_pos_embed != 0,
+        MAA_CHECK(cfg->plain || (cfg->rel_pos != 0 && cfg->use_pos_embed != 0),
                   "FastSpeech2MIDI: hparams['rel_pos'] and ['use_pos_embed'] must be true -- only RelPositionalEncoding is built for the encoder");
         MAA_CHECK(cfg->ffn_padding_same != 0,
                   "FastSpeech2MIDI: hparams['ffn_padding'] must be 'SAME' -- the causal 'LEFT' padding (kernel - 1, 0) is not built");
@@ -550,6 +562,43 @@ int maa_fs2_encode(maa_ctx* ctx, maa_fs2* fs2, const int* d_tokens, const int* d
         MAA_CHECK(B > 0 && T > 0 && (long long)B * T < (1LL << 31) / 4096, "bad fs2_encode arguments: B, T");
         bind(ctx);
         fs2->m->encode(ctx->c, d_tokens, d_pitch_midi, d_midi_dur, d_is_slur, B, T, d_encoder_out, d_xs, d_dur, d_totals);
+    });
+}
+int maa_fs2_encode_plain(maa_ctx* ctx, maa_fs2* fs2, const int* d_tokens, const float* d_spk_dur, int B, int T, float* d_encoder_out,
+                         float* d_xs, int* d_dur, int* d_totals) {
+    return guarded([&] {
+        MAA_CHECK(fs2 && d_tokens && d_encoder_out && d_xs && d_dur && d_totals, "bad fs2_encode_plain arguments: null pointer");
+        MAA_CHECK(B > 0 && T > 0 && (long long)B * T < (1LL << 31) / 4096, "bad fs2_encode_plain arguments: B, T");
+        bind(ctx);
+        fs2->m->encode_plain(ctx->c, d_tokens, d_spk_dur, B, T, d_encoder_out, d_xs, d_dur, d_totals);
+    });
+}
+int maa_fs2_speaker(maa_ctx* ctx, maa_fs2* fs2, const int* d_ids, const float* d_vec, int B, float* d_out) {
+    return guarded([&] {
+        MAA_CHECK(fs2 && d_out, "bad fs2_speaker arguments: null pointer");
+        MAA_CHECK(d_ids || d_vec, "bad fs2_speaker arguments: neither d_ids nor d_vec");
+        MAA_CHECK(B > 0 && 3LL * B < (1LL << 31) / 4096,"bad fs2_speaker arguments: B");
+        bind(ctx);
+        fs2->m->speaker(ctx->c, d_ids, d_vec, B, d_out);
+    });
+}
+int maa_fs2_add_speaker(maa_ctx* ctx, maa_fs2* fs2, const float* d_x, const float* d_spk, const int* d_mel2ph, int B, int T_mel,
+                        float* d_out) {
+    return guarded([&] {
+        MAA_CHECK(fs2 && d_x && d_spk && d_mel2ph && d_out, "bad fs2_add_speaker arguments: null pointer");
+        MAA_CHECK(B > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_add_speaker arguments: B, T_mel");
+        bind(ctx);
+        fs2->m->add_speaker(ctx->c, d_x, d_spk, d_mel2ph, B, T_mel, d_out);
+    });
+}
+int maa_fs2_finish(maa_ctx* ctx, maa_fs2* fs2, const float* d_pred_inp, const float* d_acc, const int* d_mel2ph, const float* d_energy,
+                   const float* d_spk, int B, int T_mel, float* d_decoder_inp, float* d_energy_pred, int* d_energy_bin) {
+    return guarded([&] {
+        MAA_CHECK(fs2 && d_acc && d_mel2ph && d_decoder_inp, "bad fs2_finish arguments: null pointer");
+        MAA_CHECK(B > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_finish arguments: B, T_mel");
+        MAA_CHECK(d_decoder_inp != d_acc && d_decoder_inp != d_pred_inp, "bad fs2_finish arguments: d_decoder_inp may not alias d_acc or d_pred_inp");
+        bind(ctx);
+        fs2->m->finish(ctx->c, d_pred_inp, d_acc, d_mel2ph, d_energy, d_spk, B, T_mel, d_decoder_inp, d_energy_pred, d_energy_bin);
     });
 }
 int maa_fs2_length_regulate(maa_ctx* ctx, maa_fs2* fs2, const int* d_dur, int B, int T, int T_mel, int* d_mel2ph) {
@@ -607,7 +656,20 @@ int maa_fs2_pitch_forward(maa_ctx* ctx, maa_fs2_pitch* h, const float* d_origin,
         MAA_CHECK(B > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_pitch_forward arguments: B, T_mel");
         MAA_CHECK(d_decoder_inp != d_origin, "bad fs2_pitch_forward arguments: d_decoder_inp may not alias d_origin");
         bind(ctx);
-        h->m->forward(ctx->c, d_origin, d_mel2ph, d_f0, d_uv, B, T_mel, d_decoder_inp, d_pitch_pred, d_f0_denorm, d_coarse);
+        h->m->forward(ctx->c, d_origin, d_origin, d_mel2ph, d_f0, d_uv, B, T_mel, d_decoder_inp, d_pitch_pred, d_f0_denorm, d_coarse);
+    });
+}
+int maa_fs2_pitch_forward_from(maa_ctx* ctx, maa_fs2_pitch* h, const float* d_pred_inp, const float* d_origin, const int* d_mel2ph,
+                               const float* d_f0, const float* d_uv, int B, int T_mel, float* d_decoder_inp, float* d_pitch_pred,
+                               float* d_f0_denorm, int* d_coarse) {
+    return guarded([&] {
+        MAA_CHECK(h && d_pred_inp && d_origin && d_mel2ph && d_decoder_inp && d_pitch_pred && d_f0_denorm,
+                  "bad fs2_pitch_forward_from arguments: null pointer");
+        MAA_CHECK(B > 0 && T_mel > 0 && (long long)B * T_mel < (1LL << 31) / 4096, "bad fs2_pitch_forward_from arguments: B, T_mel");
+        MAA_CHECK(d_decoder_inp != d_origin && d_decoder_inp != d_pred_inp,
+                  "bad fs2_pitch_forward_from arguments: d_decoder_inp may not alias d_origin or d_pred_inp");
+        bind(ctx);
+        h->m->forward(ctx->c, d_pred_inp, d_origin, d_mel2ph, d_f0, d_uv, B, T_mel, d_decoder_inp, d_pitch_pred, d_f0_denorm, d_coarse);
     });
 }
 

@@ -18,6 +18,10 @@
 // The cascade configurations (use_pitch_embed: inference/svs/ds_cascade.py, midi/cascade/opencs/ds60_rel.yaml) add FS2Pitch, a
 // second handle: decode without the decoder -> its PitchPredictor and pitch tail finish decoder_inp (fs2.py:125-132,187-220) ->
 // run_decoder, decode's second half on that decoder_inp.
+// The plain FastSpeech2 (cfg.plain: modules/fastspeech/fs2.py:22-226, the fs2 of every configuration without use_midi) is the same
+// handle type: the shared layers above, no note terms, sinusoid rows by token count (or rel_pos), the speaker tables or projection and
+// the energy branch; in fs2.py's order: [speaker] -> encode_plain -> length_regulate -> decode without the decoder -> [add_speaker]
+// -> [FS2Pitch, its predictor's input apart from origin] -> finish -> run_decoder.
 // The "same" Conv1d with its epilogue activation, the decoder's sinusoid table and the predictor stack are seq_layers.h's,
 // shared with pitch_extractor.cpp; what stays here is the embeddings, FFTBlocks, the length regulator and the order of the whole.
 #include "models.h"
@@ -38,10 +42,21 @@ void launch_fs2_pitch_tail(const Ctx& ctx, const float* x, long long rows, int C
                            const float* w, const float* bias, const int* mel2ph, const float* f0_in, const float* uv_in, int norm,
                            float f0_mean, float f0_std, int use_uv, const float* origin, const float* table, int H, float* pitch_pred,
                            float* f0_denorm, int* coarse, float* decoder_inp);
+void launch_fs2_embed_plain(Ctx& ctx, const int* tok, const float* E, int vocab, const float* pe, float scale, int rel, int B, int T,
+                            int H, float* x, float* nonpad, float* hidden);
+void launch_fs2_add_speaker(const Ctx& ctx, const float* x, const float* spk, const int* mel2ph, const float* mask, int B, int T, int H,
+                            float* out);
+void launch_fs2_speaker_gather(const Ctx& ctx, const float* t0, const float* t1, const float* t2, const int* ids, int split, int n_rows,
+                               int B, int H, float* out);
+void launch_fs2_energy_tail(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
+                            const float* w, const float* bias, const int* mel2ph, const float* energy_in, const float* acc,
+                            const float* table, const float* spk, int T_mel, int H, float* energy_pred, int* energy_bin,
+                            float* decoder_inp);
 
 namespace {
 
 constexpr int FS2_REL_MAX_LEN = 5000, FS2_TABLE_INIT = 2000, FS2_MIDI_ROWS = 300, FS2_PITCH_ROWS = 300, FS2_PITCH_TABLE_INIT = 4096;
+constexpr int FS2_ENERGY_ROWS = 256, FS2_SPK_VEC = 256;
 constexpr float FS2_EPS = 1e-5f;
 
 // RelPositionalEncoding's table (espnet_positional_embedding.py:24-45 with reverse = True) in fp32: row i holds position
@@ -140,20 +155,32 @@ struct FastSpeech2MIDI::Impl {
     PackedW mel_out;
     float alpha = 1.f;
     SinusoidTable table;                 // the decoder's, [max(2000, T_mel + 1), hidden_size]
+    // ---- the plain FastSpeech2 only (cfg.plain): no note terms; counted sinusoid positions unless rel_pos; speakers; energy
+    SinusoidTable enc_table;             // the encoder's, [max(2000, T + 1), hidden_size] (rel_pos 0)
+    float *spk = nullptr, *spk_dur = nullptr, *spk_f0 = nullptr;      // [num_spk + 1, H] each (use_spk_id; the last two with split)
+    PackedW spk_proj;                    // Linear(256, H) (use_spk_embed)
+    ConvPredictor ep;                    // EnergyPredictor: a PitchPredictor with odim 1 (use_energy_embed)
+    float* energy_embed = nullptr;       // [256, H]
+    float energy_alpha = 1.f;
+    SinusoidTable energy_table;          // the predictor's, [max(4096, T_mel + 1), hidden_size]
 
     void build(const StateDict& sd) {
         const int H = cfg.hidden_size;
         const HostTensor& e = get(sd, "encoder.embed_tokens.weight");
         MAA_CHECK(e.numel() == (long long)cfg.vocab_size * H, "FastSpeech2MIDI: encoder.embed_tokens.weight must be [vocab_size, hidden_size]");
-        MAA_CHECK(get(sd, "midi_embed.weight").numel() == (long long)FS2_MIDI_ROWS * H && get(sd, "is_slur_embed.weight").numel() == 2LL * H &&
-                      get(sd, "midi_dur_layer.weight").numel() == H && get(sd, "midi_dur_layer.bias").numel() == H,
-                  "FastSpeech2MIDI: midi_embed [300, H], midi_dur_layer [H, 1] + [H], is_slur_embed [2, H]");
         embed = ws.vec(sd, "encoder.embed_tokens.weight");
-        midi = ws.vec(sd, "midi_embed.weight");
-        dur_w = ws.vec(sd, "midi_dur_layer.weight");
-        dur_b = ws.vec(sd, "midi_dur_layer.bias");
-        slur = ws.vec(sd, "is_slur_embed.weight");
-        rel_pe = ws.upload(rel_pos_table(FS2_REL_MAX_LEN, H));
+        if (cfg.plain) {
+            build_plain(sd);
+        } else {
+            MAA_CHECK(get(sd, "midi_embed.weight").numel() == (long long)FS2_MIDI_ROWS * H && get(sd, "is_slur_embed.weight").numel() == 2LL * H &&
+                          get(sd, "midi_dur_layer.weight").numel() == H && get(sd, "midi_dur_layer.bias").numel() == H,
+                      "FastSpeech2MIDI: midi_embed [300, H], midi_dur_layer [H, 1] + [H], is_slur_embed [2, H]");
+            midi = ws.vec(sd, "midi_embed.weight");
+            dur_w = ws.vec(sd, "midi_dur_layer.weight");
+            dur_b = ws.vec(sd, "midi_dur_layer.bias");
+            slur = ws.vec(sd, "is_slur_embed.weight");
+        }
+        if (cfg.rel_pos) rel_pe = ws.upload(rel_pos_table(FS2_REL_MAX_LEN, H));
         enc.build(ws, sd, "encoder", cfg.enc_layers, H, cfg.num_heads, cfg.enc_ffn_kernel_size);
         dec.build(ws, sd, "decoder", cfg.dec_layers, H, cfg.num_heads, cfg.dec_ffn_kernel_size);
         dp.build(ws, sd, "DurationPredictor", "dur_predictor.", cfg.dur_predictor_layers, cfg.dur_predictor_kernel, H, Cp, 1);
@@ -162,6 +189,93 @@ struct FastSpeech2MIDI::Impl {
         alpha = get(sd, "decoder.pos_embed_alpha").data[0];
         // (encoder_embed_tokens.weight is encoder.embed_tokens.weight again; decoder.embed_positions._float_tensor is bookkeeping)
         table.build(ws, FS2_TABLE_INIT, H);
+    }
+
+    // what the plain FastSpeech2 has beside the shared layers (fs2.py:41-47, 65-72)
+    void build_plain(const StateDict& sd) {
+        const int H = cfg.hidden_size;
+        if (!cfg.rel_pos) enc_table.build(ws, FS2_TABLE_INIT, H);
+        if (cfg.use_spk_id) {
+            const long long n = ((long long)cfg.num_spk + 1) * H;
+            MAA_CHECK(get(sd, "spk_embed_proj.weight").numel() == n, "FastSpeech2: spk_embed_proj.weight must be [num_spk + 1, hidden_size]");
+            spk = spk_dur = spk_f0 = ws.vec(sd, "spk_embed_proj.weight");
+            if (cfg.use_split_spk_id) {
+                MAA_CHECK(get(sd, "spk_embed_dur.weight").numel() == n && get(sd, "spk_embed_f0.weight").numel() == n,
+                          "FastSpeech2: spk_embed_dur.weight / spk_embed_f0.weight must be [num_spk + 1, hidden_size]");
+                spk_dur = ws.vec(sd, "spk_embed_dur.weight");
+                spk_f0 = ws.vec(sd, "spk_embed_f0.weight");
+            }
+        } else if (cfg.use_spk_embed) {
+            spk_proj = ws.pack_conv(sd, "spk_embed_proj.weight", "spk_embed_proj.bias", 1, 1);
+            MAA_CHECK(spk_proj.N == H && spk_proj.K == FS2_SPK_VEC, "FastSpeech2: spk_embed_proj must be Linear(256, hidden_size)");
+        }
+        if (cfg.use_energy_embed) {
+            MAA_CHECK(get(sd, "energy_embed.weight").numel() == (long long)FS2_ENERGY_ROWS * H, "FastSpeech2: energy_embed.weight must be [256, hidden_size]");
+            energy_embed = ws.vec(sd, "energy_embed.weight");
+            ep.build(ws, sd, "FastSpeech2 EnergyPredictor", "energy_predictor.", cfg.predictor_layers, cfg.predictor_kernel, H, Cp, 1);
+            energy_alpha = get(sd, "energy_predictor.pos_embed_alpha").data[0];
+            energy_table.build(ws, FS2_PITCH_TABLE_INIT, H);
+        }
+    }
+
+    // the duration predictor on dur_inp (its padding rows are 0), then the frame totals      (tts_modules.py:98-118)
+    void durations(Ctx& ctx, const float* dur_inp, const float* nonpad, int B, int T, float* xs, int* dur, int* totals) {
+        const int H = cfg.hidden_size;
+        const long long rows = (long long)B * T;
+        const size_t wide = (size_t)rows * (H > Cp ? H : Cp);
+        float* a = ctx.ws.alloc_f(wide);
+        float* b = ctx.ws.alloc_f(wide);
+        const float* y = dp.run(ctx, dur_inp, B, T, nonpad, a, b);
+        launch_fs2_dur_head(ctx, y, rows, Cp, dp.gamma(), dp.beta(), dp.EPS, dp.lin_w, dp.lin_b, nonpad, xs, dur);
+        launch_fs2_length(ctx, dur, B, T, totals, 0, nullptr);
+    }
+
+    // FastSpeech2.forward up to add_dur (fs2.py:84-116): spk_dur [B, H] or null
+    void encode_plain(Ctx& ctx, const int* tok, const float* spk_dur_vec, int B, int T, float* encoder_out, float* xs, int* dur,
+                      int* totals) {
+        const int H = cfg.hidden_size;
+        const long long rows = (long long)B * T;
+        float* nonpad = ctx.ws.alloc_f((size_t)rows);
+        float* hidden = ctx.ws.alloc_f((size_t)rows);
+        float* x = ctx.ws.alloc_f((size_t)rows * H);
+        launch_fs2_embed_plain(ctx, tok, embed, cfg.vocab_size, cfg.rel_pos ? rel_pe : enc_table.ptr(), std::sqrt((float)H), cfg.rel_pos,
+                               B, T, H, x, nonpad, hidden);
+        enc.forward(ctx, x, B, T, nonpad, hidden, encoder_out);
+        const float* dur_inp = encoder_out;
+        if (spk_dur_vec) {
+            launch_fs2_add_speaker(ctx, encoder_out, spk_dur_vec, nullptr, nonpad, B, T, H, x);      // (x is free again)
+            dur_inp = x;
+        }
+        durations(ctx, dur_inp, nonpad, B, T, xs, dur, totals);
+    }
+
+    // ids int32 [3, B] or vec [B, 256], by the handle's mode -> out [3, B, H] = spk, spk_dur, spk_f0      (fs2.py:96-110)
+    void speaker(Ctx& ctx, const int* ids, const float* vec, int B, float* out) {
+        const int H = cfg.hidden_size;
+        if (cfg.use_spk_id) {
+            launch_fs2_speaker_gather(ctx, spk, spk_dur, spk_f0, ids, cfg.use_split_spk_id, cfg.num_spk + 1, B, H, out);
+        } else {
+            float* p = ctx.ws.alloc_f((size_t)B * H);
+            linear_into(ctx, vec, FS2_SPK_VEC, B, FS2_SPK_VEC, spk_proj, nullptr, 0, p, H);
+            launch_fs2_speaker_gather(ctx, p, p, p, nullptr, 0, B, B, H, out);
+        }
+    }
+
+    // add_energy and the last line of the variance stage (fs2.py:128-132, 165-172)
+    void finish(Ctx& ctx, const float* pred_inp, const float* acc, const int* mel2ph, const float* energy, const float* spk_vec, int B,
+                int T_mel, float* decoder_inp, float* energy_pred, int* energy_bin) {
+        const int H = cfg.hidden_size;
+        const long long rows = (long long)B * T_mel;
+        const float* y = nullptr;
+        if (cfg.use_energy_embed) {
+            const size_t wide = (size_t)rows * (H > Cp ? H : Cp);
+            float* a = ctx.ws.alloc_f(wide);
+            float* b = ctx.ws.alloc_f(wide);
+            launch_pe_pos_add(ctx, pred_inp, B, T_mel, H, energy_table.ptr(), energy_alpha, b);
+            y = ep.run(ctx, b, B, T_mel, nullptr, a, b);
+        }
+        launch_fs2_energy_tail(ctx, y, rows, Cp, y ? ep.gamma() : nullptr, y ? ep.beta() : nullptr, ep.EPS, ep.lin_w, ep.lin_b, mel2ph,
+                               energy, acc, energy_embed, spk_vec, T_mel, H, energy_pred, energy_bin, decoder_inp);
     }
 
     void encode(Ctx& ctx, const int* tok, const int* pitch_midi, const float* midi_dur, const int* is_slur, int B, int T,
@@ -174,13 +288,7 @@ struct FastSpeech2MIDI::Impl {
         launch_fs2_embed(ctx, tok, pitch_midi, midi_dur, is_slur, embed, cfg.vocab_size, midi, dur_w, dur_b, slur, rel_pe,
                          std::sqrt((float)H), B, T, H, x, nonpad, hidden);
         enc.forward(ctx, x, B, T, nonpad, hidden, encoder_out);
-        // ---- DurationPredictor on encoder_out * src_nonpadding (its padding rows are 0 already)      (tts_modules.py:98-118)
-        const size_t wide = (size_t)rows * (H > Cp ? H : Cp);
-        float* a = ctx.ws.alloc_f(wide);
-        float* b = ctx.ws.alloc_f(wide);
-        const float* y = dp.run(ctx, encoder_out, B, T, nonpad, a, b);
-        launch_fs2_dur_head(ctx, y, rows, Cp, dp.gamma(), dp.beta(), dp.EPS, dp.lin_w, dp.lin_b, nonpad, xs, dur);
-        launch_fs2_length(ctx, dur, B, T, totals, 0, nullptr);
+        durations(ctx, encoder_out, nonpad, B, T, xs, dur, totals);      // on encoder_out * src_nonpadding: its padding rows are 0 already
     }
 
     void decode(Ctx& ctx, const float* encoder_out, const int* mel2ph, int B, int T, int T_mel, float* decoder_inp, float* mel) {
@@ -228,9 +336,44 @@ const maa_fs2_config& FastSpeech2MIDI::config() const { return impl_->cfg; }
 void FastSpeech2MIDI::encode(Ctx& ctx, const int* tokens, const int* pitch_midi, const float* midi_dur, const int* is_slur, int B, int T,
                              float* encoder_out, float* xs, int* dur, int* totals) {
     Impl& m = *impl_;
+    MAA_CHECK(!m.cfg.plain, "maa_fs2_encode: this handle is the plain FastSpeech2 (plain = 1), which has no note features -- call maa_fs2_encode_plain");
     MAA_CHECK(T <= FS2_REL_MAX_LEN, "FastSpeech2MIDI: more tokens than RelPositionalEncoding's max_len (5000)");
     PrecisionGuard pg(ctx, m.precision);
     run_sized(ctx, [&] { m.encode(ctx, tokens, pitch_midi, midi_dur, is_slur, B, T, encoder_out, xs, dur, totals); });
+}
+
+void FastSpeech2MIDI::encode_plain(Ctx& ctx, const int* tokens, const float* spk_dur, int B, int T, float* encoder_out, float* xs,
+                                   int* dur, int* totals) {
+    Impl& m = *impl_;
+    MAA_CHECK(m.cfg.plain, "maa_fs2_encode_plain: this handle is FastSpeech2MIDI (plain = 0), whose encoder adds the note features -- call maa_fs2_encode");
+    MAA_CHECK(!m.cfg.rel_pos || T <= FS2_REL_MAX_LEN, "FastSpeech2: more tokens than RelPositionalEncoding's max_len (5000)");
+    PrecisionGuard pg(ctx, m.precision);
+    if (!m.cfg.rel_pos) m.enc_table.grow(ctx, T);
+    run_sized(ctx, [&] { m.encode_plain(ctx, tokens, spk_dur, B, T, encoder_out, xs, dur, totals); });
+}
+
+void FastSpeech2MIDI::speaker(Ctx& ctx, const int* ids, const float* vec, int B, float* out) {
+    Impl& m = *impl_;
+    MAA_CHECK(m.cfg.plain && (m.cfg.use_spk_id || m.cfg.use_spk_embed),
+              "maa_fs2_speaker: this handle has no speaker embedding (neither use_spk_id nor use_spk_embed)");
+    MAA_CHECK(m.cfg.use_spk_id ? ids != nullptr : vec != nullptr,
+              m.cfg.use_spk_id ? "maa_fs2_speaker: a use_spk_id handle needs d_ids" : "maa_fs2_speaker: a use_spk_embed handle needs d_vec");
+    PrecisionGuard pg(ctx, m.precision);
+    run_sized(ctx, [&] { m.speaker(ctx, ids, vec, B, out); });
+}
+
+void FastSpeech2MIDI::add_speaker(Ctx& ctx, const float* x, const float* spk, const int* mel2ph, int B, int T_mel, float* out) {
+    Impl& m = *impl_;
+    run_sized(ctx, [&] { launch_fs2_add_speaker(ctx, x, spk, mel2ph, nullptr, B, T_mel, m.cfg.hidden_size, out); });
+}
+
+void FastSpeech2MIDI::finish(Ctx& ctx, const float* pred_inp, const float* acc, const int* mel2ph, const float* energy, const float* spk,
+                             int B, int T_mel, float* decoder_inp, float* energy_pred, int* energy_bin) {
+    Impl& m = *impl_;
+    MAA_CHECK(!m.cfg.use_energy_embed || pred_inp, "maa_fs2_finish: a use_energy_embed handle needs d_pred_inp, the energy predictor's input");
+    PrecisionGuard pg(ctx, m.precision);
+    if (m.cfg.use_energy_embed) m.energy_table.grow(ctx, T_mel);
+    run_sized(ctx, [&] { m.finish(ctx, pred_inp, acc, mel2ph, energy, spk, B, T_mel, decoder_inp, energy_pred, energy_bin); });
 }
 
 void FastSpeech2MIDI::length_regulate(Ctx& ctx, const int* dur, int B, int T, int T_mel, int* mel2ph) {
@@ -274,15 +417,16 @@ struct FS2Pitch::Impl {
         table.build(ws, FS2_PITCH_TABLE_INIT, H);
     }
 
-    void forward(Ctx& ctx, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B, int T_mel, float* decoder_inp,
-                 float* pitch_pred, float* f0_denorm, int* coarse) {
+    void forward(Ctx& ctx, const float* pred_inp, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B, int T_mel,
+                 float* decoder_inp, float* pitch_pred, float* f0_denorm, int* coarse) {
         const int H = cfg.hidden_size;
         const long long rows = (long long)B * T_mel;
         const size_t wide = (size_t)rows * (H > Cp ? H : Cp);
         float* a = ctx.ws.alloc_f(wide);
         float* b = ctx.ws.alloc_f(wide);
-        // ---- PitchPredictor (tts_modules.py:247-260) on pitch_inp = origin (0 where mel2ph is 0 already); no mask between its layers
-        launch_pe_pos_add(ctx, origin, B, T_mel, H, table.ptr(), alpha, b);
+        // ---- PitchPredictor (tts_modules.py:247-260) on pitch_inp (0 where mel2ph is 0 already): origin itself without speakers,
+        // (origin + spk_f0) * tgt with them; no mask between its layers
+        launch_pe_pos_add(ctx, pred_inp, B, T_mel, H, table.ptr(), alpha, b);
         const float* y = pp.run(ctx, b, B, T_mel, nullptr, a, b);          // (a LayerNorm writes over b, which its convolution has read)
         launch_fs2_pitch_tail(ctx, y, rows, Cp, pp.gamma(), pp.beta(), pp.EPS, pp.lin_w, pp.lin_b, mel2ph, f0, uv, cfg.pitch_norm,
                               cfg.f0_mean, cfg.f0_std, cfg.use_uv, origin, embed, H, pitch_pred, f0_denorm, coarse, decoder_inp);
@@ -297,12 +441,12 @@ FS2Pitch::FS2Pitch(const maa_fs2_pitch_config& cfg, const StateDict& sd, int pre
 FS2Pitch::~FS2Pitch() = default;
 const maa_fs2_pitch_config& FS2Pitch::config() const { return impl_->cfg; }
 
-void FS2Pitch::forward(Ctx& ctx, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B, int T_mel,
-                       float* decoder_inp, float* pitch_pred, float* f0_denorm, int* coarse) {
+void FS2Pitch::forward(Ctx& ctx, const float* pred_inp, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B,
+                       int T_mel, float* decoder_inp, float* pitch_pred, float* f0_denorm, int* coarse) {
     Impl& m = *impl_;
     PrecisionGuard pg(ctx, m.precision);
     m.table.grow(ctx, T_mel);
-    run_sized(ctx, [&] { m.forward(ctx, origin, mel2ph, f0, uv, B, T_mel, decoder_inp, pitch_pred, f0_denorm, coarse); });
+    run_sized(ctx, [&] { m.forward(ctx, pred_inp, origin, mel2ph, f0, uv, B, T_mel, decoder_inp, pitch_pred, f0_denorm, coarse); });
 }
 
 }  // namespace maa

@@ -8,6 +8,9 @@
 // modules/fastspeech/fs2.py:117-122,132 expand + mask of the encoder states; and, for the cascade configurations
 // (use_pitch_embed), fs2.py:187-220 the pitch tail: the predictor's last LayerNorm + Linear(C, 2), denorm_f0,
 // utils/pitch_utils.py:15-31 f0_to_coarse, the pitch_embed gather and the mask, one launch.
+// and, for the plain FastSpeech2 (modules/fastspeech/fs2.py; tts_modules.py:365-375), the token-counted positions and the
+// embedding with the scale applied once, the speaker gather and broadcast add (fs2.py:96-125), and the energy tail (fs2.py:132,
+// 165-172): the predictor's last LayerNorm + Linear(C, 1), the bin, the energy_embed gather, the speaker add and the mask, one launch.
 // All of them are memory-bound on a few hundred to a few thousand rows.
 // The launch grid and the duration head's LayerNorm + Linear stage are row_device.h's, shared with norm.hip's LayerNorm and
 // pitch.hip's head; the decoder's masks, masked products and positional add are pitch.hip's launches (models.h).
@@ -217,6 +220,144 @@ __global__ __launch_bounds__(256) void fs2_pitch_tail_kernel(const float* __rest
     }
 }
 
+// ---- the plain FastSpeech2 (modules/fastspeech/fs2.py: the TTS configurations and both *_ds_beta6 chains)
+// make_positions on the tokens (utils/__init__.py make_positions, padding_idx 0): pos[b, t] = #{t' <= t : tok[b, t'] != 0} where
+// tok[b, t] != 0, else 0 -- a padding token inside a sample does not advance the count.  One block per sample, 256 tokens per
+// step: a ballot per wave, the waves' counts through LDS, the running count carried in a register (as pitch.hip counts frames).
+__global__ __launch_bounds__(256) void fs2_token_positions_kernel(const int* __restrict__ tok, int T, int* __restrict__ pos) {
+    __shared__ int cnt[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int* src = tok + (long long)blockIdx.x * T;
+    int* dst = pos + (long long)blockIdx.x * T;
+    int carry = 0;
+    for (int t0 = 0; t0 < T; t0 += 256) {
+        const int t = t0 + (int)threadIdx.x;
+        const bool nz = t < T && src[t] != 0;
+        const unsigned long long bal = __ballot(nz);
+        const int below = __popcll(bal & ((2ull << lane) - 1ull));          // lanes 0 .. lane, this one included
+        __syncthreads();
+        if (lane == 0) cnt[w] = __popcll(bal);
+        __syncthreads();
+        int before = carry;
+        for (int i = 0; i < w; ++i) before += cnt[i];
+        if (t < T) dst[t] = nz ? before + below : 0;
+        carry += (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+    }
+}
+
+// FastspeechEncoder.forward_embedding (tts_modules.py:365-375) and FFTBlocks' first mask.  rel == 0: x = (scale * E[tok] +
+// table[pos[row]]) * live, the scale applied once, the sinusoid row chosen by the counted position (at most T: the caller grew the
+// table to T + 1 rows).  rel != 0: x = ((scale * E[tok]) * scale + pe[t]) * live, RelPositionalEncoding on the scaled embedding
+// -- the MIDI form without its three note terms; pos is not read.  nonpad / hidden as fs2_embed_kernel.
+__global__ __launch_bounds__(256) void fs2_embed_plain_kernel(const int* __restrict__ tok, const int* __restrict__ pos,
+                                                              const float* __restrict__ E, int vocab, const float* __restrict__ pe,
+                                                              float scale, int rel, long long rows, int T, int H,
+                                                              float* __restrict__ x, float* __restrict__ nonpad,
+                                                              float* __restrict__ hidden) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int tk = tok[row];
+    const float live = tk != 0 ? 1.f : 0.f;
+    const float* e = E + (long long)clampi(tk, 0, vocab - 1) * H;
+    const float* p = pe + (long long)(rel ? (int)(row % T) : clampi(pos[row], 0, T)) * H;
+    const float outer = rel ? scale : 1.f;
+    for (int c = lane * 4; c < H; c += 256) {
+        const float4 ev = *reinterpret_cast<const float4*>(e + c);
+        const float4 pv = *reinterpret_cast<const float4*>(p + c);
+        float4 v;
+        v.x = ((scale * ev.x) * outer + pv.x) * live;
+        v.y = ((scale * ev.y) * outer + pv.y) * live;
+        v.z = ((scale * ev.z) * outer + pv.z) * live;
+        v.w = ((scale * ev.w) * outer + pv.w) * live;
+        *reinterpret_cast<float4*>(x + row * H + c) = v;
+    }
+    if (lane == 0) {
+        nonpad[row] = live;
+        hidden[row] = 1.f - live;
+    }
+}
+
+// out[r, :] = (x[r, :] + spk[r / T, :]) * live, live = mask[r] != 0 (encode's src_nonpadding) or mel2ph[r] > 0: the inputs of the
+// duration, pitch and energy predictors (fs2.py:114, 125)
+__global__ __launch_bounds__(256) void fs2_add_speaker_kernel(const float* __restrict__ x, const float* __restrict__ spk,
+                                                              const int* __restrict__ mel2ph, const float* __restrict__ mask,
+                                                              long long rows, int T, int H, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float live = (mask ? mask[row] != 0.f : mel2ph[row] > 0) ? 1.f : 0.f;
+    const float* s = spk + (row / T) * H;
+    for (int c = lane * 4; c < H; c += 256) {
+        const float4 v = *reinterpret_cast<const float4*>(x + row * H + c);
+        const float4 sv = *reinterpret_cast<const float4*>(s + c);
+        *reinterpret_cast<float4*>(out + row * H + c) =
+            make_float4((v.x + sv.x) * live, (v.y + sv.y) * live, (v.z + sv.z) * live, (v.w + sv.w) * live);
+    }
+}
+
+// out[k, b, :] = tab_k[id, :] for k = 0, 1, 2 (spk, spk_dur, spk_f0).  ids given: id = ids[k, b] with split, ids[0, b] without
+// (fs2.py:104-110), clamped into the n_rows rows; ids null: id = b, the three copies of a [B, H] projection (fs2.py:97)
+__global__ __launch_bounds__(256) void fs2_speaker_gather_kernel(const float* __restrict__ t0, const float* __restrict__ t1,
+                                                                 const float* __restrict__ t2, const int* __restrict__ ids, int split,
+                                                                 int n_rows, int B, int H, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= 3LL * B) return;
+    const int k = (int)(row / B), b = (int)(row % B);
+    const float* tab = k == 0 ? t0 : k == 1 ? t1 : t2;
+    const int id = ids ? clampi(ids[(split ? k : 0) * B + b], 0, n_rows - 1) : b;
+    for (int c = lane * 4; c < H; c += 256)
+        *reinterpret_cast<float4*>(out + row * H + c) = *reinterpret_cast<const float4*>(tab + (long long)id * H + c);
+}
+
+// The end of FastSpeech2.forward's variance stage (fs2.py:165-172, 132), one wave per frame.  With an energy branch (x given):
+// the predictor's last LayerNorm (registers, C <= 256 * NR) and Linear(C, 1) -> energy_pred[r], on every frame as the reference
+// returns it; e = energy_in[r] if given, else the prediction; bin = clamp(e * 256 // 4, max = 255) = floor(64 e) exactly in fp32,
+// clamped to [0, 255] (the reference raises IndexError below 0; a NaN lands in bin 0) -> energy_bin[r] (optional); then all lanes:
+// decoder_inp[r, :] = (acc[r, :] + energy_embed[bin, :] + spk[b, :]) * (mel2ph[r] > 0), summed in that order.  Every lane holds the
+// same dot, so no [B, T] tensor goes through memory between the head and the gather.  Without an energy branch (x null) the same
+// launch is (acc + spk[b]) * tgt; spk may be null too.
+template <int NR>
+__global__ __launch_bounds__(256) void fs2_energy_tail_kernel(const float* __restrict__ x, long long rows, int C,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                              const float* __restrict__ w, const float* __restrict__ bias,
+                                                              const int* __restrict__ mel2ph, const float* __restrict__ energy_in,
+                                                              const float* __restrict__ acc, const float* __restrict__ table,
+                                                              const float* __restrict__ spk, int T_mel, int H,
+                                                              float* __restrict__ energy_pred, int* __restrict__ energy_bin,
+                                                              float* __restrict__ decoder_inp) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float live = mel2ph[row] > 0 ? 1.f : 0.f;
+    const float* e = nullptr;
+    if (x) {
+        float d[1];
+        ln_head_dots<NR, 1>(x + row * C, C, lane, gamma, beta, eps, w, bias, d);
+        const float q = floorf((energy_in ? energy_in[row] : d[0]) * 64.f);
+        const int bin = q >= 255.f ? 255 : q > 0.f ? (int)q : 0;
+        if (lane == 0) {
+            if (energy_pred) energy_pred[row] = d[0];
+            if (energy_bin) energy_bin[row] = bin;
+        }
+        e = table + (long long)bin * H;
+    }
+    const float* s = spk ? spk + (row / T_mel) * H : nullptr;
+    for (int c = lane * 4; c < H; c += 256) {
+        float4 v = *reinterpret_cast<const float4*>(acc + row * H + c);
+        if (e) {
+            const float4 p = *reinterpret_cast<const float4*>(e + c);
+            v.x += p.x, v.y += p.y, v.z += p.z, v.w += p.w;
+        }
+        if (s) {
+            const float4 p = *reinterpret_cast<const float4*>(s + c);
+            v.x += p.x, v.y += p.y, v.z += p.z, v.w += p.w;
+        }
+        *reinterpret_cast<float4*>(decoder_inp + row * H + c) = make_float4(v.x * live, v.y * live, v.z * live, v.w * live);
+    }
+}
+
 }  // namespace
 
 void launch_fs2_embed(const Ctx& ctx, const int* tok, const int* midi, const float* midi_dur, const int* slur, const float* E, int vocab,
@@ -293,6 +434,59 @@ void launch_fs2_pitch_tail(const Ctx& ctx, const float* x, long long rows, int C
         go(fs2_pitch_tail_kernel<2>);
     else
         go(fs2_pitch_tail_kernel<4>);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_embed_plain(Ctx& ctx, const int* tok, const float* E, int vocab, const float* pe, float scale, int rel, int B, int T,
+                            int H, float* x, float* nonpad, float* hidden) {
+    const long long rows = (long long)B * T;
+    int* pos = rel ? nullptr : reinterpret_cast<int*>(ctx.ws.alloc_f((size_t)rows));
+    if (ctx.ws.dry) return;
+    MAA_CHECK(H % 4 == 0, "FastSpeech2: hidden_size must be a multiple of 4");
+    ProfScope prof(ctx, "fs2_rows", 0.0, 12.0 * rows * (double)H);
+    if (!rel) hipLaunchKernelGGL(fs2_token_positions_kernel, dim3((unsigned)B), dim3(256), 0, ctx.stream, tok, T, pos);
+    hipLaunchKernelGGL(fs2_embed_plain_kernel, row_grid(rows), dim3(256), 0, ctx.stream, tok, pos, E, vocab, pe, scale, rel, rows, T, H, x,
+                       nonpad, hidden);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_add_speaker(const Ctx& ctx, const float* x, const float* spk, const int* mel2ph, const float* mask, int B, int T, int H,
+                            float* out) {
+    if (ctx.ws.dry) return;
+    MAA_CHECK(H % 4 == 0, "FastSpeech2: hidden_size must be a multiple of 4");
+    const long long rows = (long long)B * T;
+    ProfScope prof(ctx, "fs2_rows", 0.0, 8.0 * rows * (double)H);
+    hipLaunchKernelGGL(fs2_add_speaker_kernel, row_grid(rows), dim3(256), 0, ctx.stream, x, spk, mel2ph, mask, rows, T, H, out);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_speaker_gather(const Ctx& ctx, const float* t0, const float* t1, const float* t2, const int* ids, int split, int n_rows,
+                               int B, int H, float* out) {
+    if (ctx.ws.dry) return;
+    MAA_CHECK(H % 4 == 0, "FastSpeech2: hidden_size must be a multiple of 4");
+    ProfScope prof(ctx, "fs2_rows", 0.0, 24.0 * B * (double)H);
+    hipLaunchKernelGGL(fs2_speaker_gather_kernel, row_grid(3LL * B), dim3(256), 0, ctx.stream, t0, t1, t2, ids, split, n_rows, B, H, out);
+    MAA_HIP(hipGetLastError());
+}
+
+void launch_fs2_energy_tail(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
+                            const float* w, const float* bias, const int* mel2ph, const float* energy_in, const float* acc,
+                            const float* table, const float* spk, int T_mel, int H, float* energy_pred, int* energy_bin,
+                            float* decoder_inp) {
+    if (ctx.ws.dry) return;
+    MAA_CHECK(!x || (C % 4 == 0 && C <= 1024), "FastSpeech2 energy: predictor width must be a multiple of 4, at most 1024");
+    MAA_CHECK(H % 4 == 0, "FastSpeech2: hidden_size must be a multiple of 4");
+    ProfScope prof(ctx, "fs2_rows", 0.0, 4.0 * rows * ((x ? (double)C : 0.0) + 3.0 * H));
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, row_grid(rows), dim3(256), 0, ctx.stream, x, rows, C, gamma, beta, eps, w, bias, mel2ph, energy_in, acc,
+                           table, spk, T_mel, H, energy_pred, energy_bin, decoder_inp);
+    };
+    if (!x || C <= 256)
+        go(fs2_energy_tail_kernel<1>);
+    else if (C <= 512)
+        go(fs2_energy_tail_kernel<2>);
+    else
+        go(fs2_energy_tail_kernel<4>);
     MAA_HIP(hipGetLastError());
 }
 

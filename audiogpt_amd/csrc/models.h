@@ -139,6 +139,17 @@ public:
     // dur int32 [B, T], totals int32 [B]
     void encode(Ctx& ctx, const int* tokens, const int* pitch_midi, const float* midi_dur, const int* is_slur, int B, int T,
                 float* encoder_out, float* xs, int* dur, int* totals);
+    // The plain FastSpeech2 (cfg.plain; modules/fastspeech/fs2.py): tokens int32 [B, T], spk_dur (optional) [B, H] -> as encode
+    void encode_plain(Ctx& ctx, const int* tokens, const float* spk_dur, int B, int T, float* encoder_out, float* xs, int* dur,
+                      int* totals);
+    // ids int32 [3, B] (use_spk_id) or vec [B, 256] (use_spk_embed), by the handle's mode -> out [3, B, H]: spk, spk_dur, spk_f0
+    void speaker(Ctx& ctx, const int* ids, const float* vec, int B, float* out);
+    // out [B, T_mel, H] = (x + spk[b]) * (mel2ph > 0): the pitch and energy predictors' input
+    void add_speaker(Ctx& ctx, const float* x, const float* spk, const int* mel2ph, int B, int T_mel, float* out);
+    // the energy predictor on pred_inp (when the handle has one), then decoder_inp = (acc + energy_embed[bin] + spk[b]) * (mel2ph > 0);
+    // energy / spk / energy_pred [B, T_mel] / energy_bin int32 [B, T_mel] optional
+    void finish(Ctx& ctx, const float* pred_inp, const float* acc, const int* mel2ph, const float* energy, const float* spk, int B,
+                int T_mel, float* decoder_inp, float* energy_pred, int* energy_bin);
     void length_regulate(Ctx& ctx, const int* dur, int B, int T, int T_mel, int* mel2ph);
     // encoder_out [B, T, H], mel2ph int32 [B, T_mel] -> decoder_inp [B, T_mel, H], mel_out (optional) [B, T_mel, mel bins]
     void decode(Ctx& ctx, const float* encoder_out, const int* mel2ph, int B, int T, int T_mel, float* decoder_inp, float* mel_out);
@@ -156,10 +167,11 @@ class FS2Pitch {
 public:
     FS2Pitch(const maa_fs2_pitch_config& cfg, const StateDict& sd, int precision);
     ~FS2Pitch();
-    // origin [B, T_mel, H] (decode's decoder_inp), mel2ph int32 [B, T_mel], f0 / uv (each optional) [B, T_mel] -> decoder_inp
+    // pred_inp [B, T_mel, H] (the predictor's input: origin itself, or (origin + spk_f0) * tgt), origin [B, T_mel, H] (decode's
+    // decoder_inp, which the table row is added to), mel2ph int32 [B, T_mel], f0 / uv (each optional) [B, T_mel] -> decoder_inp
     // [B, T_mel, H], pitch_pred [B, T_mel, 2], f0_denorm [B, T_mel], coarse (optional) int32 [B, T_mel]
-    void forward(Ctx& ctx, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B, int T_mel,
-                 float* decoder_inp, float* pitch_pred, float* f0_denorm, int* coarse);
+    void forward(Ctx& ctx, const float* pred_inp, const float* origin, const int* mel2ph, const float* f0, const float* uv, int B,
+                 int T_mel, float* decoder_inp, float* pitch_pred, float* f0_denorm, int* coarse);
     const maa_fs2_pitch_config& config() const;
 
 private:

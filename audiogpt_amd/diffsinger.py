@@ -27,6 +27,12 @@ f0 to the vocoder.
 
     cas = DiffSingerCascade(gd, hifigan.vocoder, FastSpeech2MIDICascade(ctx=gd.ctx, state_dict=ckpt_fs2_sd))
     wav = cas.forward_model(txt_tokens, pitch_midi, midi_dur, is_slur)      # f0=, uv=, mel2ph=: a caller's, else predicted
+
+The configurations without use_midi -- DiffSpeech (lj_ds_beta6.yaml) and the original DiffSinger (popcs_ds_beta6.yaml) -- run the
+plain `FastSpeech2` (energy branch and speaker embeddings included) in front of the same chain: `DiffSpeech`.
+
+    tts = DiffSpeech(gd, hifigan.vocoder, FastSpeech2(ctx=gd.ctx, state_dict=ckpt_fs2_sd))
+    wav = tts.forward_model(txt_tokens)                                     # spk_embed=, mel2ph=, f0=, uv=, energy=
 """
 import numpy as np
 import torch
@@ -436,6 +442,144 @@ class FastSpeech2MIDICascade(FastSpeech2MIDI):
     __call__ = forward
 
 
+class FastSpeech2(object):
+    """modules/fastspeech/fs2.py:22-226 with the reference's call surface, inference only: `fs2(txt_tokens, mel2ph=None,
+    spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None, skip_decoder=False, spk_embed_dur_id=None, spk_embed_f0_id=None,
+    infer=True)` -> the reference's dict, device tensors: 'dur', 'dur_choice' (predicted durations), 'mel2ph', 'pitch_pred' and
+    'f0_denorm' (use_pitch_embed), 'energy_pred' (use_energy_embed), 'decoder_inp', 'mel_out' (unless skip_decoder).  This is the
+    `fs2` of every configuration without use_midi: the TTS ones (config.FASTSPEECH2, FASTSPEECH2_LIBRITTS) and both *_ds_beta6
+    chains.  state_dict: the checkpoint's (a `model.fs2.` or `fs2.` prefix is stripped), seeded random weights when None.
+
+    Two handles on one context: a backend.FastSpeech2Plain (encoder with token-counted sinusoid positions, or rel_pos; speakers;
+    the energy branch) and, with use_pitch_embed, a backend.FS2Pitch built from a cfg copy with the energy / speaker keys cleared.
+    Device calls, in order: [speaker] -> encode -> (the totals read, with predicted durations: the single device-to-host read) ->
+    length_regulate -> decode without the decoder -> [add_speaker] -> [the pitch branch] -> [finish] -> run_decoder.
+
+    spk_embed: int ids [B] with use_spk_id (spk_embed_dur_id / spk_embed_f0_id too, read with use_split_spk_id only), a float
+    [B, 256] vector with use_spk_embed.  f0 / uv as FastSpeech2MIDICascade takes them; energy [B, T_mel] >= 0 replaces the
+    prediction.  Checked on the host, where the caller's preprocessing leaves them (a device tensor is copied back for that):
+    tokens, speaker ids in [0, num_spk], mel2ph, energy >= 0.  The caller's f0, uv and energy are only read.
+
+    One divergence: a NEGATIVE predicted energy raises IndexError in the reference (on any frame, padding included: the table is
+    indexed with floor(64 e)); here such a frame takes row 0 of energy_embed.
+
+    Not built, refused with the reason: pitch_type 'ph' / 'cwt', pitch_ar, use_bert, use_pos_embed false; the text front end
+    (text -> txt_tokens) is the caller's."""
+
+    def __init__(self, cfg=None, device="cuda:0", state_dict=None, ctx=None, precision=None, seed=19):
+        self.cfg = dict(cfg or C.FASTSPEECH2)
+        inner = dict(self.cfg, use_pitch_embed=False)
+        backend.fs2_plain_config(inner)                # both refuse an unsupported configuration before a context is made
+        self.use_pitch = bool(self.cfg.get("use_pitch_embed", False))
+        pitch_cfg = dict(self.cfg, use_energy_embed=False, use_spk_id=False, use_spk_embed=False)
+        if self.use_pitch:
+            backend.fs2_pitch_config(pitch_cfg)
+        self.use_energy = bool(self.cfg.get("use_energy_embed", False))
+        self.spk_mode = "id" if self.cfg.get("use_spk_id") else "embed" if self.cfg.get("use_spk_embed") else None
+        self.ctx = ctx or Context(device, precision=precision or default_precision())
+        self.device = self.ctx.device
+        sd = state_dict if state_dict is not None else WT.make_fs2_plain_state_dict(self.cfg, seed=seed)
+        sd = WT.strip_prefix(sd, "model.fs2.") or WT.strip_prefix(sd, "fs2.") or sd
+        is_pitch = lambda k: k.startswith(("pitch_embed.", "pitch_predictor."))      # noqa: E731
+        self.net = backend.FastSpeech2Plain(self.ctx, inner, {k: v for k, v in sd.items() if not is_pitch(k)})
+        self.pitch = backend.FS2Pitch(self.ctx, pitch_cfg, {k: v for k, v in sd.items() if is_pitch(k)}) if self.use_pitch else None
+
+    def _check_tokens(self, txt_tokens, mel2ph):
+        what = "FastSpeech2"
+        tok = torch.as_tensor(txt_tokens).cpu()
+        if tok.dim() != 2 or tok.shape[0] < 1 or tok.shape[1] < 1:
+            raise ValueError("%s: txt_tokens %s is not [B, T_txt]" % (what, tuple(tok.shape)))
+        V = int(self.cfg["vocab_size"])
+        if int(tok.min()) < 0 or int(tok.max()) >= V:
+            raise ValueError("%s: txt_tokens outside [0, vocab_size = %d): the token table has no such row" % (what, V))
+        if not bool((tok > 0).any(dim=1).all()):
+            raise ValueError("%s: a sample with no live token (all padding, token 0): its attention has no visible key" % what)
+        if mel2ph is not None:
+            m = torch.as_tensor(mel2ph).cpu()
+            if m.dim() != 2 or m.shape[0] != tok.shape[0] or m.shape[1] < 1:
+                raise ValueError("%s: mel2ph %s is not [B = %d, T_mel]" % (what, tuple(m.shape), tok.shape[0]))
+            if int(m.min()) < 0 or int(m.max()) > tok.shape[1]:
+                raise ValueError("%s: mel2ph outside [0, T_txt = %d]: a frame points at no token" % (what, tok.shape[1]))
+            if not bool((m > 0).any(dim=1).all()):
+                raise ValueError("%s: a sample whose mel2ph is all 0: no frame, its decoder has no visible key" % what)
+        return int(tok.shape[0])
+
+    def _speaker_ids(self, spk_embed, spk_embed_dur_id, spk_embed_f0_id, B):
+        """The [3, B] ids of a use_spk_id model (fs2.py:99-104: the dur / f0 ids default to the speaker's), checked on the host."""
+        what, n = "FastSpeech2", int(self.cfg["num_spk"])
+        if spk_embed is None:
+            raise ValueError("%s: use_spk_id needs spk_embed, the speaker ids [B]" % what)
+        rows = []
+        for name, t in (("spk_embed", spk_embed), ("spk_embed_dur_id", spk_embed_dur_id), ("spk_embed_f0_id", spk_embed_f0_id)):
+            t = torch.as_tensor(spk_embed if t is None else t).cpu()
+            if t.is_floating_point() or tuple(t.reshape(-1).shape) != (B,):
+                raise ValueError("%s: %s %s %s is not integer ids [B = %d]" % (what, name, t.dtype, tuple(t.shape), B))
+            if int(t.min()) < 0 or int(t.max()) > n:
+                raise ValueError("%s: %s outside [0, num_spk = %d]: the speaker table has no such row" % (what, name, n))
+            rows.append(t.reshape(-1).long())
+        return torch.stack(rows)
+
+    @torch.no_grad()
+    def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None, skip_decoder=False,
+                spk_embed_dur_id=None, spk_embed_f0_id=None, infer=True):
+        if not infer:
+            raise ValueError("FastSpeech2: only infer=True is built (no dropout, no losses)")
+        B = self._check_tokens(txt_tokens, mel2ph)
+        if energy is not None and self.use_energy and not bool((torch.as_tensor(energy).cpu() >= 0).all()):
+            raise ValueError("FastSpeech2: energy below 0 (or NaN): energy_embed has no such row -- the reference raises IndexError")
+        sp = None
+        if self.spk_mode == "id":
+            ids = self._speaker_ids(spk_embed, spk_embed_dur_id, spk_embed_f0_id, B)
+            sp = self.net.speaker(ids=ids)
+        elif self.spk_mode == "embed":
+            if spk_embed is None or tuple(torch.as_tensor(spk_embed).shape) != (B, 256):
+                raise ValueError("FastSpeech2: use_spk_embed needs spk_embed [B = %d, 256]" % B)
+            sp = self.net.speaker(vec=spk_embed)
+        enc, xs, dur, totals = self.net.encode(txt_tokens, spk_dur=sp[1] if sp is not None else None)
+        ret = {}
+        if mel2ph is None:
+            tot = self._read_totals(totals)            # the one device-to-host read: T_mel sizes everything after it
+            if int(tot.min()) < 1:
+                raise ValueError("FastSpeech2: the predicted durations of sample %d sum to 0 frames: the reference's decoder "
+                                 "returns NaN there" % int(tot.argmin()))
+            m2p = self.net.length_regulate(dur, int(tot.max()))
+            ret["dur"], ret["dur_choice"] = xs[:, :, None], dur.long()
+        else:
+            m2p = torch.as_tensor(mel2ph).to(device=self.device, dtype=torch.int32)
+            ret["dur"] = xs
+        ret["mel2ph"] = m2p.long()
+        T_mel = int(m2p.shape[1])
+        for name, t in (("f0", f0), ("uv", uv), ("energy", energy)):
+            if t is not None and tuple(torch.as_tensor(t).shape) != (B, T_mel):
+                raise ValueError("FastSpeech2: %s %s is not [B = %d, T_mel = %d]" % (name, tuple(torch.as_tensor(t).shape), B, T_mel))
+        origin, _ = self.net.decode(enc, m2p, skip_decoder=True)
+        pred_inp = self.net.add_speaker(origin, sp[2], m2p) if sp is not None else origin
+        acc = origin
+        if self.use_pitch:
+            acc, ret["pitch_pred"], ret["f0_denorm"] = self.pitch.forward(origin, m2p, f0=f0, uv=uv,
+                                                                         pred_inp=pred_inp if sp is not None else None)
+        if self.use_energy or sp is not None:
+            acc, energy_pred = self.net.finish(pred_inp, acc, m2p, energy=energy, spk=sp[0] if sp is not None else None)
+            if self.use_energy:
+                ret["energy_pred"] = energy_pred
+        ret["decoder_inp"] = acc                       # (without energy and speakers the tail is acc * tgt = acc: no launch)
+        if not skip_decoder:
+            ret["mel_out"] = self.net.run_decoder(acc, m2p)
+        return ret
+
+    @staticmethod
+    def _read_totals(totals):
+        return totals.cpu()
+
+    __call__ = forward
+
+    def eval(self):
+        return self
+
+    def to(self, *args, **kwargs):
+        return self
+
+
 class DiffSingerE2E(object):
     """DiffSingerE2EInfer.forward_model (inference/svs/ds_e2e.py:22-45) with BaseSVSInfer.run_vocoder (base_svs_infer.py:61-70):
     score -> (fs2, when set) decoder_inp, mel2ph, coarse mel -> the diffusion's mel_out -> f0 (pe, when set) -> waveform.
@@ -506,3 +650,25 @@ class DiffSingerCascade(DiffSingerE2E):
         ret = self.fs2(txt_tokens, mel2ph=mel2ph, f0=f0, uv=uv, infer=True, pitch_midi=pitch_midi, midi_dur=midi_dur, is_slur=is_slur)
         mel_out = self.diffusion.infer(ret["mel_out"], ret["decoder_inp"].transpose(1, 2), mel2ph=mel2ph, **draws)
         return self.run_vocoder(mel_out, f0=ret["f0_denorm"], **self._sine_draws(rand_ini, noise_sine))
+
+
+class DiffSpeech(DiffSingerE2E):
+    """GaussianDiffusion.forward(infer=True) of the configurations without use_midi (shallow_diffusion_tts.py:236-277 over the
+    plain FastSpeech2: lj_ds_beta6.yaml, popcs_ds_beta6.yaml) followed by run_vocoder: text tokens -> waveform with no model on
+    the host.  diffusion: a GaussianDiffusion (config.DIFFSPEECH_LJ_BETA6, DIFFSINGER_POPCS_BETA6); vocoder / use_nsf: as
+    DiffSingerE2E, whose run_vocoder this shares (with use_nsf the front end's f0_denorm goes to the NSF vocoder); fs2: a
+    FastSpeech2 on the same device."""
+
+    def __init__(self, diffusion, vocoder, fs2, use_nsf=False):
+        super().__init__(diffusion, vocoder, pe=None, use_nsf=use_nsf, fs2=fs2)
+
+    @torch.no_grad()
+    def forward_model(self, txt_tokens, spk_embed=None, mel2ph=None, f0=None, uv=None, energy=None, rand_ini=None, noise_sine=None,
+                      **draws):
+        """Tokens -> [1, B * T_mel * hop].  spk_embed / mel2ph / f0 / uv / energy: as FastSpeech2.forward takes them; the final mask
+        of the diffusion uses the ARGUMENT mel2ph (shallow_diffusion_tts.py:273-276), so predicted durations leave the mel unmasked.
+        rand_ini / noise_sine: SineGen's two draws (use_nsf); draws: as GaussianDiffusion.infer takes them."""
+        ret = self.fs2(txt_tokens, mel2ph=mel2ph, spk_embed=spk_embed, f0=f0, uv=uv, energy=energy, infer=True)
+        mel_out = self.diffusion.infer(ret["mel_out"], ret["decoder_inp"].transpose(1, 2), mel2ph=mel2ph, **draws)
+        f0_denorm = ret.get("f0_denorm") if self.use_nsf else None
+        return self.run_vocoder(mel_out, f0=f0_denorm, **self._sine_draws(rand_ini, noise_sine))

@@ -448,6 +448,74 @@ def make_fs2_state_dict(cfg, seed=17):
     return out
 
 
+def make_fs2_plain_state_dict(cfg, seed=19):
+    """The plain FastSpeech2 (NeuralSeq/modules/fastspeech/fs2.py:22-72) in the reference key layout and order, bookkeeping
+    entries included: encoder_embed_tokens, encoder (its `embed_positions._float_tensor` without rel_pos), decoder, mel_out,
+    spk_embed_proj / spk_embed_f0 / spk_embed_dur (by use_spk_id / use_split_spk_id / use_spk_embed), dur_predictor, pitch_embed and
+    pitch_predictor (use_pitch_embed), energy_embed and energy_predictor (use_energy_embed): 130 keys at config.FASTSPEECH2 with
+    energy and split speaker ids.  Drawn as make_fs2_state_dict draws: LayerNorm affines away from 1 / 0, the pos_embed_alphas away
+    from 1, row 0 of the token, pitch and energy tables zero (nn.Embedding(padding_idx = 0)); the speaker tables have no padding
+    row.  The optional branches are drawn after everything else, so the shared tensors do not depend on the flags."""
+    g, sd = _Gen(seed), {}
+    H, V, M = cfg["hidden_size"], cfg["vocab_size"], cfg["audio_num_mel_bins"]
+    Cp = cfg["predictor_hidden"] if cfg["predictor_hidden"] > 0 else H
+
+    def table(rows, pad):
+        w = g.normal((rows, H), H ** -0.5)
+        if pad:
+            w[0] = 0.0
+        return w
+
+    def fft(name, n_layers, k, into):
+        for i in range(n_layers):
+            p = f"{name}.layers.{i}.op."
+            into[p + "layer_norm1.weight"], into[p + "layer_norm1.bias"] = g.gamma(H), g.beta(H)
+            into[p + "self_attn.in_proj_weight"] = g.weight((3 * H, H), 1.4)
+            into[p + "self_attn.out_proj.weight"] = g.weight((H, H))
+            into[p + "layer_norm2.weight"], into[p + "layer_norm2.bias"] = g.gamma(H), g.beta(H)
+            into[p + "ffn.ffn_1.weight"], into[p + "ffn.ffn_1.bias"] = g.weight((4 * H, H, k), 1.4), g.bias(4 * H)
+            into[p + "ffn.ffn_2.weight"], into[p + "ffn.ffn_2.bias"] = g.weight((H, 4 * H)), g.bias(H)
+        into[f"{name}.layer_norm.weight"], into[f"{name}.layer_norm.bias"] = g.gamma(H), g.beta(H)
+
+    def predictor(name, n_layers, k, n_out, alpha, into):
+        if alpha is not None:
+            into[name + ".pos_embed_alpha"] = torch.tensor([alpha], dtype=torch.float32)
+        for i in range(n_layers):
+            p, cin = f"{name}.conv.{i}.", (H if i == 0 else Cp)
+            into[p + "1.weight"], into[p + "1.bias"] = g.weight((Cp, cin, k), 1.4), g.bias(Cp)
+            into[p + "3.weight"], into[p + "3.bias"] = g.gamma(Cp), g.beta(Cp)
+        into[name + ".linear.weight"], into[name + ".linear.bias"] = g.weight((n_out, Cp)), g.bias(n_out)
+        if alpha is not None:
+            into[name + ".embed_positions._float_tensor"] = torch.zeros(1, dtype=torch.float32)
+
+    sd["encoder_embed_tokens.weight"] = table(V, True)
+    fft("encoder", cfg["enc_layers"], cfg["enc_ffn_kernel_size"], sd)
+    sd["encoder.embed_tokens.weight"] = sd["encoder_embed_tokens.weight"]
+    if not cfg.get("rel_pos"):
+        sd["encoder.embed_positions._float_tensor"] = torch.zeros(1, dtype=torch.float32)
+    sd["decoder.pos_embed_alpha"] = torch.tensor([0.8], dtype=torch.float32)
+    sd["decoder.embed_positions._float_tensor"] = torch.zeros(1, dtype=torch.float32)
+    fft("decoder", cfg["dec_layers"], cfg["dec_ffn_kernel_size"], sd)
+    sd["mel_out.weight"], sd["mel_out.bias"] = g.weight((M, H)), g.bias(M)
+    dur = {}
+    predictor("dur_predictor", cfg["dur_predictor_layers"], cfg["dur_predictor_kernel"], 1, None, dur)
+    spk, pitch, energy = {}, {}, {}
+    if cfg.get("use_pitch_embed"):
+        pitch["pitch_embed.weight"] = table(300, True)
+        predictor("pitch_predictor", cfg.get("predictor_layers", 5), cfg.get("predictor_kernel", 5),
+                  2 if cfg.get("pitch_type", "frame") == "frame" else 1, 0.7, pitch)
+    if cfg.get("use_energy_embed"):
+        energy["energy_embed.weight"] = table(256, True)
+        predictor("energy_predictor", cfg.get("predictor_layers", 5), cfg.get("predictor_kernel", 5), 1, 0.6, energy)
+    if cfg.get("use_spk_id"):
+        names = ("spk_embed_proj", "spk_embed_f0", "spk_embed_dur") if cfg.get("use_split_spk_id") else ("spk_embed_proj",)
+        for name in names:
+            spk[name + ".weight"] = g.normal((cfg["num_spk"] + 1, H), 0.5)
+    elif cfg.get("use_spk_embed"):
+        spk["spk_embed_proj.weight"], spk["spk_embed_proj.bias"] = g.weight((H, 256)), g.bias(H)
+    return {**sd, **spk, **dur, **pitch, **energy}
+
+
 # ----------------------------------------------------------------------------- conditioning encoders
 def make_clap_text_state_dict(cfg, seed=11):
     """`caption_encoder.`-relative keys of the CLAP checkpoint FrozenCLAPEmbedder loads (encoders/modules.py:179-183):

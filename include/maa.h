@@ -420,6 +420,11 @@ typedef struct maa_fs2_config {
     int audio_num_mel_bins;
     int ffn_padding_same, ffn_act_gelu, dur_loss_mse, rel_pos, use_pos_embed, encoder_fft, decoder_fft;      /* must be 1 */
     int use_pitch_embed, use_energy_embed, use_spk_id, use_spk_embed, use_bert;                              /* must be 0 */
+    /* appended; all zero is FastSpeech2MIDI as above.  plain = 1: the plain FastSpeech2 of modules/fastspeech/fs2.py (the TTS
+     * configurations and the *_ds_beta6 chains): no note features, and rel_pos 0 (sinusoid rows by token count), use_energy_embed,
+     * use_spk_id (with num_spk, use_split_spk_id) or use_spk_embed are accepted; predictor_layers / predictor_kernel are the
+     * energy predictor's.  use_pitch_embed stays refused: the pitch branch is maa_fs2_pitch. */
+    int plain, num_spk, use_split_spk_id, predictor_layers, predictor_kernel;
 } maa_fs2_config;
 typedef struct maa_fs2 maa_fs2;
 /* tensors: the FastSpeech2MIDI state_dict ({encoder,decoder}.layers.{i}.op.{layer_norm1,layer_norm2}.*,
@@ -427,6 +432,10 @@ typedef struct maa_fs2 maa_fs2;
  * decoder.pos_embed_alpha, mel_out.*, dur_predictor.conv.{i}.{1,3}.*, dur_predictor.linear.*, midi_embed.weight, midi_dur_layer.*,
  * is_slur_embed.weight); encoder_embed_tokens.weight (the same tensor) and decoder.embed_positions._float_tensor are accepted and
  * ignored */
+/* plain = 1: the FastSpeech2 state_dict -- the same without midi_embed / midi_dur_layer / is_slur_embed, plus, by the flags,
+ * spk_embed_proj.weight [num_spk + 1, H] (use_spk_id; spk_embed_dur.weight / spk_embed_f0.weight with use_split_spk_id) or
+ * spk_embed_proj.{weight [H, 256], bias} (use_spk_embed), and energy_predictor.conv.{i}.{1,3}.*, energy_predictor.linear.* ([1, C_p],
+ * [1]), energy_predictor.pos_embed_alpha, energy_embed.weight [256, H] (use_energy_embed) */
 int maa_fs2_create(maa_ctx* ctx, const maa_fs2_config* cfg, const maa_tensor* tensors, int n_tensors, maa_fs2** out);
 int maa_fs2_destroy(maa_fs2* fs2);
 /* The three calls below issue launches on the context's stream only: no device-to-host copy, no synchronisation.  Integer
@@ -438,6 +447,33 @@ int maa_fs2_destroy(maa_fs2* fs2);
  * T_mel = max(d_totals) is what the caller reads back to size the outputs of the next two calls. */
 int maa_fs2_encode(maa_ctx* ctx, maa_fs2* fs2, const int* d_tokens, const int* d_pitch_midi, const float* d_midi_dur,
                    const int* d_is_slur, int B, int T, float* d_encoder_out, float* d_xs, int* d_dur, int* d_totals);
+/* ---- the plain FastSpeech2 (a handle created with plain = 1; modules/fastspeech/fs2.py:84-135,165-172, infer only) ----
+ * Call order of FastSpeech2.forward: [maa_fs2_speaker] -> maa_fs2_encode_plain -> maa_fs2_length_regulate -> maa_fs2_decode
+ * (d_mel_out NULL) -> [maa_fs2_add_speaker] -> [maa_fs2_pitch_forward_from] -> maa_fs2_finish -> maa_fs2_run_decoder.  All of them
+ * issue launches on the context's stream only; the handle's mode is read after the context is bound.
+ *
+ * encode_plain: replaces FastspeechEncoder.forward (tts_modules.py:352-375; positions = cumsum(tok != 0) * (tok != 0) into the
+ * sinusoid table, the embedding scale applied once; with rel_pos RelPositionalEncoding on the scaled embedding) and add_dur on
+ * dur_inp = (encoder_out + spk_dur) * src_nonpadding.  d_tokens [B, T] (0 = padding), d_spk_dur [B, hidden_size] or NULL ->
+ * outputs as maa_fs2_encode.  Refuses a FastSpeech2MIDI handle; maa_fs2_encode refuses a plain one. */
+int maa_fs2_encode_plain(maa_ctx* ctx, maa_fs2* fs2, const int* d_tokens, const float* d_spk_dur, int B, int T, float* d_encoder_out,
+                         float* d_xs, int* d_dur, int* d_totals);
+/* replaces: fs2.py:96-110.  d_ids int32 [3, B] (speaker, dur and f0 ids in [0, num_spk]; rows 1 and 2 are read with
+ * use_split_spk_id only) for a use_spk_id handle, d_vec [B, 256] for a use_spk_embed one; both may be non-NULL, the handle's mode
+ * chooses -> d_out [3, B, hidden_size] = spk_embed, spk_embed_dur, spk_embed_f0. */
+int maa_fs2_speaker(maa_ctx* ctx, maa_fs2* fs2, const int* d_ids, const float* d_vec, int B, float* d_out);
+/* d_out [B, T_mel, hidden_size] = (d_x + d_spk[b]) * (mel2ph > 0): pitch_inp, the pitch and energy predictors' input (fs2.py:125) */
+int maa_fs2_add_speaker(maa_ctx* ctx, maa_fs2* fs2, const float* d_x, const float* d_spk, const int* d_mel2ph, int B, int T_mel,
+                        float* d_out);
+/* replaces: add_energy and fs2.py:132.  With use_energy_embed: EnergyPredictor on d_pred_inp [B, T_mel, hidden_size] -> d_energy_pred
+ * [B, T_mel] (ret['energy_pred'], every frame); e = d_energy [B, T_mel] if given, else the prediction; bin = floor(64 e) clamped to
+ * [0, 255] -> d_energy_bin int32 [B, T_mel].  The reference computes clamp(e * 256 // 4, max = 255) and raises IndexError for a
+ * negative e on any frame; here such a frame (and a NaN) takes row 0.  Then, one launch with the head,
+ * d_decoder_inp = (d_acc + energy_embed[bin] + d_spk[b]) * (mel2ph > 0) (ret['decoder_inp']; may not alias an input).  d_acc: decode's
+ * decoder_inp, or the pitch branch's.  Without use_energy_embed: (d_acc + d_spk[b]) * (mel2ph > 0), d_pred_inp / d_energy unread and
+ * d_energy_pred / d_energy_bin unwritten.  d_pred_inp (then), d_energy, d_spk [B, hidden_size], d_energy_pred, d_energy_bin: NULL or given. */
+int maa_fs2_finish(maa_ctx* ctx, maa_fs2* fs2, const float* d_pred_inp, const float* d_acc, const int* d_mel2ph, const float* d_energy,
+                   const float* d_spk, int B, int T_mel, float* d_decoder_inp, float* d_energy_pred, int* d_energy_bin);
 /* LengthRegulator: d_dur [B, T] (>= 0) -> d_mel2ph [B, T_mel], frame -> 1-based token, 0 past the sample's total. */
 int maa_fs2_length_regulate(maa_ctx* ctx, maa_fs2* fs2, const int* d_dur, int B, int T, int T_mel, int* d_mel2ph);
 /* decode: d_encoder_out [B, T, hidden_size], d_mel2ph [B, T_mel] in [0, T] -> d_decoder_inp [B, T_mel, hidden_size]
@@ -482,6 +518,12 @@ int maa_fs2_pitch_destroy(maa_fs2_pitch* h);
 int maa_fs2_pitch_forward(maa_ctx* ctx, maa_fs2_pitch* h, const float* d_origin, const int* d_mel2ph, const float* d_f0,
                           const float* d_uv, int B, int T_mel, float* d_decoder_inp, float* d_pitch_pred, float* d_f0_denorm,
                           int* d_coarse);
+/* maa_fs2_pitch_forward with the predictor's input d_pred_inp [B, T_mel, hidden_size] -- pitch_inp = (origin + spk_f0) * tgt of a
+ * model with speakers (maa_fs2_add_speaker) -- apart from d_origin, which the pitch_embed row is added to.  maa_fs2_pitch_forward
+ * is this call with both equal.  d_decoder_inp may alias neither. */
+int maa_fs2_pitch_forward_from(maa_ctx* ctx, maa_fs2_pitch* h, const float* d_pred_inp, const float* d_origin, const int* d_mel2ph,
+                               const float* d_f0, const float* d_uv, int B, int T_mel, float* d_decoder_inp, float* d_pitch_pred,
+                               float* d_f0_denorm, int* d_coarse);
 
 /* ---- conditioning encoders (the step before the sampler: text / image -> cross-attention context) ----------
  * kind 0: the CLAP text branch as FrozenCLAPEmbedder.encode runs it (ldm/modules/encoders/modules.py:204-211):
