@@ -171,6 +171,17 @@ class maa_sampler_step_args(C.Structure):
 STEP_KINDS = {"ddim_prepare": 0, "ddim": 1, "plms": 2, "plms_euler_mid": 3, "plms_euler_final": 4, "ddpm": 5, "ds_plms": 6,
               "ds_advance": 7, "ds_ddpm": 8}
 
+
+class maa_front_rows_args(C.Structure):
+    _fields_ = [(k, C.c_int) for k in (
+        "kind", "B", "rows", "n", "T", "F", "C", "left", "total", "ldo", "mode", "nf", "ldy", "ldm", "power2",
+        "frames", "n_mels", "ldmel", "log_kind", "layout")] + [
+        ("amin", C.c_float), ("ref_db", C.c_float), ("d_x", C.c_void_p), ("h_scale", C.POINTER(C.c_float)),
+        ("h_shift", C.POINTER(C.c_float)), ("d_out", C.c_void_p)]
+
+
+FRONT_KINDS = {"pad": 0, "power": 1, "logmel": 2, "affine": 3, "pool": 4}      # MAA_FRONT_* of include/maa.h
+
 # The one list of the library's entries: name -> argument types (every entry returns an int status).  load() applies it and
 # EXPORTS is derived from it; a new entry of include/maa.h is added here and nowhere else.
 vp, ci, cf, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)
@@ -261,6 +272,7 @@ SIGNATURES = {
     "maa_op_layernorm_ex": [vp, vp, ci, ci, fp, fp, cf, vp, ci],
     "maa_op_seq_rows": [vp, C.POINTER(maa_seq_rows_args)],
     "maa_op_sampler_step": [vp, C.POINTER(maa_sampler_step_args)],
+    "maa_op_front_rows": [vp, C.POINTER(maa_front_rows_args)],
     "maa_op_split32": [vp, vp, ci, ci, cf, ci, vp],
     "maa_unet_forward_split": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, fp, vp],
     "maa_op_unfold": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp],

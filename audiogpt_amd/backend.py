@@ -326,6 +326,24 @@ class Context(_Handle):
             setattr(a, name, v)
         self._call("maa_op_sampler_step", C.byref(a))
 
+    def op_front_rows(self, kind, x, out, scale=None, shift=None, **fields):
+        """maa_op_front_rows: one small kernel of the waveform front ends / of Cnn14's ends through the library's internal launch
+        (`kind`: a key of _lib.FRONT_KINDS; include/maa.h lists what each reads and writes).  x / out are fp32 device tensors,
+        possibly views into larger buffers; scale / shift ("affine") come from the host; `fields` are the integer and float
+        members of maa_front_rows_args by name.  Writes into `out`; nothing is allocated, copied or checked beyond what the C
+        entry point checks."""
+        for t in (x, out):
+            assert t.is_cuda and t.dtype == torch.float32, (t.device, t.dtype)
+        keep = [L.host_f32(t) if t is not None else (None, None) for t in (scale, shift)]
+        a = L.maa_front_rows_args(kind=L.FRONT_KINDS[kind], d_x=x.data_ptr(), d_out=out.data_ptr(), h_scale=keep[0][1],
+                                  h_shift=keep[1][1])
+        known = {f[0]: f[1] for f in L.maa_front_rows_args._fields_ if f[1] in (C.c_int, C.c_float)}
+        for name, v in fields.items():
+            assert name in known and name != "kind", name
+            setattr(a, name, float(v) if known[name] is C.c_float else int(v))
+        self._call("maa_op_front_rows", C.byref(a))
+        return out
+
     def op_layernorm_ex(self, x, gamma, beta, eps=1e-5, out_split=0):
         """LayerNorm over the last dim of x [rows, C]; out_split = 1: the result as split32 rows in an fp32-typed tensor."""
         x = _f32(x, self.device)

@@ -1262,6 +1262,67 @@ int maa_op_sampler_step(maa_ctx* ctx, const maa_sampler_step_args* a) {
     });
 }
 
+int maa_op_front_rows(maa_ctx* ctx, const maa_front_rows_args* a) {
+    return guarded([&] {
+        MAA_CHECK(a != nullptr, "bad op_front_rows arguments: null pointer");
+        const int k = a->kind;
+        MAA_CHECK(k >= MAA_FRONT_PAD && k <= MAA_FRONT_POOL, "op_front_rows: unknown kind");
+        MAA_CHECK(a->d_x && a->d_out && (k != MAA_FRONT_AFFINE || (a->h_scale && a->h_shift)),
+                  "bad op_front_rows arguments: null pointer");
+        if (k == MAA_FRONT_PAD || k == MAA_FRONT_LOGMEL || k == MAA_FRONT_POOL) MAA_CHECK(a->B >= 1, "op_front_rows: B < 1");
+        if (k == MAA_FRONT_POWER) MAA_CHECK(a->rows >= 1, "op_front_rows: rows < 1");
+        if (k == MAA_FRONT_PAD || k == MAA_FRONT_AFFINE) MAA_CHECK(a->n >= 1, "op_front_rows: n < 1");
+        if (k == MAA_FRONT_POOL) MAA_CHECK(a->T >= 1, "op_front_rows: T < 1");
+        if (k == MAA_FRONT_AFFINE || k == MAA_FRONT_POOL) MAA_CHECK(a->F >= 1, "op_front_rows: F < 1");
+        if (k == MAA_FRONT_POOL) MAA_CHECK(a->C >= 1, "op_front_rows: C < 1");
+        if (k == MAA_FRONT_PAD) {
+            MAA_CHECK(a->mode == 0 || a->mode == 1, "op_front_rows: unknown mode");
+            MAA_CHECK(a->left >= 0, "op_front_rows: left < 0");
+            MAA_CHECK((long long)a->total >= (long long)a->left + a->n, "op_front_rows: total < left + n");
+            MAA_CHECK(a->ldo >= a->total, "op_front_rows: ldo < total");
+            // (launch_pad1d's own rule, here so that it too comes back before the context is bound)
+            MAA_CHECK(a->mode == 0 || (a->n > a->left && a->n > a->total - a->left - a->n),
+                      "reflect padding needs a signal longer than the pad");
+        }
+        if (k == MAA_FRONT_POWER) {
+            MAA_CHECK(a->nf >= 1, "op_front_rows: nf < 1");
+            MAA_CHECK((long long)a->ldy >= 2ll * a->nf, "op_front_rows: ldy < 2 nf");
+            MAA_CHECK(a->ldm >= a->nf, "op_front_rows: ldm < nf");
+        }
+        if (k == MAA_FRONT_LOGMEL) {
+            MAA_CHECK(a->frames >= 1, "op_front_rows: frames < 1");
+            MAA_CHECK(a->n_mels >= 1, "op_front_rows: n_mels < 1");
+            MAA_CHECK(a->ldmel >= a->n_mels, "op_front_rows: ldmel < n_mels");
+            MAA_CHECK(a->log_kind == 0 || a->log_kind == 1, "op_front_rows: unknown log_kind");
+            MAA_CHECK(a->layout == 0 || a->layout == 1, "op_front_rows: unknown layout");
+            MAA_CHECK(a->amin > 0.f, "op_front_rows: amin <= 0");
+        }
+        bind(ctx);
+        maa::Ctx& c = ctx->c;
+        maa::WeightStore ws(c.dtype != 0);
+        switch (k) {
+        case MAA_FRONT_PAD:
+            maa::launch_pad1d(c, a->d_x, a->B, a->n, a->left, a->total, a->ldo, a->mode, a->d_out);
+            break;
+        case MAA_FRONT_POWER:
+            maa::launch_spec_power(c, a->d_x, a->rows, a->nf, a->ldy, a->ldm, a->power2, a->d_out);
+            break;
+        case MAA_FRONT_LOGMEL:
+            maa::launch_logmel(c, a->d_x, a->B, a->frames, a->n_mels, a->ldmel, a->log_kind, a->amin, a->ref_db, a->layout, a->d_out);
+            break;
+        case MAA_FRONT_AFFINE: {
+            const float* sc = ws.upload(std::vector<float>(a->h_scale, a->h_scale + a->F));
+            const float* sh = ws.upload(std::vector<float>(a->h_shift, a->h_shift + a->F));
+            maa::launch_affine_lastdim(c, a->d_x, a->n, a->F, sc, sh, a->d_out);
+            break;
+        }
+        default:
+            maa::launch_cnn14_pool(c, a->d_x, a->B, a->T, a->F, a->C, a->d_out);
+        }
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
 int maa_op_split32(maa_ctx* ctx, const float* d_x, int rows, int C, float slope, int unpack, float* d_y) {
     return guarded([&] {
         MAA_CHECK(d_x && d_y && d_x != d_y, "bad op_split32 arguments");

@@ -22,13 +22,6 @@
 
 namespace maa {
 
-void launch_pad1d(const Ctx& ctx, const float* x, int B, int n, int left, int total, int ldo, int mode, float* out);
-void launch_spec_power(const Ctx& ctx, const float* y, long long rows, int nf, int ldy, int ldm, int power2, float* mag);
-void launch_logmel(const Ctx& ctx, const float* mel, int B, int frames, int n_mels, int ldmel, int kind, float amin,
-                   float ref_db, int layout, float* out);
-void launch_affine_lastdim(const Ctx& ctx, const float* x, long long n, int F, const float* scale, const float* shift,
-                           float* out);
-void launch_cnn14_pool(const Ctx& ctx, const float* x, int B, int T, int F, int C, float* out);
 void launch_l2norm_rows(const Ctx& ctx, const float* x, int B, int C, float* out);
 void launch_gelu(const Ctx& ctx, const float* x, long long n, float* out);
 

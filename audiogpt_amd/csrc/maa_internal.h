@@ -427,6 +427,14 @@ void launch_nsf_source(const Ctx& ctx, const float* f0, int B, int T, int hop, f
                        const float* noise, int harmonics, const float* w, const float* bias, float* sines, float* har);
 // out[i, j] = scale * <audio[i], text[j]> (spectral.hip)
 void launch_similarity(const Ctx& ctx, const float* audio, const float* text, int Na, int Nt, int D, float scale, float* out);
+// the small kernels of the waveform front ends and of Cnn14's ends (spectral.hip)
+void launch_pad1d(const Ctx& ctx, const float* x, int B, int n, int left, int total, int ldo, int mode, float* out);
+void launch_spec_power(const Ctx& ctx, const float* y, long long rows, int nf, int ldy, int ldm, int power2, float* mag);
+void launch_logmel(const Ctx& ctx, const float* mel, int B, int frames, int n_mels, int ldmel, int kind, float amin,
+                   float ref_db, int layout, float* out);
+void launch_affine_lastdim(const Ctx& ctx, const float* x, long long n, int F, const float* scale, const float* shift,
+                           float* out);
+void launch_cnn14_pool(const Ctx& ctx, const float* x, int B, int T, int F, int C, float* out);
 void launch_leaky(const Ctx& ctx, const float* x, long long n, float slope, float* out);
 void launch_clamp_affine(const Ctx& ctx, const float* x, long long n, float mul, float add, float lo, float hi,
                          float* out);

@@ -843,6 +843,38 @@ typedef struct {
     float* d_log_x0;
 } maa_sampler_step_args;
 int maa_op_sampler_step(maa_ctx* ctx, const maa_sampler_step_args* args);
+/* One small kernel of the waveform front ends or of Cnn14's ends exactly as Spectral / Resampler / ClapAudio launch it (tests of
+ * csrc/spectral.hip): `kind` selects one internal launch, the entry forwards every argument of it, synchronises the stream once
+ * and adds no arithmetic.  d_x / d_out are the caller's DEVICE buffers; h_scale / h_shift are HOST arrays, uploaded as the model
+ * uploads its folded BatchNorm.  kind:
+ *   MAA_FRONT_PAD     d_x [B, n] -> d_out [B, ldo]: d_out[b, left + i] = d_x[b, i], columns 0 .. left-1 and left+n .. total-1 by
+ *                     `mode` (0 zeros, 1 numpy "reflect": needs n > left and n > total - left - n), columns total .. ldo-1 zeros.
+ *   MAA_FRONT_POWER   d_x [rows, ldy] = nf real parts then nf imaginary parts per row -> d_out [rows, ldm] = re^2 + im^2
+ *                     (power2 != 0) or its square root, columns nf .. ldm-1 zeros.
+ *   MAA_FRONT_LOGMEL  d_x [B * frames, ldmel] -> log_kind 0: 10 log10(max(x, amin)) - ref_db; log_kind 1: clip((20 log10(max(x,
+ *                     amin)) - 20 + 100) / 100, 0, 1); layout 0: d_out [B, frames, n_mels], 1: d_out [B, n_mels, frames].
+ *   MAA_FRONT_AFFINE  d_out [n] = d_x [n] * h_scale[i % F] + h_shift[i % F], h_scale / h_shift [F] (Cnn14.bn0 over the mel bins).
+ *   MAA_FRONT_POOL    d_x [B, T, F, C] channels-last -> d_out [B, C] = max_t m + mean_t m, m[t] = mean_f x (Cnn14's pooling).
+ * Checked here, before the context is touched: null pointers, every size the kind reads >= 1, left >= 0, total >= left + n,
+ * ldo >= total, the reflect rule, ldy >= 2 nf, ldm >= nf, ldmel >= n_mels, amin > 0, kind / mode / log_kind / layout known. */
+#define MAA_FRONT_PAD 0
+#define MAA_FRONT_POWER 1
+#define MAA_FRONT_LOGMEL 2
+#define MAA_FRONT_AFFINE 3
+#define MAA_FRONT_POOL 4
+typedef struct {
+    int kind;
+    int B, rows, n, T, F, C;
+    int left, total, ldo, mode;
+    int nf, ldy, ldm, power2;
+    int frames, n_mels, ldmel, log_kind, layout;
+    float amin, ref_db;
+    const float* d_x;
+    const float* h_scale;
+    const float* h_shift;
+    float* d_out;
+} maa_front_rows_args;
+int maa_op_front_rows(maa_ctx* ctx, const maa_front_rows_args* args);
 /* The split32 row codec on its own, d_x / d_y [rows,C] on the device, C % 32 == 0: unpack = 0 writes the split32 rows of
  * leaky_relu(x, slope) (slope 1: of x), unpack = 1 reads split32 rows and writes hi + lo as fp32 (slope is ignored). */
 int maa_op_split32(maa_ctx* ctx, const float* d_x, int rows, int C, float slope, int unpack, float* d_y);

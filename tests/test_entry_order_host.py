@@ -72,6 +72,8 @@ def _configs():
         L.maa_sampler_step_args: _struct(L.maa_sampler_step_args, kind=L.STEP_KINDS["ddim"], B=1, nB=1, S=2, n=8, per=8, per_in=8,
                                          scale=1.0, temperature=1.0, d_x=_base, d_xin=_base + 256, d_eps_u=_base + 512,
                                          d_coef=_base + 768, d_step=_base + 1024),
+        L.maa_front_rows_args: _struct(L.maa_front_rows_args, kind=L.FRONT_KINDS["pad"], B=1, n=8, left=2, total=12, ldo=12, mode=1,
+                                       d_x=_base, d_out=_base + 256),
         L.maa_prof_row: C.cast(_base, C.POINTER(L.maa_prof_row)),
         L.maa_tensor: None,          # an empty tensor list, with n_tensors = 0
     }

@@ -259,6 +259,88 @@ def test_sampler_step_test_entry_is_bound_and_refuses_by_name(lib_path):
         assert b"unknown kind" in lib.maa_last_error()
 
 
+def test_front_rows_test_entry_is_bound_and_refuses_by_name(lib_path):
+    """maa_op_front_rows (tests/test_gpu_frontend_ops.py) is declared, exported, bound with the header's argument count and a
+    structure that has the header's fields in the header's order and the size the header's types give, the kinds' #defines match,
+    and every host-side refusal comes back with its own message before the context is touched."""
+    from audiogpt_amd import _lib
+    lib = _lib.load()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "maa.h")).read(), flags=re.S)
+    name = "maa_op_front_rows"
+    assert name in _lib.EXPORTS and name in _declared_symbols()
+    decl = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
+    assert len(getattr(lib, name).argtypes) == len(decl.split(",")) == 2, name
+    body = re.search(r"typedef struct \{([^}]*)\} maa_front_rows_args;", src).group(1)
+    ctype = {"int": ctypes.c_int, "float": ctypes.c_float}
+    fields = []
+    for stmt in body.split(";"):
+        stmt = stmt.strip()
+        if stmt:
+            m = re.match(r"^(const\s+)?(float|int)\s*(\*?)\s*(.*)$", stmt)
+            pointer = (ctypes.POINTER(ctypes.c_float) if m.group(4).startswith("h_") else ctypes.c_void_p) if m.group(3) else None
+            fields += [(f.strip(), pointer or ctype[m.group(2)]) for f in m.group(4).split(",")]
+    assert fields == list(_lib.maa_front_rows_args._fields_)
+
+    class Mirror(ctypes.Structure):          # the header's fields under the C layout rules
+        _fields_ = fields
+    assert ctypes.sizeof(Mirror) == ctypes.sizeof(_lib.maa_front_rows_args) == 20 * 4 + 2 * 4 + 4 * 8
+    for kind, value in _lib.FRONT_KINDS.items():
+        assert re.search(r"#define MAA_FRONT_%s %d\b" % (kind.upper(), value), src), kind
+    assert sorted(_lib.FRONT_KINDS.values()) == [0, 1, 2, 3, 4]
+    assert lib.maa_op_front_rows(None, None) < 0 and b"null pointer" in lib.maa_last_error()
+    import numpy as np
+    buf = np.zeros(64, np.float32)
+    fp = buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    dp = buf.ctypes.data                                     # stands in for device memory; never read
+    base = {
+        "pad": dict(B=2, n=8, left=3, total=16, ldo=20, mode=1, d_x=dp, d_out=dp),
+        "power": dict(rows=2, nf=5, ldy=10, ldm=8, power2=1, d_x=dp, d_out=dp),
+        "logmel": dict(B=1, frames=2, n_mels=8, ldmel=8, log_kind=0, layout=1, amin=1e-10, ref_db=0.0, d_x=dp, d_out=dp),
+        "affine": dict(n=16, F=8, d_x=dp, h_scale=fp, h_shift=fp, d_out=dp),
+        "pool": dict(B=1, T=2, F=2, C=4, d_x=dp, d_out=dp),
+    }
+    assert sorted(base) == sorted(_lib.FRONT_KINDS)
+
+    def refused(kind, message, **kw):
+        d = dict(base[kind], kind=_lib.FRONT_KINDS[kind])
+        d.update(kw)
+        st = lib.maa_op_front_rows(None, ctypes.byref(_lib.maa_front_rows_args(**d)))
+        assert st < 0 and message in lib.maa_last_error(), (kind, kw, lib.maa_last_error())
+
+    for kind in base:
+        refused(kind, b"null context")                                  # past every argument check
+        for p in [k for k in base[kind] if k.startswith(("d_", "h_"))]:
+            refused(kind, b"null pointer", **{p: None})
+    for kind, sizes in (("pad", "B n"), ("power", "rows nf"), ("logmel", "B frames n_mels"), ("affine", "n F"), ("pool", "B T F C")):
+        for s in sizes.split():
+            for bad in (0, -1):
+                refused(kind, ("op_front_rows: %s < 1" % s).encode(), **{s: bad})
+    refused("pad", b"total < left + n", total=10)
+    refused("pad", b"null context", total=11, ldo=11, mode=0)
+    refused("pad", b"ldo < total", ldo=15)
+    refused("pad", b"null context", ldo=16)
+    refused("pad", b"left < 0", left=-1)
+    refused("pad", b"unknown mode", mode=2)
+    refused("pad", b"unknown mode", mode=-1)
+    refused("pad", b"reflect padding needs a signal longer than the pad", left=8, total=20)          # n == left
+    refused("pad", b"reflect padding needs a signal longer than the pad", left=0)                    # n == right
+    refused("pad", b"null context", left=7, total=16, ldo=16)                                         # n = left + 1 = right + 7
+    refused("pad", b"null context", left=8, total=20, mode=0)                                         # zeros take any widths
+    refused("power", b"ldy < 2 nf", ldy=9)
+    refused("power", b"ldm < nf", ldm=4)
+    refused("power", b"null context", ldm=5, power2=0)
+    refused("logmel", b"ldmel < n_mels", ldmel=7)
+    refused("logmel", b"null context", ldmel=11, log_kind=1, layout=0, amin=1e-5)
+    refused("logmel", b"amin <= 0", amin=0.0)
+    refused("logmel", b"amin <= 0", amin=-1.0)
+    refused("logmel", b"unknown log_kind", log_kind=2)
+    refused("logmel", b"unknown layout", layout=2)
+    refused("logmel", b"unknown layout", layout=-1)
+    for kind in (-1, 5):
+        assert lib.maa_op_front_rows(None, ctypes.byref(_lib.maa_front_rows_args(kind=kind))) < 0
+        assert b"unknown kind" in lib.maa_last_error()
+
+
 def test_contraction_test_entry_is_bound_and_rejects_null(lib_path):
     """maa_op_igemm_ex (tests/test_gpu_igemm_ops.py) is declared, exported, bound with the header's argument count and a structure
     that has the header's fields in the header's order, and fails with a message on null arguments, on a pitch below its width and
