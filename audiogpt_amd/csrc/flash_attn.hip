@@ -46,15 +46,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int KT = 32;      // keys per tile
 
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
-    hi = pk_bf16(a, b);
-    lo = pk_bf16(a - __builtin_bit_cast(float, hi << 16), b - __builtin_bit_cast(float, hi & 0xffff0000u));
-}
 struct Frag {      // 8 bf16 = 4 dwords, bit-castable to the MFMA operand type
     unsigned w[4];
 };

@@ -25,19 +25,6 @@ namespace {
 
 constexpr int NT = 256;
 
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);      // v_cvt_pk_bf16_f32 (round to nearest even)
-    return __builtin_bit_cast(unsigned, h);
-}
-// (a, b) -> packed hi pair and packed lo pair
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
-    hi = pk_bf16(a, b);
-    const float fa = __builtin_bit_cast(float, hi << 16);
-    const float fb = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pk_bf16(a - fa, b - fb);
-}
-
 // A_SPLIT / B_SPLIT: the operand already sits in memory pre-split ("split32" format: each group of 32 consecutive k
 // of a row occupies one 128-byte line = [32 bf16 hi | 32 bf16 lo], so a row has the byte pitch of its fp32 form):
 // GroupNorm / LayerNorm outputs and packed weights in the bf16 modes.  A tile row of one K chunk is then exactly one

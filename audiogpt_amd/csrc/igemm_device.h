@@ -14,7 +14,18 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BK = 32;      // K depth of one LDS stage of the bf16 engines = one split32 line (32 bf16 hi | 32 bf16 lo)
+// split32 of a pair of floats: hi = bf16(v) of both packed in one dword (low half = a), lo = bf16(v - hi) likewise
+__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
+    f32x2 f = {a, b};
+    bf16x2 h = __builtin_convertvector(f, bf16x2);      // v_cvt_pk_bf16_f32 (round to nearest even)
+    return __builtin_bit_cast(unsigned, h);
+}
+__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
+    hi = pk_bf16(a, b);
+    lo = pk_bf16(a - __builtin_bit_cast(float, hi << 16), b - __builtin_bit_cast(float, hi & 0xffff0000u));
+}
+
+constexpr int BK = 32;     // K depth of one LDS stage of the bf16 engines = one split32 line (32 bf16 hi | 32 bf16 lo)
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {

@@ -24,11 +24,6 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    f32x2 f = {a, b};
-    bf16x2 h = __builtin_convertvector(f, bf16x2);
-    return __builtin_bit_cast(unsigned, h);
-}
 // write 4 consecutive channels (c % 4 == 0) of row `row` either as fp32 or in the "split32" form read by the bf16
 // GEMM engine: every 32 channels of a row take one 128-byte line [32 bf16 hi | 32 bf16 lo], hi = bf16(v),
 // lo = bf16(v - hi); the row pitch is the same C*4 bytes as fp32
@@ -39,10 +34,8 @@ __device__ __forceinline__ void store4(float* out, long long row, int c, int C, 
     }
     unsigned short* o = reinterpret_cast<unsigned short*>(out) + row * C * 2 + (c >> 5) * 64 + (c & 31);
     uint2 hi, lo;
-    hi.x = pk_bf16(v.x, v.y);
-    hi.y = pk_bf16(v.z, v.w);
-    lo.x = pk_bf16(v.x - __builtin_bit_cast(float, hi.x << 16), v.y - __builtin_bit_cast(float, hi.x & 0xffff0000u));
-    lo.y = pk_bf16(v.z - __builtin_bit_cast(float, hi.y << 16), v.w - __builtin_bit_cast(float, hi.y & 0xffff0000u));
+    split2(v.x, v.y, hi.x, lo.x);
+    split2(v.z, v.w, hi.y, lo.y);
     *reinterpret_cast<uint2*>(o) = hi;
     *reinterpret_cast<uint2*>(o + 32) = lo;
 }

@@ -161,26 +161,33 @@ def test_halo_kernels_are_taken_where_the_limits_allow(ctxs, C):
 @pytest.mark.parametrize("C", R.MRF_C)
 def test_halo_switching_is_bit_identical(ctxs, C, precision):
     """MAA_HALO=single (two halo launches) and MAA_HALO=off (implicit GEMM) against the default (fused pair): the three engines
-    promise the same products in the same order."""
+    promise the same products in the same order.  Every tile geometry: all pairs, and as a single step every (k, d) the halo
+    kernel covers, at one row, a tile and a one-row tail, two tiles and a one-row tail; B = 3, out_scale = 1/3, accumulate."""
     from audiogpt_amd.backend import reload_tuning
-    ctx, (k1, d1, k2, d2) = ctxs[precision], (7, 3, 7, 1)
-    L = R.mrf_lengths(C, k2, d2)[-1]
-    case = (C, k1, d1, k2, d2, L, "randn", 1.0 / 3.0, True)
-    y, ref = _run_case(ctx, *case)
-    check(_name(precision, *case) + "_default", y, ref, R.TOL[precision])
+    ctx = ctxs[precision]
+    steps = list(R.MRF_PAIRS) + [(k, d, 0, 1) for (k, d) in R.MRF_SINGLES if R.halo_single_covers(C, k, d)]
+    cases = [(C, k1, d1, k2, d2, L, "randn", 1.0 / 3.0, True) for (k1, d1, k2, d2) in steps
+             for L in (1, R.tile_out(C, k2 or 1, d2) + 1, 2 * R.tile_out(C, k2 or 1, d2) + 1)]
+    halo = precision == "bf16x3" and C != 48
+    default = {}
+    for case in cases:
+        default[case], ref = _run_case(ctx, *case)
+        check(_name(precision, *case) + "_default", default[case], ref, R.TOL[precision])
     try:
         for mode, rows_want in (("single", [f"halo_conv1d_bf16x3<{C}>"]), ("off", [])):
             os.environ["MAA_HALO"] = mode
             reload_tuning()
-            got = {}
-            rows = _halo_rows(ctx, lambda: got.update(y=_run_case(ctx, *case)[0]))
-            check(_name(precision, *case) + "_" + mode, got["y"], ref, R.TOL[precision])
-            assert torch.equal(got["y"], y), (mode, float((got["y"] - y).abs().max()))
-            assert rows == (rows_want if precision == "bf16x3" and C != 48 else []), (mode, rows)
+            for case in cases:
+                got = {}
+                rows = _halo_rows(ctx, lambda: got.update(zip(("y", "ref"), _run_case(ctx, *case))))
+                check(_name(precision, *case) + "_" + mode, got["y"], got["ref"], R.TOL[precision])
+                assert torch.equal(got["y"], default[case]), (mode, case, float((got["y"] - default[case]).abs().max()))
+                assert rows == (rows_want if halo else []), (mode, case, rows)
     finally:
         os.environ.pop("MAA_HALO", None)
         reload_tuning()
-    assert torch.equal(_run_case(ctx, *case)[0], y)
+    for case in cases:
+        assert torch.equal(_run_case(ctx, *case)[0], default[case]), case
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
