@@ -87,6 +87,12 @@ class maa_pitch_extractor_config(C.Structure):
                 ("f0_mean", C.c_float), ("f0_std", C.c_float)]
 
 
+class maa_glow_config(C.Structure):
+    _fields_ = [(k, C.c_int) for k in (
+        "in_channels", "hidden_channels", "kernel_size", "dilation_rate", "n_blocks", "n_layers", "n_split", "n_sqz",
+        "gin_channels", "share_cond_layers", "share_wn_layers", "sigmoid_scale")]
+
+
 class maa_fs2_config(C.Structure):
     _fields_ = [(k, C.c_int) for k in (
         "vocab_size", "hidden_size", "enc_layers", "dec_layers", "num_heads", "enc_ffn_kernel_size", "dec_ffn_kernel_size",
@@ -226,6 +232,9 @@ SIGNATURES = {
     "maa_pitch_extractor_create": [vp, C.POINTER(maa_pitch_extractor_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
     "maa_pitch_extractor_destroy": [vp],
     "maa_pitch_extractor_forward": [vp, vp, vp, ci, ci, vp, vp, vp],
+    "maa_glow_create": [vp, C.POINTER(maa_glow_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
+    "maa_glow_destroy": [vp],
+    "maa_glow_reverse": [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp],
     "maa_fs2_create": [vp, C.POINTER(maa_fs2_config), C.POINTER(maa_tensor), ci, C.POINTER(vp)],
     "maa_fs2_destroy": [vp],
     "maa_fs2_encode": [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],

@@ -1153,6 +1153,78 @@ class PitchExtractor(_Handle):
     __call__ = forward
 
 
+GLOW_FIELDS = ("in_channels", "hidden_channels", "kernel_size", "dilation_rate", "n_blocks", "n_layers", "n_split", "n_sqz",
+               "gin_channels", "share_cond_layers", "share_wn_layers", "sigmoid_scale")
+
+
+def glow_config(cfg):
+    """maa_glow_config of a Glow hparams dict (config.GENERSPEECH_POST_GLOW); refuses what the library does not build, with the
+    reason, before any device is touched.  p_dropout is not read (eval)."""
+    kind = cfg.get("inv_conv_type", "near")
+    if kind != "near":
+        raise L.MaaError("Glow: inv_conv_type %r is not supported: only 'near' (InvConvNear, the 4 x 4 mix over channel groups) "
+                         "is built, the full-width 'invconv' is not" % (kind,))
+    if int(cfg.get("n_sqz", 2)) != 2:
+        raise L.MaaError("Glow: n_sqz %r is not supported: the squeeze is built as the pairing of neighbouring frames (n_sqz 2) "
+                         "only" % (cfg.get("n_sqz"),))
+    if int(cfg.get("n_split", 4)) != 4:
+        raise L.MaaError("Glow: n_split %r is not supported: InvConvNear is built as the 4 x 4 mix (n_split 4) only" % (cfg.get("n_split"),))
+    if int(cfg["kernel_size"]) < 1 or int(cfg["kernel_size"]) % 2 == 0:
+        raise L.MaaError("Glow: kernel_size %r must be odd: WN asserts it ('same' padding keeps the length only then)" % (cfg["kernel_size"],))
+    if int(cfg["hidden_channels"]) < 2 or int(cfg["hidden_channels"]) % 2 != 0:
+        raise L.MaaError("Glow: hidden_channels %r must be even: WN asserts it" % (cfg["hidden_channels"],))
+    if int(cfg["hidden_channels"]) % 4 != 0:
+        raise L.MaaError("Glow: hidden_channels %r must be a multiple of 4: the row kernels move 16 bytes per lane" % (cfg["hidden_channels"],))
+    if int(cfg["in_channels"]) < 4 or int(cfg["in_channels"]) % 4 != 0:
+        raise L.MaaError("Glow: in_channels %r: in_channels %% 4 != 0 -- the row kernels move 16 bytes per lane and the 4 x 4 mix stays "
+                         "inside a lane" % (cfg["in_channels"],))
+    if int(cfg.get("gin_channels", 0)) < 0 or int(cfg.get("gin_channels", 0)) % 4 != 0:
+        raise L.MaaError("Glow: gin_channels %r must be 0 (no conditioning) or a multiple of 4" % (cfg.get("gin_channels"),))
+    c = L.maa_glow_config()
+    for k in GLOW_FIELDS:
+        setattr(c, k, int(cfg.get(k, {"n_split": 4, "n_sqz": 2, "dilation_rate": 1}.get(k, 0))))
+    return c
+
+
+class Glow(_Handle):
+    """maa_glow handle: the Glow post-net in reverse (NeuralSeq/modules/GenerSpeech/model/glow_modules.py:496-580) on channels-last
+    rows."""
+
+    _destroy = "maa_glow_destroy"
+
+    def __init__(self, ctx, cfg, state_dict):
+        self.cfg = dict(cfg)
+        self._create(ctx, "maa_glow_create", C.byref(glow_config(self.cfg)), state_dict=state_dict)
+
+    def reverse(self, z, g=None, mask=None, return_logdet=True, return_hiddens=False):
+        """z [B, T, in_channels], g [B, T, gin_channels] (None exactly when gin_channels == 0), mask [B, T] of 0 / 1 (None: all
+        ones) -> (x [B, 2 (T // 2), in_channels], logdet [B] or None, hiddens [3 n_blocks, B, T // 2, 2 in_channels] or None)."""
+        Cc, gin = self.cfg["in_channels"], self.cfg["gin_channels"]
+        z = _f32(z, self.ctx.device)
+        if z.dim() != 3 or z.shape[2] != Cc or z.shape[0] < 1:
+            raise L.MaaError("Glow.reverse: z %s is not [B, T, %d]" % (tuple(z.shape), Cc))
+        B, T, _ = z.shape
+        if T < 2:
+            raise L.MaaError("Glow.reverse: T < 2 -- the squeeze pairs frames, T = %d leaves no row" % T)
+        if (g is None) != (gin == 0):
+            raise L.MaaError("Glow.reverse: g must be given exactly when gin_channels > 0 (gin_channels = %d)" % gin)
+        if g is not None:
+            g = _f32(g, self.ctx.device)
+            if tuple(g.shape) != (B, T, gin):
+                raise L.MaaError("Glow.reverse: g %s is not [%d, %d, %d]" % (tuple(g.shape), B, T, gin))
+        if mask is not None:
+            mask = _f32(mask, self.ctx.device)
+            if tuple(mask.shape) != (B, T):
+                raise L.MaaError("Glow.reverse: mask %s is not [%d, %d]" % (tuple(mask.shape), B, T))
+        Ts = T // 2
+        x = self._empty(B, 2 * Ts, Cc)
+        logdet = self._empty(B) if return_logdet else None
+        hs = self._empty(3 * self.cfg["n_blocks"], B, Ts, 2 * Cc) if return_hiddens else None
+        p = lambda t: L.dptr(t) if t is not None else None          # noqa: E731
+        self._call("maa_glow_reverse", L.dptr(z), p(g), p(mask), B, T, L.dptr(x), p(logdet), p(hs))
+        return x, logdet, hs
+
+
 def fs2_config(cfg):
     """maa_fs2_config of a FastSpeech2MIDI hparams dict (config.FASTSPEECH2_MIDI); refuses what the library does not build, with
     the reason, before any device is touched."""

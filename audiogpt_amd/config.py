@@ -149,6 +149,19 @@ FASTSPEECH2 = dict(vocab_size=64, hidden_size=256, enc_layers=4, dec_layers=4, n
 # egs/datasets/audio/libritts/fs2.yaml (use_spk_id true, num_spk 2320; vctk/fs2.yaml: 400)
 FASTSPEECH2_LIBRITTS = dict(FASTSPEECH2, use_spk_id=True, num_spk=2320)
 
+# The Glow post-net GenerSpeech runs in reverse over its decoder's mel (modules/GenerSpeech/model/generspeech.py:57-72, 233-260):
+# modules/GenerSpeech/config/generspeech.yaml:83-92 (post_glow_hidden 128, post_glow_kernel_size 3, post_glow_n_blocks 8,
+# post_glow_n_block_layers 3, share_wn_layers 4, sigmoid_scale false, post_share_cond_layers false, use_txt_cond true, noise_scale
+# 0.8) over hidden_size 256.  The conditioning is [mel_out 80 | decoder_inp 256 | spk, emo, ref_prosody 3 x 256] = 1104 channels.
+GENERSPEECH_POST_GLOW = dict(in_channels=80, hidden_channels=128, kernel_size=3, dilation_rate=1, n_blocks=8, n_layers=3, n_split=4,
+                             n_sqz=2, gin_channels=80 + 256 + 3 * 256, share_cond_layers=False, share_wn_layers=4,
+                             sigmoid_scale=False, inv_conv_type="near", p_dropout=0.0, hidden_size=256, use_txt_cond=True,
+                             n_cond_vectors=3, noise_scale=0.8)
+# PortaSpeech's post-net, egs_bases/tts/ps_flow.yaml:7-18 (post_glow_hidden 192, 12 blocks, 3 layers, share_wn_layers 4, noise_scale
+# 0.8) over hidden_size 192: the conditioning is [mel_out 80 | decoder_inp 192], no per-utterance vectors.
+PORTASPEECH_POST_GLOW = dict(GENERSPEECH_POST_GLOW, hidden_channels=192, n_blocks=12, gin_channels=80 + 192, hidden_size=192,
+                             n_cond_vectors=0)
+
 # BigVGAN's args.yml (vocoder/logs/bigv16k53w) does not ship with the reference
 # (SURVEY.md section 0.3); these are the generator defaults it is exercised with here.
 BIGVGAN_16K = dict(

@@ -30,6 +30,7 @@ struct maa_vae : Handle<maa::VAE> {};
 struct maa_vocoder : Handle<maa::Vocoder> {};
 struct maa_diffnet : Handle<maa::DiffNet> {};
 struct maa_pitch_extractor : Handle<maa::PitchExtractor> {};
+struct maa_glow : Handle<maa::Glow> {};
 struct maa_fs2 : Handle<maa::FastSpeech2MIDI> {};
 struct maa_fs2_pitch : Handle<maa::FS2Pitch> {};
 struct maa_encoder : Handle<maa::Encoder> {};
@@ -508,6 +509,30 @@ int maa_pitch_extractor_forward(maa_ctx* ctx, maa_pitch_extractor* pe, const flo
         MAA_CHECK(B > 0 && T > 0 && (long long)B * T < (1LL << 31) / 1024, "bad pitch_extractor_forward arguments: B, T");
         bind(ctx);
         pe->m->forward(ctx->c, d_mel, B, T, d_pitch_pred, d_f0, d_mel_hidden);
+    });
+}
+
+// ------------------------------------------------------------------------------------------ Glow post-net (reverse)
+int maa_glow_create(maa_ctx* ctx, const maa_glow_config* cfg, const maa_tensor* tensors, int n_tensors, maa_glow** out) {
+    return guarded([&] {
+        MAA_CHECK(cfg && out, "bad glow_create arguments: null pointer");
+        maa::check_glow_config(*cfg);
+        // The one entry that binds before its last argument check: the tensor list is converted (and a null list with
+        // n_tensors > 0 refused) only here, after the context.  The entry-order test calls every create entry with a null list of one
+        // tensor and expects the null context to be what refuses it.
+        bind(ctx);
+        auto sd = to_state_dict(tensors, n_tensors);
+        create_handle(out, *cfg, sd, ctx->c.dtype);
+    });
+}
+int maa_glow_destroy(maa_glow* glow) { return destroy_handle(glow); }
+int maa_glow_reverse(maa_ctx* ctx, maa_glow* glow, const float* d_z, const float* d_g, const float* d_mask, int B, int T,
+                     float* d_x, float* d_logdet, float* d_hiddens) {
+    return guarded([&] {
+        maa::check_glow_reverse_args(glow, d_z, B, T, d_x);
+        bind(ctx);
+        // (T < 2 and d_g against the model's gin_channels are refused in the model: they need the handle's state)
+        glow->m->reverse(ctx->c, d_z, d_g, d_mask, B, T, d_x, d_logdet, d_hiddens);
     });
 }
 

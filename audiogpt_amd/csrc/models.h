@@ -94,6 +94,34 @@ private:
     std::unique_ptr<Impl> impl_;
 };
 
+// The Glow post-net of GenerSpeech / PortaSpeech in reverse (glow.cpp, glow.hip): latent + conditioning -> mel
+class Glow {
+public:
+    Glow(const maa_glow_config& cfg, const StateDict& sd, int precision);
+    ~Glow();
+    // z [B, T, C], g [B, T, gin] (null exactly when gin_channels == 0), mask [B, T] of 0 / 1 (null: all ones) -> x [B, 2 (T / 2), C];
+    // logdet [B] and hiddens [3 n_blocks, B, T / 2, 2C] (every flow's output in execution order, squeezed rows) optional
+    void reverse(Ctx& ctx, const float* z, const float* g, const float* mask, int B, int T, float* x, float* logdet, float* hiddens);
+    const maa_glow_config& config() const;      // zero fields resolved
+
+private:
+    struct Impl;
+    std::unique_ptr<Impl> impl_;
+};
+// the checks of maa_glow_create / maa_glow_reverse that touch no device (api.cpp calls them before it binds the context)
+maa_glow_config glow_resolved(const maa_glow_config& cfg);      // a zero size field -> GenerSpeech's shipped value (maa.h)
+void check_glow_config(const maa_glow_config& cfg);
+void check_glow_reverse_args(const void* glow, const float* d_z, int B, int T, const float* d_x);
+// Row launches of glow.hip (the kernels carry the formulas): C, H and gin multiples of 4, every pointer 16-byte aligned
+void launch_glow_squeeze(const Ctx& ctx, const float* in, const float* mask, int B, int T, int C, float* out, float* mask_out);
+void launch_glow_gate(const Ctx& ctx, const float* y, long long rows, int H, float* z);
+void launch_glow_wn_residual(const Ctx& ctx, const float* rs, long long rows, int H, const float* mask, bool first, bool last, float* x,
+                             float* skip);
+void launch_glow_block_tail(const Ctx& ctx, const float* x, const float* eo, const float* mask, long long rows, int C, int sigmoid_scale,
+                            const float* winv, const float* an_bias, const float* an_einv, bool first, float* out, float* rowld,
+                            float* h_cpl, float* h_inv, float* h_act);
+void launch_glow_logdet(const Ctx& ctx, const float* rowld, const float* mask, int B, int Ts, float per_len, float* logdet);
+
 // DiffSinger's PitchExtractor (pitch_extractor.cpp, pitch.hip): the generated mel -> f0 for the NSF vocoder
 class PitchExtractor {
 public:

@@ -380,6 +380,67 @@ def make_pe_state_dict(cfg, seed=13):
     return sd
 
 
+def _invconv_near(g, n_split=4):
+    """InvConvNear's tensors as its constructor makes them (glow_modules.py:123-143): a random orthogonal matrix with a positive
+    determinant, LU-decomposed with partial pivoting -- drawn again until the permutation is not the identity and sign_s has both
+    signs, so a loader that skipped either shows.  log_s is moved off the decomposition's (whose sum is 0 for an orthogonal
+    matrix), so the log-determinant term is not vacuous."""
+    while True:
+        q = torch.linalg.qr(g.normal((n_split, n_split), 1.0).double())[0]
+        if torch.det(q) < 0:
+            q[:, 0] = -q[:, 0]
+        lu, piv = torch.linalg.lu_factor(q)
+        p, l, u = torch.lu_unpack(lu, piv)
+        s = torch.diagonal(u)
+        sign = torch.sign(s)
+        if not torch.equal(p, torch.eye(n_split, dtype=p.dtype)) and sign.min() < 0 < sign.max():
+            break
+    f = torch.float32
+    return {"l": l.to(f), "log_s": (torch.log(s.abs()).to(f) + g.normal((n_split,), 0.1)), "u": torch.triu(u, 1).to(f), "p": p.to(f),
+            "sign_s": sign.to(f), "l_mask": torch.tril(torch.ones(n_split, n_split), -1), "eye": torch.eye(n_split)}
+
+
+def make_glow_state_dict(cfg, seed=23, coupling_gain=1.0):
+    """The Glow post-net (NeuralSeq/modules/GenerSpeech/model/glow_modules.py:496-554) in the reference key layout: 35 keys per
+    block at GenerSpeech's configuration (280 in all; 420 at PortaSpeech's), convolutions as weight-norm pairs, InvConvNear's
+    l / log_s / u / p / sign_s / l_mask / eye, and with share_wn_layers = n the group's in_layers / res_skip_layers repeated under
+    every member's keys (the same tensors).  What the reference initialises to nothing is drawn: `end` (zero at init, which makes
+    every coupling the identity) and ActNorm's logs / bias.  coupling_gain scales those draws (the couplings' amplification
+    compounds over the blocks)."""
+    g, sd = _Gen(seed), {}
+    C, H, k, L = cfg["in_channels"], cfg["hidden_channels"], cfg["kernel_size"], cfg["n_layers"]
+    gin, share, share_cond = cfg["gin_channels"], cfg["share_wn_layers"], bool(cfg["share_cond_layers"])
+    if gin and share_cond:
+        sd["cond_layer.bias"] = g.bias(2 * H * L)
+        _wn(sd, g, "cond_layer", (2 * H * L, 2 * gin, 1))
+    wn = None
+    for b in range(cfg["n_blocks"]):
+        pa, pi, pc = "flows.%d." % (3 * b), "flows.%d." % (3 * b + 1), "flows.%d." % (3 * b + 2)
+        sd[pa + "logs"] = g.normal((1, 2 * C, 1), 0.1 * coupling_gain)
+        sd[pa + "bias"] = g.normal((1, 2 * C, 1), 0.1)
+        for name, t in _invconv_near(g).items():
+            sd[pi + name] = t
+        sd[pc + "start.bias"] = g.bias(H)
+        _wn(sd, g, pc + "start", (H, C, 1))
+        sd[pc + "end.weight"] = g.normal((2 * C, H, 1), 0.3 * coupling_gain / math.sqrt(H))
+        sd[pc + "end.bias"] = g.normal((2 * C,), 0.05 * coupling_gain)
+        if wn is None or share <= 0 or b % share == 0:
+            wn = {}
+            for i in range(L):
+                wn["in_layers.%d.bias" % i] = g.bias(2 * H)
+                _wn(wn, g, "in_layers.%d" % i, (2 * H, H, k))
+            for i in range(L):
+                n_out = 2 * H if i < L - 1 else H
+                wn["res_skip_layers.%d.bias" % i] = g.bias(n_out)
+                _wn(wn, g, "res_skip_layers.%d" % i, (n_out, H, 1))
+        for name, t in wn.items():
+            sd[pc + "wn." + name] = t
+        if gin and not share_cond:
+            sd[pc + "wn.cond_layer.bias"] = g.bias(2 * H * L)
+            _wn(sd, g, pc + "wn.cond_layer", (2 * H * L, 2 * gin, 1))
+    return sd
+
+
 def make_fs2_state_dict(cfg, seed=17):
     """FastSpeech2MIDI (NeuralSeq/modules/diffsinger_midi/fs2.py:46-53 over modules/fastspeech/fs2.py:22-55) in the reference key
     layout and order: 116 keys at config.FASTSPEECH2_MIDI, the shared `encoder_embed_tokens.weight` / `encoder.embed_tokens.weight`

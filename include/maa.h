@@ -409,6 +409,35 @@ int maa_pitch_extractor_destroy(maa_pitch_extractor* pe);
 int maa_pitch_extractor_forward(maa_ctx* ctx, maa_pitch_extractor* pe, const float* d_mel, int B, int T, float* d_pitch_pred,
                                 float* d_f0, float* d_mel_hidden);
 
+/* ---- Glow post-net in reverse (GenerSpeech's and PortaSpeech's last stage: latent + conditioning -> mel) ----
+ * NeuralSeq/modules/GenerSpeech/model/glow_modules.py:496-580 Glow.forward(reverse=True) over CouplingBlock, InvConvNear, ActNorm
+ * and model/wavenet.py:14-78 WN, as generspeech.py:233-260 run_post_glow calls it; the hparams are post_glow_hidden /
+ * post_glow_kernel_size / post_glow_n_blocks / post_glow_n_block_layers / share_wn_layers / sigmoid_scale /
+ * post_share_cond_layers (modules/GenerSpeech/config/generspeech.yaml:83-92, egs_bases/tts/ps_flow.yaml).
+ * A zero in in_channels, hidden_channels, kernel_size, dilation_rate, n_blocks, n_layers, n_split or n_sqz selects GenerSpeech's
+ * shipped value (80, 128, 3, 1, 8, 3, 4, 2); gin_channels, share_cond_layers, share_wn_layers and sigmoid_scale are taken as
+ * given (0: no conditioning / false / no sharing).  Refused at creation, with the reason: n_sqz other than 2, n_split other than 4
+ * (inv_conv_type 'near' is the one built), an even kernel_size, an odd hidden_channels (and one that is no multiple of 4),
+ * in_channels or gin_channels that is no multiple of 4.  p_dropout is not read (eval).  The training direction is not built. */
+typedef struct { int in_channels, hidden_channels, kernel_size, dilation_rate, n_blocks, n_layers,
+                 n_split, n_sqz, gin_channels, share_cond_layers, share_wn_layers, sigmoid_scale; } maa_glow_config;
+typedef struct maa_glow maa_glow;
+/* tensors: the Glow state_dict (flows.{3b}.{logs,bias}, flows.{3b+1}.{p,sign_s,l,log_s,u}; its constant buffers l_mask / eye are accepted and not read,
+ * flows.{3b+2}.{start,end}.*, flows.{3b+2}.wn.{in_layers,res_skip_layers}.{i}.*, flows.{3b+2}.wn.cond_layer.* or, with
+ * share_cond_layers, cond_layer.*); every convolution as the weight-norm pair weight_g / weight_v or as the plain weight that
+ * store_inverse leaves.  With share_wn_layers = n the blocks of a group must carry equal in_layers / res_skip_layers.
+ * The tensor list is read after the context is bound: with a null context the call fails on the context, whatever the list. */
+int maa_glow_create(maa_ctx* ctx, const maa_glow_config* cfg, const maa_tensor* tensors, int n_tensors, maa_glow** out);
+int maa_glow_destroy(maa_glow* glow);
+/* replaces: Glow.forward(z, x_mask, g=g, reverse=True, return_hiddens=...) in channels-last rows: d_z [B, T, in_channels],
+ * d_g [B, T, gin_channels] (null exactly when gin_channels == 0), d_mask [B, T] of 0 / 1 floats (null: all ones) ->
+ * d_x [B, 2 (T / 2), in_channels]: an odd last frame is dropped, as the reference's squeeze drops it; a frame pair whose second
+ * frame is masked is exact zeros.  d_logdet: null, or [B].  d_hiddens: null, or [3 n_blocks, B, T / 2, 2 in_channels], every
+ * flow's output in execution order as squeezed rows (channel s * in_channels + c of row t' is frame 2t' + s).  T < 2 is refused
+ * (after the context is bound).  Launches on the context's stream only; two identical calls give the same bits. */
+int maa_glow_reverse(maa_ctx* ctx, maa_glow* glow, const float* d_z, const float* d_g, const float* d_mask, int B, int T,
+                     float* d_x, float* d_logdet, float* d_hiddens);
+
 /* ---- DiffSinger FastSpeech2MIDI (the e2e singing configurations' front end: score -> decoder_inp, mel2ph, coarse mel) ----
  * NeuralSeq/modules/diffsinger_midi/fs2.py:46-118 over modules/fastspeech/fs2.py:22-72,140-163,222-226 and
  * tts_modules.py:59-143,179-214,276-384, as DiffSingerE2EInfer.forward_model calls it (inference/svs/ds_e2e.py).  The flags
