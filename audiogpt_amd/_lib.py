@@ -162,6 +162,20 @@ class maa_seq_rows_args(C.Structure):
 SEQ_KINDS = {"frame_mask": 0, "affine_mask": 1, "gn_relu_res": 2, "pos_add": 3, "head": 4}      # MAA_SEQ_* of include/maa.h
 
 
+class maa_tts_rows_args(C.Structure):
+    _fields_ = [(k, C.c_int) for k in (
+        "kind", "rows", "B", "T", "C", "H", "first", "last", "sigmoid_scale", "rel", "split", "vocab", "pe_rows", "n_rows")] + [
+        ("eps", C.c_float), ("alpha", C.c_float)] + [(k, C.c_void_p) for k in (
+            "d_x", "d_y", "d_mask", "d_spk", "d_energy", "d_tok", "d_mel2ph", "d_ids")] + [(k, C.POINTER(C.c_float)) for k in (
+                "h_gamma", "h_beta", "h_w", "h_bias", "h_table", "h_t1", "h_t2", "h_pe", "h_winv", "h_an_bias", "h_an_einv")] + [
+        (k, C.c_void_p) for k in ("d_out", "d_out2", "d_out3", "d_rowld", "d_h_cpl", "d_h_inv", "d_h_act", "d_energy_pred", "d_bin")]
+
+
+# MAA_TTS_* of include/maa.h
+TTS_KINDS = {"glow_squeeze": 0, "glow_gate": 1, "glow_wn_residual": 2, "glow_block_tail": 3, "glow_logdet": 4, "fs2_embed_plain": 5,
+             "fs2_add_speaker": 6, "fs2_speaker_gather": 7, "fs2_energy_tail": 8, "fs2_tgt_mask": 9}
+
+
 class maa_sampler_step_args(C.Structure):
     _fields_ = [("kind", C.c_int), ("B", C.c_int), ("nB", C.c_int), ("S", C.c_int),
                 ("n", C.c_int64), ("per", C.c_int64), ("per_in", C.c_int64),
@@ -280,6 +294,7 @@ SIGNATURES = {
     "maa_op_igemm_ex": [vp, C.POINTER(maa_igemm_ex_args)],
     "maa_op_layernorm_ex": [vp, vp, ci, ci, fp, fp, cf, vp, ci],
     "maa_op_seq_rows": [vp, C.POINTER(maa_seq_rows_args)],
+    "maa_op_tts_rows": [vp, C.POINTER(maa_tts_rows_args)],
     "maa_op_sampler_step": [vp, C.POINTER(maa_sampler_step_args)],
     "maa_op_front_rows": [vp, C.POINTER(maa_front_rows_args)],
     "maa_op_split32": [vp, vp, ci, ci, cf, ci, vp],

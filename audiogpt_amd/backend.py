@@ -311,6 +311,31 @@ class Context(_Handle):
         self._call("maa_op_seq_rows", C.byref(a))
         return out
 
+    def op_tts_rows(self, kind, **fields):
+        """maa_op_tts_rows: one row kernel of the Glow post-net or of the plain FastSpeech2 through the library's internal launch
+        (`kind`: a key of _lib.TTS_KINDS; include/maa.h lists what each reads and writes).  `fields` are the members of
+        maa_tts_rows_args by name: integers and floats as they are, d_* as device tensors (fp32; int32 for d_tok / d_mel2ph / d_ids /
+        d_bin), possibly views into larger buffers, h_* as host tensors.  Nothing is allocated, copied or checked beyond what the C
+        entry point checks."""
+        a = L.maa_tts_rows_args(kind=L.TTS_KINDS[kind])
+        types = dict(L.maa_tts_rows_args._fields_)
+        keep = []
+        for name, v in fields.items():
+            assert name in types and name != "kind", name
+            if v is None:
+                continue
+            if name.startswith("h_"):
+                keep.append(L.host_f32(v))
+                v = keep[-1][1]
+            elif name.startswith("d_"):
+                assert v.is_cuda and v.dtype == (torch.int32 if name in ("d_tok", "d_mel2ph", "d_ids", "d_bin") else torch.float32), \
+                    (name, v.device, v.dtype)
+                v = v.data_ptr()
+            else:
+                v = float(v) if types[name] is C.c_float else int(v)
+            setattr(a, name, v)
+        self._call("maa_op_tts_rows", C.byref(a))
+
     def op_sampler_step(self, kind, **fields):
         """maa_op_sampler_step: one step kernel of the sampling loops through the library's internal launch (`kind`: a key of
         _lib.STEP_KINDS; include/maa.h lists what each reads and writes).  `fields` are the members of maa_sampler_step_args by

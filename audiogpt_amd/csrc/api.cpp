@@ -1187,6 +1187,109 @@ int maa_op_seq_rows(maa_ctx* ctx, const maa_seq_rows_args* a) {
     });
 }
 
+int maa_op_tts_rows(maa_ctx* ctx, const maa_tts_rows_args* a) {
+    return guarded([&] {
+        MAA_CHECK(a != nullptr, "bad op_tts_rows arguments: null pointer");
+        const int k = a->kind;
+        MAA_CHECK(k >= MAA_TTS_GLOW_SQUEEZE && k <= MAA_TTS_FS2_TGT_MASK, "op_tts_rows: unknown kind");
+        const bool per_sample = k == MAA_TTS_GLOW_SQUEEZE || k == MAA_TTS_GLOW_LOGDET || k == MAA_TTS_FS2_EMBED_PLAIN ||
+                                k == MAA_TTS_FS2_ADD_SPEAKER;                                      // rows = B * T
+        const bool head = k == MAA_TTS_FS2_ENERGY_TAIL && a->d_x != nullptr;
+        bool ptrs = a->d_out != nullptr;
+        if (k <= MAA_TTS_GLOW_LOGDET || k == MAA_TTS_FS2_ADD_SPEAKER) ptrs = ptrs && a->d_x;
+        if (k == MAA_TTS_GLOW_WN_RESIDUAL) ptrs = ptrs && a->d_mask && a->d_out2;
+        if (k == MAA_TTS_GLOW_BLOCK_TAIL) ptrs = ptrs && a->d_y && a->d_mask && a->h_winv && a->h_an_bias && a->h_an_einv && a->d_rowld;
+        if (k == MAA_TTS_GLOW_LOGDET) ptrs = ptrs && a->d_mask;
+        if (k == MAA_TTS_FS2_EMBED_PLAIN) ptrs = ptrs && a->d_tok && a->h_table && a->h_pe && a->d_out2 && a->d_out3;
+        if (k == MAA_TTS_FS2_ADD_SPEAKER) ptrs = ptrs && a->d_spk && (a->d_mask || a->d_mel2ph);
+        if (k == MAA_TTS_FS2_SPEAKER_GATHER) ptrs = ptrs && a->h_table && a->h_t1 && a->h_t2;
+        if (k == MAA_TTS_FS2_ENERGY_TAIL) ptrs = ptrs && a->d_y && a->d_mel2ph;
+        if (head) ptrs = ptrs && a->h_gamma && a->h_beta && a->h_w && a->h_bias && a->h_table;
+        if (k == MAA_TTS_FS2_TGT_MASK) ptrs = ptrs && a->d_mel2ph;
+        MAA_CHECK(ptrs, "bad op_tts_rows arguments: null pointer");
+        if (per_sample)
+            MAA_CHECK(a->B >= 1 && a->T >= 1 && (long long)a->B * a->T < (1ll << 31), "op_tts_rows: rows < 1 (B and T must be at least 1)");
+        else if (k == MAA_TTS_FS2_SPEAKER_GATHER)
+            MAA_CHECK(a->B >= 1, "op_tts_rows: rows < 1 (B must be at least 1)");
+        else
+            MAA_CHECK(a->rows >= 1, "op_tts_rows: rows < 1");
+        if (k == MAA_TTS_GLOW_SQUEEZE) MAA_CHECK(a->T >= 2, "op_tts_rows: T < 2 (the squeeze pairs frames)");
+        if (k != MAA_TTS_GLOW_LOGDET && k != MAA_TTS_FS2_TGT_MASK && (k != MAA_TTS_FS2_ENERGY_TAIL || head))
+            MAA_CHECK(a->C >= 4 && a->C % 4 == 0, "op_tts_rows: C % 4 != 0 (channel counts are positive multiples of 4)");
+        if (k == MAA_TTS_GLOW_WN_RESIDUAL)
+            MAA_CHECK((a->first == 0 || a->first == 1) && (a->last == 0 || a->last == 1), "op_tts_rows: first and last are 0 or 1");
+        if (k == MAA_TTS_GLOW_BLOCK_TAIL)
+            MAA_CHECK((a->first == 0 || a->first == 1) && (a->sigmoid_scale == 0 || a->sigmoid_scale == 1),
+                      "op_tts_rows: first and sigmoid_scale are 0 or 1");
+        if (k == MAA_TTS_FS2_EMBED_PLAIN) {
+            MAA_CHECK(a->rel == 0 || a->rel == 1, "op_tts_rows: rel is 0 or 1");
+            MAA_CHECK(a->vocab >= 1, "op_tts_rows: vocab < 1");
+            MAA_CHECK(a->pe_rows >= a->T + (a->rel ? 0 : 1), "op_tts_rows: pe_rows too small (T rows with rel, T + 1 without)");
+        }
+        if (k == MAA_TTS_FS2_ADD_SPEAKER)
+            MAA_CHECK((a->d_mask == nullptr) != (a->d_mel2ph == nullptr), "op_tts_rows: mask or mel2ph, not both");
+        if (k == MAA_TTS_FS2_SPEAKER_GATHER) {
+            MAA_CHECK(a->split == 0 || a->split == 1, "op_tts_rows: split is 0 or 1");
+            MAA_CHECK(a->n_rows >= 1 && (a->d_ids || a->n_rows >= a->B), "op_tts_rows: n_rows < 1, or < B without ids");
+        }
+        if (k == MAA_TTS_FS2_ENERGY_TAIL) {
+            MAA_CHECK(a->H >= 4 && a->H % 4 == 0, "op_tts_rows: H % 4 != 0 (channel counts are positive multiples of 4)");
+            MAA_CHECK(a->T >= 1 && a->rows % a->T == 0, "op_tts_rows: rows % T != 0 (rows is whole samples of T >= 1 frames)");
+            if (head) MAA_CHECK(a->C <= 1024 && a->eps > 0.f, "op_tts_rows: energy head C > 1024 or eps <= 0");
+        }
+        bind(ctx);
+        maa::Ctx& c = ctx->c;
+        maa::WeightStore ws(c.dtype != 0);
+        const int C = a->C;
+        auto up = [&](const float* h, size_t n) { return h ? ws.upload(std::vector<float>(h, h + n)) : nullptr; };
+        switch (k) {
+        case MAA_TTS_GLOW_SQUEEZE:
+            maa::launch_glow_squeeze(c, a->d_x, a->d_mask, a->B, a->T, C, a->d_out, a->d_out2);
+            break;
+        case MAA_TTS_GLOW_GATE:
+            maa::launch_glow_gate(c, a->d_x, a->rows, C, a->d_out);
+            break;
+        case MAA_TTS_GLOW_WN_RESIDUAL:
+            maa::launch_glow_wn_residual(c, a->d_x, a->rows, C, a->d_mask, a->first != 0, a->last != 0, a->d_out, a->d_out2);
+            break;
+        case MAA_TTS_GLOW_BLOCK_TAIL:
+            maa::launch_glow_block_tail(c, a->d_x, a->d_y, a->d_mask, a->rows, C, a->sigmoid_scale, up(a->h_winv, 16),
+                                        up(a->h_an_bias, 2 * (size_t)C), up(a->h_an_einv, 2 * (size_t)C), a->first != 0, a->d_out,
+                                        a->d_rowld, a->d_h_cpl, a->d_h_inv, a->d_h_act);
+            break;
+        case MAA_TTS_GLOW_LOGDET:
+            maa::launch_glow_logdet(c, a->d_x, a->d_mask, a->B, a->T, a->alpha, a->d_out);
+            break;
+        case MAA_TTS_FS2_EMBED_PLAIN: {
+            const float *E = up(a->h_table, (size_t)a->vocab * C), *pe = up(a->h_pe, (size_t)a->pe_rows * C);
+            maa::run_sized(c, [&] {
+                maa::launch_fs2_embed_plain(c, a->d_tok, E, a->vocab, pe, a->alpha, a->rel, a->B, a->T, C, a->d_out, a->d_out2, a->d_out3);
+            });
+            break;
+        }
+        case MAA_TTS_FS2_ADD_SPEAKER:
+            maa::launch_fs2_add_speaker(c, a->d_x, a->d_spk, a->d_mel2ph, a->d_mask, a->B, a->T, C, a->d_out);
+            break;
+        case MAA_TTS_FS2_SPEAKER_GATHER: {
+            const size_t n = (size_t)a->n_rows * C;
+            maa::launch_fs2_speaker_gather(c, up(a->h_table, n), up(a->h_t1, n), up(a->h_t2, n), a->d_ids, a->split, a->n_rows, a->B, C,
+                                           a->d_out);
+            break;
+        }
+        case MAA_TTS_FS2_ENERGY_TAIL: {
+            const float *g = nullptr, *b = nullptr, *w = nullptr, *bi = nullptr, *tab = nullptr;
+            if (head) g = up(a->h_gamma, C), b = up(a->h_beta, C), w = up(a->h_w, C), bi = up(a->h_bias, 1), tab = up(a->h_table, 256 * (size_t)a->H);
+            maa::launch_fs2_energy_tail(c, a->d_x, a->rows, C, g, b, a->eps, w, bi, a->d_mel2ph, a->d_energy, a->d_y, tab, a->d_spk, a->T,
+                                        a->H, a->d_energy_pred, a->d_bin, a->d_out);
+            break;
+        }
+        default:
+            maa::launch_fs2_tgt_mask(c, a->d_mel2ph, a->rows, a->d_out);
+        }
+        MAA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
 int maa_op_sampler_step(maa_ctx* ctx, const maa_sampler_step_args* a) {
     return guarded([&] {
         MAA_CHECK(a != nullptr, "bad op_sampler_step arguments: null pointer");

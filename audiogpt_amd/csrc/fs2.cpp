@@ -37,21 +37,10 @@ void launch_fs2_embed(const Ctx& ctx, const int* tok, const int* midi, const flo
                       float* x, float* nonpad, float* hidden);
 void launch_fs2_length(Ctx& ctx, const int* dur, int B, int T, int* totals, int T_mel, int* mel2ph);
 void launch_fs2_expand(const Ctx& ctx, const float* enc, const int* mel2ph, int B, int T, int T_mel, int H, float* out, float* tgt);
-void launch_fs2_tgt_mask(const Ctx& ctx, const int* mel2ph, long long rows, float* tgt);
 void launch_fs2_pitch_tail(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
                            const float* w, const float* bias, const int* mel2ph, const float* f0_in, const float* uv_in, int norm,
                            float f0_mean, float f0_std, int use_uv, const float* origin, const float* table, int H, float* pitch_pred,
                            float* f0_denorm, int* coarse, float* decoder_inp);
-void launch_fs2_embed_plain(Ctx& ctx, const int* tok, const float* E, int vocab, const float* pe, float scale, int rel, int B, int T,
-                            int H, float* x, float* nonpad, float* hidden);
-void launch_fs2_add_speaker(const Ctx& ctx, const float* x, const float* spk, const int* mel2ph, const float* mask, int B, int T, int H,
-                            float* out);
-void launch_fs2_speaker_gather(const Ctx& ctx, const float* t0, const float* t1, const float* t2, const int* ids, int split, int n_rows,
-                               int B, int H, float* out);
-void launch_fs2_energy_tail(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
-                            const float* w, const float* bias, const int* mel2ph, const float* energy_in, const float* acc,
-                            const float* table, const float* spk, int T_mel, int H, float* energy_pred, int* energy_bin,
-                            float* decoder_inp);
 
 namespace {
 

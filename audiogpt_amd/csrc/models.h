@@ -157,6 +157,18 @@ void launch_pe_head(const Ctx& ctx, const float* x, long long rows, int C, const
                     float* pitch_pred, float* f0);
 void launch_fs2_dur_head(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
                          const float* w, const float* bias, const float* nonpad, float* xs, int* dur);
+// The plain FastSpeech2's rows and run_decoder's mask (fs2.hip), declared here for fs2.cpp and for maa_op_tts_rows
+void launch_fs2_tgt_mask(const Ctx& ctx, const int* mel2ph, long long rows, float* tgt);
+void launch_fs2_embed_plain(Ctx& ctx, const int* tok, const float* E, int vocab, const float* pe, float scale, int rel, int B, int T,
+                            int H, float* x, float* nonpad, float* hidden);
+void launch_fs2_add_speaker(const Ctx& ctx, const float* x, const float* spk, const int* mel2ph, const float* mask, int B, int T, int H,
+                            float* out);
+void launch_fs2_speaker_gather(const Ctx& ctx, const float* t0, const float* t1, const float* t2, const int* ids, int split, int n_rows,
+                               int B, int H, float* out);
+void launch_fs2_energy_tail(const Ctx& ctx, const float* x, long long rows, int C, const float* gamma, const float* beta, float eps,
+                            const float* w, const float* bias, const int* mel2ph, const float* energy_in, const float* acc,
+                            const float* table, const float* spk, int T_mel, int H, float* energy_pred, int* energy_bin,
+                            float* decoder_inp);
 
 // DiffSinger's FastSpeech2MIDI front end (fs2.cpp, fs2.hip): score -> encoder_out / durations, then mel2ph -> decoder_inp / mel_out
 class FastSpeech2MIDI {

@@ -803,6 +803,99 @@ typedef struct {
     int* d_dur;
 } maa_seq_rows_args;
 int maa_op_seq_rows(maa_ctx* ctx, const maa_seq_rows_args* args);
+/* One row kernel of the Glow post-net run in reverse (csrc/glow.hip) or of the plain FastSpeech2 (csrc/fs2.hip) exactly as the
+ * models launch it (tests/test_gpu_tts_ops.py): `kind` selects one internal launch, the entry forwards every argument of it, each
+ * nullable pointer included, synchronises the stream once and adds no arithmetic.  d_* are DEVICE buffers the caller has laid
+ * out, channels-last rows; h_* are HOST arrays, uploaded as the models upload their weights and tables.  Channel counts are
+ * positive multiples of 4.  kind:
+ *   MAA_TTS_GLOW_SQUEEZE      d_x [B, T, C] -> d_out [B * (T / 2), 2C]: row t' = [x[2t'], x[2t' + 1]] times d_mask[b, 2t' + 1] (d_mask
+ *                             [B, T] or NULL: ones); an odd last frame is not read; d_out2 (or NULL) [B * (T / 2)] receives the
+ *                             pairs' mask.  T >= 2.
+ *
+ *   MAA_TTS_GLOW_GATE         d_x [rows, 2C] -> d_out [rows, C] = tanh(d_x[:, :C]) * sigmoid(d_x[:, C:]).
+ *
+ *   MAA_TTS_GLOW_WN_RESIDUAL  WN's bookkeeping after one res_skip layer, d_mask [rows], d_out = x [rows, C] and d_out2 = skip
+ *                             [rows, C] updated in place.  last = 0: d_x = rs [rows, 2C], x = (x + rs[:, :C]) * mask, skip (+)= rs[:,
+ *                             C:].  last = 1: d_x = rs [rows, C], skip = (skip + rs) * mask, x untouched.  first = 1: skip is
+ *                             written, not read.
+ *
+ *   MAA_TTS_GLOW_BLOCK_TAIL   one flow block's tail in reverse on d_x [rows, 2C] with d_y = end(WN(..)) [rows, 2C] = [m | logs] and
+ *                             d_mask [rows]: the affine coupling inverse (logs = log(1e-6 + sigmoid(logs + 2)) under
+ *                             sigmoid_scale), InvConvNear's 4 x 4 mix with h_winv [16] (row-major [out, in]), ActNorm with h_an_bias
+ *                             [2C] and h_an_einv [2C] = exp(-logs) -> d_out [rows, 2C] (may be d_x); d_rowld [rows] (+)= the row's
+ *                             share of the coupling's log-determinant (first = 1: written); d_h_cpl / d_h_inv / d_h_act (each
+ *                             [rows, 2C] or NULL) receive the three flows' outputs.
+ *
+ *   MAA_TTS_GLOW_LOGDET       d_out [B] = sum over the sample's T rows of d_x [B, T] + alpha * sum of d_mask [B, T] (alpha: the
+ *                             per-frame log-determinant of the mix and ActNorm).
+ *
+ *   MAA_TTS_FS2_EMBED_PLAIN   forward_embedding of the plain FastSpeech2 as its encode launches it, token positions first: d_tok int
+ *                             [B, T], h_table [vocab, C], h_pe [pe_rows, C] (rel = 0: the sinusoid rows, read at the counted
+ *                             position, pe_rows > T; rel = 1: RelPositionalEncoding's rows, read at t, pe_rows >= T), alpha = the
+ *                             embedding scale -> d_out [B * T, C], d_out2 [B * T] = nonpad, d_out3 [B * T] = 1 - nonpad.
+ *
+ *   MAA_TTS_FS2_ADD_SPEAKER   d_out [B * T, C] = (d_x + d_spk[b]) * live, d_spk [B, C]; live = d_mask[row] != 0 when d_mask is given,
+ *                             else d_mel2ph[row] > 0: exactly one of the two.
+ *
+ *   MAA_TTS_FS2_SPEAKER_GATHER d_out [3, B, C]: slab k = rows of table k (h_table, h_t1, h_t2, each [n_rows, C]) by d_ids int
+ *                             [3, B] (row k with split, row 0 without), clamped into the table; d_ids NULL: row b (n_rows >= B).
+ *
+ *   MAA_TTS_FS2_ENERGY_TAIL   the end of the variance stage on `rows` frames, T per sample.  With d_x [rows, C], C <= 1024: the
+ *                             predictor's last LayerNorm (h_gamma / h_beta [C], eps) + Linear(C, 1) (h_w [C], h_bias [1]) ->
+ *                             d_energy_pred (or NULL) [rows]; bin = floor(64 e) in [0, 255] of d_energy (or NULL: of the
+ *                             prediction) -> d_bin (or NULL) int [rows]; d_out [rows, H] = (d_y + h_table[bin] + d_spk[b]) *
+ *                             (d_mel2ph > 0), h_table [256, H], d_spk [B, H] or NULL.  d_x NULL: d_out = (d_y + d_spk[b]) * (d_mel2ph
+ *                             > 0), nothing else is read or written.
+ *
+ *   MAA_TTS_FS2_TGT_MASK      d_out [rows] = (d_mel2ph[rows] > 0).
+ * Checked here, before the context is touched: null pointers per kind, rows (B, T) >= 1, the squeeze's T >= 2, C (and H) positive
+ * multiples of 4, the energy head's C <= 1024 and eps, vocab, pe_rows and n_rows against what the kind reads, first / last / rel /
+ * split / sigmoid_scale 0 or 1, mask against mel2ph. */
+#define MAA_TTS_GLOW_SQUEEZE 0
+#define MAA_TTS_GLOW_GATE 1
+#define MAA_TTS_GLOW_WN_RESIDUAL 2
+#define MAA_TTS_GLOW_BLOCK_TAIL 3
+#define MAA_TTS_GLOW_LOGDET 4
+#define MAA_TTS_FS2_EMBED_PLAIN 5
+#define MAA_TTS_FS2_ADD_SPEAKER 6
+#define MAA_TTS_FS2_SPEAKER_GATHER 7
+#define MAA_TTS_FS2_ENERGY_TAIL 8
+#define MAA_TTS_FS2_TGT_MASK 9
+typedef struct {
+    int kind;
+    int rows, B, T, C, H;
+    int first, last, sigmoid_scale, rel, split, vocab, pe_rows, n_rows;
+    float eps, alpha;
+    const float* d_x;
+    const float* d_y;
+    const float* d_mask;
+    const float* d_spk;
+    const float* d_energy;
+    const int* d_tok;
+    const int* d_mel2ph;
+    const int* d_ids;
+    const float* h_gamma;
+    const float* h_beta;
+    const float* h_w;
+    const float* h_bias;
+    const float* h_table;
+    const float* h_t1;
+    const float* h_t2;
+    const float* h_pe;
+    const float* h_winv;
+    const float* h_an_bias;
+    const float* h_an_einv;
+    float* d_out;
+    float* d_out2;
+    float* d_out3;
+    float* d_rowld;
+    float* d_h_cpl;
+    float* d_h_inv;
+    float* d_h_act;
+    float* d_energy_pred;
+    int* d_bin;
+} maa_tts_rows_args;
+int maa_op_tts_rows(maa_ctx* ctx, const maa_tts_rows_args* args);
 /* One step kernel of the sampling loops exactly as the loops launch it (tests of the ddim_* / ldm_plms_* / ddpm_step kernels of
  * misc.hip and the ds_* step kernels of diffsinger.hip): `kind` selects one internal launch, the entry forwards every argument
  * of it, synchronises the stream once and does nothing else.  EVERY buffer is the caller's DEVICE pointer and is passed through

@@ -109,8 +109,14 @@ def encode(sd, cfg, txt_tokens, pitch_midi, midi_dur=None, is_slur=None, dtype=t
     x = x * scale + rel_pos_table(T, H).to(dt)[None]
     pad = txt_tokens.eq(0)
     enc = fft_blocks(sd, "encoder", x, pad, heads, cfg["enc_layers"], cfg["enc_ffn_kernel_size"], dt)
+    xs, dur = durations(sd, cfg, enc, pad, dt)
+    return enc, xs, dur
+
+
+def durations(sd, cfg, enc, pad, dt):
+    """DurationPredictor on the encoder states and out2dur -> (xs [B, T], dur_choice [B, T] long) in `dt`; pad [B, T] bool."""
+    w = lambda key: sd[key].to(dt)      # noqa: E731
     keep = (~pad).to(dt)
-    # ---- DurationPredictor
     k = cfg["dur_predictor_kernel"]
     y = (enc * keep[:, :, None]).transpose(1, 2)
     for i in range(cfg["dur_predictor_layers"]):
@@ -120,7 +126,7 @@ def encode(sd, cfg, txt_tokens, pitch_midi, midi_dur=None, is_slur=None, dtype=t
         y = y * keep[:, None, :]
     xs = F.linear(y.transpose(1, 2), w("dur_predictor.linear.weight"), w("dur_predictor.linear.bias"))[..., 0] * keep
     dur = torch.clamp(torch.round(xs.exp() - 1.0), min=0).long()
-    return enc, xs, dur
+    return xs, dur
 
 
 def forward(sd, cfg, txt_tokens, pitch_midi, midi_dur=None, is_slur=None, mel2ph=None, dtype=torch.float32):

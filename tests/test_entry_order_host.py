@@ -69,6 +69,7 @@ def _configs():
                                      KW=1, stride=1, dil=1, pad_h=-1, alpha=1.0, out_scale=1.0, d_c=_base, ldc=32),
         L.maa_seq_rows_args: _struct(L.maa_seq_rows_args, kind=L.SEQ_KINDS["head"], rows=1, C=32, d_x=_base, d_mask=_base, h_gamma=_fp,
                                      h_beta=_fp, h_w=_fp, h_bias=_fp, eps=1e-5, n_out=2, d_out=_base, d_out2=_base),
+        L.maa_tts_rows_args: _struct(L.maa_tts_rows_args, **_tts_rows()["glow_block_tail"]),
         L.maa_sampler_step_args: _struct(L.maa_sampler_step_args, kind=L.STEP_KINDS["ddim"], B=1, nB=1, S=2, n=8, per=8, per_in=8,
                                          scale=1.0, temperature=1.0, d_x=_base, d_xin=_base + 256, d_eps_u=_base + 512,
                                          d_coef=_base + 768, d_step=_base + 1024),
@@ -77,6 +78,36 @@ def _configs():
         L.maa_prof_row: C.cast(_base, C.POINTER(L.maa_prof_row)),
         L.maa_tensor: None,          # an empty tensor list, with n_tensors = 0
     }
+
+
+def _tts_rows():
+    """{kind: the fields of a well-formed maa_tts_rows_args} -- one per kind of maa_op_tts_rows."""
+    d, h = _base, _fp
+    calls = {
+        "glow_squeeze": dict(B=1, T=4, C=8, d_x=d, d_mask=d + 256, d_out=d + 512, d_out2=d + 768),
+        "glow_gate": dict(rows=2, C=8, d_x=d, d_out=d + 256),
+        "glow_wn_residual": dict(rows=2, C=8, d_x=d, d_mask=d + 256, first=0, last=1, d_out=d + 512, d_out2=d + 768),
+        "glow_block_tail": dict(rows=2, C=8, d_x=d, d_y=d + 256, d_mask=d + 512, sigmoid_scale=1, h_winv=h, h_an_bias=h, h_an_einv=h,
+                                first=0, d_out=d + 768, d_rowld=d + 1024, d_h_cpl=d + 1280, d_h_inv=d + 1536, d_h_act=d + 1792),
+        "glow_logdet": dict(B=2, T=3, d_x=d, d_mask=d + 256, alpha=-1.5, d_out=d + 512),
+        "fs2_embed_plain": dict(B=2, T=3, C=8, d_tok=d, h_table=h, vocab=5, h_pe=h, pe_rows=4, alpha=2.0, rel=0, d_out=d + 256,
+                                d_out2=d + 512, d_out3=d + 768),
+        "fs2_add_speaker": dict(B=2, T=3, C=8, d_x=d, d_spk=d + 256, d_mel2ph=d + 512, d_out=d + 768),
+        "fs2_speaker_gather": dict(B=2, C=8, h_table=h, h_t1=h, h_t2=h, d_ids=d, split=1, n_rows=3, d_out=d + 256),
+        "fs2_energy_tail": dict(rows=6, T=3, C=8, H=12, d_x=d, h_gamma=h, h_beta=h, h_w=h, h_bias=h, eps=1e-5, d_mel2ph=d + 256,
+                                d_energy=d + 512, d_y=d + 768, h_table=h, d_spk=d + 1024, d_energy_pred=d + 1280, d_bin=d + 1536,
+                                d_out=d + 1792),
+        "fs2_tgt_mask": dict(rows=5, d_mel2ph=d, d_out=d + 256),
+    }
+    return {k: dict(v, kind=L.TTS_KINDS[k]) for k, v in calls.items()}
+
+
+# one malformed call per kind of maa_op_tts_rows: the field that makes it so
+TTS_MALFORMED = {
+    "glow_squeeze": dict(T=1), "glow_gate": dict(C=6), "glow_wn_residual": dict(d_out2=None), "glow_block_tail": dict(h_winv=None),
+    "glow_logdet": dict(d_mask=None), "fs2_embed_plain": dict(pe_rows=3), "fs2_add_speaker": dict(d_mask=_base + 1280),
+    "fs2_speaker_gather": dict(n_rows=0), "fs2_energy_tail": dict(rows=7), "fs2_tgt_mask": dict(rows=0),
+}
 
 
 def _struct_of(s):
@@ -156,6 +187,17 @@ def test_a_malformed_call_is_refused_by_an_argument_check(lib, name):
     if name in MALFORMED:
         zeros = list(MALFORMED[name])
     assert fn(None, *zeros) < 0
+    assert len(lib.maa_last_error()) > 0 and b"null context" not in lib.maa_last_error(), lib.maa_last_error()
+
+
+@pytest.mark.parametrize("kind", sorted(L.TTS_KINDS))
+def test_every_kind_of_op_tts_rows_checks_before_the_context(lib, kind):
+    """maa_op_tts_rows is ten launches behind one entry: the rule holds for each of them."""
+    assert sorted(TTS_MALFORMED) == sorted(L.TTS_KINDS) == sorted(_tts_rows())
+    good = _tts_rows()[kind]
+    assert lib.maa_op_tts_rows(None, _struct(L.maa_tts_rows_args, **good)) < 0
+    assert b"null context" in lib.maa_last_error(), lib.maa_last_error()
+    assert lib.maa_op_tts_rows(None, _struct(L.maa_tts_rows_args, **dict(good, **TTS_MALFORMED[kind]))) < 0
     assert len(lib.maa_last_error()) > 0 and b"null context" not in lib.maa_last_error(), lib.maa_last_error()
 
 

@@ -159,6 +159,107 @@ def test_sequence_row_test_entry_is_bound_and_refuses_by_name(lib_path):
     assert lib.maa_op_seq_rows(None, ctypes.byref(_lib.maa_seq_rows_args(kind=5))) < 0 and b"unknown kind" in lib.maa_last_error()
 
 
+def test_tts_row_test_entry_is_bound_and_refuses_by_name(lib_path):
+    """maa_op_tts_rows (tests/test_gpu_tts_ops.py) is declared, exported, bound with the header's argument count and a structure
+    that has the header's fields in the header's order, with the header's types; the kinds' #defines match; a null structure, an
+    unknown kind and every host-side refusal come back with their message before the context is touched."""
+    from audiogpt_amd import _lib
+    lib = _lib.load()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "maa.h")).read(), flags=re.S)
+    name = "maa_op_tts_rows"
+    assert name in _lib.EXPORTS and name in _declared_symbols()
+    decl = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
+    assert len(getattr(lib, name).argtypes) == len(decl.split(",")) == 2, name
+    body = re.search(r"typedef struct \{([^}]*)\} maa_tts_rows_args;", src).group(1)
+    ctype = {"int": ctypes.c_int, "float": ctypes.c_float}
+    fields = []
+    for stmt in body.split(";"):
+        stmt = stmt.strip()
+        if stmt:
+            m = re.match(r"^(const\s+)?(float|int)\s*(\*?)\s*(.*)$", stmt)
+            pointer = (ctypes.POINTER(ctypes.c_float) if m.group(4).startswith("h_") else ctypes.c_void_p) if m.group(3) else None
+            fields += [(f.strip(), pointer or ctype[m.group(2)]) for f in m.group(4).split(",")]
+    assert fields == list(_lib.maa_tts_rows_args._fields_)
+
+    class Mirror(ctypes.Structure):          # the header's fields under the C layout rules
+        _fields_ = fields
+    assert ctypes.sizeof(Mirror) == ctypes.sizeof(_lib.maa_tts_rows_args) == 14 * 4 + 2 * 4 + 28 * 8
+    for kind, value in _lib.TTS_KINDS.items():
+        assert re.search(r"#define MAA_TTS_%s %d\b" % (kind.upper(), value), src), kind
+    assert sorted(_lib.TTS_KINDS.values()) == list(range(10))
+    assert not re.search(r"#define MAA_SEQ_\w+ [5-9]\b", src)                 # nothing was added to maa_op_seq_rows
+    assert lib.maa_op_tts_rows(None, None) < 0 and b"null pointer" in lib.maa_last_error()
+    import numpy as np
+    buf = np.zeros(64, np.float32)
+    fp = buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    dp = buf.ctypes.data                                     # stands in for device memory; never read
+    base = {
+        "glow_squeeze": dict(B=1, T=2, C=8, d_x=dp, d_out=dp),
+        "glow_gate": dict(rows=1, C=8, d_x=dp, d_out=dp),
+        "glow_wn_residual": dict(rows=1, C=8, d_x=dp, d_mask=dp, first=1, last=0, d_out=dp, d_out2=dp),
+        "glow_block_tail": dict(rows=1, C=8, d_x=dp, d_y=dp, d_mask=dp, h_winv=fp, h_an_bias=fp, h_an_einv=fp, first=1, d_out=dp,
+                                d_rowld=dp),
+        "glow_logdet": dict(B=1, T=1, d_x=dp, d_mask=dp, alpha=1.0, d_out=dp),
+        "fs2_embed_plain": dict(B=1, T=3, C=8, d_tok=dp, h_table=fp, vocab=4, h_pe=fp, pe_rows=4, alpha=1.0, d_out=dp, d_out2=dp,
+                                d_out3=dp),
+        "fs2_add_speaker": dict(B=1, T=3, C=8, d_x=dp, d_spk=dp, d_mask=dp, d_out=dp),
+        "fs2_speaker_gather": dict(B=2, C=8, h_table=fp, h_t1=fp, h_t2=fp, n_rows=2, d_out=dp),
+        "fs2_energy_tail": dict(rows=6, T=3, C=8, H=8, d_x=dp, h_gamma=fp, h_beta=fp, h_w=fp, h_bias=fp, eps=1e-5, d_mel2ph=dp, d_y=dp,
+                                h_table=fp, d_out=dp),
+        "fs2_tgt_mask": dict(rows=1, d_mel2ph=dp, d_out=dp),
+    }
+    assert sorted(base) == sorted(_lib.TTS_KINDS)
+
+    def refused(kind, message, **kw):
+        d = dict(base[kind], kind=_lib.TTS_KINDS[kind])
+        d.update(kw)
+        st = lib.maa_op_tts_rows(None, ctypes.byref(_lib.maa_tts_rows_args(**d)))
+        assert st < 0 and message in lib.maa_last_error(), (kind, kw, lib.maa_last_error())
+
+    for kind in base:
+        refused(kind, b"null context")                                  # past every argument check
+        for p in [k for k in base[kind] if k.startswith(("d_", "h_"))]:
+            if (kind, p) != ("fs2_energy_tail", "d_x"):                 # (the tail's d_x is nullable: the form without a branch)
+                refused(kind, b"null pointer", **{p: None})
+        if "C" in base[kind]:
+            refused(kind, b"C % 4 != 0", C=6)
+            refused(kind, b"C % 4 != 0", C=0)
+        if "rows" in base[kind]:
+            refused(kind, b"rows < 1", rows=0)
+        else:
+            refused(kind, b"rows < 1", B=0)
+        if "T" in base[kind] and "rows" not in base[kind]:
+            refused(kind, b"rows < 1", T=0)
+    # every nullable pointer may be given
+    refused("glow_squeeze", b"null context", d_mask=dp, d_out2=dp)
+    refused("glow_block_tail", b"null context", d_h_cpl=dp, d_h_inv=dp, d_h_act=dp)
+    refused("fs2_add_speaker", b"null context", d_mask=None, d_mel2ph=dp)
+    refused("fs2_speaker_gather", b"null context", d_ids=dp, split=1, n_rows=1)
+    refused("fs2_energy_tail", b"null context", d_energy=dp, d_spk=dp, d_energy_pred=dp, d_bin=dp)
+    refused("fs2_energy_tail", b"null context", d_x=None, C=0, h_gamma=None, h_beta=None, h_w=None, h_bias=None, h_table=None)
+    # the kinds' own rules
+    refused("glow_squeeze", b"T < 2", T=1)
+    refused("glow_wn_residual", b"0 or 1", last=2)
+    refused("glow_wn_residual", b"0 or 1", first=-1)
+    refused("glow_block_tail", b"0 or 1", sigmoid_scale=2)
+    refused("fs2_embed_plain", b"rel is 0 or 1", rel=2)
+    refused("fs2_embed_plain", b"vocab < 1", vocab=0)
+    refused("fs2_embed_plain", b"pe_rows too small", pe_rows=3)
+    refused("fs2_embed_plain", b"null context", pe_rows=3, rel=1)
+    refused("fs2_add_speaker", b"not both", d_mel2ph=dp)
+    refused("fs2_speaker_gather", b"split is 0 or 1", split=2)
+    refused("fs2_speaker_gather", b"n_rows", n_rows=1)                    # without ids row b is read: n_rows >= B
+    refused("fs2_speaker_gather", b"n_rows", n_rows=0, d_ids=dp)
+    refused("fs2_energy_tail", b"H % 4 != 0", H=6)
+    refused("fs2_energy_tail", b"rows % T != 0", rows=7)
+    refused("fs2_energy_tail", b"rows % T != 0", T=0)
+    refused("fs2_energy_tail", b"C > 1024", C=1028)
+    refused("fs2_energy_tail", b"eps", eps=0.0)
+    for kind in (-1, 10):
+        assert lib.maa_op_tts_rows(None, ctypes.byref(_lib.maa_tts_rows_args(kind=kind))) < 0
+        assert b"unknown kind" in lib.maa_last_error()
+
+
 def test_sampler_step_test_entry_is_bound_and_refuses_by_name(lib_path):
     """maa_op_sampler_step (tests/test_gpu_sampler_ops.py) is declared, exported, bound with the header's argument count and a
     structure that has the header's fields in the header's order and the size the header's types give, and every host-side refusal
