@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libaudiogpt_mi355x.so")
-SOURCES = ["igemm_f32.hip", "igemm_bf16.hip", "igemm_dma.hip", "igemm_dma2.hip", "igemm_pp.hip", "calib.hip", "nsf.hip", "diffsinger.hip", "pitch.hip", "fs2.hip", "glow.hip", "halo_conv1d.hip", "encoders.hip", "spectral.hip", "flash_attn.hip", "norm.hip", "misc.hip", "split.hip", "igemm_dispatch.cpp", "runtime.cpp", "blocks.cpp", "unet.cpp", "vae.cpp",
+SOURCES = ["igemm_f32.hip", "igemm_bf16.hip", "igemm_dma.hip", "igemm_dma2.hip", "igemm_pp.hip", "calib.hip", "nsf.hip", "diffsinger.hip", "pitch.hip", "fs2.hip", "glow.hip", "halo_conv1d.hip", "encoders.hip", "spectral.hip", "flash_attn.hip", "norm.hip", "misc.hip", "sampler_steps.hip", "split.hip", "igemm_dispatch.cpp", "runtime.cpp", "blocks.cpp", "unet.cpp", "vae.cpp",
            "vocoder.cpp", "diffnet.cpp", "seq_layers.cpp", "pitch_extractor.cpp", "fs2.cpp", "glow.cpp", "encoders.cpp", "clap_audio.cpp", "ddim.cpp", "api.cpp"]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-Wall", "-Wno-unused-function",

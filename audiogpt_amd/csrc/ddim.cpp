@@ -321,7 +321,7 @@ void ddim_decode(Ctx& ctx, UNet& unet, const maa_ddim_args& a, int t_start, floa
 }
 
 // PLMSSampler.plms_sampling + p_sample_plms (plms.py:115-236) on the DDIM loop's state (Loop above) with sigma = 0 (the
-// reference's noise draws are multiplied by it; the caller makes them) and a ring of three e_t slabs (ldm_plms_* in misc.hip):
+// reference's noise draws are multiplied by it; the caller makes them) and a ring of three e_t slabs (ldm_plms_* in sampler_steps.hip):
 //   step 0 (no history): prepare, eps(x, t), Euler mid-point kernel (e_t -> ring slot 0, the blended x -> the latent slab,
 //     x_mid -> the UNet input, t / embedding slots -> t_next), eps(x_mid, t_next), final kernel (update with (e_t + e_next) / 2);
 //   steps 1 .. S-1: prepare, eps(x, t), one kernel (Adams-Bashforth over the ring, update, logs).

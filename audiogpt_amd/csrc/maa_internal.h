@@ -334,7 +334,6 @@ void launch_softmax_masked(const Ctx& ctx, float* s, long long rows, int cols, i
 // ------------------------------------------------------------------------------------------ elementwise
 void launch_timestep_embedding(const Ctx& ctx, const float* t, int B, int dim, float* out);   // [cos | sin]
 void launch_silu(const Ctx& ctx, const float* x, long long n, float* out);
-void launch_add(const Ctx& ctx, const float* a, const float* b, long long n, float* out);
 void launch_nchw_to_nhwc(const Ctx& ctx, const float* x, int B, int C, int HW, float* out);
 void launch_nhwc_to_nchw(const Ctx& ctx, const float* x, int B, int C, int HW, float* out, int ld_in);
 void launch_avgpool2(const Ctx& ctx, const float* x, int B, int H, int W, int C, float* out);
@@ -353,11 +352,14 @@ void launch_split_fold(const Ctx& ctx, const float* e, const float* wT, const fl
                        int kw, int sh, int sw, float* out);
 void launch_repeat_rows(const Ctx& ctx, const float* src, long long rows, long long len, int rep, float* dst);
 void launch_scale(const Ctx& ctx, const float* x, long long n, float s, float* out);
+
+// ------------------------------------------------------------------------------------------ sampler steps (sampler_steps.hip)
+// The step kernels of the five sampling loops: DDIM, PLMS and the ancestral chain of Make-An-Audio (ddim.cpp), PLMS and the
+// ancestral chain of DiffSinger (diffnet.cpp).
 // eps = eu + scale*(ec - eu); x0 = (x - somat*eps)/sqrt(a_t); x' = sqrt(a_prev)*x0 + sqrt(1-a_prev-sig^2)*eps
 // coef = device pointer to {a_t, a_prev, sigma, sqrt_one_minus_at}; eps_c may be null (no CFG)
-// step (optional): device DDIM index, decremented for the next step
 void launch_ddim_update(const Ctx& ctx, const float* x, const float* eps_u, const float* eps_c, float scale,
-                        const float* coef, long long n, float* x_prev, float* pred_x0, int* step = nullptr);
+                        const float* coef, long long n, float* x_prev, float* pred_x0);
 // UNet input of a step (latents duplicated for CFG when nB = 2B, or concatenated with the inpaint conditioning) and the
 // step's timestep / coefficient slots (8 floats per DDIM index: a_t, a_prev, sigma, sqrt(1-a_t), sqrt(ac_t), sqrt(1-ac_t), log
 // slot, 0), selected from device tables by the device index *step; mask / x0 / noise_q: the mask blend of ddim.py:147-150
@@ -401,9 +403,19 @@ void launch_ddpm_update(const Ctx& ctx, const float* x, const float* eps, const 
 void launch_ddim_stochastic_encode(const Ctx& ctx, const float* x0, const float* moments, float scale_factor, const float* n_post,
                                    const int* t, const float* tab, int n_tab, const float* noise, int B, long long per, float* out,
                                    int* bad);
-// DiffSinger's DiffNet elementwise kernels and the step kernels of its two sampling loops (diffsinger.hip; the kernels carry the
-// formulas).  ds_plms: st = {t, history count, ring head}, hist [3][n], mode 0 multistep / 1 predictor into x_out / 2 corrector;
-// ds_plms_advance: one workgroup, B <= 256; ds_ddpm_step / ds_ddpm_update: n (per) % 4 == 0, x / e / noise 16-byte aligned.
+// DiffSinger's two loops (the kernels carry the formulas).  ds_plms: st = {t, history count, ring head}, hist [3][n], mode 0
+// multistep / 1 predictor into x_out / 2 corrector; ds_plms_advance: one workgroup, B <= 256; ds_ddpm_step / ds_ddpm_update:
+// n (per) % 4 == 0, x / e / noise 16-byte aligned.
+void launch_ds_plms(const Ctx& ctx, float* x, const float* e, const float* e_prev, float* hist, long long n,
+                    const float* ac, int interval, int* st, int mode, float* x_out);
+void launch_ds_plms_advance(const Ctx& ctx, int* st, int interval, float* t_slot, int B);
+void launch_ds_ddpm_step(const Ctx& ctx, float* x, const float* e, const float* noise, long long n, const float* tab,
+                         int timesteps, const int* st, int start, int n_steps, int clip);
+void launch_ds_ddpm_update(const Ctx& ctx, float* x, const float* e, const float* noise, int B, long long per, const float* t,
+                           const float* tab, int timesteps, int clip, int* bad);
+
+// ------------------------------------------------------------------------------------------ elementwise (continued)
+// DiffSinger's DiffNet elementwise kernels (diffsinger.hip; the kernels carry the formulas)
 void launch_ds_pos_emb(const Ctx& ctx, const float* t, int B, int dim, float* out);
 void launch_ds_mish(const Ctx& ctx, const float* x, long long n, float* out);
 void launch_ds_add_step(const Ctx& ctx, const float* x, const float* step, int ld_step, long long rows, int T, int C,
@@ -411,14 +423,7 @@ void launch_ds_add_step(const Ctx& ctx, const float* x, const float* step, int l
 void launch_ds_gate(const Ctx& ctx, const float* y, long long rows, int C, float* z);
 void launch_ds_residual(const Ctx& ctx, const float* y2, long long rows, int T, int C, float* x, float* skip, int first,
                         const float* next_step, int ld_step, float* xin);
-void launch_ds_plms(const Ctx& ctx, float* x, const float* e, const float* e_prev, float* hist, long long n,
-                    const float* ac, int interval, int* st, int mode, float* x_out);
-void launch_ds_plms_advance(const Ctx& ctx, int* st, int interval, float* t_slot, int B);
 void launch_ds_fill(const Ctx& ctx, float* p, int n, float v);
-void launch_ds_ddpm_step(const Ctx& ctx, float* x, const float* e, const float* noise, long long n, const float* tab,
-                         int timesteps, const int* st, int start, int n_steps, int clip);
-void launch_ds_ddpm_update(const Ctx& ctx, float* x, const float* e, const float* noise, int B, long long per, const float* t,
-                           const float* tab, int timesteps, int clip, int* bad);
 // BigVGAN Activation1d on [B, L, C]: up2 FIR -> snake -> down2 FIR (replicate padding)
 void launch_snake_aa(const Ctx& ctx, const float* x, int B, int L, int C, const float* inv_beta, const float* alpha,
                      float* out);
@@ -435,9 +440,6 @@ void launch_logmel(const Ctx& ctx, const float* mel, int B, int frames, int n_me
 void launch_affine_lastdim(const Ctx& ctx, const float* x, long long n, int F, const float* scale, const float* shift,
                            float* out);
 void launch_cnn14_pool(const Ctx& ctx, const float* x, int B, int T, int F, int C, float* out);
-void launch_leaky(const Ctx& ctx, const float* x, long long n, float slope, float* out);
-void launch_clamp_affine(const Ctx& ctx, const float* x, long long n, float mul, float add, float lo, float hi,
-                         float* out);
 void launch_spec_from_mel(const Ctx& ctx, const float* mel, long long n, float* spec);      // clamp((mel + 1) / 2, 0, 1)
 
 // box calibration (calib.hip): kind 0 -> dense bf16 MFMA TFLOP/s of a fixed register-only loop, kind 1 -> GB/s of a 256 MiB copy

@@ -1,6 +1,6 @@
 // Small kernels of the waveform front ends and of the CLAP audio tower (clap_audio.cpp): everything there that is not a
 // GEMM.  The contractions (framed DFT, mel filter bank, polyphase resampler, Cnn14's convolutions) run on the igemm engines.
-#include "maa_internal.h"
+#include "elementwise_launch.h"
 
 namespace maa {
 
@@ -116,13 +116,6 @@ __global__ __launch_bounds__(64) void similarity_kernel(const float* __restrict_
     for (int d = threadIdx.x; d < D; d += 64) s += a[(long long)i * D + d] * t[(long long)j * D + d];
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if (threadIdx.x == 0) out[blockIdx.x] = scale * s;
-}
-
-inline dim3 grid_for(long long n) {
-    long long b = (n + NT - 1) / NT;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return dim3((unsigned)b);
 }
 
 }  // namespace

@@ -9,7 +9,7 @@
 // The weighting is held transposed, wT [L][kh * kw], so that a crop's weights are contiguous along the crop's rows like its eps.
 // All three are one coalesced pass over a few hundred kilobytes; 16-byte accesses along W where kw, sw and W are multiples of 4
 // (then four neighbouring columns lie in the same crops and every row starts 16-byte aligned).
-#include "maa_internal.h"
+#include "elementwise_launch.h"
 
 namespace maa {
 namespace {
@@ -17,13 +17,6 @@ namespace {
 struct SplitGeom {
     int C, H, W, kh, kw, sh, sw, Ly, Lx;
 };
-
-inline dim3 grid_for(long long n) {
-    long long b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 4096) b = 4096;
-    return dim3((unsigned)b);
-}
 
 template <int V>
 struct Vec {
@@ -168,9 +161,9 @@ void launch_split_unfold(const Ctx& ctx, const float* x, int nB, int C, int H, i
     const long long n = (long long)nB * g.Ly * g.Lx * C * kh * kw;
     ProfScope prof(ctx, "split_unfold_kernel", 0.0, 8.0 * (double)n);
     if (kw % 4 == 0 && sw % 4 == 0 && W % 4 == 0 && al16(x) && al16(out))
-        hipLaunchKernelGGL(split_unfold_kernel<4>, grid_for(n / 4), dim3(256), 0, ctx.stream, x, g, n / 4, out);
+        hipLaunchKernelGGL(split_unfold_kernel<4>, grid_for(n / 4, 4096), dim3(256), 0, ctx.stream, x, g, n / 4, out);
     else
-        hipLaunchKernelGGL(split_unfold_kernel<1>, grid_for(n), dim3(256), 0, ctx.stream, x, g, n, out);
+        hipLaunchKernelGGL(split_unfold_kernel<1>, grid_for(n, 4096), dim3(256), 0, ctx.stream, x, g, n, out);
     MAA_HIP(hipGetLastError());
 }
 
@@ -179,7 +172,7 @@ void launch_split_norm(const Ctx& ctx, const float* wT, int H, int W, int kh, in
     MAA_CHECK(wT && norm, "split norm: empty problem");
     if (ctx.ws.dry) return;
     ProfScope prof(ctx, "split_norm_kernel", 0.0, 4.0 * (double)H * W);
-    hipLaunchKernelGGL(split_norm_kernel, grid_for((long long)H * W), dim3(256), 0, ctx.stream, wT, g, norm);
+    hipLaunchKernelGGL(split_norm_kernel, grid_for((long long)H * W, 4096), dim3(256), 0, ctx.stream, wT, g, norm);
     MAA_HIP(hipGetLastError());
 }
 
@@ -192,9 +185,9 @@ void launch_split_fold(const Ctx& ctx, const float* e, const float* wT, const fl
     ProfScope prof(ctx, "split_fold_kernel", 2.0 * (double)nB * g.Ly * g.Lx * C * kh * kw,
                    4.0 * ((double)n + 2.0 * (double)nB * g.Ly * g.Lx * C * kh * kw));
     if (kw % 4 == 0 && sw % 4 == 0 && W % 4 == 0 && al16(e) && al16(wT) && al16(norm) && al16(out))
-        hipLaunchKernelGGL(split_fold_kernel<4>, grid_for(n / 4), dim3(256), 0, ctx.stream, e, wT, norm, g, n / 4, out);
+        hipLaunchKernelGGL(split_fold_kernel<4>, grid_for(n / 4, 4096), dim3(256), 0, ctx.stream, e, wT, norm, g, n / 4, out);
     else
-        hipLaunchKernelGGL(split_fold_kernel<1>, grid_for(n), dim3(256), 0, ctx.stream, e, wT, norm, g, n, out);
+        hipLaunchKernelGGL(split_fold_kernel<1>, grid_for(n, 4096), dim3(256), 0, ctx.stream, e, wT, norm, g, n, out);
     MAA_HIP(hipGetLastError());
 }
 
@@ -204,9 +197,9 @@ void launch_repeat_rows(const Ctx& ctx, const float* src, long long rows, long l
     const long long n = rows * rep * len;
     ProfScope prof(ctx, "repeat_rows_kernel", 0.0, 8.0 * (double)n);
     if (len % 4 == 0 && al16(src) && al16(dst))
-        hipLaunchKernelGGL(repeat_rows_kernel<4>, grid_for(n / 4), dim3(256), 0, ctx.stream, src, len / 4, rep, n / 4, dst);
+        hipLaunchKernelGGL(repeat_rows_kernel<4>, grid_for(n / 4, 4096), dim3(256), 0, ctx.stream, src, len / 4, rep, n / 4, dst);
     else
-        hipLaunchKernelGGL(repeat_rows_kernel<1>, grid_for(n), dim3(256), 0, ctx.stream, src, len, rep, n, dst);
+        hipLaunchKernelGGL(repeat_rows_kernel<1>, grid_for(n, 4096), dim3(256), 0, ctx.stream, src, len, rep, n, dst);
     MAA_HIP(hipGetLastError());
 }
 

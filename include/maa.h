@@ -896,8 +896,8 @@ typedef struct {
     int* d_bin;
 } maa_tts_rows_args;
 int maa_op_tts_rows(maa_ctx* ctx, const maa_tts_rows_args* args);
-/* One step kernel of the sampling loops exactly as the loops launch it (tests of the ddim_* / ldm_plms_* / ddpm_step kernels of
- * misc.hip and the ds_* step kernels of diffsinger.hip): `kind` selects one internal launch, the entry forwards every argument
+/* One step kernel of the sampling loops exactly as the loops launch it (tests of the ddim_* / ldm_plms_* / ddpm_step and the
+ * ds_plms* / ds_ddpm_step kernels of sampler_steps.hip): `kind` selects one internal launch, the entry forwards every argument
  * of it, synchronises the stream once and does nothing else.  EVERY buffer is the caller's DEVICE pointer and is passed through
  * unchanged -- the coefficient slot, the device step index, the tables, the ring, the loop state: no hidden state, no workspace.
  * n = B * per elements of the latent, one sample per `per`; the step's model input d_xin holds nB rows of per_in >= per floats

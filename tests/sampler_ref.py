@@ -1,4 +1,4 @@
-"""References of the sampling loops' step kernels (tests/test_gpu_sampler_ops.py through maa_op_sampler_step, maa_ddim_update,
+"""References of the sampling loops' step kernels (csrc/sampler_steps.hip; tests/test_gpu_sampler_ops.py through maa_op_sampler_step, maa_ddim_update,
 maa_ddim_stochastic_encode, maa_ddpm_update, maa_ds_ddpm_update), written from the reference's own lines and not from the kernels:
 
   ldm/models/diffusion/ddim.py        p_sample_ddim (:199, :210-225), the mask blend of ddim_sampling (:147-150), stochastic_encode

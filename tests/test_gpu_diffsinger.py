@@ -1,4 +1,4 @@
-"""DiffSinger's denoiser (DiffNet) and the PLMS loop on the device (csrc/diffnet.cpp, diffsinger.hip).
+"""DiffSinger's denoiser (DiffNet) and the PLMS loop on the device (csrc/diffnet.cpp, diffsinger.hip; the loop's step kernels in sampler_steps.hip).
 
 Golden: tests/golden/diffsinger_ds1000.npz, produced by the reference's DiffNet (NeuralSeq/modules/diff/net.py:84-130)
 and GaussianDiffusion.p_sample_plms (shallow_diffusion_tts.py:166-201) over K_step = 60, pndm_speedup = 10: the

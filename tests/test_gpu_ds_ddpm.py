@@ -1,4 +1,4 @@
-"""DiffSinger's ancestral sampling branch on the device: ds_ddpm_step_kernel / ds_ddpm_update_kernel (csrc/diffsinger.hip),
+"""DiffSinger's ancestral sampling branch on the device: ds_ddpm_step_kernel / ds_ddpm_update_kernel (csrc/sampler_steps.hip),
 DiffNet::ddpm_sample (csrc/diffnet.cpp), and GaussianDiffusion.p_sample / sample_ddpm / infer, OfflineGaussianDiffusion
 (audiogpt_amd/diffsinger.py).
 

@@ -1,6 +1,6 @@
-"""The sampling loops' step kernels on their own (csrc/misc.hip ddim_* / ldm_plms_* / ddpm_*, csrc/diffsinger.hip ds_plms* /
-ds_ddpm*), launched exactly as the loops launch them through maa_op_sampler_step (which forwards every argument of one internal
-launch and adds nothing) and through maa_ddim_update, maa_ddim_stochastic_encode, maa_ddpm_update and maa_ds_ddpm_update.
+"""The sampling loops' step kernels on their own (csrc/sampler_steps.hip: ddim_* / ldm_plms_* / ddpm_* / ds_plms* / ds_ddpm*),
+launched exactly as the loops launch them through maa_op_sampler_step (which forwards every argument of one internal launch and
+adds nothing) and through maa_ddim_update, maa_ddim_stochastic_encode, maa_ddpm_update and maa_ds_ddpm_update.
 
 Gates.  Every output is held twice (tests/sampler_ref.py): torch.equal to the fp32 restatement of the reference's lines, one
 correctly rounded operation at a time in the reference's term order, and within a rel-max gate of the float64 evaluation of the
@@ -43,7 +43,13 @@ Which case hits which mechanism:
                                         test_ds_ddpm_update
   emb_w loop with fewer threads         test_prepare_embedding_and_crop_rows (emb_w = 1284, one block)
   n_t > nB                              test_prepare_embedding_and_crop_rows, test_euler_mid_moves_the_timestep
-  ds_plms_advance at B = 256, clamp     test_ds_advance"""
+  ds_plms_advance at B = 256, clamp     test_ds_advance
+The device helpers two loops share (sampler_steps.hip), each branch from both sides:
+  adams_bashforth orders 1, 2, 3        test_ldm_chain[plms] steps i = 1, 2, 3.. (S = 7); test_ds_plms_chain history counts 1, 2, 3..
+  posterior_mean clamp on / off         test_ldm_chain[ddpm] variants 1, 3 / 0, 2 and test_ddpm_update; test_ds_ddpm_chain and
+                                        test_ds_ddpm_update, clip False / True
+  ddim_x_prev scalar and vector         test_ddim_step with maa_ddim_update (V = 1 kernels); test_ldm_chain[plms],
+                                        test_euler_mid_moves_the_timestep"""
 import ctypes as C
 
 import numpy as np
