@@ -192,7 +192,7 @@ int maa_ctx_workspace_bytes(maa_ctx* ctx, size_t* out) {
 
 int maa_ctx_set_concurrency(maa_ctx* ctx, int n) {
     return guarded([&] {
-        MAA_CHECK(n >= -1 && n != 0, "concurrency: -1 (guess from the live contexts) or the number of contexts kept in flight (>= 1)");
+        MAA_CHECK(n >= -1 && n != 0, "concurrency: -1 (not told: treated as 1) or the number of contexts kept in flight (>= 1)");
         bind(ctx);
         if (ctx->c.kept_full() != (n >= 3)) ctx->c.drop_step_graphs();      // captured under the other arrangement's launches
         ctx->c.concurrency = n;
@@ -835,7 +835,9 @@ int maa_op_linear(maa_ctx* ctx, const float* d_a, int M, int K, const float* h_w
                 maa::launch_split32_pack(c, d_a, M, K, sp);
                 a = sp;
             }
-            maa::linear_into(c, a, K, M, K, pw, d_res, N, d_y, geglu ? N / 2 : N, geglu, 0, pre ? M : 0, c_split);
+            maa::LinOpt o(pre, c_split);
+            o.geglu = geglu;
+            maa::linear_into(c, a, K, M, K, pw, d_res, N, d_y, geglu ? N / 2 : N, o);
         });
         MAA_HIP(hipStreamSynchronize(c.stream));
     });
@@ -856,22 +858,22 @@ int maa_op_conv(maa_ctx* ctx, const float* d_x, int B, int Cin, int H, int W, co
         maa::WeightStore ws(ctx->c.dtype != 0);
         maa::Ctx& c = ctx->c;
         maa::PackedW pw = ws.pack_conv(s.sd, "w", h_bias ? "b" : "", KH, KW);
+        const bool plain3x3 = KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1;
         maa::PackedW pw4;      // Upsample + conv3x3: the four-phase form the models take in the bf16 modes (blocks.cpp conv_up2_into)
-        if (upsample2 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1 && leaky_slope == 0.f)
-            pw4 = ws.pack_conv_up2(s.sd, "w", h_bias ? "b" : "");
+        if (upsample2 && plain3x3 && leaky_slope == 0.f) pw4 = ws.pack_conv_up2(s.sd, "w", h_bias ? "b" : "");
+        const bool presplit = !pw4.w && op_presplit(c, Cin, leaky_slope != 0.f);
+        maa::PackedW pn;       // the UNet's output convolution on its own kernel (unet.cpp finish), packed once, outside the sized run
+        if (presplit && Cout <= 4 && h_bias && plain3x3 && !upsample2 && !extras && c.tune.up2) pn = ws.pack_narrow3x3(s.sd, "w", "b");
         maa::run_sized(c, [&] {
             maa::T4 x = maa::alloc_t(c, B, H, W, Cin);
             maa::launch_nchw_to_nhwc(c, d_x, B, Cin, H * W, x.p);
-            if (!pw4.w && op_presplit(c, Cin, leaky_slope != 0.f)) {
+            if (presplit) {
                 maa::T4 xs = maa::alloc_t(c, B, H, W, Cin);
                 maa::launch_split32_pack(c, x.p, (long long)B * H * W, Cin, xs.p);
                 xs.split = true;
                 x = xs;
             }
-            if (x.split && Cout <= 4 && h_bias && KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1 && !upsample2 && !extras && c.tune.up2) {
-                maa::PackedW pn = ws.pack_narrow3x3(s.sd, "w", "b");      // the UNet's output convolution (unet.cpp forward_body)
-                if (maa::launch_narrow_conv3x3(c, x.p, Cin, B, H, W, Cin, pn.w, pn.bias, Cout, d_y)) return;
-            }
+            if (pn.w && maa::launch_narrow_conv3x3(c, x.p, Cin, B, H, W, Cin, pn.w, pn.bias, Cout, d_y)) return;
             maa::T4 y = maa::alloc_t(c, B, Ho, Wo, Cout);
             maa::ConvOpt o;
             o.KH = KH;

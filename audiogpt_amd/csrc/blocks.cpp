@@ -138,8 +138,15 @@ bool conv_up2_into(Ctx& ctx, const T4& x, const PackedW& w4, T4& out) {
     return ok;
 }
 
+void upsample_conv3x3(Ctx& ctx, const T4& x, const PackedW& w, const PackedW& w_up2, T4& out) {
+    if (conv_up2_into(ctx, x, w_up2, out)) return;
+    ConvOpt o = conv3x3();
+    o.up = 1;
+    conv_into(ctx, x, nullptr, w, o, out);
+}
+
 void linear_into(Ctx& ctx, const float* a, int lda, long long rows, int K, const PackedW& w, const float* res,
-                 int ldr, float* out, int ldc, int geglu, int a_act, long long a_split_rows, int c_split, int act) {
+                 int ldr, float* out, int ldc, const LinOpt& o) {
     IGemm p;
     p.a1 = a;
     p.lda1 = lda;
@@ -154,16 +161,14 @@ void linear_into(Ctx& ctx, const float* a, int lda, long long rows, int K, const
     p.ldb = w.ld;
     p.b_nk = w.nk;
     p.b_split = w.split;
-    if (a_split_rows > 0) {
-        p.a_split = 1;
-    }
+    p.a_split = o.a_split;
     p.bias = w.bias;
     p.res = res;
     p.ldr = ldr;
-    p.geglu = geglu;
-    p.a_act = a_act;
-    p.c_split = c_split;
-    p.act = act;
+    p.geglu = o.geglu;
+    p.a_act = o.a_act;
+    p.c_split = o.c_split;
+    p.act = o.act;
     p.c = out;
     p.ldc = ldc;
     launch_igemm(ctx, p);
@@ -228,6 +233,24 @@ void attention_into(Ctx& ctx, const float* q, int ldq, int hsq, const float* k, 
     r.ldc = ldo;
     launch_igemm(ctx, r);
     ctx.ws.release(mk);
+}
+
+T4 attn_block(Ctx& ctx, const T4& x, const float* ng, const float* nb, float eps, const PackedW& qkv, const PackedW& proj, int heads,
+              int hs, int koff, float alpha) {
+    const int C = x.C, HW = x.H * x.W;
+    const long long M = x.rows();
+    T4 out = alloc_t(ctx, x.B, x.H, x.W, C);
+    const size_t mk = ctx.ws.mark();
+    float* xn = ctx.ws.alloc_f((size_t)M * C);
+    const bool sp = split_for_gemm(ctx, C);
+    launch_groupnorm(ctx, x.p, C, C, nullptr, 0, 0, x.B, HW, 32, ng, nb, eps, 0, xn, sp);
+    float* t = ctx.ws.alloc_f((size_t)M * 3 * C);
+    linear_into(ctx, xn, C, M, C, qkv, nullptr, 0, t, 3 * C, LinOpt(sp));
+    float* o = ctx.ws.alloc_f((size_t)M * C);
+    attention_into(ctx, t, 3 * C, hs, t + koff, 3 * C, hs, t + 2 * koff, 3 * C, hs, x.B, heads, C / heads, HW, HW, alpha, o, C);
+    linear_into(ctx, o, C, M, C, proj, x.p, C, out.p, C);
+    ctx.ws.release(mk);
+    return out;
 }
 
 }  // namespace maa

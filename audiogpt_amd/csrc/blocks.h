@@ -14,14 +14,17 @@ struct T4 {              // dense channels-last activation [B, H, W, C] (sequenc
     long long rows() const { return (long long)B * H * W; }
 };
 
-inline T4 alloc_t(Ctx& ctx, int B, int H, int W, int C) {
+inline T4 view_t(float* p, int B, int H, int W, int C) {      // [B, H, W, C] at p
     T4 t;
+    t.p = p;
     t.B = B;
     t.H = H;
     t.W = W;
     t.C = C;
-    t.p = ctx.ws.alloc_f((size_t)t.numel());
     return t;
+}
+inline T4 alloc_t(Ctx& ctx, int B, int H, int W, int C) {
+    return view_t(ctx.ws.alloc_f((size_t)B * H * W * C), B, H, W, C);
 }
 
 struct ConvOpt {
@@ -45,6 +48,14 @@ struct ConvOpt {
     int ldr = 0, ldc = 0, ldc2 = 0;      // row pitches of res / the output / c2 in floats; 0 = dense (the output's C)
 };
 
+inline ConvOpt conv3x3(int stride = 1) {      // the models' 3x3 convolution with padding 1
+    ConvOpt o;
+    o.KH = o.KW = 3;
+    o.pad = 1;
+    o.stride = stride;
+    return o;
+}
+
 // out = conv(x1 ++ x2) with packed weight `w`; output spatial size given by (Ho, Wo)
 void conv_into(Ctx& ctx, const T4& x1, const T4* x2, const PackedW& w, const ConvOpt& o, T4& out);
 // Dilated "same" Conv1d(C, C, k, dilation = dil) on a sequence [B, 1, L, C] with a leaky-ReLU prologue (leaky = 0: none) and the
@@ -59,15 +70,24 @@ void mrf_pair(Ctx& ctx, const T4& x, const PackedW& w1, int k1, int d1, float sl
 // ConvTranspose1d(k, stride, padding = (k - stride) / 2) as the polyphase GEMMs of WeightStore::pack_convtr_phase: throws on a
 // (k, stride) they do not cover -- L * stride output rows and the carry groups 0 and 1 are all that is launched.
 void check_convtr_polyphase(int k, int stride);
-// linear over rows of a [rows, K] matrix (any leading layout, row pitch lda)
 // Upsample (nearest 2x) + conv3x3 as four 2x2 phase convolutions of the low-resolution source (4 / 9 of the multiplications; bf16
 // modes, weights from WeightStore::pack_conv_up2).  false: not applicable here -- the caller runs the 3x3 convolution with ConvOpt::up
 bool conv_up2_into(Ctx& ctx, const T4& x, const PackedW& w4, T4& out);
+// Upsample + conv3x3 of the UNet and the VAE decoder: the four-phase form, else (exact-fp32 mode, odd channel counts, MAA_PP=off,
+// MAA_UP2=0) the 3x3 convolution `w` reading through the virtual-upsample gather
+void upsample_conv3x3(Ctx& ctx, const T4& x, const PackedW& w, const PackedW& w_up2, T4& out);
+struct LinOpt {
+    int geglu = 0;
+    int a_act = 0;
+    bool a_split = false;         // `a` holds split32 rows (row pitch lda floats)
+    int c_split = 0;              // write `out` as split32 rows
+    int act = 0;                  // output activation of the igemm epilogue (IGemm::act), applied after bias and residual
+    LinOpt() = default;
+    explicit LinOpt(bool a_split_, int c_split_ = 0) : a_split(a_split_), c_split(c_split_) {}
+};
+// linear over rows of a [rows, K] matrix (any leading layout, row pitch lda)
 void linear_into(Ctx& ctx, const float* a, int lda, long long rows, int K, const PackedW& w, const float* res,
-                 int ldr, float* out, int ldc, int geglu = 0, int a_act = 0, long long a_split_rows = 0,
-                 int c_split = 0, int act = 0);
-// act: output activation of the igemm epilogue (IGemm::act), applied after bias and residual
-// a_split_rows > 0: `a` holds split32 rows (row pitch lda floats);  c_split: write `out` as split32 rows
+                 int ldr, float* out, int ldc, const LinOpt& o = LinOpt());
 
 // softmax(alpha * Q K^T) V for `heads` heads of width dh stored head-major inside rows of q/k/v
 //   q: [B, Nq, *] pitch ldq;  k, v: [B, Nk, *] pitch ldk / ldv;  per-head column offset = h * head_stride_{q,k,v}
@@ -79,6 +99,10 @@ void attention_into(Ctx& ctx, const float* q, int ldq, int hsq, const float* k, 
 // key_mask [B, Nk]: a key whose entry is non-zero is hidden from every query of its sample (MultiheadAttention's key_padding_mask,
 //   weight exactly 0); a sample with no visible key is written as zeros.  Not together with causal.
 // out_split: write split32 rows (only where flash_attention_covers(ctx, dh))
+// x + proj(attention(qkv(GroupNorm32(x)))) with q, k, v from one GEMM (N = 3C): `heads` heads of width C / heads, head h's q / k / v
+// at columns h * hs + {0, koff, 2 koff} of the qkv rows
+T4 attn_block(Ctx& ctx, const T4& x, const float* ng, const float* nb, float eps, const PackedW& qkv, const PackedW& proj, int heads,
+              int hs, int koff, float alpha);
 
 // In the bf16 modes a normalisation whose only consumer is a bf16-engine contraction writes bf16 hi/lo planes
 // (no per-tile re-splitting of the same activation for every tap and N-tile)

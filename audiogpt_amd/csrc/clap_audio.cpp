@@ -133,7 +133,9 @@ struct ClapAudio::Impl {
         float* pooled = ctx.ws.alloc_f((size_t)B * C);
         launch_cnn14_pool(ctx, x.p, B, H, W, C, pooled);
         float* emb = d_emb ? d_emb : ctx.ws.alloc_f((size_t)B * E);
-        linear_into(ctx, pooled, C, B, C, fc1, nullptr, 0, emb, E, 0, 0, 0, 0, /*act=*/2);
+        LinOpt relu;
+        relu.act = 2;
+        linear_into(ctx, pooled, C, B, C, fc1, nullptr, 0, emb, E, relu);
         float* e1 = ctx.ws.alloc_f((size_t)B * D);
         float* g = ctx.ws.alloc_f((size_t)B * D);
         float* e2 = ctx.ws.alloc_f((size_t)B * D);

@@ -165,18 +165,24 @@ struct Loop {
             in = zin, out = ecrop, h = a.split_kh, w = a.split_kw;
         }
         const int half = a.B * crops;      // UNet rows of one half of a guided step
+        const float* emb_row = emb_hoist ? cur_emb : nullptr;
         if (lane2) {
             MAA_HIP(hipEventRecord(ctx.ev_fork, ctx.stream));
             MAA_HIP(hipStreamWaitEvent(lane2->stream, ctx.ev_fork, 0));
-            // (the conditional lane starts from the unconditional lane's layers before the first cross-attention: unet.cpp)
-            unet.forward(ctx, in, cur_t, unet.context_ptr, half, h, w, out, emb_hoist ? cur_emb : nullptr, 0, share ? 2 : 0);
+            // (the conditional lane starts from the unconditional lane's layers before the first cross-attention: this call's
+            // hand-over, filled by the first forward and read by the second)
+            CfgPrefix handover;
+            handover.ready = ctx.ev_prefix;
+            UNetForwardOpt o{emb_row, 0, share ? CfgShare::Export : CfgShare::None, &handover};
+            unet.forward(ctx, in, cur_t, unet.context_ptr, half, h, w, out, o);
+            o.batch_off = half, o.mode = share ? CfgShare::Import : CfgShare::None;
             unet.forward(*lane2, in + (size_t)half * per_crop_in, cur_t + half, unet.context_ptr, half, h, w,
-                         out + (size_t)half * per_crop, emb_hoist ? cur_emb : nullptr, half, share ? 3 : 0);
+                         out + (size_t)half * per_crop, o);
             MAA_HIP(hipEventRecord(ctx.ev_join, lane2->stream));
             MAA_HIP(hipStreamWaitEvent(ctx.stream, ctx.ev_join, 0));
         } else
-            // (one stream: the halves of cat([x] * 2) share every layer before the first cross-attention -- unet.cpp `dup`)
-            unet.forward(ctx, in, cur_t, unet.context_ptr, rows, h, w, out, emb_hoist ? cur_emb : nullptr, -1, share ? 1 : 0);
+            // (one stream: the halves of cat([x] * 2) share every layer before the first cross-attention)
+            unet.forward(ctx, in, cur_t, unet.context_ptr, rows, h, w, out, {emb_row, -1, share ? CfgShare::Dup : CfgShare::None, nullptr});
         if (split)
             launch_split_fold(ctx, ecrop, wT, norm, nB, a.C, a.H, a.W, a.split_kh, a.split_kw, a.split_sh, a.split_sw, eps);
     }
@@ -218,6 +224,8 @@ struct Loop {
                                      (unsigned long long)reinterpret_cast<uintptr_t>(lane2 ? lane2->stream : nullptr),
                                      (unsigned long long)reinterpret_cast<uintptr_t>(lane2 ? lane2->ws.base() : nullptr),
                                      (unsigned long long)(lane2 ? lane2->ws.capacity() : 0),
+                                     // the guided step's arrangement: the shared prefix changes the launches, as the lanes do
+                                     (unsigned long long)share, (unsigned long long)(lane2 != nullptr),
                                      // the split: a step with it launches other kernels on other shapes than one without
                                      (unsigned long long)a.split_kh, (unsigned long long)a.split_kw, (unsigned long long)a.split_sh,
                                      (unsigned long long)a.split_sw, (unsigned long long)reinterpret_cast<uintptr_t>(wT)})

@@ -160,14 +160,16 @@ struct Encoder::Impl {
         const int sp = split_for_gemm(ctx, W) ? 1 : 0;
         const int o_sp = sp && flash_attention_covers(ctx, W / cfg.heads) ? 1 : 0;
         const int f_sp = split_for_gemm(ctx, F) ? 1 : 0;
+        LinOpt gelu(sp, f_sp);
+        gelu.act = 3;
         for (const Layer& l : layers) {
             launch_layernorm(ctx, x, M, W, l.ln1g, l.ln1b, cfg.ln_eps, ln, sp);
-            linear_into(ctx, ln, W, M, W, l.qkv, nullptr, 0, qkv, 3 * W, 0, 0, sp ? M : 0);
+            linear_into(ctx, ln, W, M, W, l.qkv, nullptr, 0, qkv, 3 * W, LinOpt(sp));
             attend(ctx, qkv, B, L, o, o_sp, causal);
-            linear_into(ctx, o, W, M, W, l.out, x, W, y, W, 0, 0, o_sp ? M : 0);
+            linear_into(ctx, o, W, M, W, l.out, x, W, y, W, LinOpt(o_sp));
             launch_layernorm(ctx, y, M, W, l.ln2g, l.ln2b, cfg.ln_eps, ln, sp);
-            linear_into(ctx, ln, W, M, W, l.fc1, nullptr, 0, f, F, 0, 0, sp ? M : 0, f_sp, /*act=*/3);
-            linear_into(ctx, f, F, M, F, l.fc2, y, W, x, W, 0, 0, f_sp ? M : 0);
+            linear_into(ctx, ln, W, M, W, l.fc1, nullptr, 0, f, F, gelu);
+            linear_into(ctx, f, F, M, F, l.fc2, y, W, x, W, LinOpt(f_sp));
         }
     }
 
@@ -206,13 +208,15 @@ struct Encoder::Impl {
         float* f = ctx.ws.alloc_f((size_t)M * F);
         const int o_sp = split_for_gemm(ctx, W) && flash_attention_covers(ctx, W / cfg.heads) ? 1 : 0;
         const int f_sp = split_for_gemm(ctx, F) ? 1 : 0;
+        LinOpt gelu(false, f_sp);
+        gelu.act = 3;
         for (const Layer& l : layers) {
             linear_into(ctx, h, W, M, W, l.qkv, nullptr, 0, qkv, 3 * W);
             attend(ctx, qkv, B, L, o, o_sp);
-            linear_into(ctx, o, W, M, W, l.out, h, W, t, W, 0, 0, o_sp ? M : 0);
+            linear_into(ctx, o, W, M, W, l.out, h, W, t, W, LinOpt(o_sp));
             launch_layernorm(ctx, t, M, W, l.ln1g, l.ln1b, cfg.ln_eps, x);
-            linear_into(ctx, x, W, M, W, l.fc1, nullptr, 0, f, F, 0, 0, 0, f_sp, /*act=*/3);
-            linear_into(ctx, f, F, M, F, l.fc2, x, W, t, W, 0, 0, f_sp ? M : 0);
+            linear_into(ctx, x, W, M, W, l.fc1, nullptr, 0, f, F, gelu);
+            linear_into(ctx, f, F, M, F, l.fc2, x, W, t, W, LinOpt(f_sp));
             launch_layernorm(ctx, t, M, W, l.ln2g, l.ln2b, cfg.ln_eps, h);
         }
         // Projection on every token (FrozenCLAPEmbedder) or on the [CLS] rows (the scorer)

@@ -181,6 +181,7 @@ struct Ctx {
     // step graph.  Created on first use (side_lane), owned by this context; shares the zero page, the device and the tuning.
     Ctx* side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_prefix = nullptr;      // "the shared prefix of this step is written": handed to the UNet in the step's CfgPrefix (models.h)
     // How many contexts' launches the caller keeps in flight on this device (maa_ctx_set_concurrency).  >= 3 = the chip is kept
     // full from outside: a launch then costs the sum of its workgroups' time, not the rounds its own grid makes -- one stream per
     // guided DDIM step and igemm tiles by least total workgroup time; 1 or 2 = this context (nearly) owns the GPU: two CFG lanes

@@ -8,6 +8,39 @@
 
 namespace maa {
 
+// A guided DDIM step evaluates the model on cat([x] * 2) with cat([uncond, cond]) (ddim.py:177-199): the halves are the same tensor
+// before the first cross-attention, so those layers need computing once.  How one forward takes part in that:
+//   None    the whole network
+//   Dup     the batch is cat([x] * 2) on one stream -- samples [B/2, B) repeat [0, B/2): those layers run on one half, and their
+//           outputs are duplicated where the halves part
+//   Export  the unconditional lane (batch_off 0): the whole network, and it leaves those layers' outputs in its workspace
+//   Import  the conditional lane (batch_off B), called after Export with the same CfgPrefix: starts from them
+enum class CfgShare { None, Dup, Export, Import };
+// What the Export forward hands to the Import forward of the same step.  The step owns it (ddim.cpp Loop::forward, one per
+// call) and supplies `ready`, which orders the importing stream behind the exporting one; the step's join orders the next step's
+// writes behind the reads.  hs0: conv_in's output (the first skip tensor); xres, y1, q: the first transformer's input, its
+// residual stream after attn1 and attn2's queries -- all in the exporting context's workspace.
+struct CfgPrefix {
+    const float *hs0 = nullptr, *xres = nullptr, *y1 = nullptr, *q = nullptr;
+    int B = 0, H = 0, W = 0;
+    bool filled = false;
+    hipEvent_t ready = nullptr;
+};
+
+// What holds for one UNet forward only.
+// emb_row: the ResBlocks' time-embedding row of this step from emb_table() (one row for all samples: every sample of a DDIM
+//   step shares t); null: computed from t (and, I2A, the context) as the reference does per forward
+// batch_off >= 0: this call covers samples [batch_off, batch_off + B) of the batch set_context saw (one lane of a CFG step);
+//   x / t / out already point at that sample, the context rows and the cross-attention K/V caches are offset inside
+// mode (with emb_row only), prefix (Export / Import only): see CfgShare.  A UNet the hand-over is not written for (unet.cpp
+//   prefix_ok) runs the whole network in both lanes.
+struct UNetForwardOpt {
+    const float* emb_row = nullptr;
+    int batch_off = -1;
+    CfgShare mode = CfgShare::None;
+    CfgPrefix* prefix = nullptr;
+};
+
 class UNet {
 public:
     // precision: 0 exact fp32 MFMA, 1 bf16x3 split, 2 plain bf16 operands (fixed at creation: it decides the
@@ -21,16 +54,8 @@ public:
     // classifier-free guidance: context rows [uncond (B) ; cond (B)] assembled in a buffer the UNet owns (it stays
     // valid for later forwards, e.g. the I2A time-embedding add), then set_context over 2B rows
     void set_context_cfg(Ctx& ctx, const float* d_uncond, const float* d_cond, int B, int L, int rep = 1);
-    // emb_row: optional, the ResBlocks' time-embedding row of this step from emb_table() (one row for all samples: every
-    // sample of a DDIM step shares t); null: computed from t (and, I2A, the context) as the reference does per forward
-    // batch_off >= 0: this call covers samples [batch_off, batch_off + B) of the batch set_context saw (one lane of a CFG
-    // step); x / t / out already point at that sample, the context rows and the cross-attention K/V caches are offset inside
-    // cfg_share (with emb_row; a guided DDIM step, whose halves are the same tensor before the first cross-attention): 1 = the
-    // batch is cat([x] * 2) on one stream -- samples [B/2, B) repeat [0, B/2) -- and those layers run on one half; 2 / 3 = this
-    // call is the unconditional / conditional lane (batch_off 0 / B): lane 2 leaves those layers' outputs in its workspace,
-    // lane 3 (called after it) starts from them (unet.cpp forward_body)
-    void forward(Ctx& ctx, const float* x_nchw, const float* t, const float* context, int B, int H, int W,
-                 float* out_nchw, const float* emb_row = nullptr, int batch_off = -1, int cfg_share = 0);
+    void forward(Ctx& ctx, const float* x_nchw, const float* t, const float* context, int B, int H, int W, float* out_nchw,
+                 const UNetForwardOpt& opt = UNetForwardOpt());
     // Linear(SiLU(time_embed(timestep_embedding(t)))) of every ResBlock for `rows` timesteps at once -> [rows, emb_width()]
     // (openaimodel.py:725-726, 218-224): the sampling loop computes its S rows once instead of per step.  Not for the
     // I2A variant, whose embedding also takes the sample's context (custom_openaimodel.py:352-354).

@@ -173,6 +173,7 @@ Ctx::~Ctx() {
     }
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
+    if (ev_prefix) (void)hipEventDestroy(ev_prefix);
 }
 Ctx& side_lane(Ctx& ctx) {
     if (!ctx.side) {
@@ -185,6 +186,7 @@ Ctx& side_lane(Ctx& ctx) {
         ctx.side = sd;
         MAA_HIP(hipEventCreateWithFlags(&ctx.ev_fork, hipEventDisableTiming));
         MAA_HIP(hipEventCreateWithFlags(&ctx.ev_join, hipEventDisableTiming));
+        MAA_HIP(hipEventCreateWithFlags(&ctx.ev_prefix, hipEventDisableTiming));
     }
     ctx.side->tune = ctx.tune;
     ctx.side->dtype = ctx.dtype;

@@ -14,7 +14,10 @@
 //   * a guided DDIM step evaluates the model on cat([x] * 2) with cat([uncond, cond]) (ddim.py:177-199): the two halves differ
 //     only in the context, so every layer before the first cross-attention (conv_in, the first ResBlock, the first
 //     transformer's norm / proj_in / self-attention / to_q) is the same tensor twice -- computed on one half and duplicated
-//     where the halves part (forward_body `dup`; round 6).  Every kernel is batch-invariant, so the result is bit-identical.
+//     where the halves part (CfgShare::Dup; as two lanes the unconditional lane hands them to the conditional one in the step's
+//     CfgPrefix, Export / Import; models.h).  Every kernel is batch-invariant, so the result is bit-identical.
+// UNet::Impl holds what outlives a forward: the weights, the layer lists, the K/V cache and the context slabs.  What holds for one
+// forward only is a Pass on the stack of Impl::forward, and everything under "execution" is a const member that takes it.
 #include "models.h"
 
 #include <atomic>
@@ -58,6 +61,34 @@ struct Layer {
     int idx;
 };
 
+// One forward: the context it runs on, the ResBlocks' embedding rows, the lane and the guided step's arrangement
+struct Pass {
+    Ctx& ctx;
+    const float* emb_out = nullptr;
+    int emb_ld = 0;           // pitch between the samples' rows of emb_out (0: one row for every sample)
+    // a forward over samples [batch_off, batch_off + B) of the batch set_context saw (a lane of a CFG step: ddim.cpp); the
+    // caller's x / t / out pointers already stand at that sample, the context rows and the K/V caches are offset here
+    int batch_off = 0;
+    bool lane = false;
+    CfgShare mode = CfgShare::None;
+    CfgPrefix* prefix = nullptr;      // Export / Import: the step's hand-over
+};
+// What a SpatialTransformer's layers before the first cross-attention leave for the rest: the block input (proj_out's residual,
+// for every output sample), the residual stream after attn1 and attn2's queries
+struct StMid {
+    const float *xres, *y1, *q;
+};
+// The sizes and operand forms of a SpatialTransformer's rows for B samples.  Attention outputs and the GEGLU product feed exactly
+// one projection each: in the bf16 modes they are written as split32 rows, so to_out / ff.net.2 take the LDS-DMA engine with no
+// per-tile conversion (o_sp, g_sp)
+struct StRows {
+    int B, HW, inner;
+    long long M;
+    bool sp_in, sp;
+    int o_sp, g_sp;
+    float scale;
+};
+
 }  // namespace
 
 struct UNet::Impl {
@@ -86,19 +117,9 @@ struct UNet::Impl {
     size_t kv_cap_rows = 0;
     DevSlab cfg_context;      // [uncond ; cond] rows of a CFG sample() call
     DevSlab tiled_context;    // the context rows once per crop (set_context with rep > 1, add_context_to_emb only)
-    // The shared prefix of a guided step run as two lanes (ddim.cpp): the unconditional lane computes the layers before the
-    // first cross-attention as part of its own pass and leaves their four outputs where they are in ITS workspace (share 2);
-    // the conditional lane starts at that cross-attention and reads them (share 3) -- `ready` orders the two streams, the
-    // step's join orders the next step's writes behind the reads.
-    struct Prefix {
-        const float *hs0 = nullptr, *xres = nullptr, *y1 = nullptr, *q = nullptr;
-        int B = 0, H = 0, W = 0;
-        hipEvent_t ready = nullptr;
-    } prefix;
-    int share = 0;            // this forward: 0 whole network, 1 one stream [x ; x] (dup), 2 lane that exports, 3 lane that imports
 
-    // conv_in, then [ResBlock, SpatialTransformer]: the shape the lanes' hand-over is written for (T2A; anything else keeps
-    // the whole evaluation per lane)
+    // conv_in, then [ResBlock, SpatialTransformer]: the shape the lanes' hand-over (CfgPrefix) is written for (T2A; anything else
+    // keeps the whole evaluation per lane)
     bool prefix_ok() const {
         return cfg.use_spatial_transformer && !cfg.add_context_to_emb && input.size() >= 2 && input[0].size() == 1 &&
                input[0][0].kind == kConv && input[1].size() == 2 && input[1][0].kind == kRes && input[1][1].kind == kST &&
@@ -108,7 +129,6 @@ struct UNet::Impl {
     ~Impl() {
         for (float* p : kv_cache)
             if (p) (void)hipFree(p);
-        if (prefix.ready) (void)hipEventDestroy(prefix.ready);
     }
 
     // ---- construction ---------------------------------------------------------------------------
@@ -128,8 +148,6 @@ struct UNet::Impl {
         MAA_CHECK(r.has_skip == (cin != cout), "skip_connection presence " + p);
         r.emb_off = emb_total;
         emb_total += cout;
-        emb_w.push_back(p + "emb_layers.1.weight");
-        emb_b.push_back(p + "emb_layers.1.bias");
         res.push_back(r);
         return {kRes, (int)res.size() - 1};
     }
@@ -187,29 +205,31 @@ struct UNet::Impl {
         convs.push_back(c);
         return {kind, (int)convs.size() - 1};
     }
-    std::vector<std::string> emb_w, emb_b;
-
-    int cur_heads = 0;
-    Layer attn_layer(const StateDict& sd, const std::string& p, int ch) {
-        // openaimodel.py:534-553 head bookkeeping
-        int heads, dh;
-        if (cfg.num_head_channels == -1) {
-            heads = cur_heads;
-            dh = ch / heads;
-        } else {
-            heads = ch / cfg.num_head_channels;
-            cur_heads = heads;
-            dh = cfg.num_head_channels;
-        }
-        if (cfg.legacy) dh = cfg.use_spatial_transformer ? ch / heads : cfg.num_head_channels;
-        if (cfg.use_spatial_transformer) return add_st(sd, p, ch, heads, dh);
-        return add_attn(sd, p, ch, dh == -1 ? heads : ch / dh);
-    }
 
     void build(const StateDict& sd) {
         const int mc = cfg.model_channels;
         emb_dim = mc * 4;
-        cur_heads = cfg.num_heads;
+        std::vector<std::string> emb_w, emb_b;      // every ResBlock's emb_layers Linear, in emb_off order: packed as one GEMM
+        auto res_block = [&](const std::string& p, int cin, int cout, int updown) {
+            emb_w.push_back(p + "emb_layers.1.weight");
+            emb_b.push_back(p + "emb_layers.1.bias");
+            return add_res(sd, p, cin, cout, updown);
+        };
+        int cur_heads = cfg.num_heads;
+        auto attn_layer = [&](const std::string& p, int ch) {      // openaimodel.py:534-553 head bookkeeping
+            int heads, dh;
+            if (cfg.num_head_channels == -1) {
+                heads = cur_heads;
+                dh = ch / heads;
+            } else {
+                heads = ch / cfg.num_head_channels;
+                cur_heads = heads;
+                dh = cfg.num_head_channels;
+            }
+            if (cfg.legacy) dh = cfg.use_spatial_transformer ? ch / heads : cfg.num_head_channels;
+            if (cfg.use_spatial_transformer) return add_st(sd, p, ch, heads, dh);
+            return add_attn(sd, p, ch, dh == -1 ? heads : ch / dh);
+        };
         te0 = ws.pack_conv(sd, "time_embed.0.weight", "time_embed.0.bias", 1, 1);
         te2 = ws.pack_conv(sd, "time_embed.2.weight", "time_embed.2.bias", 1, 1);
         auto in_attn = [&](int ds) {
@@ -226,25 +246,25 @@ struct UNet::Impl {
             for (int i = 0; i < cfg.num_res_blocks; ++i) {
                 const std::string p = "input_blocks." + std::to_string(input.size()) + ".";
                 std::vector<Layer> blk;
-                blk.push_back(add_res(sd, p + "0.", ch, m * mc, 0));
+                blk.push_back(res_block(p + "0.", ch, m * mc, 0));
                 ch = m * mc;
-                if (in_attn(ds)) blk.push_back(attn_layer(sd, p + "1.", ch));
+                if (in_attn(ds)) blk.push_back(attn_layer(p + "1.", ch));
                 input.push_back(blk);
                 chans.push_back(ch);
             }
             if (level != cfg.n_channel_mult - 1) {
                 const std::string p = "input_blocks." + std::to_string(input.size()) + ".0.";
                 if (cfg.resblock_updown)
-                    input.push_back({add_res(sd, p, ch, ch, 1)});
+                    input.push_back({res_block(p, ch, ch, 1)});
                 else
                     input.push_back({add_conv(sd, p + "op.", ch, ch, kDown)});
                 chans.push_back(ch);
                 ds *= 2;
             }
         }
-        middle.push_back(add_res(sd, "middle_block.0.", ch, ch, 0));
-        middle.push_back(attn_layer(sd, "middle_block.1.", ch));
-        middle.push_back(add_res(sd, "middle_block.2.", ch, ch, 0));
+        middle.push_back(res_block("middle_block.0.", ch, ch, 0));
+        middle.push_back(attn_layer("middle_block.1.", ch));
+        middle.push_back(res_block("middle_block.2.", ch, ch, 0));
         for (int level = cfg.n_channel_mult - 1; level >= 0; --level) {
             const int m = cfg.channel_mult[level];
             for (int i = 0; i < cfg.num_res_blocks + 1; ++i) {
@@ -252,14 +272,14 @@ struct UNet::Impl {
                 chans.pop_back();
                 const std::string p = "output_blocks." + std::to_string(output.size()) + ".";
                 std::vector<Layer> blk;
-                blk.push_back(add_res(sd, p + "0.", ch + ich, mc * m, 0));
+                blk.push_back(res_block(p + "0.", ch + ich, mc * m, 0));
                 ch = mc * m;
                 int j = 1;
-                if (in_attn(ds)) blk.push_back(attn_layer(sd, p + std::to_string(j++) + ".", ch));
+                if (in_attn(ds)) blk.push_back(attn_layer(p + std::to_string(j++) + ".", ch));
                 if (level && i == cfg.num_res_blocks) {
                     const std::string q = p + std::to_string(j++) + ".";
                     if (cfg.resblock_updown)
-                        blk.push_back(add_res(sd, q, ch, ch, 2));
+                        blk.push_back(res_block(q, ch, ch, 2));
                     else
                         blk.push_back(add_conv(sd, q + "conv.", ch, ch, kUp));
                     ds /= 2;
@@ -275,8 +295,9 @@ struct UNet::Impl {
         MAA_CHECK(emb_all.N == emb_total, "emb_layers packing");
     }
 
-    // ---- execution ------------------------------------------------------------------------------
-    T4 run_res(Ctx& ctx, const ResW& r, const T4& x1, const T4* x2, const float* emb_out) {
+    // ---- execution: const members over the forward's Pass -----------------------------------------
+    T4 run_res(const Pass& p, const ResW& r, const T4& x1, const T4* x2) const {
+        Ctx& ctx = p.ctx;
         const int B = x1.B, H = x1.H, W = x1.W;
         const int Ho = r.updown == 1 ? H / 2 : (r.updown == 2 ? H * 2 : H);
         const int Wo = r.updown == 1 ? W / 2 : (r.updown == 2 ? W * 2 : W);
@@ -295,11 +316,9 @@ struct UNet::Impl {
         launch_groupnorm(ctx, x1.p, x1.C, x1.C, x2 ? x2->p : nullptr, x2 ? x2->C : 0, x2 ? x2->C : 0, B, H * W, 32,
                          r.g1, r.b1, 1e-5f, 1, t1.p, t1.split, xraw.p);
         T4 h1 = alloc_t(ctx, B, Ho, Wo, r.cout);
-        ConvOpt o1;
-        o1.KH = o1.KW = 3;
-        o1.pad = 1;
-        o1.rowadd = emb_out + r.emb_off;
-        o1.ld_rowadd = emb_ld;
+        ConvOpt o1 = conv3x3();
+        o1.rowadd = p.emb_out + r.emb_off;
+        o1.ld_rowadd = p.emb_ld;
         const float* resid = nullptr;
         if (r.updown == 1) {          // openaimodel.py:212-214,256-261: avg-pool both h and x, then conv
             MAA_CHECK(!x2, "down ResBlock takes one source");
@@ -325,192 +344,179 @@ struct UNet::Impl {
         if (r.has_skip) {
             MAA_CHECK(r.updown == 0, "skip conv with up/down");
             T4 sk = alloc_t(ctx, B, H, W, r.cout);
-            ConvOpt os;
             if (xraw.p)
-                conv_into(ctx, xraw, nullptr, r.skip, os, sk);
+                conv_into(ctx, xraw, nullptr, r.skip, ConvOpt(), sk);
             else
-                conv_into(ctx, x1, x2, r.skip, os, sk);
+                conv_into(ctx, x1, x2, r.skip, ConvOpt(), sk);
             resid = sk.p;
         } else {
             MAA_CHECK(!x2, "identity skip needs a single source");
         }
-        ConvOpt o2;
-        o2.KH = o2.KW = 3;
-        o2.pad = 1;
+        ConvOpt o2 = conv3x3();
         o2.res = resid;
         conv_into(ctx, t2, nullptr, r.conv2, o2, out);
         ctx.ws.release(mk);
         return out;
     }
 
-    // expand: x holds ONE half of a guided step's batch (both halves are equal up to here); the block's first cross-attention
-    // is where they part, so everything before it runs on x.B samples and the output has 2 x.B
-    // xp: 2 = this lane leaves y1 / q of the first block for the other lane (allocated outside the block's scratch scope so that
-    // they outlive it), 3 = this lane starts at the first block's cross-attention with the other lane's y1 / q / block input
-    T4 run_st(Ctx& ctx, const STW& s, const T4& x, bool expand = false, int xp = 0) {
-        const int HW = x.H * x.W, inner = s.heads * s.dh;
-        int B = x.B;                                   // samples of the current tensors
-        const int Bo = expand ? 2 * x.B : x.B;
-        long long M = (long long)B * HW;
-        const long long Mo = (long long)Bo * HW;
-        T4 out = alloc_t(ctx, Bo, x.H, x.W, s.ch);
-        float *y1_keep = nullptr, *q_keep = nullptr;
-        if (xp == 2) {
-            y1_keep = ctx.ws.alloc_f((size_t)M * inner);
-            q_keep = ctx.ws.alloc_f((size_t)M * inner);
+    StRows st_rows(const Ctx& ctx, const STW& s, int B, int HW) const {
+        const int inner = s.heads * s.dh;
+        const bool sp = split_for_gemm(ctx, inner);
+        return {B, HW, inner, (long long)B * HW, split_for_gemm(ctx, s.ch), sp, sp && flash_attention_covers(ctx, s.dh) ? 1 : 0,
+                split_for_gemm(ctx, 4 * inner) ? 1 : 0, 1.0f / std::sqrt((float)s.dh)};
+    }
+
+    // A transformer block up to its cross-attention: x = attn1(norm1(x)) + x (attention.py:212) -> y1, then attn2's queries of
+    // norm2(x) (:213) -> q.  ln, o: scratch rows the whole block shares (LayerNorm output, attention output).  y1, q null: allocated
+    // here, each where it is first written (after the self-attention, whose own scratch is the workspace's high-water mark)
+    void st_block_head(const Pass& p, const STW& s, const STBlockW& b, const StRows& d, const float* y, float* ln, float* o, float*& y1,
+                       float*& q) const {
+        Ctx& ctx = p.ctx;
+        const int inner = d.inner;
+        launch_layernorm(ctx, y, d.M, inner, b.ln1g, b.ln1b, 1e-5f, ln, d.sp);
+        float* qkv = ctx.ws.alloc_f((size_t)d.M * 3 * inner);
+        linear_into(ctx, ln, inner, d.M, inner, b.qkv1, nullptr, 0, qkv, 3 * inner, LinOpt(d.sp));
+        attention_into(ctx, qkv, 3 * inner, s.dh, qkv + inner, 3 * inner, s.dh, qkv + 2 * inner, 3 * inner, s.dh, d.B, s.heads, s.dh,
+                       d.HW, d.HW, d.scale, o, inner, d.o_sp);
+        if (!y1) y1 = ctx.ws.alloc_f((size_t)d.M * inner);
+        linear_into(ctx, o, inner, d.M, inner, b.out1, y, inner, y1, inner, LinOpt(d.o_sp));
+        launch_layernorm(ctx, y1, d.M, inner, b.ln2g, b.ln2b, 1e-5f, ln, d.sp);
+        if (!q) q = ctx.ws.alloc_f((size_t)d.M * inner);
+        linear_into(ctx, ln, inner, d.M, inner, b.q2, nullptr, 0, q, inner, LinOpt(d.sp));
+    }
+
+    // The block from its cross-attention on: x = attn2(norm2(x), context) + x (:213), x = ff(norm3(x)) + x (:214) -> the block's
+    // output.  The last block's output feeds only proj_out: written as split32 as well (bias + residual are applied before the
+    // split, in the same epilogue)
+    float* st_block_tail(const Pass& p, const STW& s, const STBlockW& b, const StRows& d, const float* y1, const float* q, float* ln,
+                         float* o) const {
+        Ctx& ctx = p.ctx;
+        const int inner = d.inner;
+        MAA_CHECK(ctx.ws.dry || (kv_cache[b.kv_slot] && (p.lane ? p.batch_off + d.B <= kv_batch : kv_batch == d.B)),
+                  "set_context must precede forward (batch)");
+        const float* kv = kv_cache[b.kv_slot] + (size_t)p.batch_off * kv_len * 2 * inner;
+        attention_into(ctx, q, inner, s.dh, kv, 2 * inner, s.dh, kv + inner, 2 * inner, s.dh, d.B, s.heads, s.dh, d.HW, kv_len, d.scale,
+                       o, inner, d.o_sp);
+        float* y2 = ctx.ws.alloc_f((size_t)d.M * inner);
+        linear_into(ctx, o, inner, d.M, inner, b.out2, y1, inner, y2, inner, LinOpt(d.o_sp));
+        launch_layernorm(ctx, y2, d.M, inner, b.ln3g, b.ln3b, 1e-5f, ln, d.sp);
+        float* g = ctx.ws.alloc_f((size_t)d.M * 4 * inner);
+        LinOpt geglu(d.sp, d.g_sp);
+        geglu.geglu = 1;
+        linear_into(ctx, ln, inner, d.M, inner, b.ff1, nullptr, 0, g, 4 * inner, geglu);
+        float* y3 = ctx.ws.alloc_f((size_t)d.M * inner);
+        const bool last = &b == &s.blocks.back();
+        linear_into(ctx, g, 4 * inner, d.M, 4 * inner, b.ff2, y2, inner, y3, inner, LinOpt(d.g_sp, last && d.sp));
+        return y3;
+    }
+
+    // GroupNorm, proj_in and the first block up to its cross-attention, on x's samples: everything a guided step's halves share.
+    // y1, q: where to leave the results (null: the block's own scratch)
+    StMid st_prefix(const Pass& p, const STW& s, const T4& x, const StRows& d, float* ln, float* o, float* y1 = nullptr,
+                    float* q = nullptr) const {
+        Ctx& ctx = p.ctx;
+        float* xn = ctx.ws.alloc_f((size_t)d.M * s.ch);
+        launch_groupnorm(ctx, x.p, s.ch, s.ch, nullptr, 0, 0, d.B, d.HW, 32, s.ng, s.nb, 1e-6f, 0, xn, d.sp_in);
+        float* y = ctx.ws.alloc_f((size_t)d.M * d.inner);
+        linear_into(ctx, xn, s.ch, d.M, s.ch, s.proj_in, nullptr, 0, y, d.inner, LinOpt(d.sp_in));
+        st_block_head(p, s, s.blocks.front(), d, y, ln, o, y1, q);
+        return {x.p, y1, q};
+    }
+
+    // The first block from its cross-attention on, the further blocks in full, proj_out + the block input -> out
+    void st_rest(const Pass& p, const STW& s, const StRows& d, const StMid& m, float* ln, float* o, T4& out) const {
+        Ctx& ctx = p.ctx;
+        const float* y = st_block_tail(p, s, s.blocks.front(), d, m.y1, m.q, ln, o);
+        for (size_t i = 1; i < s.blocks.size(); ++i) {
+            const size_t n = (size_t)d.M * d.inner;
+            float *ln_i = ctx.ws.alloc_f(n), *o_i = ctx.ws.alloc_f(n), *y1 = nullptr, *q = nullptr;
+            st_block_head(p, s, s.blocks[i], d, y, ln_i, o_i, y1, q);
+            y = st_block_tail(p, s, s.blocks[i], d, y1, q, ln_i, o_i);
         }
+        linear_into(ctx, y, d.inner, d.M, d.inner, s.proj_out, m.xres, s.ch, out.p, s.ch, LinOpt(d.sp));
+    }
+
+    // A SpatialTransformer under one of the four arrangements of a guided step (models.h CfgShare).  Dup: x holds ONE half of the
+    // batch (both halves are equal up to here) and the output has 2 x.B samples; Import: x is the Export lane's block input.
+    // What the Export lane publishes (hs0 in forward_body; xres, y1, q here) must be allocated outside every mark / release
+    // scope that closes before that lane's forward returns: the other lane reads it until the step's join, which is also what
+    // orders the next step's writes behind those reads.
+    T4 run_st(const Pass& p, const STW& s, const T4& x, CfgShare mode) const {
+        MAA_CHECK(!s.blocks.empty(), "SpatialTransformer without a transformer block");
+        Ctx& ctx = p.ctx;
+        const StRows in = st_rows(ctx, s, x.B, x.H * x.W), full = st_rows(ctx, s, mode == CfgShare::Dup ? 2 * x.B : x.B, in.HW);
+        const size_t n_in = (size_t)in.M * in.inner, n_full = (size_t)full.M * in.inner;
+        T4 out = alloc_t(ctx, full.B, x.H, x.W, s.ch);
+        float *y1 = nullptr, *q = nullptr;
+        if (mode == CfgShare::Export) y1 = ctx.ws.alloc_f(n_in), q = ctx.ws.alloc_f(n_in);
         const size_t mk = ctx.ws.mark();
-        const float* xres = x.p;                       // proj_out's residual: the block input, for every output sample
-        if (expand) {
-            float* xd = ctx.ws.alloc_f((size_t)Mo * s.ch);
-            launch_dup_half(ctx, x.p, M * s.ch, xd);
-            xres = xd;
-        }
-        const bool sp_in = split_for_gemm(ctx, s.ch), sp = split_for_gemm(ctx, inner);
-        float* y = nullptr;
-        if (xp != 3) {
-            float* xn = ctx.ws.alloc_f((size_t)M * s.ch);
-            launch_groupnorm(ctx, x.p, s.ch, s.ch, nullptr, 0, 0, B, HW, 32, s.ng, s.nb, 1e-6f, 0, xn, sp_in);
-            y = ctx.ws.alloc_f((size_t)M * inner);
-            linear_into(ctx, xn, s.ch, M, s.ch, s.proj_in, nullptr, 0, y, inner, 0, 0, sp_in ? M : 0);
-        }
-        const float scale = 1.0f / std::sqrt((float)s.dh);
-        // attention outputs and the GEGLU product feed exactly one projection each: in the bf16 modes they are written
-        // as split32 rows, so to_out / ff.net.2 take the LDS-DMA engine with no per-tile conversion
-        const bool no_osplit = false;
-        const int o_sp = !no_osplit && sp && flash_attention_covers(ctx, s.dh) ? 1 : 0;
-        const int g_sp = !no_osplit && split_for_gemm(ctx, 4 * inner) ? 1 : 0;
-        int y_sp = 0;
-        for (const STBlockW& b : s.blocks) {
-            const bool first_block = &b == &s.blocks.front();
-            float* ln = ctx.ws.alloc_f((size_t)Mo * inner);
-            float* o = ctx.ws.alloc_f((size_t)Mo * inner);
-            float *y1 = nullptr, *q = nullptr;
-            if (xp == 3 && first_block) {
-                // the other lane computed this far on the same x: its residual stream and queries, read in place
-                y1 = const_cast<float*>(prefix.y1);
-                q = const_cast<float*>(prefix.q);
-            } else {
-                // x = attn1(norm1(x)) + x      (attention.py:212)
-                launch_layernorm(ctx, y, M, inner, b.ln1g, b.ln1b, 1e-5f, ln, sp);
-                float* qkv = ctx.ws.alloc_f((size_t)M * 3 * inner);
-                linear_into(ctx, ln, inner, M, inner, b.qkv1, nullptr, 0, qkv, 3 * inner, 0, 0, sp ? M : 0);
-                attention_into(ctx, qkv, 3 * inner, s.dh, qkv + inner, 3 * inner, s.dh, qkv + 2 * inner, 3 * inner, s.dh,
-                               B, s.heads, s.dh, HW, HW, scale, o, inner, o_sp);
-                y1 = xp == 2 && first_block ? y1_keep : ctx.ws.alloc_f((size_t)M * inner);
-                linear_into(ctx, o, inner, M, inner, b.out1, y, inner, y1, inner, 0, 0, o_sp ? M : 0);
-                // x = attn2(norm2(x), context) + x      (:213)
-                launch_layernorm(ctx, y1, M, inner, b.ln2g, b.ln2b, 1e-5f, ln, sp);
-                q = xp == 2 && first_block ? q_keep : ctx.ws.alloc_f((size_t)M * inner);
-                linear_into(ctx, ln, inner, M, inner, b.q2, nullptr, 0, q, inner, 0, 0, sp ? M : 0);
-                if (xp == 2 && first_block) {
-                    prefix.y1 = y1;
-                    prefix.q = q;
-                    prefix.xres = x.p;
-                    if (!ctx.ws.dry) MAA_HIP(hipEventRecord(prefix.ready, ctx.stream));
-                }
+        float *ln = ctx.ws.alloc_f(n_full), *o = ctx.ws.alloc_f(n_full);
+        StMid m;
+        switch (mode) {
+            case CfgShare::None:
+                m = st_prefix(p, s, x, in, ln, o);
+                break;
+            case CfgShare::Dup: {      // the halves part here: the same block input, queries and residual stream meet two contexts
+                float* xd = ctx.ws.alloc_f((size_t)full.M * s.ch);
+                launch_dup_half(ctx, x.p, in.M * s.ch, xd);
+                m = st_prefix(p, s, x, in, ln, o);
+                float *qd = ctx.ws.alloc_f(n_full), *yd = ctx.ws.alloc_f(n_full);
+                launch_dup_half(ctx, m.q, (long long)n_in, qd);
+                launch_dup_half(ctx, m.y1, (long long)n_in, yd);
+                m = {xd, yd, qd};
+                break;
             }
-            if (B != Bo) {      // the halves part here: the same queries and the same residual stream meet two contexts
-                float* qd = ctx.ws.alloc_f((size_t)Mo * inner);
-                float* yd = ctx.ws.alloc_f((size_t)Mo * inner);
-                launch_dup_half(ctx, q, M * inner, qd);
-                launch_dup_half(ctx, y1, M * inner, yd);
-                q = qd;
-                y1 = yd;
-                B = Bo;
-                M = Mo;
-            }
-            MAA_CHECK(ctx.ws.dry || (kv_cache[b.kv_slot] && (lane ? batch_off + B <= kv_batch : kv_batch == B)),
-                      "set_context must precede forward (batch)");
-            const float* kv = kv_cache[b.kv_slot] + (size_t)batch_off * kv_len * 2 * inner;
-            attention_into(ctx, q, inner, s.dh, kv, 2 * inner, s.dh, kv + inner, 2 * inner, s.dh, B, s.heads, s.dh, HW,
-                           kv_len, scale, o, inner, o_sp);
-            float* y2 = ctx.ws.alloc_f((size_t)M * inner);
-            linear_into(ctx, o, inner, M, inner, b.out2, y1, inner, y2, inner, 0, 0, o_sp ? M : 0);
-            // x = ff(norm3(x)) + x      (:214)
-            launch_layernorm(ctx, y2, M, inner, b.ln3g, b.ln3b, 1e-5f, ln, sp);
-            float* g = ctx.ws.alloc_f((size_t)M * 4 * inner);
-            linear_into(ctx, ln, inner, M, inner, b.ff1, nullptr, 0, g, 4 * inner, /*geglu=*/1, 0, sp ? M : 0, g_sp);
-            float* y3 = ctx.ws.alloc_f((size_t)M * inner);
-            // the last block's output feeds only proj_out: written as split32 as well (bias + residual are applied
-            // before the split, in the same epilogue)
-            const bool last = &b == &s.blocks.back();
-            y_sp = last && sp && !no_osplit ? 1 : 0;
-            linear_into(ctx, g, 4 * inner, M, 4 * inner, b.ff2, y2, inner, y3, inner, 0, 0, g_sp ? M : 0, y_sp);
-            y = y3;
+            case CfgShare::Export:
+                m = st_prefix(p, s, x, in, ln, o, y1, q);
+                p.prefix->xres = m.xres, p.prefix->y1 = m.y1, p.prefix->q = m.q;
+                p.prefix->filled = true;
+                if (!ctx.ws.dry) MAA_HIP(hipEventRecord(p.prefix->ready, ctx.stream));
+                break;
+            case CfgShare::Import:      // the other lane computed this far on the same x: read in place
+                m = {x.p, p.prefix->y1, p.prefix->q};
+                break;
         }
-        MAA_CHECK(B == Bo, "SpatialTransformer without a transformer block cannot part the halves of a guided step");
-        linear_into(ctx, y, inner, M, inner, s.proj_out, xres, s.ch, out.p, s.ch, 0, 0, y_sp ? M : 0);
+        st_rest(p, s, full, m, ln, o, out);
         ctx.ws.release(mk);
         return out;
     }
 
-    T4 run_attn(Ctx& ctx, const AttnW& a, const T4& x) {
+    T4 run_attn(const Pass& p, const AttnW& a, const T4& x) const {
         // openaimodel.py:317-324 + QKVAttentionLegacy :356-372: per head h the qkv channels are
         // [q_h | k_h | v_h]; q and k are each scaled by ch^-1/4
-        const int B = x.B, HW = x.H * x.W, C = a.ch, dh = C / a.heads;
-        const long long M = (long long)B * HW;
-        T4 out = alloc_t(ctx, B, x.H, x.W, C);
-        const size_t mk = ctx.ws.mark();
-        float* xn = ctx.ws.alloc_f((size_t)M * C);
-        const bool sp = split_for_gemm(ctx, C);
-        launch_groupnorm(ctx, x.p, C, C, nullptr, 0, 0, B, HW, 32, a.ng, a.nb, 1e-5f, 0, xn, sp);
-        float* qkv = ctx.ws.alloc_f((size_t)M * 3 * C);
-        linear_into(ctx, xn, C, M, C, a.qkv, nullptr, 0, qkv, 3 * C, 0, 0, sp ? M : 0);
-        float* o = ctx.ws.alloc_f((size_t)M * C);
+        const int dh = a.ch / a.heads;
         const float sc = 1.0f / std::sqrt(std::sqrt((float)dh));
-        attention_into(ctx, qkv, 3 * C, 3 * dh, qkv + dh, 3 * C, 3 * dh, qkv + 2 * dh, 3 * C, 3 * dh, B, a.heads, dh, HW,
-                       HW, sc * sc, o, C);
-        linear_into(ctx, o, C, M, C, a.proj, x.p, C, out.p, C);
-        ctx.ws.release(mk);
-        return out;
+        return attn_block(p.ctx, x, a.ng, a.nb, 1e-5f, a.qkv, a.proj, a.heads, 3 * dh, dh, sc * sc);
     }
 
-    // shared (in/out): h holds one half of a guided step's batch; cleared by the SpatialTransformer that parts the halves
-    T4 run_layers(Ctx& ctx, const std::vector<Layer>& layers, T4 h, const T4* skip, const float* emb_out, bool* shared = nullptr) {
+    // part (in / out): the arrangement the next SpatialTransformer runs under; it parts the halves, so it leaves None behind
+    T4 run_layers(const Pass& p, const std::vector<Layer>& layers, T4 h, const T4* skip, CfgShare* part = nullptr) const {
+        Ctx& ctx = p.ctx;
         bool first = true;
         for (const Layer& l : layers) {
             const T4* x2 = first ? skip : nullptr;
             switch (l.kind) {
-                case kConv: {
-                    T4 o = alloc_t(ctx, h.B, h.H, h.W, convs[l.idx].cout);
-                    ConvOpt co;
-                    co.KH = co.KW = 3;
-                    co.pad = 1;
-                    conv_into(ctx, h, nullptr, convs[l.idx].w, co, o);
+                case kConv:
+                case kDown: {   // Downsample: conv3x3 stride 2 pad 1 (openaimodel.py:151-153)
+                    const int stride = l.kind == kDown ? 2 : 1;
+                    T4 o = alloc_t(ctx, h.B, (h.H - 1) / stride + 1, (h.W - 1) / stride + 1, convs[l.idx].cout);
+                    conv_into(ctx, h, nullptr, convs[l.idx].w, conv3x3(stride), o);
                     h = o;
                     break;
                 }
                 case kRes:
-                    h = run_res(ctx, res[l.idx], h, x2, emb_out);
+                    h = run_res(p, res[l.idx], h, x2);
                     break;
                 case kST:
-                    h = run_st(ctx, st[l.idx], h, shared && *shared, exporting ? 2 : 0);
-                    exporting = false;
-                    if (shared) *shared = false;
+                    h = run_st(p, st[l.idx], h, part ? *part : CfgShare::None);
+                    if (part) *part = CfgShare::None;
                     break;
                 case kAttn:
-                    h = run_attn(ctx, attn[l.idx], h);
+                    h = run_attn(p, attn[l.idx], h);
                     break;
-                case kDown: {   // Downsample: conv3x3 stride 2 pad 1 (openaimodel.py:151-153)
-                    T4 o = alloc_t(ctx, h.B, (h.H + 2 - 3) / 2 + 1, (h.W + 2 - 3) / 2 + 1, convs[l.idx].cout);
-                    ConvOpt co;
-                    co.KH = co.KW = 3;
-                    co.pad = 1;
-                    co.stride = 2;
-                    conv_into(ctx, h, nullptr, convs[l.idx].w, co, o);
-                    h = o;
-                    break;
-                }
                 case kUp: {     // Upsample: nearest 2x then conv3x3 (:116-118), the gather reads through the upsample
                     T4 o = alloc_t(ctx, h.B, h.H * 2, h.W * 2, convs[l.idx].cout);
-                    if (!conv_up2_into(ctx, h, convs[l.idx].w_up2, o)) {      // (exact-fp32 mode, odd channel counts, MAA_PP=off)
-                        ConvOpt co;
-                        co.KH = co.KW = 3;
-                        co.pad = 1;
-                        co.up = 1;
-                        conv_into(ctx, h, nullptr, convs[l.idx].w, co, o);
-                    }
+                    upsample_conv3x3(ctx, h, convs[l.idx].w, convs[l.idx].w_up2, o);
                     h = o;
                     break;
                 }
@@ -523,7 +529,7 @@ struct UNet::Impl {
     // rows = one per timestep: emb_layers(SiLU(time_embed(timestep_embedding(t)))) for every ResBlock (openaimodel.py:725-726,
     // 218-224, 264) -> out [rows, emb_all.Npad].  `add` (I2A: context.squeeze(1), custom_openaimodel.py:352-354) is a residual
     // of the second time_embed Linear.
-    void emb_rows(Ctx& ctx, const float* t, int rows, const float* add, float* out) {
+    void emb_rows(Ctx& ctx, const float* t, int rows, const float* add, float* out) const {
         const int mc = cfg.model_channels;
         float* te = ctx.ws.alloc_f((size_t)rows * mc);
         launch_timestep_embedding(ctx, t, rows, mc, te);
@@ -536,105 +542,88 @@ struct UNet::Impl {
         launch_silu(ctx, emb, (long long)rows * emb_dim, semb);
         linear_into(ctx, semb, emb_dim, rows, emb_dim, emb_all, nullptr, 0, out, emb_all.Npad);
     }
-    bool exporting = false;      // the next SpatialTransformer run_layers meets hands its prefix over (share 2)
-    int emb_ld = 0;      // pitch between the samples' rows of the current forward's emb_out (0: one row for every sample)
-    // a forward over samples [batch_off, batch_off + B) of the batch set_context saw (a lane of a CFG step: ddim.cpp); the
-    // caller's x / t / out pointers already stand at that sample, the context rows and the K/V caches are offset here
-    int batch_off = 0;
-    bool lane = false;
 
-    // emb_row != null: the step's ResBlock time-embedding row computed beforehand (UNet::emb_table), shared by all samples
-    // share_req (guided steps, one time-embedding row for all samples = emb_row): 1 = the batch is cat([x] * 2) on one stream,
-    // 2 / 3 = this call is the unconditional / conditional lane of such a step (the caller runs 2 before 3)
-    void forward(Ctx& ctx, const float* x_nchw, const float* t, const float* context, int B, int H, int W,
-                 float* out_nchw, const float* emb_row = nullptr, int share_req = 0) {
-        if (context && batch_off) context += (size_t)batch_off * kv_len * cfg.context_dim;
-        share = 0;
-        exporting = false;      // (a forward that threw half-way must not leave its hand-over armed)
-        if (emb_row) {
-            emb_ld = 0;
-            if (share_req == 1 && cfg.use_spatial_transformer && !lane && B % 2 == 0) share = 1;
-            if ((share_req == 2 || share_req == 3) && lane && prefix_ok()) share = share_req;
-            forward_body(ctx, x_nchw, B, H, W, out_nchw, emb_row);
-            share = 0;
-            return;
+    // One forward (run twice by run_sized: the dry pass sizes the workspace).  The caller's mode is honoured only with the step's
+    // hoisted embedding row, which is what makes the halves of a guided step equal before the first cross-attention: Dup on one
+    // stream over an even batch, Export / Import as a lane of a UNet the hand-over is written for (prefix_ok); else None.
+    void forward(Ctx& ctx, const float* x_nchw, const float* t, const float* context, int B, int H, int W, float* out_nchw,
+                 const UNetForwardOpt& o) const {
+        Pass p{ctx};
+        p.lane = o.batch_off >= 0;
+        p.batch_off = p.lane ? o.batch_off : 0;
+        if (context && p.batch_off) context += (size_t)p.batch_off * kv_len * cfg.context_dim;
+        const bool handed = o.mode == CfgShare::Export || o.mode == CfgShare::Import;
+        MAA_CHECK(!handed || (o.prefix && o.prefix->ready), "guided step: a lane that shares the prefix needs the step's CfgPrefix and its event");
+        if (o.emb_row) {
+            p.emb_out = o.emb_row;
+            if (o.mode == CfgShare::Dup && cfg.use_spatial_transformer && !p.lane && B % 2 == 0) p.mode = CfgShare::Dup;
+            if (handed && p.lane && prefix_ok()) p.mode = o.mode, p.prefix = o.prefix;
+        } else {
+            float* emb_out = ctx.ws.alloc_f((size_t)B * emb_all.Npad);
+            emb_rows(ctx, t, B, cfg.add_context_to_emb ? context : nullptr, emb_out);
+            p.emb_out = emb_out;
+            p.emb_ld = emb_all.Npad;
         }
-        float* emb_out = ctx.ws.alloc_f((size_t)B * emb_all.Npad);
-        emb_rows(ctx, t, B, cfg.add_context_to_emb ? context : nullptr, emb_out);
-        emb_ld = emb_all.Npad;
-        forward_body(ctx, x_nchw, B, H, W, out_nchw, emb_out);
+        if (p.mode == CfgShare::Import)
+            forward_rest_of_lane(p, B, H, W, out_nchw);
+        else
+            forward_body(p, x_nchw, B, H, W, out_nchw);
     }
 
-    void forward_body(Ctx& ctx, const float* x_nchw, int B, int H, int W, float* out_nchw, const float* emb_out) {
-        if (share == 3) {
-            forward_rest_of_lane(ctx, B, H, W, out_nchw, emb_out);
-            return;
+    void forward_body(const Pass& p, const float* x_nchw, int B, int H, int W, float* out_nchw) const {
+        Ctx& ctx = p.ctx;
+        if (p.mode == CfgShare::Export) {
+            p.prefix->B = B, p.prefix->H = H, p.prefix->W = W;
+            p.prefix->filled = false;
         }
-        if (share == 2) {
-            if (!prefix.ready) MAA_HIP(hipEventCreateWithFlags(&prefix.ready, hipEventDisableTiming));
-            prefix.B = B;
-            prefix.H = H;
-            prefix.W = W;
-            exporting = true;
-        }
-        // share 1: samples [B/2, B) repeat samples [0, B/2) (x and the embedding row); only the context rows differ, and the context
+        // Dup: samples [B/2, B) repeat samples [0, B/2) (x and the embedding row); only the context rows differ, and the context
         // enters at the first cross-attention -- until then one half is computed and the skip tensors are written twice
-        bool shared = share == 1;
+        CfgShare part = p.mode;      // None once the halves have parted
         auto both = [&](const T4& t) {
             T4 d = alloc_t(ctx, 2 * t.B, t.H, t.W, t.C);
             launch_dup_half(ctx, t.p, (long long)t.B * t.H * t.W * t.C, d.p);
             return d;
         };
-        T4 h = alloc_t(ctx, shared ? B / 2 : B, H, W, cfg.in_channels);
+        T4 h = alloc_t(ctx, part == CfgShare::Dup ? B / 2 : B, H, W, cfg.in_channels);
         launch_nchw_to_nhwc(ctx, x_nchw, h.B, cfg.in_channels, H * W, h.p);
         std::vector<T4> hs;
         for (auto& blk : input) {
-            h = run_layers(ctx, blk, h, nullptr, emb_out, &shared);
-            hs.push_back(shared ? both(h) : h);
-            if (share == 2 && hs.size() == 1) prefix.hs0 = h.p;      // conv_in's output: the other lane's first skip tensor
+            h = run_layers(p, blk, h, nullptr, &part);
+            hs.push_back(part == CfgShare::Dup ? both(h) : h);
+            if (p.mode == CfgShare::Export && hs.size() == 1) p.prefix->hs0 = h.p;      // conv_in's output: the other lane's first skip tensor
         }
-        exporting = false;
-        if (shared) {          // (no transformer on the way down: the halves part at the middle block at the latest)
-            h = both(h);
-            shared = false;
-        }
-        finish(ctx, h, hs, B, H, W, out_nchw, emb_out);
+        if (part == CfgShare::Dup) h = both(h);      // (no transformer on the way down: the halves part at the middle block at the latest)
+        finish(p, h, hs, B, H, W, out_nchw);
     }
 
-    // The conditional lane of a guided step (share 3): conv_in, the first ResBlock and the first transformer up to attn2's
+    // The conditional lane of a guided step (Import): conv_in, the first ResBlock and the first transformer up to attn2's
     // queries are the unconditional lane's -- same x, same embedding row -- and are read from its workspace.
-    void forward_rest_of_lane(Ctx& ctx, int B, int H, int W, float* out_nchw, const float* emb_out) {
-        MAA_CHECK(prefix.B == B && prefix.H == H && prefix.W == W && prefix.ready, "guided step: the lanes disagree on the shared prefix");
-        if (!ctx.ws.dry) MAA_HIP(hipStreamWaitEvent(ctx.stream, prefix.ready, 0));
+    void forward_rest_of_lane(const Pass& p, int B, int H, int W, float* out_nchw) const {
+        Ctx& ctx = p.ctx;
+        const CfgPrefix& f = *p.prefix;
+        MAA_CHECK(f.filled && f.B == B && f.H == H && f.W == W, "guided step: the lanes disagree on the shared prefix");
+        if (!ctx.ws.dry) MAA_HIP(hipStreamWaitEvent(ctx.stream, f.ready, 0));
         const STW& s0 = st[input[1][1].idx];
-        auto view = [&](const float* p, int C) {
-            T4 t;
-            t.B = B;
-            t.H = H;
-            t.W = W;
-            t.C = C;
-            t.p = const_cast<float*>(p);
-            return t;
-        };
         std::vector<T4> hs;
-        hs.push_back(view(prefix.hs0, cfg.model_channels));
-        T4 h = run_st(ctx, s0, view(prefix.xres, s0.ch), false, 3);
+        hs.push_back(view_t(const_cast<float*>(f.hs0), B, H, W, cfg.model_channels));
+        T4 h = run_st(p, s0, view_t(const_cast<float*>(f.xres), B, H, W, s0.ch), CfgShare::Import);
         hs.push_back(h);
         for (size_t i = 2; i < input.size(); ++i) {
-            h = run_layers(ctx, input[i], h, nullptr, emb_out);
+            h = run_layers(p, input[i], h, nullptr);
             hs.push_back(h);
         }
-        finish(ctx, h, hs, B, H, W, out_nchw, emb_out);
+        finish(p, h, hs, B, H, W, out_nchw);
     }
 
     // middle block, the way up with the skip tensors, the output head
-    void finish(Ctx& ctx, T4 h, std::vector<T4>& hs, int B, int H, int W, float* out_nchw, const float* emb_out) {
+    void finish(const Pass& p, T4 h, std::vector<T4>& hs, int B, int H, int W, float* out_nchw) const {
+        Ctx& ctx = p.ctx;
         const int mc = cfg.model_channels;
-        h = run_layers(ctx, middle, h, nullptr, emb_out);
+        h = run_layers(p, middle, h, nullptr);
         for (auto& blk : output) {
             T4 skip = hs.back();
             hs.pop_back();
-            h = run_layers(ctx, blk, h, &skip, emb_out);
+            h = run_layers(p, blk, h, &skip);
         }
         T4 hn = alloc_t(ctx, B, H, W, mc);
         hn.split = split_for_gemm(ctx, mc);
@@ -643,10 +632,7 @@ struct UNet::Impl {
             launch_narrow_conv3x3(ctx, hn.p, mc, B, H, W, mc, out_narrow.w, out_narrow.bias, cfg.out_channels, out_nchw))
             return;      // (bf16x3: the 320 -> 4 convolution on its own kernel, straight to NCHW)
         T4 o = alloc_t(ctx, B, H, W, cfg.out_channels);
-        ConvOpt co;
-        co.KH = co.KW = 3;
-        co.pad = 1;
-        conv_into(ctx, hn, nullptr, out_conv, co, o);
+        conv_into(ctx, hn, nullptr, out_conv, conv3x3(), o);
         launch_nhwc_to_nchw(ctx, o.p, B, cfg.out_channels, H * W, out_nchw, cfg.out_channels);
     }
 };
@@ -716,21 +702,11 @@ void UNet::set_context_cfg(Ctx& ctx, const float* d_uncond, const float* d_cond,
     set_context(ctx, reinterpret_cast<const float*>(buf), 2 * B, L, rep);
 }
 
-void UNet::forward(Ctx& ctx, const float* x_nchw, const float* t, const float* context, int B, int H, int W,
-                   float* out_nchw, const float* emb_row, int batch_off, int cfg_share) {
-    Impl& m = *impl_;
+void UNet::forward(Ctx& ctx, const float* x_nchw, const float* t, const float* context, int B, int H, int W, float* out_nchw,
+                   const UNetForwardOpt& opt) {
+    const Impl& m = *impl_;
     PrecisionGuard pg(ctx, m.precision);
-    m.lane = batch_off >= 0;
-    m.batch_off = m.lane ? batch_off : 0;
-    try {
-        run_sized(ctx, [&] { m.forward(ctx, x_nchw, t, context, B, H, W, out_nchw, emb_row, cfg_share); });
-    } catch (...) {
-        m.batch_off = 0;
-        m.lane = false;
-        throw;
-    }
-    m.batch_off = 0;
-    m.lane = false;
+    run_sized(ctx, [&] { m.forward(ctx, x_nchw, t, context, B, H, W, out_nchw, opt); });
 }
 int UNet::emb_width() const { return impl_->emb_all.Npad; }
 void UNet::emb_table(Ctx& ctx, const float* d_t, int rows, float* d_out) {

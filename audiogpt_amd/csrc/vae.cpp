@@ -161,21 +161,17 @@ struct VAE::Impl {
         t1.split = split_for_gemm(ctx, r.cin);
         launch_groupnorm(ctx, x.p, r.cin, r.cin, nullptr, 0, 0, x.B, x.H * x.W, 32, r.g1, r.b1, 1e-6f, 1, t1.p, t1.split);
         T4 h1 = alloc_t(ctx, x.B, x.H, x.W, r.cout);
-        ConvOpt o;
-        o.KH = o.KW = 3;
-        o.pad = 1;
-        conv_into(ctx, t1, nullptr, r.conv1, o, h1);
+        conv_into(ctx, t1, nullptr, r.conv1, conv3x3(), h1);
         T4 t2 = alloc_t(ctx, x.B, x.H, x.W, r.cout);
         t2.split = split_for_gemm(ctx, r.cout);
         launch_groupnorm(ctx, h1.p, r.cout, r.cout, nullptr, 0, 0, x.B, x.H * x.W, 32, r.g2, r.b2, 1e-6f, 1, t2.p, t2.split);
         const float* resid = x.p;
         if (r.has_nin) {
             T4 sk = alloc_t(ctx, x.B, x.H, x.W, r.cout);
-            ConvOpt os;
-            conv_into(ctx, x, nullptr, r.nin, os, sk);
+            conv_into(ctx, x, nullptr, r.nin, ConvOpt(), sk);
             resid = sk.p;
         }
-        ConvOpt o2 = o;
+        ConvOpt o2 = conv3x3();
         o2.res = resid;
         conv_into(ctx, t2, nullptr, r.conv2, o2, out);
         ctx.ws.release(mk);
@@ -183,22 +179,9 @@ struct VAE::Impl {
     }
 
     T4 run_attn(Ctx& ctx, const VAttnW& a, const T4& x) {
-        const int C = a.c, HW = x.H * x.W;
-        const long long M = (long long)x.B * HW;
-        T4 out = alloc_t(ctx, x.B, x.H, x.W, C);
-        const size_t mk = ctx.ws.mark();
-        float* xn = ctx.ws.alloc_f((size_t)M * C);
-        const bool sp = split_for_gemm(ctx, C);
-        launch_groupnorm(ctx, x.p, C, C, nullptr, 0, 0, x.B, HW, 32, a.ng, a.nb, 1e-6f, 0, xn, sp);
-        float* qkv = ctx.ws.alloc_f((size_t)M * 3 * C);
-        linear_into(ctx, xn, C, M, C, a.qkv, nullptr, 0, qkv, 3 * C, 0, 0, sp ? M : 0);
-        float* o = ctx.ws.alloc_f((size_t)M * C);
-        // w = softmax(q k^T * C^-1/2) over keys; h = w v   (model.py:186-198)
-        const float sc = (float)std::pow((double)(int)C, -0.5);
-        attention_into(ctx, qkv, 3 * C, 0, qkv + C, 3 * C, 0, qkv + 2 * C, 3 * C, 0, x.B, 1, C, HW, HW, sc, o, C);
-        linear_into(ctx, o, C, M, C, a.proj, x.p, C, out.p, C);
-        ctx.ws.release(mk);
-        return out;
+        // one head over [q | k | v]: w = softmax(q k^T * C^-1/2) over keys; h = w v   (model.py:186-198)
+        const float sc = (float)std::pow((double)(int)a.c, -0.5);
+        return attn_block(ctx, x, a.ng, a.nb, 1e-6f, a.qkv, a.proj, 1, 0, a.c, sc);
     }
 
     // spec = true: the tools' next line folded in -- clamp((mel + 1) / 2, 0, 1) (audio-chatgpt.py:175-176), written as [B, H, W]
@@ -208,12 +191,9 @@ struct VAE::Impl {
         launch_nchw_to_nhwc(ctx, z_nchw, B, cfg.embed_dim, h * w, z.p);
         if (inv_scale != 1.0f) launch_scale(ctx, z.p, z.numel(), inv_scale, z.p);   // z / scale_factor
         T4 zq = alloc_t(ctx, B, h, w, cfg.z_channels);
-        ConvOpt o1;
-        conv_into(ctx, z, nullptr, post_quant, o1, zq);
+        conv_into(ctx, z, nullptr, post_quant, ConvOpt(), zq);
         T4 hcur = alloc_t(ctx, B, h, w, d_block_in_top);
-        ConvOpt o3;
-        o3.KH = o3.KW = 3;
-        o3.pad = 1;
+        ConvOpt o3 = conv3x3();
         conv_into(ctx, zq, nullptr, d_conv_in, o3, hcur);
         hcur = run_res(ctx, d_mid1, hcur);
         hcur = run_attn(ctx, d_mid_attn, hcur);
@@ -226,11 +206,7 @@ struct VAE::Impl {
             }
             if (L.has_resample) {
                 T4 up = alloc_t(ctx, B, hcur.H * 2, hcur.W * 2, L.resample_c);
-                if (!conv_up2_into(ctx, hcur, L.resample_up2, up)) {
-                    ConvOpt ou = o3;
-                    ou.up = 1;
-                    conv_into(ctx, hcur, nullptr, L.resample, ou, up);
-                }
+                upsample_conv3x3(ctx, hcur, L.resample, L.resample_up2, up);
                 hcur = up;
             }
         }
@@ -253,9 +229,7 @@ struct VAE::Impl {
         const int nres = cfg.n_ch_mult;
         T4 x = alloc_t(ctx, B, H, W, cfg.in_channels);
         launch_nchw_to_nhwc(ctx, mel_nchw, B, cfg.in_channels, H * W, x.p);
-        ConvOpt o3;
-        o3.KH = o3.KW = 3;
-        o3.pad = 1;
+        ConvOpt o3 = conv3x3();
         T4 hcur = alloc_t(ctx, B, H, W, cfg.ch);
         conv_into(ctx, x, nullptr, e_conv_in, o3, hcur);
         for (int lvl = 0; lvl < nres; ++lvl) {
@@ -267,9 +241,7 @@ struct VAE::Impl {
             if (L.has_resample) {   // pad (0,1,0,1) then conv3x3 stride 2 pad 0 (model.py:72-77)
                 const int Ho = (hcur.H + 1 - 3) / 2 + 1, Wo = (hcur.W + 1 - 3) / 2 + 1;
                 T4 dn = alloc_t(ctx, B, Ho, Wo, L.resample_c);
-                ConvOpt od;
-                od.KH = od.KW = 3;
-                od.stride = 2;
+                ConvOpt od = conv3x3(2);
                 od.pad = 0;
                 od.pad_h = 0;
                 conv_into(ctx, hcur, nullptr, L.resample, od, dn);
@@ -287,8 +259,7 @@ struct VAE::Impl {
         T4 eo = alloc_t(ctx, B, hcur.H, hcur.W, oc);
         conv_into(ctx, hn, nullptr, e_conv_out, o3, eo);
         T4 mo = alloc_t(ctx, B, hcur.H, hcur.W, 2 * cfg.embed_dim);
-        ConvOpt o1;
-        conv_into(ctx, eo, nullptr, quant, o1, mo);
+        conv_into(ctx, eo, nullptr, quant, ConvOpt(), mo);
         launch_nhwc_to_nchw(ctx, mo.p, B, 2 * cfg.embed_dim, hcur.H * hcur.W, moments_nchw, 2 * cfg.embed_dim);
     }
 };
